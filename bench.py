@@ -325,6 +325,49 @@ def dp_path_in_child(args, n, limit_s=240):
         return {"dp_path_error": repr(e)[:300]}
 
 
+DUMP_BYTES = 64_000_000  # --dump-outputs budget for the files, headers included: above it, a fixed seeded sample of envs is written
+NPY_HEADER = 128         # bytes np.save puts in front of a 1- or 2-d float array
+
+
+def rollout_actions(n, rank, dev):
+    """The synthetic U(-1,1) actions of the rollout: ACTION_RING batches of n envs, seeded by the rank alone."""
+    import torch
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1000 + rank)
+    return (torch.rand(ACTION_RING, n * 18, device=dev, generator=gen) * 2 - 1).contiguous()
+
+
+def step_outputs(sim, abi):
+    """Host copies of what a caller of bez_sim_step reads after the call (VecTask.step's buffers and the refreshed Isaac
+    state tensors), one row per env: float32 as computed, the int64 buffers as float64 (exact).  The refresh kernels only
+    read the simulator state, so the steps that follow are unchanged."""
+    import torch
+    live = {"obs": abi.TENSOR_OBS, "rew": abi.TENSOR_REW, "reset": abi.TENSOR_RESET, "progress": abi.TENSOR_PROGRESS,
+            "timeout": abi.TENSOR_TIMEOUT}
+    refreshed = {"dof_target": abi.TENSOR_DOF_TARGET, "root_state": abi.TENSOR_ROOT_STATE, "dof_state": abi.TENSOR_DOF_STATE,
+                 "rigid_body_state": abi.TENSOR_RIGID_BODY_STATE}
+    ts = {k: sim.tensor(w) for k, w in live.items()}
+    ts.update({k: sim.refresh(w) for k, w in refreshed.items()})
+    torch.cuda.synchronize()
+    return {k: t.reshape(sim.num_envs, -1).to("cpu", torch.float64 if t.dtype == torch.int64 else torch.float32).numpy()
+            for k, t in ts.items()}
+
+
+def write_outputs(outs, path, budget=DUMP_BYTES):
+    """Writes path/<name>.npy per array; if the files would exceed `budget` bytes, the same seeded sample of env rows from
+    each, and the sampled env ids as path/env_ids.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = next(iter(outs.values())).shape[0]
+    per_env = sum(a.nbytes for a in outs.values()) // n
+    if per_env * n + NPY_HEADER * len(outs) > budget:
+        rows = (budget - NPY_HEADER * (len(outs) + 1)) // (per_env + 8)
+        ids = np.sort(np.random.default_rng(0).choice(n, rows, replace=False))
+        outs = dict({k: a[ids] for k, a in outs.items()}, env_ids=ids.astype(np.float64))
+    for k, a in outs.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def stub_main(args, rank, world):
     """The multi-rank skeleton of main() on the CPU (gloo), the env step replaced by a no-op: rendezvous, barrier-bracketed timed
     region, MAX over ranks, one JSON line from rank 0.  Exercised by tests/test_bench_launcher.py."""
@@ -385,7 +428,11 @@ def main():
                     "friction / gains / limits / gravity + observation and action noise, redrawn on the device at reset time)")
     ap.add_argument("--stub-cpu", action="store_true", help="launcher self-test: gloo on the CPU, the env step replaced by a no-op "
                     "(tests/test_bench_launcher.py); prints the same JSON skeleton with metric 'stub'")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last of them computed (rank 0's envs) as "
+                    "DIR/<name>.npy, float32 / float64, at most 64 MB in all; the inputs depend only on the arguments")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))  # nothing above this line has touched a GPU
@@ -419,9 +466,7 @@ def main():
         # (net contact force rows, feet, prev_lin_vel: 308 of the 912 B an env-step writes; the obs' feet flags are unaffected)
         cfg.flags |= abi.FLAG_LEAN_STEP
     sim = BezSim(cfg, local_rank)
-    gen = torch.Generator(device=dev)
-    gen.manual_seed(1000 + rank)
-    actions = (torch.rand(ACTION_RING, n * 18, device=dev, generator=gen) * 2 - 1).contiguous()
+    actions = rollout_actions(n, rank, dev)
 
     def barrier():
         if world > 1:
@@ -454,6 +499,7 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    outputs = step_outputs(sim, abi) if args.dump_outputs and rank == 0 else None
     # sanity: the rollout really ran (resets happen with random actions; everything finite)
     obs = sim.tensor(abi.TENSOR_OBS)
     assert torch.isfinite(obs).all()
@@ -565,6 +611,8 @@ def main():
             out["cpu_baseline"] = "N=1 only"
         if collective is not None:
             out["collective"] = collective
+        if outputs is not None:
+            write_outputs(outputs, args.dump_outputs)
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

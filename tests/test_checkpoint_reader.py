@@ -1,8 +1,9 @@
 """CPU: the no-unpickle reader of rl_games checkpoints (bez_isaacgym_amd/utils/rlg_checkpoint.py).
 
-Always: a synthetic torch.save file round-trips through the reader and unexpected globals / opcodes are refused.
-Where the reference tree is present (build container only): the shipped Bez_Kick_33.pth has the layout SURVEY.md section 6
-reports and loads into this build's PPO modules under the same key names (checkpoint interop)."""
+A synthetic torch.save file round-trips through the reader and unexpected globals / opcodes are refused.  The reference's shipped
+policy (Bez_Kick_33.pth; its numbers are tests/golden/bez_kick_33_policy.npz, tests/golden/make_policy_fixture.py), saved here in
+rl_games' checkpoint layout, has the layout SURVEY.md section 6 reports and loads into this build's PPO modules under the same key
+names (checkpoint interop)."""
 import os
 import pickle
 
@@ -13,7 +14,26 @@ import torch
 from bez_isaacgym_amd.ppo.a2c_continuous import ModelA2CContinuousLogStd, RunningMeanStd
 from bez_isaacgym_amd.utils.rlg_checkpoint import _symbolic_eval, load_into_agent_modules, read_rlgames_checkpoint
 
-REF_CK = "/root/reference/bez_isaacgym/results/Bez_Kick/Normal/Bez_Kick_33.pth"
+POLICY = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bez_kick_33_policy.npz")
+
+
+def _save_policy_as_rlgames_checkpoint(path):
+    """torch.save of the shipped policy in the layout of rl_games' get_full_state_weights (a2c_common.py): state dicts with their
+    _metadata, Adam's state keyed by parameter index, the AMP scaler state, fp64 running statistics, last_mean_rewards as a numpy
+    scalar."""
+    z = np.load(POLICY)
+    m = ModelA2CContinuousLogStd(54, 18, (400, 200, 100)); rms = RunningMeanStd((54,)); vms = RunningMeanStd((1,))
+    m.load_state_dict({k[len("model/"):]: torch.from_numpy(z[k]) for k in z.files if k.startswith("model/")})
+    for mod, grp in ((rms, "running_mean_std"), (vms, "reward_mean_std")):
+        mod.load_state_dict({k: torch.from_numpy(np.array(z[grp + "/" + k])) for k in ("running_mean", "running_var", "count")})
+    opt = torch.optim.Adam(m.parameters(), lr=5e-5, eps=1e-8)
+    for p in m.parameters():
+        p.grad = torch.zeros_like(p)
+    opt.step()   # zero gradients: Adam's state exists, the weights do not move
+    torch.save({"model": m.state_dict(), "epoch": int(z["epoch"]), "frame": int(z["frame"]), "optimizer": opt.state_dict(),
+                "last_mean_rewards": np.float64(z["last_mean_rewards"]), "env_state": None, "running_mean_std": rms.state_dict(),
+                "reward_mean_std": vms.state_dict(),
+                "scaler": {"scale": 4096.0, "growth_factor": 2.0, "backoff_factor": 0.5, "growth_interval": 2000, "_growth_tracker": 0}}, path)
 
 
 def test_roundtrip_of_own_checkpoint(tmp_path):
@@ -44,10 +64,13 @@ def test_refuses_anything_executable():
         _symbolic_eval(pickle.dumps({"x": Evil()}, protocol=2))
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CK), reason="reference checkpoint only exists in the build container")
-def test_reference_checkpoint_layout_and_interop():
-    ck = read_rlgames_checkpoint(REF_CK)
+def test_reference_checkpoint_layout_and_interop(tmp_path):
+    path = str(tmp_path / "Bez_Kick_33.pth")
+    _save_policy_as_rlgames_checkpoint(path)
+    ck = read_rlgames_checkpoint(path)
     assert {"model", "running_mean_std", "reward_mean_std", "optimizer", "epoch", "frame", "last_mean_rewards"} <= set(ck)
+    assert ck["optimizer"]["param_groups"][0]["params"] == list(range(11)) and sorted(ck["optimizer"]["state"]) == list(range(11))
+    assert ck["optimizer"]["state"][1]["exp_avg"].shape == (400, 54) and ck["scaler"]["growth_interval"] == 2000 and ck["env_state"] is None
     assert sum(v.size for v in ck["model"].values() if isinstance(v, np.ndarray)) == 124237
     assert ck["epoch"] == 6156 and ck["frame"] == 806879232 and abs(ck["last_mean_rewards"] - 87.55) < 0.01
     m = ModelA2CContinuousLogStd(54, 18, (400, 200, 100)); rms = RunningMeanStd((54,)); vms = RunningMeanStd((1,))

@@ -214,12 +214,15 @@ def _cli_worker(rank, world, port, out, tmp):
 
 
 @pytest.mark.timeout(300)
-def test_train_cli_multi_gpu_wiring_on_gloo(tmp_path):
+def test_train_cli_multi_gpu_wiring_on_gloo(tmp_path, monkeypatch):
     """`train.py task=bez_kick multi_gpu=True` under torch.distributed.run's environment (rlgames_utils.py:71-81, config.yaml:40):
     process group, rank -> env shard (global env-id offset = rank * num_envs), data-parallel agent, rank-0-only run directory."""
     mgr = mp.Manager()
     out = mgr.dict()
     port = 33500 + (os.getpid() % 2000)
+    # the workers see no GPU, so launch() takes its gloo path on every box (on a 1-GPU box RCCL would hand rank 1 a missing device)
+    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "")
+    monkeypatch.setenv("CUDA_VISIBLE_DEVICES", "")
     mp.spawn(_cli_worker, args=(2, port, out, str(tmp_path)), nprocs=2, join=True)
     assert out[0][0] == {"rank": 0, "offset": 0, "n": 32} and out[1][0] == {"rank": 1, "offset": 32, "n": 32}
     assert out[0][1] == out[1][1] == 2

@@ -12,7 +12,7 @@ from bez_isaacgym_amd.utils.trajectories import JOINT_ORDER, Trajectory, read_cs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TABLES = os.path.join(ROOT, "tests", "golden", "trajectories.json")
-REF_CSV = "/root/reference/resources/library/trajectories/trajectories/simulation_rightkick.csv"
+REF_CSV = os.path.join(os.environ.get("BEZ_REFERENCE_ROOT", "/root/reference"), "resources/library/trajectories/trajectories/simulation_rightkick.csv")
 
 
 def _tables():
