@@ -28,12 +28,15 @@ FLAG_TGS_SOLVER = 512
 FLAG_ANKLE_STOP = 1024          # scenario harness: calf <-> foot-plate contact (one-env-per-lane kernel, stl asset without cleats)
 FLAG_ALL_GROUND_SHAPES = 2048   # scenario harness: ground contact at every collision shape's corners (same)
 FLAG_FIX_BASE = 4096            # urdfAsset.fixBaseLink: the torso welded to the world
+FLAG_NONFINITE_GUARD = 8192     # per-env non-finite guard of the post-physics (on by default; include/bez_sim.h)
+HEALTH_NONFINITE = 1            # health word bits (TENSOR_HEALTH, BezSim.health)
+HEALTH_SPIN_TIMEOUT = 2
 TASK_KICK, TASK_WALK, TASK_ORIENT = 0, 1, 2
 TASK_IDS = {"bez_kick": TASK_KICK, "bez_walk": TASK_WALK, "bez_orient": TASK_ORIENT}
 
 (TENSOR_ROOT_STATE, TENSOR_DOF_STATE, TENSOR_RIGID_BODY_STATE, TENSOR_NET_CONTACT_FORCE, TENSOR_OBS,
  TENSOR_REW, TENSOR_RESET, TENSOR_PROGRESS, TENSOR_TIMEOUT, TENSOR_DOF_TARGET, TENSOR_PREV_LIN_VEL,
- TENSOR_FEET, TENSOR_GOAL, TENSOR_RANDOMIZE_BUF, TENSOR_DR_NOISE, TENSOR_COUNT) = range(16)
+ TENSOR_FEET, TENSOR_GOAL, TENSOR_RANDOMIZE_BUF, TENSOR_DR_NOISE, TENSOR_NONFINITE_COUNT, TENSOR_HEALTH, TENSOR_COUNT) = range(18)
 DTYPE_F32, DTYPE_I64 = 0, 1
 (PARAM_FRICTION, PARAM_KP_SCALE, PARAM_KD_SCALE, PARAM_MASS_SCALE, PARAM_GRAVITY, PARAM_DOF_LOWER, PARAM_DOF_UPPER,
  PARAM_COUNT) = range(8)
@@ -159,7 +162,7 @@ def default_config(num_envs=4096, seed=42, env_id_offset=0):
     c.goal[:] = [1.5, 0.0]
     for k, v in CONTACT_DEFAULTS.items():
         setattr(c, k, v)
-    c.flags = FLAG_IMU_PREV_ALIAS
+    c.flags = FLAG_IMU_PREV_ALIAS | FLAG_NONFINITE_GUARD
     c.seed = int(seed)
     c.env_id_offset = int(env_id_offset)
     return c
@@ -217,6 +220,8 @@ def config_from_task_cfg(cfg, seed=42, env_id_offset=0, strict_reference_quirks=
         if k in sim.get("bez", {}):
             setattr(c, k, float(sim["bez"][k]))
     c.flags = FLAG_IMU_PREV_ALIAS if strict_reference_quirks else 0
+    if env.get("nonfiniteGuard", True):  # not a key of the reference's yaml: this build's per-env non-finite guard, on unless False
+        c.flags |= FLAG_NONFINITE_GUARD
     if env.get("asset", {}).get("cleats", False):
         c.flags |= FLAG_CLEATS
     if not env.get("asset", {}).get("stl", True):  # kick_env.py:266-276: soccerbot_box*.urdf

@@ -356,7 +356,7 @@ BEZ_DEV void leg_role(const Params& P, float* lds, int lane, int e, bool active,
     }
     WS_STAMP(side, 24 + s);
     ws_barrier();  // B1c: both helper parts' leg<->leg contact wrenches are in LDS
-    const float sc = wq_chain_self_correction<LEN>(P, Q, lds, lane, side, s + 1, p3, pA, X_IA + side * 27 + 9);
+    const float sc = wq_chain_self_correction<LEN, CL>(P, Q, lds, lane, side, s + 1, p3, pA, X_IA + side * 27 + 9);
 #else
     P3 p3[LEN];
     Sym6 IA = sym6zero(); SV pA = svzero();
@@ -369,7 +369,7 @@ BEZ_DEV void leg_role(const Params& P, float* lds, int lane, int e, bool active,
     }
     WS_STAMP(side, 24 + s);
     ws_barrier();  // B1c: both helper parts' leg<->leg contact wrenches are in LDS
-    const float sc = ws_chain_self_correction<LEN>(P, lds, lane, side, s + 1, p3, pA);   // (stores the bias part of the chain's X_IA block)
+    const float sc = ws_chain_self_correction<LEN, CL>(P, lds, lane, side, s + 1, p3, pA);   // (stores the bias part of the chain's X_IA block)
 #endif
     WS_STAMP(side, 4 + 8 * s);
     ws_barrier();  // B2
@@ -575,8 +575,9 @@ BEZ_DEV void post_imu_orn(const Params& P, float* lds, int lane, int e, bool act
 #pragma unroll
   for (int i = 0; i < 8; ++i) obs_row[36 + i] = tail[i];
   if (active && !P.lean) {
+    const bool guard = guard_on(P);   // the non-finite guard: a non-finite prev_lin_vel is stored as 0
 #pragma unroll
-    for (int i = 0; i < 3; ++i) st[(size_t)(F_PREV + i) * n + e] = prev[i];
+    for (int i = 0; i < 3; ++i) st[(size_t)(F_PREV + i) * n + e] = guard ? finite_or(prev[i], 0.f) : prev[i];
   }
 }
 template <bool CL>
@@ -836,6 +837,14 @@ BEZ_DEV void root_role(const Params& P, float* lds, int lane, int e, bool active
       progress = 0; reset = 0;
     }
   }
+  // the non-finite guard, root / ball part: the orientation and spin of the ball are not read behind the last barrier -- tested here, into a
+  // mask (no VGPR across the barrier); the rest is tested there, where the reward keeps it live anyway
+  bool ball_bad = false;
+  if (POST && guard_on(P)) {
+    ball_bad = v3_nonfinite(ball_ang);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ball_bad |= nonfinite(bq[i]);
+  }
   if (active) {
 #if BEZ_WS_SUB == 4
     int es = e;
@@ -869,6 +878,18 @@ BEZ_DEV void root_role(const Params& P, float* lds, int lane, int e, bool active
     }
     float rew;
     reward_of(P, root_pos, rq, root_lin, root_ang, ball_pos, ball_lin, pn, orn, rew, reset, progress, goal_x, goal_y);
+    // the trip: root / ball, any chain role's joints (their pose-error share is NaN then: ws_chain_epilogue), the reward
+    if (guard_on(P)) {
+      const bool bad = ball_bad | v3_nonfinite(root_pos) | v3_nonfinite(root_lin) | v3_nonfinite(root_ang) | v3_nonfinite(ball_pos) |
+                       v3_nonfinite(ball_lin) | nonfinite(rq[0]) | nonfinite(rq[1]) | nonfinite(rq[2]) | nonfinite(rq[3]) | nonfinite(pn) | nonfinite(rew);
+      if (bad) {   // cold
+        rew = 0.f; reset = 1;
+        if (active) {
+          guard_trip(P, e);
+          root_ball_sanitize(P, st, n, e);   // the stores before the barrier again, non-finite values replaced (same lane, program order)
+        }
+      }
+    }
     if (active) { P.rew[e] = rew; P.reset[e] = reset; P.progress[e] = progress; P.timeout[e] = timeout; }
   }
   WS_STAMP_ROOT_N(14, 3, 21);
@@ -893,7 +914,7 @@ __global__ __launch_bounds__(WS_BLOCK) void step_kernel_ws8(Params P) {
     const float* src = P.actions + (size_t)env0 * BEZ_ND;
     for (int i = tid; i < nloc * BEZ_ND; i += WS_BLOCK) act[(i / BEZ_ND) * WS_ACT_STRIDE + (i % BEZ_ND)] = src[i];
   }
-  if (tid < (WS_SUB == 4 ? 4 : 2)) reinterpret_cast<int*>(lds + X_PAIRSEQ * WS_LANES)[tid] = 0;   // (published before B0; words 2 / 3: the package hand-over of the lane-group form)
+  if (tid < 5) reinterpret_cast<int*>(lds + X_PAIRSEQ * WS_LANES)[tid] = 0;   // (published before B0; words 2 / 3: the package hand-over of the lane-group form; word 4: a spin wait timed out)
   // contact-force rows start from zero: bodies nothing touches are never accumulated into
   constexpr int NROW = (nb_of<CL>() + 1) * 3;  // contact-force rows of this asset (robot bodies + ball)
   for (int i = tid; i < NROW * WS_LANES; i += WS_BLOCK) lds[X_CF * WS_LANES + i] = 0.f;
@@ -928,6 +949,12 @@ __global__ __launch_bounds__(WS_BLOCK) void step_kernel_ws8(Params P) {
 #else
     const int ctid = tid - (role > 3 ? 64 : 0);
 #endif
+    // the non-finite guard: non-finite contact-force and observation entries leave the kernel as 0 (whatever env they belong to)
+    const bool guard = POST && guard_on(P);
+    auto fin4 = [&](float4 v) __attribute__((always_inline)) {
+      if (guard) { v.x = finite_or(v.x, 0.f); v.y = finite_or(v.y, 0.f); v.z = finite_or(v.z, 0.f); v.w = finite_or(v.w, 0.f); }
+      return v;
+    };
     if (!P.lean) {
       // net contact force: SoA rows of 64 consecutive envs each -> coalesced
       float* dst = P.state + (size_t)F_CF * P.n + env0;
@@ -935,9 +962,14 @@ __global__ __launch_bounds__(WS_BLOCK) void step_kernel_ws8(Params P) {
       const bool zero = POST && lds[X_RESETF * WS_LANES + ((ctid & (WS_ENVS - 1)) << WS_SUB_SHIFT)] != 0.f;  // env reset by this step: no contact forces
       for (int i = ctid; i < NROW * WS_ENVS; i += NT) {
         const int k = i >> WS_ENV_SHIFT, l = i & (WS_ENVS - 1);
-        if (l < nloc) dst[(size_t)k * P.n + l] = zero ? 0.f : lds[(X_CF + k) * WS_LANES + (l << WS_SUB_SHIFT)];
+        if (l < nloc) {
+          const float v = lds[(X_CF + k) * WS_LANES + (l << WS_SUB_SHIFT)];
+          dst[(size_t)k * P.n + l] = (zero || (guard && nonfinite(v))) ? 0.f : v;
+        }
       }
     }
+    if (ctid == 0 && reinterpret_cast<const int*>(lds + X_PAIRSEQ * WS_LANES)[4] != 0 && P.health)   // (cold: ws_spin_timeout)
+      atomicOr(P.health, (unsigned long long)BEZ_HEALTH_SPIN_TIMEOUT);
     if (DR && POST && P.dr_snap && blockIdx.x == 0 && ctid == 0) {   // the next step's action-noise parameters: a copy (bez_kernels.h DrSnap)
       const unsigned long long f = P.dr_state->frame;
       *P.dr_snap = DrSnap{P.dr_state->noise[2], P.dr_state->noise[3], (unsigned int)f, (unsigned int)(f >> 32)};
@@ -958,13 +990,18 @@ __global__ __launch_bounds__(WS_BLOCK) void step_kernel_ws8(Params P) {
           dr_noise_quad(P.seed, P.env_off, frame, 0, q0 + i, z);
           float4 v = rows[i];
           v.x += fmaf(z[0], sd, mean); v.y += fmaf(z[1], sd, mean); v.z += fmaf(z[2], sd, mean); v.w += fmaf(z[3], sd, mean);
-          dst[i] = v;
+          dst[i] = fin4(v);
         }
-        for (int i = (nvec << 2) + ctid; i < nloc * P.nobs; i += NT)
-          P.obs[(size_t)env0 * P.nobs + i] = obs_with_noise(P, (long long)env0 * P.nobs + i, lds[X_STAGE * WS_LANES + i]);
+        for (int i = (nvec << 2) + ctid; i < nloc * P.nobs; i += NT) {
+          const float v = obs_with_noise(P, (long long)env0 * P.nobs + i, lds[X_STAGE * WS_LANES + i]);
+          P.obs[(size_t)env0 * P.nobs + i] = guard ? finite_or(v, 0.f) : v;
+        }
       } else {
-        for (int i = ctid; i < nvec; i += NT) dst[i] = rows[i];
-        for (int i = (nvec << 2) + ctid; i < nloc * P.nobs; i += NT) P.obs[(size_t)env0 * P.nobs + i] = lds[X_STAGE * WS_LANES + i];
+        for (int i = ctid; i < nvec; i += NT) dst[i] = fin4(rows[i]);
+        for (int i = (nvec << 2) + ctid; i < nloc * P.nobs; i += NT) {
+          const float v = lds[X_STAGE * WS_LANES + i];
+          P.obs[(size_t)env0 * P.nobs + i] = guard ? finite_or(v, 0.f) : v;
+        }
       }
     }
   }

@@ -92,7 +92,21 @@ struct Params {
   const float* dr_upper;     // (N,18)   or null
   float* xhit;               // != null: BEZ_FLAG_ALL_GROUND_SHAPES -- scratch for the BEZ_NXPT extra ground-point records, [(point * 8 + k) * n + env]
   unsigned long long* stamps; // diagnostic builds only (-DBEZ_WS_STAMPS): s_memtime per role / phase of workgroup 0
+  int64_t* nonfinite;        // (N) trips of the non-finite guard per env (BEZ_FLAG_NONFINITE_GUARD): written by the env's owning thread only
+  unsigned long long* health; // the sim's health word (BEZ_HEALTH_*): atomicOr on the cold paths only
 };
+// the non-finite guard (BEZ_FLAG_NONFINITE_GUARD) is on for this launch
+BEZ_DEV bool guard_on(const Params& P) { return (P.flags & BEZ_FLAG_NONFINITE_GUARD) != 0u; }
+// NaN or +-infinity, as a class test (v_cmp_class_f32: sNaN | qNaN | -inf | +inf).  The guard assumes the default compiler flags: with
+// -ffinite-math-only (BEZ_HIPCC_FLAGS) the compiler may assume no value is NaN or infinite and fold this test, like isfinite(), away.
+BEZ_DEV bool nonfinite(float v) { return __builtin_amdgcn_class(v, 0x207); }
+BEZ_DEV float finite_or(float v, float r) { return nonfinite(v) ? r : v; }
+// the trip's bookkeeping (cold path): the env's counter (its one owning thread, plain load / store) and the sim's health word
+BEZ_DEV void guard_trip(const Params& P, int e) {
+  P.nonfinite[e] = P.nonfinite[e] + 1;
+  atomicOr(P.health, (unsigned long long)BEZ_HEALTH_NONFINITE);
+}
+
 // the goal an env reset by this launch receives (bez_walk / bez_orient)
 BEZ_DEV float reset_goal(const Params& P, int k) { return P.goal_dev ? P.goal_dev[k] : P.goal_draw[k]; }
 
@@ -176,6 +190,39 @@ BEZ_DEV void store_state(float* __restrict__ s, int n, int e, const EnvState& S)
   st(F_BALL_POS, S.ball_pos.x); st(F_BALL_POS + 1, S.ball_pos.y); st(F_BALL_POS + 2, S.ball_pos.z);
   st(F_BALL_LIN, S.ball_lin.x); st(F_BALL_LIN + 1, S.ball_lin.y); st(F_BALL_LIN + 2, S.ball_lin.z);
   st(F_BALL_ANG, S.ball_ang.x); st(F_BALL_ANG + 1, S.ball_ang.y); st(F_BALL_ANG + 2, S.ball_ang.z);
+}
+
+// ---- the non-finite guard (BEZ_FLAG_NONFINITE_GUARD) on a lane's working copy: root 13, ball 13, q 18, qd 18
+BEZ_DEV bool v3_nonfinite(V3 v) { return nonfinite(v.x) | nonfinite(v.y) | nonfinite(v.z); }
+BEZ_DEV bool state_nonfinite(const EnvState& S) {
+  bool bad = v3_nonfinite(S.root_pos) | v3_nonfinite(S.root_lin) | v3_nonfinite(S.root_ang);
+  bad |= v3_nonfinite(S.ball_pos) | v3_nonfinite(S.ball_lin) | v3_nonfinite(S.ball_ang);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) bad |= nonfinite(S.rq[i]) | nonfinite(S.bq[i]);
+#pragma unroll
+  for (int j = 0; j < BEZ_ND; ++j) bad |= nonfinite(S.q[j]) | nonfinite(S.qd[j]);
+  return bad;
+}
+// each non-finite value -> its replacement: poses from the init pose (bez_init / ball_init), joints at the default position, velocities 0
+BEZ_DEV V3 v3_finite_or(V3 v, float x, float y, float z) { return mk(finite_or(v.x, x), finite_or(v.y, y), finite_or(v.z, z)); }
+BEZ_DEV void state_sanitize(const Params& P, EnvState& S) {
+  S.root_pos = v3_finite_or(S.root_pos, P.bez_init[0], P.bez_init[1], P.bez_init[2]);
+  S.ball_pos = v3_finite_or(S.ball_pos, P.ball_init[0], P.ball_init[1], P.ball_init[2]);
+  S.root_lin = v3_finite_or(S.root_lin, 0.f, 0.f, 0.f); S.root_ang = v3_finite_or(S.root_ang, 0.f, 0.f, 0.f);
+  S.ball_lin = v3_finite_or(S.ball_lin, 0.f, 0.f, 0.f); S.ball_ang = v3_finite_or(S.ball_ang, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { S.rq[i] = finite_or(S.rq[i], P.bez_init[3 + i]); S.bq[i] = finite_or(S.bq[i], P.ball_init[3 + i]); }
+#pragma unroll
+  for (int j = 0; j < BEZ_ND; ++j) { S.q[j] = finite_or(S.q[j], (float)BEZ_DOF_DEFAULT[j]); S.qd[j] = finite_or(S.qd[j], 0.f); }
+}
+
+// the stored root / ball state of env e, each non-finite value rewritten as its replacement (cold path of the 8-role-wave kernels)
+BEZ_DEV void root_ball_sanitize(const Params& P, float* st, int n, int e) {
+  auto fix = [&](int f, float r) { float* p = st + (size_t)f * n + e; if (nonfinite(*p)) *p = r; };
+#pragma unroll
+  for (int k = 0; k < 7; ++k) { fix(F_ROOT_POS + k, P.bez_init[k]); fix(F_BALL_POS + k, P.ball_init[k]); }   // pos3 quat4 each
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { fix(F_ROOT_LIN + k, 0.f); fix(F_BALL_LIN + k, 0.f); }                     // lin3 ang3 each
 }
 
 // Per-env model parameters that domain randomisation may change
@@ -1194,6 +1241,7 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(Params P) {
   CfOut co;
   co.base = st + (size_t)F_CF * n + e; co.n = n;
   co.lf = co.rf = mk(0, 0, 0);
+  bool tripped = false;   // POST: the non-finite guard tripped this env
   if (SIM) {
     EnvDyn D;
     D.mu = P.mu; D.g = mk(P.g[0], P.g[1], P.g[2]);
@@ -1262,13 +1310,29 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(Params P) {
       }
     }
     env_observe_reward(P, S, co, prev, feet, obs, rew, reset, progress, goal_x, goal_y, CL ? cleats : nullptr);
+    // the non-finite guard: the state after the physics and the pending reset, and the reward
+    const bool guard = !P.obs_only && guard_on(P);
+    if (guard && (state_nonfinite(S) || nonfinite(rew))) {   // cold: the stores below and behind this block write the replacements
+      tripped = true;
+      state_sanitize(P, S);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) prev[i] = finite_or(prev[i], 0.f);
+#pragma unroll
+      for (int j = 0; j < BEZ_ND; ++j) target[j] = finite_or(target[j], (float)BEZ_DOF_DEFAULT[j]);
+      rew = 0.f; reset = 1;
+      guard_trip(P, e);
+    }
 #pragma unroll
     for (int i = 0; i < 3; ++i) st[(size_t)(F_PREV + i) * n + e] = prev[i];
 #pragma unroll
     for (int i = 0; i < 8; ++i) st[(size_t)(F_FEET + i) * n + e] = feet[i];
 #pragma unroll
     for (int i = 0; i < BEZ_NUM_OBS; ++i)
-      if (i < P.nobs) P.obs[(size_t)e * P.nobs + i] = P.obs_noise ? obs_with_noise(P, (long long)e * P.nobs + i, obs[i]) : obs[i];
+      if (i < P.nobs) {
+        float v = P.obs_noise ? obs_with_noise(P, (long long)e * P.nobs + i, obs[i]) : obs[i];
+        if (guard) v = finite_or(v, 0.f);
+        P.obs[(size_t)e * P.nobs + i] = v;
+      }
     P.rew[e] = rew; P.reset[e] = reset; P.progress[e] = progress;
     if (DR && P.dr_snap && e == 0) {
       const unsigned long long f = P.dr_state->frame;
@@ -1283,6 +1347,9 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(Params P) {
     }
 #pragma unroll
     for (int j = 0; j < BEZ_ND; ++j) st[(size_t)(F_TARGET + j) * n + e] = target[j];
+  }
+  if (tripped) {   // the contact-force rows this thread wrote during the substeps / above: non-finite entries -> 0
+    for (int k = 0; k < BEZ_NBE_MAX * 3; ++k) co.base[(size_t)k * n] = finite_or(co.base[(size_t)k * n], 0.f);
   }
 }
 

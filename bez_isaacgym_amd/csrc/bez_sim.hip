@@ -73,6 +73,8 @@ struct BezSim {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   unsigned long long* stamps = nullptr;  // diagnostic builds only
   float* xhit = nullptr;                 // BEZ_FLAG_ALL_GROUND_SHAPES: records of the extra ground points (BEZ_NXPT x 8 floats per env)
+  int64_t* nonfinite = nullptr;          // (N) trips of the non-finite guard per env (BEZ_TENSOR_NONFINITE_COUNT)
+  unsigned long long* health = nullptr;  // BEZ_HEALTH_* bits (BEZ_TENSOR_HEALTH)
 };
 
 namespace {
@@ -215,6 +217,7 @@ Params make_params(const BezSim* s, const float* actions) {
   P.dr_lower = s->dr[BEZ_PARAM_DOF_LOWER]; P.dr_upper = s->dr[BEZ_PARAM_DOF_UPPER];
   P.dr_pack = s->dr_pack; P.dr_gravity_uniform = (s->dr[BEZ_PARAM_GRAVITY] && s->gravity_uniform) ? 1 : 0;
   P.stamps = s->stamps;
+  P.nonfinite = s->nonfinite; P.health = s->health;
   P.xhit = (c.flags & BEZ_FLAG_ALL_GROUND_SHAPES) ? s->xhit : nullptr;
   return P;
 }
@@ -465,7 +468,7 @@ int bez_sim_default_config(BezSimConfig* c, int32_t num_envs) {
   c->limit_k = 200.0f; c->limit_d = 2.0f; c->jfric_veps = 0.1f; c->ball_ang_damping = 0.5f;
   c->self_kn = 2.0e4f; c->self_cn = 5.0f;
   c->ball_kn = 0.0f; c->ball_cn = 0.0f;
-  c->flags = BEZ_FLAG_IMU_PREV_ALIAS;
+  c->flags = BEZ_FLAG_IMU_PREV_ALIAS | BEZ_FLAG_NONFINITE_GUARD;
   c->seed = 42;
   c->env_id_offset = 0;
   return 0;
@@ -490,7 +493,8 @@ int bez_sim_destroy(BezSim* s) {
   if (!s) return 0;
   (void)hipSetDevice(s->device);
   void* bufs[] = {s->state, s->obs, s->rew, s->reset, s->progress, s->timeout, s->episode, s->root_states, s->dof_state,
-                  s->rigid_body, s->contact, s->targets_aos, s->prev_aos, s->feet_aos, s->goal_aos, s->goal_draw_dev, s->post_calls_dev, s->randomize, s->dr_state, s->dr_snap, s->dr_pack, s->xhit};
+                  s->rigid_body, s->contact, s->targets_aos, s->prev_aos, s->feet_aos, s->goal_aos, s->goal_draw_dev, s->post_calls_dev, s->randomize, s->dr_state, s->dr_snap, s->dr_pack, s->xhit,
+                  s->nonfinite, s->health};
   for (void* b : bufs) if (b) (void)hipFree(b);
   for (int i = 0; i < BEZ_PARAM_COUNT; ++i) if (s->dr[i]) (void)hipFree(s->dr[i]);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
@@ -538,7 +542,8 @@ int bez_sim_create(const BezSimConfig* cfg, int device_id, BezSim** out) {
       {(void**)&s->targets_aos, n * BEZ_ND * sizeof(float)}, {(void**)&s->prev_aos, n * 3 * sizeof(float)},
       {(void**)&s->feet_aos, n * 8 * sizeof(float)}, {(void**)&s->goal_aos, n * 2 * sizeof(float)},
       {(void**)&s->goal_draw_dev, 2 * sizeof(float)}, {(void**)&s->post_calls_dev, sizeof(unsigned long long)},
-      {(void**)&s->randomize, n * sizeof(int64_t)}, {(void**)&s->dr_state, sizeof(DrState)}, {(void**)&s->dr_snap, sizeof(DrSnap)}};
+      {(void**)&s->randomize, n * sizeof(int64_t)}, {(void**)&s->dr_state, sizeof(DrState)}, {(void**)&s->dr_snap, sizeof(DrSnap)},
+      {(void**)&s->nonfinite, n * sizeof(int64_t)}, {(void**)&s->health, sizeof(unsigned long long)}};
   for (auto& a : allocs) {
     e = hipMalloc(a.p, a.bytes);
     if (e == hipSuccess) e = hipMemset(*a.p, 0, a.bytes);
@@ -582,6 +587,8 @@ int bez_sim_get_tensor(BezSim* s, int which, void** dev_ptr, int64_t shape[3], i
     case BEZ_TENSOR_GOAL: *dev_ptr = s->goal_aos; shape[0] = n; shape[1] = 2; *ndim = 2; break;
     case BEZ_TENSOR_RANDOMIZE_BUF: *dev_ptr = s->randomize; shape[0] = n; *ndim = 1; *dtype = BEZ_DTYPE_I64; break;
     case BEZ_TENSOR_DR_NOISE: *dev_ptr = s->dr_state->noise; shape[0] = 4; *ndim = 1; break;
+    case BEZ_TENSOR_NONFINITE_COUNT: *dev_ptr = s->nonfinite; shape[0] = n; *ndim = 1; *dtype = BEZ_DTYPE_I64; break;
+    case BEZ_TENSOR_HEALTH: *dev_ptr = s->health; shape[0] = 1; *ndim = 1; *dtype = BEZ_DTYPE_I64; break;
     default: return fail(s, -1, "bez_sim_get_tensor: unknown tensor id");
   }
   return 0;
@@ -604,7 +611,8 @@ int bez_sim_refresh_tensor(BezSim* s, int which, void* stream_) {
     case BEZ_TENSOR_PREV_LIN_VEL: hipLaunchKernelGGL(refresh_rows_kernel, blocks((size_t)n * 3), dim3(TB), 0, stream, s->state, s->prev_aos, n, (int)F_PREV, 3); break;
     case BEZ_TENSOR_FEET: hipLaunchKernelGGL(refresh_rows_kernel, blocks((size_t)n * 8), dim3(TB), 0, stream, s->state, s->feet_aos, n, (int)F_FEET, 8); break;
     case BEZ_TENSOR_GOAL: hipLaunchKernelGGL(refresh_rows_kernel, blocks((size_t)n * 2), dim3(TB), 0, stream, s->state, s->goal_aos, n, (int)F_GOAL, 2); break;
-    case BEZ_TENSOR_OBS: case BEZ_TENSOR_REW: case BEZ_TENSOR_RESET: case BEZ_TENSOR_PROGRESS: case BEZ_TENSOR_TIMEOUT: break;  // always live
+    case BEZ_TENSOR_OBS: case BEZ_TENSOR_REW: case BEZ_TENSOR_RESET: case BEZ_TENSOR_PROGRESS: case BEZ_TENSOR_TIMEOUT:
+    case BEZ_TENSOR_NONFINITE_COUNT: case BEZ_TENSOR_HEALTH: break;  // always live
     default: return fail(s, -1, "bez_sim_refresh_tensor: unknown tensor id");
   }
   hipError_t e = hipGetLastError();
@@ -877,6 +885,17 @@ int bez_sim_calibrate(void* buf_dev, uint64_t n_floats, int32_t write, void* str
   if (write) hipLaunchKernelGGL(calib_write_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, (float*)buf_dev, (size_t)n_floats);
   else hipLaunchKernelGGL(calib_read_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, (const float*)buf_dev, (float*)buf_dev, (size_t)n_floats);
   return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int bez_sim_health(BezSim* s, uint64_t* bits, int32_t clear, void* stream_) {
+  if (!s || !bits) return fail(s, -1, "bez_sim_health: null argument");
+  hipStream_t stream = (hipStream_t)stream_;
+  unsigned long long h = 0;
+  HIP_TRY(s, hipMemcpyAsync(&h, s->health, sizeof(h), hipMemcpyDeviceToHost, stream));
+  if (clear) HIP_TRY(s, hipMemsetAsync(s->health, 0, sizeof(h), stream));
+  HIP_TRY(s, hipStreamSynchronize(stream));
+  *bits = (uint64_t)h;
+  return 0;
 }
 
 int bez_sim_seed(BezSim* s, uint64_t seed) { if (!s) return -1; s->cfg.seed = seed; s->dr_prelaunched = false; return 0; }

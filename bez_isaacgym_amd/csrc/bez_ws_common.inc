@@ -206,14 +206,29 @@ BEZ_DEV void ws_pair_publish(float* lds, int side, int seq) {
   lds_word_t* flag = (lds_word_t*)(lds + X_PAIRSEQ * WS_LANES);
   flag[side] = seq;
 }
+// a bounded hand-over wait that gave up: the step goes on with stale words, and says so -- a word in LDS (lane 4 of the X_PAIRSEQ slot,
+// zeroed at kernel entry), turned into BEZ_HEALTH_SPIN_TIMEOUT in the health word by one copy-out thread behind the last barrier
+BEZ_DEV void ws_spin_timeout(const float* lds) { ((lds_word_t*)(lds + X_PAIRSEQ * WS_LANES))[4] = 1; }
+// EXIT_IN_LOOP: where the timeout is noticed -- at the bound inside the loop, or by a second read behind it.  The two compile to the same
+// waits; the cleats kernels keep their register budget with the first, the others with the second (tools/kernel_resources.sh).
+template <bool EXIT_IN_LOOP>
 BEZ_DEV void ws_pair_wait(const float* lds, int side, int seq) {
   lds_word_t* flag = (lds_word_t*)(lds + X_PAIRSEQ * WS_LANES);
   // bounded: a wave that never arrives would be a bug, not a reason to hang the GPU (the bound is ~10^3 times the longest wait seen)
+  if constexpr (EXIT_IN_LOOP) {
 #pragma unroll 1
-  for (int guard = 0; guard < (1 << 16) && flag[1 - side] < seq; ++guard) __builtin_amdgcn_s_sleep(1);
+    for (int guard = 0; flag[1 - side] < seq; ++guard) {
+      if (guard == (1 << 16)) { ws_spin_timeout(lds); break; }
+      __builtin_amdgcn_s_sleep(1);
+    }
+  } else {
+#pragma unroll 1
+    for (int guard = 0; guard < (1 << 16) && flag[1 - side] < seq; ++guard) __builtin_amdgcn_s_sleep(1);
+    if (flag[1 - side] < seq) ws_spin_timeout(lds);   // still missing after the bound
+  }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
-template <int LEN>
+template <int LEN, bool CL>
 BEZ_DEV float ws_chain_self_correction(const Params& P, float* lds, int lane, int side, int seq, P3* p3, SV& pAo) {
   static_assert(LEN == 6, "legs only");
   SV w[LEN];  // all wrenches are fetched up front (one burst of LDS reads): the chain below is serial and would expose each latency
@@ -241,7 +256,7 @@ BEZ_DEV float ws_chain_self_correction(const Params& P, float* lds, int lane, in
   });
   XS(X_SELFSUM + side * 2) = am; XS(X_SELFSUM + side * 2 + 1) = as;
   ws_pair_publish(lds, side, seq);
-  ws_pair_wait(lds, side, seq);
+  ws_pair_wait<CL>(lds, side, seq);
   SelfSums Z;
   Z.am = XS(X_SELFSUM) + XS(X_SELFSUM + 2); Z.as = XS(X_SELFSUM + 1) + XS(X_SELFSUM + 3); Z.f2 = XS(X_SELFF2) + XS(X_SELFF2 + 1);   // (the helper parts' sums of |force|^2)
   const float sc = self_scale(P, Z);
@@ -290,6 +305,7 @@ BEZ_DEV void ws_chain_epilogue(const Params& P, float* lds, int lane, int e, boo
                                float* q, float* qd, float* target) {
   const int n = P.n;
   asm volatile("" : "+v"(e));  // the store addresses below are formed HERE, not hoisted to the kernel entry and carried (64-bit) through the physics
+  bool bad = false;             // the non-finite guard tripped on this role's joints
   if (POST) {
     if (do_reset) {
       const int64_t genv = P.env_off + e;
@@ -325,6 +341,14 @@ BEZ_DEV void ws_chain_epilogue(const Params& P, float* lds, int lane, int e, boo
       float dd = (float)BEZ_DOF_DEFAULT[d] - q[i];
       psum = fmaf(dd, dd, psum);
     });
+    // the non-finite guard: psum is non-finite when a q is (or overflows); the velocities are checked through their sum.  A bad joint
+    // publishes a NaN pose-error share (the root role reads the trip from it behind the last barrier) and takes the cold re-store below.
+    if (guard_on(P)) {
+      float vs = 0.f;
+      static_for<role_ndof(ROLE)>([&](auto I) { vs += qd[decltype(I)::value]; });
+      bad = nonfinite(psum) | nonfinite(vs);
+      if (bad) psum = __builtin_nanf("");
+    }
     XS(X_PSUM + ROLE) = psum;
   }
   if (active) {
@@ -334,6 +358,14 @@ BEZ_DEV void ws_chain_epilogue(const Params& P, float* lds, int lane, int e, boo
       constexpr int d = role_dof(ROLE, i);
       st[(size_t)(F_Q + d) * n + e] = q[i]; st[(size_t)(F_QD + d) * n + e] = qd[i]; st[(size_t)(F_TARGET + d) * n + e] = target[i];
     });
+    if (bad) {   // cold: the non-finite values again, as their replacements (default position, zero velocity); same lane, program order
+      static_for<role_ndof(ROLE)>([&](auto I) {
+        constexpr int i = decltype(I)::value;
+        constexpr int d = role_dof(ROLE, i);
+        if (nonfinite(q[i])) st[(size_t)(F_Q + d) * n + e] = (float)BEZ_DOF_DEFAULT[d];
+        if (nonfinite(qd[i])) st[(size_t)(F_QD + d) * n + e] = 0.f;
+      });
+    }
   }
 }
 

@@ -78,6 +78,7 @@ BEZ_DEV void ws_pkg_wait(const float* lds, int side, int seq) {
   lds_word_t* flag = (lds_word_t*)(lds + X_PAIRSEQ * WS_LANES);
 #pragma unroll 1
   for (int guard = 0; guard < (1 << 16) && flag[2 + side] < seq; ++guard) __builtin_amdgcn_s_sleep(1);
+  if (flag[2 + side] < seq) ws_spin_timeout(lds);   // still missing after the bound (bez_ws_common.inc)
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
 template <int L>
@@ -193,7 +194,7 @@ BEZ_DEV void wq_chain_pass2(const Params& P, const Quad& Q, float* lds, int lane
 }
 
 // ---- the leg<->leg correction (ws_chain_self_correction in the quad form); pAo: the lane's half of the chain's bias
-template <int LEN>
+template <int LEN, bool CL>
 BEZ_DEV float wq_chain_self_correction(const Params& P, const Quad& Q, float* lds, int lane, int side, int seq, P3q* p3, V3& pAo, int slot_bias) {
   static_assert(LEN == 6, "legs only");
   V3 w[LEN];
@@ -218,7 +219,7 @@ BEZ_DEV float wq_chain_self_correction(const Params& P, const Quad& Q, float* ld
   });
   XS(X_SELFSUM + side * 2) = am; XS(X_SELFSUM + side * 2 + 1) = as;
   ws_pair_publish(lds, side, seq);
-  ws_pair_wait(lds, side, seq);
+  ws_pair_wait<CL>(lds, side, seq);
   SelfSums Z;
   Z.am = XS(X_SELFSUM) + XS(X_SELFSUM + 2); Z.as = XS(X_SELFSUM + 1) + XS(X_SELFSUM + 3); Z.f2 = XS(X_SELFF2) + XS(X_SELFF2 + 1);
   const float sc = self_scale(P, Z);

@@ -418,6 +418,12 @@ class A2CAgent:
             self.lr_t.fill_(self.last_lr)
         else:
             self.lr_t = torch.tensor(self.last_lr, device=self.device, dtype=torch.float32)
+        # the simulator's non-finite guard (abi.FLAG_NONFINITE_GUARD): its per-env trip counters and health word, folded into the same
+        # epoch report (slots _NF_SLOT / _HEALTH_SLOT, written by two small eager launches behind the update: no host sync, graphs unchanged)
+        genv = getattr(vec_env, "env", vec_env)
+        self._nonfinite_buf = getattr(genv, "nonfinite_buf", None)
+        self._health_buf = getattr(genv, "health_buf", None)
+        self._nf_seen = self._nonfinite_buf.sum().reshape(1) if self._nonfinite_buf is not None else None
         # fused + capturable Adam: takes GradScaler's found_inf / scale as tensors (no .item()), so scaler.step() is graph-safe
         self.optimizer = torch.optim.Adam(self.model.parameters(), lr=self.lr_t if on_gpu else self.last_lr, eps=1e-8,
                                           capturable=on_gpu, fused=on_gpu)
@@ -1392,6 +1398,30 @@ class A2CAgent:
             self.game_rewards = [sum(r for _, r, _ in self._ep_hist) / tot]
             self.game_lengths = [sum(l for _, _, l in self._ep_hist) / tot]
 
+    _NF_SLOT, _HEALTH_SLOT = 62, 63   # fp64 words of the epoch report (the KL accumulators end at fp32 12 + mini_epochs)
+
+    def _guard_in_report(self):
+        return self._report is not None and 12 + self.mini_epochs <= 2 * self._NF_SLOT
+
+    def _fold_guard(self):
+        """Device side, at the end of an epoch: the trips of this epoch (increments of the env's counters since the last call) and the
+        health word into the epoch report.  Returns None there; without the packed report: (trips, health) as tensors, or ints without counters."""
+        nf, hw = self._nonfinite_buf, self._health_buf
+        if nf is None:
+            return None if self._guard_in_report() and self.mb is not None else (0, 0)
+        tot = nf.sum().reshape(1)
+        delta = tot - self._nf_seen
+        self._nf_seen.copy_(tot)
+        if self._guard_in_report() and self.mb is not None:
+            self._report[self._NF_SLOT:self._NF_SLOT + 1].copy_(delta)
+            if hw is not None:
+                self._report[self._HEALTH_SLOT:self._HEALTH_SLOT + 1].copy_(hw.reshape(1))
+            return None
+        return delta, (hw.reshape(-1)[0] if hw is not None else torch.zeros((), dtype=torch.int64, device=delta.device))
+
+    def _guard_from_report(self, rep):
+        return (int(rep[self._NF_SLOT]), int(rep[self._HEALTH_SLOT])) if self._guard_in_report() else (0, 0)
+
     def train_epoch(self):
         t0 = time.perf_counter()
         packed = self._report is not None and self.mb is not None and self.ep_stats.data_ptr() == self._report.data_ptr()
@@ -1404,7 +1434,9 @@ class A2CAgent:
             ev[1].record()
             self.run_update()
             ev[2].record()
+            guard = self._fold_guard()
             rep = self._report.cpu()     # the epoch's host sync
+            nf, health = (int(guard[0]), int(guard[1])) if guard is not None else self._guard_from_report(rep)
             f32 = rep.view(torch.float32)
             self.last_lr = float(f32[8])
             kls = f32[12:12 + self.mini_epochs].tolist()
@@ -1419,7 +1451,15 @@ class A2CAgent:
                 torch.cuda.synchronize()
             t_play = time.perf_counter() - t0
             self.run_update()
-            self.last_lr = float(self.lr_t.item())  # the epoch's only other host sync
+            guard = self._fold_guard()
+            if guard is not None and self.device.type == "cuda" and self._nonfinite_buf is not None:
+                # the guard's two numbers ride on the learning-rate read: still the epoch's only other host sync
+                v = torch.cat([self.lr_t.reshape(1).double(), guard[0].double().reshape(1).to(self.device),
+                               guard[1].double().reshape(1).to(self.device)]).cpu().tolist()
+                self.last_lr, nf, health = float(v[0]), int(v[1]), int(v[2])
+            else:
+                self.last_lr = float(self.lr_t.item())  # the epoch's only other host sync
+                nf, health = (int(guard[0]), int(guard[1])) if guard is not None else self._guard_from_report(self._report.cpu())
             kls = self.kl_acc.tolist()
             a_l, c_l = (self.loss_acc / (self.mini_epochs * self.num_minibatches)).tolist()
             self._drain_episode_stats()
@@ -1429,7 +1469,7 @@ class A2CAgent:
         self.frame += self.batch_size * self.world
         self._weights_sig = self._weights_signature()   # whatever this epoch's own optimiser steps did to the versions is not "external"
         return dict(play_time=t_play, update_time=t_total - t_play, total_time=t_total, kl=sum(kls) / len(kls),
-                    a_loss=a_l, c_loss=c_l, lr=self.last_lr)
+                    a_loss=a_l, c_loss=c_l, lr=self.last_lr, nonfinite_resets=nf, sim_health=health)
 
     # ---- pipelined epochs: the host reads epoch k's report while epoch k + 1 is already queued.  train_epoch() ends in the epoch's one
     # device-to-host copy and only then launches the next rollout: between the two the GPU waits for the host (wake-up from the copy, the
@@ -1463,6 +1503,7 @@ class A2CAgent:
         self.run_update()
         if timed:
             ev[2].record()
+        st["guard"] = self._fold_guard()   # (None: folded into the report copied below)
         st["host"].copy_(self._report, non_blocking=True)
         self.ep_stats.zero_()            # (stream order: behind the copy, in front of the next rollout's first count)
         st["done"].record()
@@ -1487,6 +1528,8 @@ class A2CAgent:
         kls = f32[12:12 + self.mini_epochs].tolist()
         a_l, c_l = (f32[10:12] / (self.mini_epochs * self.num_minibatches)).tolist()
         self._drain_episode_stats(rep[0:3].tolist(), zero=False)
+        g = st.get("guard")
+        nf, health = (int(g[0]), int(g[1])) if g is not None else self._guard_from_report(rep)
         now = time.perf_counter()
         t_total = now - max(st["t0"], getattr(self, "_pipe_last_report", 0.0))
         self._pipe_last_report = now
@@ -1496,7 +1539,7 @@ class A2CAgent:
             self._play_share = dev_play / max(dev_play + dev_upd, 1e-9)
         t_play = t_total * getattr(self, "_play_share", 0.35)
         return dict(play_time=t_play, update_time=t_total - t_play, total_time=t_total, kl=sum(kls) / len(kls), a_loss=a_l, c_loss=c_l,
-                    lr=self.last_lr, epoch=st["epoch"], frame=st["frame"])
+                    lr=self.last_lr, epoch=st["epoch"], frame=st["frame"], nonfinite_resets=nf, sim_health=health)
 
     def release_env(self):
         """Hands the env back to other consumers: lean stepping off, so env.net_contact_forces / feet / prev_lin_vel are
@@ -1510,15 +1553,16 @@ class A2CAgent:
         except Exception:
             pass
 
-    def train(self, max_epochs=None, log=print):
+    def train(self, max_epochs=None, log=print, on_report=None):
+        """on_report(row): called with every epoch's row on every rank (train.py: the health warning)."""
         if self._lean_env is not None:
             self._lean_env.set_lean(True)  # a second train() after release_env(): the captured rollout graphs step lean
         try:
-            return self._train(max_epochs, log)
+            return self._train(max_epochs, log, on_report)
         finally:
             self.release_env()
 
-    def _train(self, max_epochs=None, log=print):
+    def _train(self, max_epochs=None, log=print, on_report=None):
         self.obs = self.env_reset()
         max_epochs = max_epochs or self.max_epochs
         total_time = 0.0
@@ -1528,6 +1572,8 @@ class A2CAgent:
             nonlocal total_time, won
             total_time += st["total_time"]
             epoch, frame = st.get("epoch", self.epoch_num), st.get("frame", self.frame)
+            if on_report is not None:
+                on_report(st)
             mean_rew = sum(self.game_rewards) / len(self.game_rewards) if self.game_rewards else float("nan")
             if self.rank == 0:
                 fps = self.batch_size * self.world / st["total_time"]

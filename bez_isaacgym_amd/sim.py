@@ -55,6 +55,7 @@ def load_library():
         "bez_sim_set_randomization": (C.c_int, [vp, C.POINTER(abi.BezDrConfig), vp]),
         "bez_sim_add_dr_noise": (C.c_int, [vp, fp, fp, i64, i32, vp]),
         "bez_sim_seed": (C.c_int, [vp, u64]),
+        "bez_sim_health": (C.c_int, [vp, C.POINTER(u64), i32, vp]),
         "bez_sim_calibrate": (C.c_int, [vp, u64, i32, vp]),
         "bez_sim_time_steps": (C.c_int, [vp, fp, i32, vp, C.POINTER(C.c_float)]),
     }
@@ -71,7 +72,7 @@ EXPORTS = ["bez_sim_default_config", "bez_sim_create", "bez_sim_destroy", "bez_s
            "bez_sim_set_net_contact_force_tensor", "bez_sim_set_prev_lin_vel_tensor", "bez_sim_set_goal_tensor", "bez_sim_set_flags",
            "bez_sim_set_obs_calls", "bez_sim_pre_physics", "bez_sim_simulate", "bez_sim_post_physics", "bez_sim_observe_reward", "bez_sim_step",
            "bez_sim_step_many", "bez_sim_reset_indexed", "bez_sim_set_env_params", "bez_sim_get_env_params", "bez_sim_set_randomization", "bez_sim_dr_prelaunch", "bez_sim_dr_step_args", "bez_sim_dr_cancel", "bez_sim_action_noise_source", "bez_sim_add_dr_noise", "bez_sim_seed", "bez_sim_time_steps",
-           "bez_sim_calibrate"]
+           "bez_sim_calibrate", "bez_sim_health"]
 # (the bez_ppo_* entry points of the same library are bound in ppo/fused.py)
 
 
@@ -183,6 +184,18 @@ class BezSim:
 
     def set_flags(self, flags):
         self._check(self.lib.bez_sim_set_flags(self.h, int(flags)))
+
+    # ---- the non-finite guard (abi.FLAG_NONFINITE_GUARD)
+    def health(self, clear=False):
+        """The health word (abi.HEALTH_* bits), read synchronously on the current stream; `clear` zeroes it after the read."""
+        bits = C.c_uint64()
+        self._check(self.lib.bez_sim_health(self.h, C.byref(bits), 1 if clear else 0, self._stream()))
+        return int(bits.value)
+
+    @property
+    def nonfinite_counts(self):
+        """(N,) int64 zero-copy view: how often each env tripped the guard (never cleared by the library; writable)."""
+        return self.tensor(abi.TENSOR_NONFINITE_COUNT)
 
     def set_obs_calls(self, n):
         self._check(self.lib.bez_sim_set_obs_calls(self.h, int(n)))

@@ -132,6 +132,8 @@ class VecTask(Env):
         self.timeout_buf = s.tensor(abi.TENSOR_TIMEOUT)
         self.progress_buf = s.tensor(abi.TENSOR_PROGRESS)
         self.randomize_buf = s.tensor(abi.TENSOR_RANDOMIZE_BUF)
+        self.nonfinite_buf = s.tensor(abi.TENSOR_NONFINITE_COUNT)  # trips of the non-finite guard per env (abi.FLAG_NONFINITE_GUARD)
+        self.health_buf = s.tensor(abi.TENSOR_HEALTH)              # the sim's health word (abi.HEALTH_* bits)
         self.extras = {}
 
     def get_state(self):

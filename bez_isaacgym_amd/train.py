@@ -102,11 +102,25 @@ def launch(argv=None, vec_env_factory=None):
             dist.barrier()
             dist.destroy_process_group()
         return result
-    result = agent.train()
+    result = agent.train(on_report=_health_warning(rank))
     if multi_gpu:
         dist.barrier()
         dist.destroy_process_group()
     return result
+
+
+def _health_warning(rank):
+    """Epoch-row hook: one warning the first time the simulator's health word carries BEZ_HEALTH_SPIN_TIMEOUT (a lost LDS hand-over
+    inside the step kernel: that step's results are suspect)."""
+    from . import abi
+    seen = []
+
+    def hook(row):
+        if not seen and int(row.get("sim_health", 0)) & abi.HEALTH_SPIN_TIMEOUT:
+            seen.append(True)
+            print("WARNING (rank %d): the simulator reported BEZ_HEALTH_SPIN_TIMEOUT: a bounded hand-over wait of the step kernel gave up; "
+                  "the steps involved went on with stale values" % rank)
+    return hook
 
 
 if __name__ == "__main__":

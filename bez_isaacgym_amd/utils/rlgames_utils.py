@@ -76,5 +76,7 @@ class RLGPUAlgoObserver:
             # rlgames_utils.py:150-153: add_scalar('scores/mean', m, frame), ('scores/iter', m, epoch_num), ('scores/time', m, total_time) --
             # one value under three tags that differ by their STEP axis; a line-oriented log keeps (value, step) per tag
             out["scalars"] = {"scores/mean": [mean, row.get("frame")], "scores/iter": [mean, row.get("epoch")], "scores/time": [mean, row.get("time")]}
+        if "nonfinite_resets" in row:   # envs the simulator's non-finite guard reset during the epoch (this rank)
+            out.setdefault("scalars", {})["env/nonfinite_resets"] = [row["nonfinite_resets"], row.get("frame")]
         self.f.write(json.dumps(out) + "\n")
         self.f.flush()

@@ -100,6 +100,25 @@ extern "C" {
                                           rides on the kernel's copy-out, bit-identical to what bez_sim_add_dr_noise(OBS, OBS, 0) adds), \
                                           and that call on the observation tensor becomes a no-op: one launch less per control step */
 
+#define BEZ_FLAG_NONFINITE_GUARD 8192u /* per-env non-finite guard (set by bez_sim_default_config; bez_sim_set_flags may clear it).  Every \
+                                         launch that contains the post-physics bookkeeping (bez_sim_step, bez_sim_step_many, \
+                                         bez_sim_post_physics; not bez_sim_observe_reward) TRIPS an env when, after its physics and any \
+                                         pending reset, its root state, ball state, joint positions / velocities or reward hold a NaN or \
+                                         an infinity.  A tripped env gets rew = 0, reset_buf = 1, nonfinite_count += 1 and \
+                                         BEZ_HEALTH_NONFINITE in the health word; each non-finite stored value is replaced: positions by \
+                                         the init pose (bez_init / ball_init), joint positions and targets by the default joint position, \
+                                         velocities, prev_lin_vel and contact-force rows by 0.  Non-finite observation entries are written \
+                                         as 0.  The next launch steps that finite replacement and then performs the ordinary reset (the \
+                                         trip itself does not advance the episode counter).  Other envs, and every run without a \
+                                         non-finite value, are bit-identical to a run without the flag.  Detection is class tests, plus \
+                                         two sums (the pose error, a chain's joint velocities): a finite value so large \
+                                         that one of them overflows trips too. */
+
+/* Bits of the health word (BEZ_TENSOR_HEALTH, bez_sim_health): set on the device, cleared only by the caller. */
+#define BEZ_HEALTH_NONFINITE 1u    /* an env tripped the non-finite guard since the word was last cleared */
+#define BEZ_HEALTH_SPIN_TIMEOUT 2u /* an LDS hand-over wait of the 8-role-wave kernel gave up after its bound (the step went on with \
+                                      stale words: its results are suspect).  Set whether or not BEZ_FLAG_NONFINITE_GUARD is. */
+
 /* Tasks sharing the robot, the physics and the tensor API; they differ in the post-physics logic (observation tail,
  * reward, reset conditions, goal sampling) and in the ball actor (bez_kick only). */
 #define BEZ_TASK_KICK 0   /* tasks/kick_env.py    54 obs, ball + goal point                              */
@@ -170,7 +189,10 @@ enum BezTensor {
   BEZ_TENSOR_RANDOMIZE_BUF = 13,    /* i64 (N)        randomize_buf vec_task.py:247 (device-side domain randomisation) */
   BEZ_TENSOR_DR_NOISE = 14,         /* f32 (4)        mean / std of the observation noise, mean / std of the action noise as the schedule
                                                       currently has them (vec_task.py:544-618): the caller's noise lambdas read them on the device */
-  BEZ_TENSOR_COUNT = 15
+  BEZ_TENSOR_NONFINITE_COUNT = 15, /* i64 (N)       trips of the non-finite guard per env: 0 at create, never cleared by the library
+                                                      (the view is writable: the caller may zero it) */
+  BEZ_TENSOR_HEALTH = 16,           /* i64 (1)        health word: BEZ_HEALTH_* bits (read outside the hot loop: bez_sim_health) */
+  BEZ_TENSOR_COUNT = 17
 };
 enum BezDtype { BEZ_DTYPE_F32 = 0, BEZ_DTYPE_I64 = 1 };
 
@@ -306,6 +328,11 @@ int bez_sim_observe_reward(BezSim* sim, void* stream);
 int bez_sim_set_goal_tensor(BezSim* sim, const float* goal_dev, void* stream);
 /* number of compute_observations passes already done: only pass 0 differences against prev = zeros (Q1) */
 int bez_sim_set_obs_calls(BezSim* sim, int64_t calls);
+
+/* Reads the health word (BEZ_HEALTH_* bits) into *bits, synchronously on `stream` (work enqueued before on that stream is
+ * included), and clears it when `clear` != 0.  For callers outside the hot loop: the word is also a zero-copy tensor
+ * (BEZ_TENSOR_HEALTH) that a caller can fold into a device-side report of its own. */
+int bez_sim_health(BezSim* sim, uint64_t* bits, int32_t clear, void* stream);
 
 /* Re-keys the reset-noise stream (utils/utils.py:45-70 set_seed). */
 int bez_sim_seed(BezSim* sim, uint64_t seed);
