@@ -96,6 +96,11 @@ constexpr int WS_LDS_FLOATS = X_SLOTS * WS_LANES;
 static_assert(WS_LDS_FLOATS * 4 <= 160 * 1024, "LDS budget");
 static_assert(5 * 27 >= 54 && 5 * 27 >= WS_ACT_STRIDE, "staging fits the aliased block");
 
+// The default kernel of the lane-group form (no per-env parameters, no cleats) moves work off the ends of the step: the action staging onto
+// the roles that load nothing at entry, the root / ball guard tests and the episode counter's load in front of the last barrier
+// (step_kernel_ws8, root_role).  The one-lane form and the DR / cleats kernels keep the earlier order: with it they spill less.
+template <bool DR, bool CL> BEZ_DEV constexpr bool lean_ends() { return WS_SUB == 4 && !DR && !CL; }
+
 // joints (dof index) of the chain-owning roles
 BEZ_DEV constexpr int role_ndof(int role) { return role <= 1 ? 6 : 2; }
 BEZ_DEV constexpr int role_dof(int role, int i) { return role == 0 ? 4 + i : (role == 1 ? 12 + i : (role == 2 ? i : (role == 4 ? 2 + i : 10 + i))); }
@@ -837,14 +842,24 @@ BEZ_DEV void root_role(const Params& P, float* lds, int lane, int e, bool active
       progress = 0; reset = 0;
     }
   }
-  // the non-finite guard, root / ball part: the orientation and spin of the ball are not read behind the last barrier -- tested here, into a
-  // mask (no VGPR across the barrier); the rest is tested there, where the reward keeps it live anyway
+  // the non-finite guard, root / ball part, into a mask (no VGPR across the barrier).  Default kernel: every value is final here -- all of it is
+  // tested now, while the other roles are still busy with their post-physics, and behind the last barrier only the pose-error sum and
+  // the reward are left.  DR / cleats kernels: the orientation and spin of the ball only (the rest is tested behind the barrier, where the
+  // reward keeps it live anyway); the other way round they spill more (tools/kernel_resources.sh).
   bool ball_bad = false;
   if (POST && guard_on(P)) {
     ball_bad = v3_nonfinite(ball_ang);
 #pragma unroll
     for (int i = 0; i < 4; ++i) ball_bad |= nonfinite(bq[i]);
+    if constexpr (lean_ends<DR, CL>()) {
+      ball_bad |= v3_nonfinite(root_pos) | v3_nonfinite(root_lin) | v3_nonfinite(root_ang) | v3_nonfinite(ball_pos) | v3_nonfinite(ball_lin) |
+                  nonfinite(rq[0]) | nonfinite(rq[1]) | nonfinite(rq[2]) | nonfinite(rq[3]);
+    }
   }
+  // default kernel: the episode counter of an env reset here is bumped behind the last barrier (below); its load is issued now, so that its
+  // latency hides behind the state stores and the barrier instead of sitting on the tail (in its own branch there it was a full round trip)
+  uint32_t episode0 = 0u;
+  if constexpr (lean_ends<DR, CL>()) { if (POST && active && new_episode) episode0 = P.episode[e]; }
   if (active) {
 #if BEZ_WS_SUB == 4
     int es = e;
@@ -868,7 +883,7 @@ BEZ_DEV void root_role(const Params& P, float* lds, int lane, int e, bool active
   // The chain roles key their reset draw with P.episode[e] / P.reset[e], loaded before B4 and CONSUMED (hence waited for) before
   // this barrier; ws_barrier() itself does not wait for outstanding global loads (vmcnt), so the two words are only rewritten here,
   // behind the last barrier -- no reliance on the memory pipeline serving another wave's earlier load before this store.
-  if (POST && active && new_episode) P.episode[e] = P.episode[e] + 1;
+  if (POST && active && new_episode) P.episode[e] = (lean_ends<DR, CL>() ? episode0 : P.episode[e]) + 1;
   if (POST) {
     const float pn = (((XS(X_PSUM + 2) + XS(X_PSUM + 4)) + XS(X_PSUM + 5)) + XS(X_PSUM + 0)) + XS(X_PSUM + 1);
     OrnOut orn; orn.ux = orn.uy = orn.gn = orn.ang_goal = 0.f;
@@ -880,8 +895,9 @@ BEZ_DEV void root_role(const Params& P, float* lds, int lane, int e, bool active
     reward_of(P, root_pos, rq, root_lin, root_ang, ball_pos, ball_lin, pn, orn, rew, reset, progress, goal_x, goal_y);
     // the trip: root / ball, any chain role's joints (their pose-error share is NaN then: ws_chain_epilogue), the reward
     if (guard_on(P)) {
-      const bool bad = ball_bad | v3_nonfinite(root_pos) | v3_nonfinite(root_lin) | v3_nonfinite(root_ang) | v3_nonfinite(ball_pos) |
-                       v3_nonfinite(ball_lin) | nonfinite(rq[0]) | nonfinite(rq[1]) | nonfinite(rq[2]) | nonfinite(rq[3]) | nonfinite(pn) | nonfinite(rew);
+      const bool bad = lean_ends<DR, CL>() ? (ball_bad | nonfinite(pn) | nonfinite(rew)) :   // (default kernel: the state was tested before the barrier)
+                       (ball_bad | v3_nonfinite(root_pos) | v3_nonfinite(root_lin) | v3_nonfinite(root_ang) | v3_nonfinite(ball_pos) |
+                        v3_nonfinite(ball_lin) | nonfinite(rq[0]) | nonfinite(rq[1]) | nonfinite(rq[2]) | nonfinite(rq[3]) | nonfinite(pn) | nonfinite(rew));
       if (bad) {   // cold
         rew = 0.f; reset = 1;
         if (active) {
@@ -908,16 +924,34 @@ __global__ __launch_bounds__(WS_BLOCK) void step_kernel_ws8(Params P) {
   const int e = env0 + (valid ? ws_env_of(lane) : 0);  // inactive lanes shadow env0 (loads only; every global store is guarded)
   const bool active = valid && ((lane & (WS_SUB - 1)) == 0);   // the lane that stores its env's results (a quad's lanes hold the same ones)
   WS_STAMP(role, 22);
-  if (PRE) {
-    // coalesced stage of this workgroup's contiguous (nloc,18) action block, transposed to [lane][19]
-    float* act = lds + X_STAGE * WS_LANES;
-    const float* src = P.actions + (size_t)env0 * BEZ_ND;
-    for (int i = tid; i < nloc * BEZ_ND; i += WS_BLOCK) act[(i / BEZ_ND) * WS_ACT_STRIDE + (i % BEZ_ND)] = src[i];
-  }
-  if (tid < 5) reinterpret_cast<int*>(lds + X_PAIRSEQ * WS_LANES)[tid] = 0;   // (published before B0; words 2 / 3: the package hand-over of the lane-group form; word 4: a spin wait timed out)
-  // contact-force rows start from zero: bodies nothing touches are never accumulated into
   constexpr int NROW = (nb_of<CL>() + 1) * 3;  // contact-force rows of this asset (robot bodies + ball)
-  for (int i = tid; i < NROW * WS_LANES; i += WS_BLOCK) lds[X_CF * WS_LANES + i] = 0.f;
+  if constexpr (lean_ends<DR, CL>()) {
+    // The legs and the root role load their state at entry and publish it before B0: they stage nothing, so that their loads are not
+    // queued behind an action load and the LDS store that waits for it.  The five roles that load nothing needed before B0 (2, 4..7:
+    // 320 threads) stage the (nloc,18) action block -- one word each -- and zero the contact-force rows while their load is in flight.
+    if (role == 2 || role >= 4) {
+      constexpr int NH = WS_BLOCK - 3 * 64;
+      static_assert(WS_ENVS * BEZ_ND <= NH, "one action word per staging thread");
+      const int h = tid - (role == 2 ? 2 * 64 : 3 * 64);
+      const bool stage = PRE && h < nloc * BEZ_ND;
+      float a = 0.f;
+      if (stage) a = P.actions[(size_t)env0 * BEZ_ND + h];
+      // contact-force rows start from zero: bodies nothing touches are never accumulated into
+      for (int i = h; i < NROW * WS_LANES; i += NH) lds[X_CF * WS_LANES + i] = 0.f;
+      if (stage) lds[X_STAGE * WS_LANES + (h / BEZ_ND) * WS_ACT_STRIDE + (h % BEZ_ND)] = a;   // transposed to [env][19]
+    }
+    if (tid < 5) reinterpret_cast<int*>(lds + X_PAIRSEQ * WS_LANES)[tid] = 0;   // (published before B0; words 2 / 3: the package hand-over of the lane-group form; word 4: a spin wait timed out)
+  } else {
+    if (PRE) {
+      // coalesced stage of this workgroup's contiguous (nloc,18) action block, transposed to [lane][19]
+      float* act = lds + X_STAGE * WS_LANES;
+      const float* src = P.actions + (size_t)env0 * BEZ_ND;
+      for (int i = tid; i < nloc * BEZ_ND; i += WS_BLOCK) act[(i / BEZ_ND) * WS_ACT_STRIDE + (i % BEZ_ND)] = src[i];
+    }
+    if (tid < 5) reinterpret_cast<int*>(lds + X_PAIRSEQ * WS_LANES)[tid] = 0;   // (as above)
+    // contact-force rows start from zero: bodies nothing touches are never accumulated into
+    for (int i = tid; i < NROW * WS_LANES; i += WS_BLOCK) lds[X_CF * WS_LANES + i] = 0.f;
+  }
   WS_STAMP(role, 18);
 #ifdef BEZ_AB_ONLY_ROLE   // offline diagnostics (tools/role_resources.sh): the register / spill figures of ONE role's code; never launched
   if (BEZ_AB_ONLY_ROLE == 0) leg_role<5, PRE, POST, DR, CL>(P, lds, lane, e, active, 0);

@@ -160,7 +160,12 @@ BEZ_DEV void wq_chain_pass2(const Params& P, const Quad& Q, float* lds, int lane
     constexpr int i = LEN - 1 - decltype(I)::value;
     constexpr int L = FIRST + i;
     if constexpr (PKG) {   // the packages come from the arm role of this side (links 0..3) and from the pair roles (4, 5)
-      if constexpr (i == PKG_LINKS - 1) ws_pkg_wait(lds, side, seq);
+      if constexpr (i == PKG_LINKS - 1) {
+        ws_pkg_wait(lds, side, seq);
+#ifdef BEZ_WS_STAMPS
+        if constexpr (FIRST == 5) WS_STAMP(0, 20);   // the wait is over (left leg, last substep): tools/stamp_probe.py "pass2 pkg wait done"
+#endif
+      }
       blk_add_link_pkg<i, L>(M, pA, PB, side, Q);
     } else {
       blk_add_link(M, LI[i], Q);
