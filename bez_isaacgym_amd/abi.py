@@ -29,6 +29,7 @@ FLAG_ANKLE_STOP = 1024          # scenario harness: calf <-> foot-plate contact 
 FLAG_ALL_GROUND_SHAPES = 2048   # scenario harness: ground contact at every collision shape's corners (same)
 FLAG_FIX_BASE = 4096            # urdfAsset.fixBaseLink: the torso welded to the world
 FLAG_NONFINITE_GUARD = 8192     # per-env non-finite guard of the post-physics (on by default; include/bez_sim.h)
+FLAG_REWARD_TERMS = 16384       # env.debug.rewards: per-env sums of the reward's terms (EPISODE_REWARD_TERMS; off by default)
 HEALTH_NONFINITE = 1            # health word bits (TENSOR_HEALTH, BezSim.health)
 HEALTH_SPIN_TIMEOUT = 2
 TASK_KICK, TASK_WALK, TASK_ORIENT = 0, 1, 2
@@ -37,7 +38,29 @@ TASK_IDS = {"bez_kick": TASK_KICK, "bez_walk": TASK_WALK, "bez_orient": TASK_ORI
 (TENSOR_ROOT_STATE, TENSOR_DOF_STATE, TENSOR_RIGID_BODY_STATE, TENSOR_NET_CONTACT_FORCE, TENSOR_OBS,
  TENSOR_REW, TENSOR_RESET, TENSOR_PROGRESS, TENSOR_TIMEOUT, TENSOR_DOF_TARGET, TENSOR_PREV_LIN_VEL,
  TENSOR_FEET, TENSOR_GOAL, TENSOR_RANDOMIZE_BUF, TENSOR_DR_NOISE, TENSOR_NONFINITE_COUNT, TENSOR_HEALTH, TENSOR_COUNT) = range(18)
-DTYPE_F32, DTYPE_I64 = 0, 1
+DTYPE_F32, DTYPE_I64, DTYPE_I32 = 0, 1, 2
+# episode statistics (include/bez_sim.h BezEpisodeTensor, BezSim.episode_tensor): why episodes end, and the reward's terms
+EPISODE_END_BITS, EPISODE_END_COUNTS, EPISODE_REWARD_TERMS, EPISODE_TENSORS = range(4)
+# cause codes: code k has bit 1 << k in EPISODE_END_BITS and row k in EPISODE_END_COUNTS
+(END_CARRIED, END_FALL, END_OUT_OF_BOUNDS, END_OFF_COURSE, END_GOAL, END_TIMEOUT, END_NONFINITE) = range(7)
+END_CAUSES = 8
+END_NAMES = ("carried", "fall", "out_of_bounds", "off_course", "goal", "timeout", "nonfinite", "reserved")
+# the deciding cause: the last test that fired in the reference's order, per task (CARRIED only when none did; NONFINITE always)
+END_ORDER = {TASK_KICK: (END_FALL, END_OUT_OF_BOUNDS, END_OFF_COURSE, END_GOAL, END_TIMEOUT),
+             TASK_WALK: (END_FALL, END_GOAL, END_OFF_COURSE, END_TIMEOUT),
+             TASK_ORIENT: (END_FALL, END_GOAL, END_OUT_OF_BOUNDS, END_TIMEOUT)}
+REWARD_TERM_SLOTS = 8
+REWARD_TERM_TERMINAL = 5   # the slot that holds a terminating step's reward
+
+
+def end_cause(task, bits):
+    """The deciding cause code of a nonzero EPISODE_END_BITS word (include/bez_sim.h)."""
+    if bits & (1 << END_NONFINITE):
+        return END_NONFINITE
+    for k in reversed(END_ORDER[int(task)]):
+        if bits & (1 << k):
+            return k
+    return END_CARRIED
 (PARAM_FRICTION, PARAM_KP_SCALE, PARAM_KD_SCALE, PARAM_MASS_SCALE, PARAM_GRAVITY, PARAM_DOF_LOWER, PARAM_DOF_UPPER,
  PARAM_COUNT) = range(8)
 PARAM_WIDTH = {PARAM_FRICTION: 1, PARAM_KP_SCALE: 18, PARAM_KD_SCALE: 18, PARAM_MASS_SCALE: 19, PARAM_GRAVITY: 3,
@@ -222,6 +245,8 @@ def config_from_task_cfg(cfg, seed=42, env_id_offset=0, strict_reference_quirks=
     c.flags = FLAG_IMU_PREV_ALIAS if strict_reference_quirks else 0
     if env.get("nonfiniteGuard", True):  # not a key of the reference's yaml: this build's per-env non-finite guard, on unless False
         c.flags |= FLAG_NONFINITE_GUARD
+    if (env.get("debug") or {}).get("rewards", False):  # bez_kick.yaml:125-126 env.debug.rewards: the reward's terms per env (kick_env.py:584-600)
+        c.flags |= FLAG_REWARD_TERMS
     if env.get("asset", {}).get("cleats", False):
         c.flags |= FLAG_CLEATS
     if not env.get("asset", {}).get("stl", True):  # kick_env.py:266-276: soccerbot_box*.urdf

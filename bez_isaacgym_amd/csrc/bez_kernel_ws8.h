@@ -891,22 +891,26 @@ BEZ_DEV void root_role(const Params& P, float* lds, int lane, int e, bool active
       float t6, t7;
       orn = obs_off_orn(P, root_pos, rq, goal_x, goal_y, t6, t7);
     }
-    float rew;
-    reward_of(P, root_pos, rq, root_lin, root_ang, ball_pos, ball_lin, pn, orn, rew, reset, progress, goal_x, goal_y);
+    float rew, terms[5];
+    uint32_t bits;
+    reward_of(P, root_pos, rq, root_lin, root_ang, ball_pos, ball_lin, pn, orn, rew, reset, progress, goal_x, goal_y, bits, terms);
     // the trip: root / ball, any chain role's joints (their pose-error share is NaN then: ws_chain_epilogue), the reward
     if (guard_on(P)) {
       const bool bad = lean_ends<DR, CL>() ? (ball_bad | nonfinite(pn) | nonfinite(rew)) :   // (default kernel: the state was tested before the barrier)
                        (ball_bad | v3_nonfinite(root_pos) | v3_nonfinite(root_lin) | v3_nonfinite(root_ang) | v3_nonfinite(ball_pos) |
                         v3_nonfinite(ball_lin) | nonfinite(rq[0]) | nonfinite(rq[1]) | nonfinite(rq[2]) | nonfinite(rq[3]) | nonfinite(pn) | nonfinite(rew));
       if (bad) {   // cold
-        rew = 0.f; reset = 1;
+        rew = 0.f; reset = 1; bits = 1u << BEZ_END_NONFINITE;
         if (active) {
           guard_trip(P, e);
           root_ball_sanitize(P, st, n, e);   // the stores before the barrier again, non-finite values replaced (same lane, program order)
         }
       }
     }
-    if (active) { P.rew[e] = rew; P.reset[e] = reset; P.progress[e] = progress; P.timeout[e] = timeout; }
+    if (active) {
+      P.rew[e] = rew; P.reset[e] = reset; P.progress[e] = progress; P.timeout[e] = timeout;
+      episode_end_store(P, e, bits, rew, terms, true);   // (stores and no-return atomics only: nothing waited for behind B5)
+    }
   }
   WS_STAMP_ROOT_N(14, 3, 21);
 }

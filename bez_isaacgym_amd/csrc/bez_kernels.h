@@ -94,7 +94,13 @@ struct Params {
   unsigned long long* stamps; // diagnostic builds only (-DBEZ_WS_STAMPS): s_memtime per role / phase of workgroup 0
   int64_t* nonfinite;        // (N) trips of the non-finite guard per env (BEZ_FLAG_NONFINITE_GUARD): written by the env's owning thread only
   unsigned long long* health; // the sim's health word (BEZ_HEALTH_*): atomicOr on the cold paths only
+  // the episode statistics, one allocation (one kernel-argument pointer: the 8-role-wave kernels are short of scalar registers):
+  // (8,N) i64 BEZ_EPISODE_END_COUNTS [cause][env], then (8,N) f32 BEZ_EPISODE_REWARD_TERMS [slot][env], then (N) i32 BEZ_EPISODE_END_BITS
+  unsigned long long* episode_stats;
 };
+BEZ_DEV unsigned long long* end_counts_of(const Params& P) { return P.episode_stats; }
+BEZ_DEV float* reward_terms_of(const Params& P) { return reinterpret_cast<float*>(P.episode_stats + (size_t)BEZ_END_CAUSES * P.n); }
+BEZ_DEV int32_t* end_bits_of(const Params& P) { return reinterpret_cast<int32_t*>(reward_terms_of(P) + (size_t)BEZ_END_CAUSES * P.n); }
 // the non-finite guard (BEZ_FLAG_NONFINITE_GUARD) is on for this launch
 BEZ_DEV bool guard_on(const Params& P) { return (P.flags & BEZ_FLAG_NONFINITE_GUARD) != 0u; }
 // NaN or +-infinity, as a class test (v_cmp_class_f32: sNaN | qNaN | -inf | +inf).  The guard assumes the default compiler flags: with
@@ -105,6 +111,41 @@ BEZ_DEV float finite_or(float v, float r) { return nonfinite(v) ? r : v; }
 BEZ_DEV void guard_trip(const Params& P, int e) {
   P.nonfinite[e] = P.nonfinite[e] + 1;
   atomicOr(P.health, (unsigned long long)BEZ_HEALTH_NONFINITE);
+}
+
+// ---- episode statistics (include/bez_sim.h: BEZ_END_*, BezEpisodeTensor)
+// the deciding cause of a nonzero BEZ_END_* word: the last test, in the task's order, that fired (the one whose reward stands)
+BEZ_DEV int end_cause(int task, uint32_t b) {
+  if (b & (1u << BEZ_END_NONFINITE)) return BEZ_END_NONFINITE;
+  if (b & (1u << BEZ_END_TIMEOUT)) return BEZ_END_TIMEOUT;
+  if (task == BEZ_TASK_KICK) {   // fall, out of bounds, goal angle, goal, timeout
+    if (b & (1u << BEZ_END_GOAL)) return BEZ_END_GOAL;
+    if (b & (1u << BEZ_END_OFF_COURSE)) return BEZ_END_OFF_COURSE;
+    if (b & (1u << BEZ_END_OUT_OF_BOUNDS)) return BEZ_END_OUT_OF_BOUNDS;
+  } else {                       // walk: fall, goal, heading, timeout; orient: fall, goal, drift, timeout
+    const int late = task == BEZ_TASK_WALK ? BEZ_END_OFF_COURSE : BEZ_END_OUT_OF_BOUNDS;
+    if (b & (1u << late)) return late;
+    if (b & (1u << BEZ_END_GOAL)) return BEZ_END_GOAL;
+  }
+  if (b & (1u << BEZ_END_FALL)) return BEZ_END_FALL;
+  return BEZ_END_CARRIED;
+}
+// The env's bits, stored by its owning thread beside rew / reset.  In launches with bookkeeping (`book`): the deciding cause's counter
+// and, with BEZ_FLAG_REWARD_TERMS, the reward's terms (slots 0-4 of `terms` on a step no test ended; the reward in slot 5 on one that
+// ended).  No-return atomics: nothing waits for them, and each slot has one adder per launch (exact integers, deterministic floats).
+BEZ_DEV void episode_end_store(const Params& P, int e, uint32_t bits, float rew, const float* terms, bool book) {
+  end_bits_of(P)[e] = (int32_t)bits;
+  if (!book) return;
+  const size_t n = (size_t)P.n;
+  const bool split = (P.flags & BEZ_FLAG_REWARD_TERMS) != 0u;
+  if (bits) {
+    atomicAdd(end_counts_of(P) + (size_t)end_cause(P.task, bits) * n + e, 1ull);
+    if (split) unsafeAtomicAdd(reward_terms_of(P) + 5 * n + e, rew);
+  } else if (split) {
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+      if (terms[k] != 0.f) unsafeAtomicAdd(reward_terms_of(P) + (size_t)k * n + e, terms[k]);
+  }
 }
 
 // the goal an env reset by this launch receives (bez_walk / bez_orient)
@@ -1130,8 +1171,11 @@ BEZ_DEV void obs_feet(const Params& P, CfOut& co, const float* cleats, float* fe
   for (int i = 0; i < 8; ++i) tail[8 + i] = feet[i];
   tail[16] = P.ball_init[0]; tail[17] = P.ball_init[1];  // constant ball_init (quirk Q5, kick_env.py:776); bez_kick only
 }
+// bits: the BEZ_END_* tests that fired (include/bez_sim.h); terms: slots 0-4 of the reward's split (BEZ_EPISODE_REWARD_TERMS), whose sum
+// is the reward when no test fired
 BEZ_DEV void reward_of(const Params& P, V3 root_pos, const float* rq, V3 v, V3 w, V3 ball_pos, V3 ball_lin, float pn, const OrnOut& o,
-                       float& rew, int64_t& reset, int64_t progress, float goal_x, float goal_y) {
+                       float& rew, int64_t& reset, int64_t progress, float goal_x, float goal_y, uint32_t& bits, float* terms) {
+  bits = reset != 0 ? (1u << BEZ_END_CARRIED) : 0u;
   if (P.task != BEZ_TASK_KICK) {
     // compute_bez_reward of walk_env.py:826-1031 / orient_env.py:843-1018
     const float qx = rq[0], qy = rq[1];
@@ -1146,22 +1190,27 @@ BEZ_DEV void reward_of(const Params& P, V3 root_pos, const float* rq, V3 v, V3 w
       const float vel_height = vfwd * 10.f - (dh + 5.f * (pos_reward * 0.05f));
       near = gn;
       reward = gn < 0.05f ? height_vel_pos : vel_height;
+      terms[0] = 0.f; terms[1] = gn < 0.05f ? 0.f : vfwd * 10.f;
+      terms[4] = gn < 0.05f ? -(pos_reward * 0.05f) : -(5.f * (pos_reward * 0.05f));
     } else {
       const float vel_height = fabsf(ang_goal) * -0.5f - (dh + 0.05f * (pos_reward * 0.05f));
       near = ang_goal;  // signed, as the reference compares it (orient_env.py:935)
       reward = ang_goal < 0.05f ? height_vel_pos : vel_height;
+      terms[0] = ang_goal < 0.05f ? 0.f : fabsf(ang_goal) * -0.5f; terms[1] = 0.f;
+      terms[4] = ang_goal < 0.05f ? -(pos_reward * 0.05f) : -(0.05f * (pos_reward * 0.05f));
     }
-    if (up_proj < 0.7f) { reset = 1; reward = -100.f; }
+    terms[2] = -dh; terms[3] = near < 0.05f ? -(vel_reward * 0.05f) : 0.f;
+    if (up_proj < 0.7f) { reset = 1; reward = -100.f; bits |= 1u << BEZ_END_FALL; }
     const int state = (near < 0.05f) + (pos_reward < 0.15f) + (vel_ang < 0.1f) + (vel_lin < 0.1f);
-    if (state == 4) { reset = 1; reward = 1000.0f - 1000.0f * ((float)progress / (float)P.max_len); }
+    if (state == 4) { reset = 1; reward = 1000.0f - 1000.0f * ((float)progress / (float)P.max_len); bits |= 1u << BEZ_END_GOAL; }
     if (P.task == BEZ_TASK_WALK) {
       const float gnn = sqrtf(goal_x * goal_x + goal_y * goal_y);
-      if (fabsf(atan2f(goal_y / gnn, goal_x / gnn) - atan2f(uy, ux)) > 1.5708f) { reset = 1; reward = -100.f; }
+      if (fabsf(atan2f(goal_y / gnn, goal_x / gnn) - atan2f(uy, ux)) > 1.5708f) { reset = 1; reward = -100.f; bits |= 1u << BEZ_END_OFF_COURSE; }
     } else {
       const float tx = root_pos.x - P.bez_init[0], ty = root_pos.y - P.bez_init[1];
-      if (sqrtf(tx * tx + ty * ty) > 0.3f) { reset = 1; reward = -5.f; }
+      if (sqrtf(tx * tx + ty * ty) > 0.3f) { reset = 1; reward = -5.f; bits |= 1u << BEZ_END_OUT_OF_BOUNDS; }
     }
-    if (progress >= (int64_t)P.max_len) { reset = 1; reward = 0.f; }
+    if (progress >= (int64_t)P.max_len) { reset = 1; reward = 0.f; bits |= 1u << BEZ_END_TIMEOUT; }
     rew = reward;
     return;
   }
@@ -1184,25 +1233,28 @@ BEZ_DEV void reward_of(const Params& P, V3 root_pos, const float* rq, V3 v, V3 w
   float r_after = ball_fwd * 0.1f - height_vel_pos;
   float r_before = ball_fwd * 0.1f + (vel_fwd * 0.05f - height);
   float reward = kicked > 0.3f ? r_after : r_before;
-  if (root_pos.z < 0.275f) { reset = 1; reward = -1.f; }
+  terms[0] = ball_fwd * 0.1f; terms[1] = kicked > 0.3f ? 0.f : vel_fwd * 0.05f; terms[2] = -height;
+  terms[3] = kicked > 0.3f ? -(vel_reward * 0.05f) : 0.f; terms[4] = kicked > 0.3f ? -(pos_reward * 0.05f) : 0.f;
+  if (root_pos.z < 0.275f) { reset = 1; reward = -1.f; bits |= 1u << BEZ_END_FALL; }
   float tx = root_pos.x - P.bez_init[0], ty = root_pos.y - P.bez_init[1];
-  if (sqrtf(tx * tx + ty * ty) > 0.5f) { reset = 1; reward = -1.f; }
-  if (goal_angle_diff > 1.5708f) { reset = 1; reward = -1.f; }
-  if (dgn < 0.05f) { reset = 1; reward = 100.0f - 100.0f * ((float)progress / (float)P.max_len); }
-  if (progress >= (int64_t)P.max_len) { reset = 1; reward = 0.f; }
+  if (sqrtf(tx * tx + ty * ty) > 0.5f) { reset = 1; reward = -1.f; bits |= 1u << BEZ_END_OUT_OF_BOUNDS; }
+  if (goal_angle_diff > 1.5708f) { reset = 1; reward = -1.f; bits |= 1u << BEZ_END_OFF_COURSE; }
+  if (dgn < 0.05f) { reset = 1; reward = 100.0f - 100.0f * ((float)progress / (float)P.max_len); bits |= 1u << BEZ_END_GOAL; }
+  if (progress >= (int64_t)P.max_len) { reset = 1; reward = 0.f; bits |= 1u << BEZ_END_TIMEOUT; }
   rew = reward;
 }
 // the three parts in sequence: writes tail[18] = imu(6) off_orn(2) feet(8) ball_init(2)
 BEZ_DEV void env_observe_core(const Params& P, V3 root_pos, const float* rq, V3 v, V3 w, V3 ball_pos, V3 ball_lin, CfOut& co,
                               float* prev, float* feet, float* tail, float pn, float& rew, int64_t& reset, int64_t progress,
-                              float goal_x, float goal_y, const float* cleats) {
+                              float goal_x, float goal_y, const float* cleats, uint32_t& bits, float* terms) {
   const OrnOut o = obs_imu_orn(P, root_pos, rq, v, w, prev, goal_x, goal_y, tail);
   obs_feet(P, co, cleats, feet, tail);
-  reward_of(P, root_pos, rq, v, w, ball_pos, ball_lin, pn, o, rew, reset, progress, goal_x, goal_y);
+  reward_of(P, root_pos, rq, v, w, ball_pos, ball_lin, pn, o, rew, reset, progress, goal_x, goal_y, bits, terms);
 }
 
 BEZ_DEV void env_observe_reward(const Params& P, const EnvState& S, CfOut& co, float* prev, float* feet, float* obs,
-                                float& rew, int64_t& reset, int64_t progress, float goal_x, float goal_y, const float* cleats) {
+                                float& rew, int64_t& reset, int64_t progress, float goal_x, float goal_y, const float* cleats,
+                                uint32_t& bits, float* terms) {
   float pn = 0.f;
 #pragma unroll
   for (int j = 0; j < BEZ_ND; ++j) {
@@ -1210,7 +1262,7 @@ BEZ_DEV void env_observe_reward(const Params& P, const EnvState& S, CfOut& co, f
     float d = (float)BEZ_DOF_DEFAULT[j] - S.q[j];
     pn = fmaf(d, d, pn);
   }
-  env_observe_core(P, S.root_pos, S.rq, S.root_lin, S.root_ang, S.ball_pos, S.ball_lin, co, prev, feet, obs + 36, pn, rew, reset, progress, goal_x, goal_y, cleats);
+  env_observe_core(P, S.root_pos, S.rq, S.root_lin, S.root_ang, S.ball_pos, S.ball_lin, co, prev, feet, obs + 36, pn, rew, reset, progress, goal_x, goal_y, cleats, bits, terms);
 }
 
 // ---- the fused kernel: PRE (targets) / SIM (substeps) / POST (bookkeeping, reset, obs, reward)
@@ -1309,7 +1361,9 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(Params P) {
         cleats[12 + k] = co.base[(size_t)(BEZ_RCLEAT_BODY_CL * 3 + k) * n];
       }
     }
-    env_observe_reward(P, S, co, prev, feet, obs, rew, reset, progress, goal_x, goal_y, CL ? cleats : nullptr);
+    uint32_t bits;
+    float terms[5];
+    env_observe_reward(P, S, co, prev, feet, obs, rew, reset, progress, goal_x, goal_y, CL ? cleats : nullptr, bits, terms);
     // the non-finite guard: the state after the physics and the pending reset, and the reward
     const bool guard = !P.obs_only && guard_on(P);
     if (guard && (state_nonfinite(S) || nonfinite(rew))) {   // cold: the stores below and behind this block write the replacements
@@ -1319,9 +1373,10 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(Params P) {
       for (int i = 0; i < 3; ++i) prev[i] = finite_or(prev[i], 0.f);
 #pragma unroll
       for (int j = 0; j < BEZ_ND; ++j) target[j] = finite_or(target[j], (float)BEZ_DOF_DEFAULT[j]);
-      rew = 0.f; reset = 1;
+      rew = 0.f; reset = 1; bits = 1u << BEZ_END_NONFINITE;
       guard_trip(P, e);
     }
+    episode_end_store(P, e, bits, rew, terms, !P.obs_only);   // (here, not beside the rew store below: the terms die before the obs stores)
 #pragma unroll
     for (int i = 0; i < 3; ++i) st[(size_t)(F_PREV + i) * n + e] = prev[i];
 #pragma unroll

@@ -75,6 +75,8 @@ struct BezSim {
   float* xhit = nullptr;                 // BEZ_FLAG_ALL_GROUND_SHAPES: records of the extra ground points (BEZ_NXPT x 8 floats per env)
   int64_t* nonfinite = nullptr;          // (N) trips of the non-finite guard per env (BEZ_TENSOR_NONFINITE_COUNT)
   unsigned long long* health = nullptr;  // BEZ_HEALTH_* bits (BEZ_TENSOR_HEALTH)
+  unsigned long long* episode_stats = nullptr;  // one allocation: (8,N) i64 BEZ_EPISODE_END_COUNTS, (8,N) f32 BEZ_EPISODE_REWARD_TERMS,
+                                                // (N) i32 BEZ_EPISODE_END_BITS (bez_kernels.h end_counts_of / reward_terms_of / end_bits_of)
 };
 
 namespace {
@@ -218,6 +220,7 @@ Params make_params(const BezSim* s, const float* actions) {
   P.dr_pack = s->dr_pack; P.dr_gravity_uniform = (s->dr[BEZ_PARAM_GRAVITY] && s->gravity_uniform) ? 1 : 0;
   P.stamps = s->stamps;
   P.nonfinite = s->nonfinite; P.health = s->health;
+  P.episode_stats = s->episode_stats;
   P.xhit = (c.flags & BEZ_FLAG_ALL_GROUND_SHAPES) ? s->xhit : nullptr;
   return P;
 }
@@ -494,7 +497,7 @@ int bez_sim_destroy(BezSim* s) {
   (void)hipSetDevice(s->device);
   void* bufs[] = {s->state, s->obs, s->rew, s->reset, s->progress, s->timeout, s->episode, s->root_states, s->dof_state,
                   s->rigid_body, s->contact, s->targets_aos, s->prev_aos, s->feet_aos, s->goal_aos, s->goal_draw_dev, s->post_calls_dev, s->randomize, s->dr_state, s->dr_snap, s->dr_pack, s->xhit,
-                  s->nonfinite, s->health};
+                  s->nonfinite, s->health, s->episode_stats};
   for (void* b : bufs) if (b) (void)hipFree(b);
   for (int i = 0; i < BEZ_PARAM_COUNT; ++i) if (s->dr[i]) (void)hipFree(s->dr[i]);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
@@ -543,7 +546,8 @@ int bez_sim_create(const BezSimConfig* cfg, int device_id, BezSim** out) {
       {(void**)&s->feet_aos, n * 8 * sizeof(float)}, {(void**)&s->goal_aos, n * 2 * sizeof(float)},
       {(void**)&s->goal_draw_dev, 2 * sizeof(float)}, {(void**)&s->post_calls_dev, sizeof(unsigned long long)},
       {(void**)&s->randomize, n * sizeof(int64_t)}, {(void**)&s->dr_state, sizeof(DrState)}, {(void**)&s->dr_snap, sizeof(DrSnap)},
-      {(void**)&s->nonfinite, n * sizeof(int64_t)}, {(void**)&s->health, sizeof(unsigned long long)}};
+      {(void**)&s->nonfinite, n * sizeof(int64_t)}, {(void**)&s->health, sizeof(unsigned long long)},
+      {(void**)&s->episode_stats, BEZ_END_CAUSES * n * (sizeof(int64_t) + sizeof(float)) + n * sizeof(int32_t)}};
   for (auto& a : allocs) {
     e = hipMalloc(a.p, a.bytes);
     if (e == hipSuccess) e = hipMemset(*a.p, 0, a.bytes);
@@ -590,6 +594,19 @@ int bez_sim_get_tensor(BezSim* s, int which, void** dev_ptr, int64_t shape[3], i
     case BEZ_TENSOR_NONFINITE_COUNT: *dev_ptr = s->nonfinite; shape[0] = n; *ndim = 1; *dtype = BEZ_DTYPE_I64; break;
     case BEZ_TENSOR_HEALTH: *dev_ptr = s->health; shape[0] = 1; *ndim = 1; *dtype = BEZ_DTYPE_I64; break;
     default: return fail(s, -1, "bez_sim_get_tensor: unknown tensor id");
+  }
+  return 0;
+}
+
+int bez_sim_get_episode_tensor(BezSim* s, int which, void** dev_ptr, int64_t shape[3], int* ndim, int* dtype) {
+  if (!s || !dev_ptr || !shape || !ndim || !dtype) return fail(s, -1, "bez_sim_get_episode_tensor: null argument");
+  const int64_t n = s->n;
+  shape[0] = shape[1] = shape[2] = 0;
+  switch (which) {   // (always live: the step kernels write them in place, there is nothing to refresh)
+    case BEZ_EPISODE_END_COUNTS: *dev_ptr = s->episode_stats; shape[0] = BEZ_END_CAUSES; shape[1] = n; *ndim = 2; *dtype = BEZ_DTYPE_I64; break;
+    case BEZ_EPISODE_REWARD_TERMS: *dev_ptr = s->episode_stats + BEZ_END_CAUSES * n; shape[0] = BEZ_END_CAUSES; shape[1] = n; *ndim = 2; *dtype = BEZ_DTYPE_F32; break;
+    case BEZ_EPISODE_END_BITS: *dev_ptr = (float*)(s->episode_stats + BEZ_END_CAUSES * n) + BEZ_END_CAUSES * n; shape[0] = n; *ndim = 1; *dtype = BEZ_DTYPE_I32; break;
+    default: return fail(s, -1, "bez_sim_get_episode_tensor: unknown tensor id");
   }
   return 0;
 }

@@ -27,6 +27,8 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from .. import abi
+
 
 # measurement only: BEZ_PPO_MEASURE_NO_COLLECTIVE=1 leaves the per-step all-reduce call out of the segmented update, to separate what
 # the graph boundaries cost from what the collective call costs on the 1-GPU box.  Never set it in a real data-parallel run.
@@ -424,6 +426,11 @@ class A2CAgent:
         self._nonfinite_buf = getattr(genv, "nonfinite_buf", None)
         self._health_buf = getattr(genv, "health_buf", None)
         self._nf_seen = self._nonfinite_buf.sum().reshape(1) if self._nonfinite_buf is not None else None
+        # why episodes end (abi.END_*): the env's per-cause counters and, with env.debug.rewards, its reward-term sums, folded into the same
+        # report (slots _ENDS_SLOT.. / _TERMS_SLOT..) the same way
+        self._end_counts = getattr(genv, "episode_end_counts", None)
+        self._terms_buf = getattr(genv, "reward_terms_buf", None) if getattr(genv, "reward_terms_on", False) else None
+        self._end_seen = self._end_counts.sum(1) if self._end_counts is not None else None
         # fused + capturable Adam: takes GradScaler's found_inf / scale as tensors (no .item()), so scaler.step() is graph-safe
         self.optimizer = torch.optim.Adam(self.model.parameters(), lr=self.lr_t if on_gpu else self.last_lr, eps=1e-8,
                                           capturable=on_gpu, fused=on_gpu)
@@ -543,6 +550,8 @@ class A2CAgent:
 
     def env_reset(self):
         obs = self.vec_env.reset()["obs"].to(self.device)
+        if self._end_counts is not None:   # episodes ended outside the epochs (the reset itself) are no epoch's
+            self._end_seen.copy_(self._end_counts.sum(1))
         if self.obs is None or self.obs.shape != obs.shape:
             self.obs = obs.clone()
         else:
@@ -1422,6 +1431,45 @@ class A2CAgent:
     def _guard_from_report(self, rep):
         return (int(rep[self._NF_SLOT]), int(rep[self._HEALTH_SLOT])) if self._guard_in_report() else (0, 0)
 
+    _ENDS_SLOT, _TERMS_SLOT = 46, 54   # fp64 words 46-53: ended episodes per cause, 54-61: reward-term sums (below the guard's 62-63)
+
+    def _ends_in_report(self):
+        return self._report is not None and self.mb is not None and 12 + self.mini_epochs <= 2 * self._ENDS_SLOT
+
+    def _fold_episode_stats(self):
+        """Device side, at the end of an epoch: the episodes that ended during it per deciding cause (increments of the env's counters since
+        the last call) and, with env.debug.rewards, the sums of the reward's terms (the env's buffer is zeroed behind the read).  Returns
+        None where they went into the epoch report; else one (16,) fp64 tensor [8 cause deltas, 8 term sums], or None without counters."""
+        cnt = self._end_counts
+        if cnt is None:
+            return None
+        packed = self._ends_in_report()
+        if packed:
+            out = self._report[self._ENDS_SLOT:self._TERMS_SLOT + abi.END_CAUSES]
+        else:
+            out = torch.zeros(2 * abi.END_CAUSES, dtype=torch.float64, device=cnt.device)
+        tot = cnt.sum(1)
+        torch.sub(tot, self._end_seen, out=out[:abi.END_CAUSES])
+        self._end_seen.copy_(tot)
+        if self._terms_buf is not None:
+            torch.sum(self._terms_buf, 1, dtype=torch.float64, out=out[abi.END_CAUSES:])
+            self._terms_buf.zero_()
+        return None if packed else out
+
+    def _episode_stats_row(self, v):
+        """The epoch row's entries from the 16 host values of _fold_episode_stats (None: no counters): episode_ends {cause: count} and,
+        with env.debug.rewards, reward_terms {slot: mean per env-step}.  Per rank, like nonfinite_resets."""
+        if v is None or self._end_counts is None:
+            return {}
+        row = dict(episode_ends={abi.END_NAMES[k]: int(round(v[k])) for k in range(abi.END_CAUSES - 1)})
+        if self._terms_buf is not None:
+            steps = max(self.batch_size, 1)
+            row["reward_terms"] = {k: v[abi.END_CAUSES + k] / steps for k in range(abi.REWARD_TERM_SLOTS)}
+        return row
+
+    def _ends_from_report(self, rep):
+        return rep[self._ENDS_SLOT:self._TERMS_SLOT + abi.END_CAUSES].tolist() if self._end_counts is not None and self._ends_in_report() else None
+
     def train_epoch(self):
         t0 = time.perf_counter()
         packed = self._report is not None and self.mb is not None and self.ep_stats.data_ptr() == self._report.data_ptr()
@@ -1435,8 +1483,10 @@ class A2CAgent:
             self.run_update()
             ev[2].record()
             guard = self._fold_guard()
+            ends = self._fold_episode_stats()
             rep = self._report.cpu()     # the epoch's host sync
             nf, health = (int(guard[0]), int(guard[1])) if guard is not None else self._guard_from_report(rep)
+            ends = self._ends_from_report(rep) if ends is None else ends.tolist()
             f32 = rep.view(torch.float32)
             self.last_lr = float(f32[8])
             kls = f32[12:12 + self.mini_epochs].tolist()
@@ -1452,14 +1502,22 @@ class A2CAgent:
             t_play = time.perf_counter() - t0
             self.run_update()
             guard = self._fold_guard()
+            ends = self._fold_episode_stats()
             if guard is not None and self.device.type == "cuda" and self._nonfinite_buf is not None:
-                # the guard's two numbers ride on the learning-rate read: still the epoch's only other host sync
+                # the guard's two numbers and the episode statistics ride on the learning-rate read: still the epoch's only other host sync
                 v = torch.cat([self.lr_t.reshape(1).double(), guard[0].double().reshape(1).to(self.device),
-                               guard[1].double().reshape(1).to(self.device)]).cpu().tolist()
+                               guard[1].double().reshape(1).to(self.device)] + ([ends] if ends is not None else [])).cpu().tolist()
                 self.last_lr, nf, health = float(v[0]), int(v[1]), int(v[2])
+                ends = v[3:] if ends is not None else None
             else:
                 self.last_lr = float(self.lr_t.item())  # the epoch's only other host sync
-                nf, health = (int(guard[0]), int(guard[1])) if guard is not None else self._guard_from_report(self._report.cpu())
+                if guard is not None:
+                    nf, health = int(guard[0]), int(guard[1])
+                    ends = ends.tolist() if ends is not None else None
+                else:
+                    rep = self._report.cpu()
+                    nf, health = self._guard_from_report(rep)
+                    ends = self._ends_from_report(rep) if ends is None else ends.tolist()
             kls = self.kl_acc.tolist()
             a_l, c_l = (self.loss_acc / (self.mini_epochs * self.num_minibatches)).tolist()
             self._drain_episode_stats()
@@ -1469,7 +1527,7 @@ class A2CAgent:
         self.frame += self.batch_size * self.world
         self._weights_sig = self._weights_signature()   # whatever this epoch's own optimiser steps did to the versions is not "external"
         return dict(play_time=t_play, update_time=t_total - t_play, total_time=t_total, kl=sum(kls) / len(kls),
-                    a_loss=a_l, c_loss=c_l, lr=self.last_lr, nonfinite_resets=nf, sim_health=health)
+                    a_loss=a_l, c_loss=c_l, lr=self.last_lr, nonfinite_resets=nf, sim_health=health, **self._episode_stats_row(ends))
 
     # ---- pipelined epochs: the host reads epoch k's report while epoch k + 1 is already queued.  train_epoch() ends in the epoch's one
     # device-to-host copy and only then launches the next rollout: between the two the GPU waits for the host (wake-up from the copy, the
@@ -1504,6 +1562,7 @@ class A2CAgent:
         if timed:
             ev[2].record()
         st["guard"] = self._fold_guard()   # (None: folded into the report copied below)
+        st["ends"] = self._fold_episode_stats()   # (same)
         st["host"].copy_(self._report, non_blocking=True)
         self.ep_stats.zero_()            # (stream order: behind the copy, in front of the next rollout's first count)
         st["done"].record()
@@ -1530,6 +1589,8 @@ class A2CAgent:
         self._drain_episode_stats(rep[0:3].tolist(), zero=False)
         g = st.get("guard")
         nf, health = (int(g[0]), int(g[1])) if g is not None else self._guard_from_report(rep)
+        ends = st.get("ends")
+        ends = self._ends_from_report(rep) if ends is None else ends.tolist()
         now = time.perf_counter()
         t_total = now - max(st["t0"], getattr(self, "_pipe_last_report", 0.0))
         self._pipe_last_report = now
@@ -1539,7 +1600,7 @@ class A2CAgent:
             self._play_share = dev_play / max(dev_play + dev_upd, 1e-9)
         t_play = t_total * getattr(self, "_play_share", 0.35)
         return dict(play_time=t_play, update_time=t_total - t_play, total_time=t_total, kl=sum(kls) / len(kls), a_loss=a_l, c_loss=c_l,
-                    lr=self.last_lr, epoch=st["epoch"], frame=st["frame"], nonfinite_resets=nf, sim_health=health)
+                    lr=self.last_lr, epoch=st["epoch"], frame=st["frame"], nonfinite_resets=nf, sim_health=health, **self._episode_stats_row(ends))
 
     def release_env(self):
         """Hands the env back to other consumers: lean stepping off, so env.net_contact_forces / feet / prev_lin_vel are

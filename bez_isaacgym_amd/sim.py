@@ -34,6 +34,7 @@ def load_library():
         "bez_sim_last_error": (C.c_char_p, [vp]),
         "bez_sim_get_tensor": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "bez_sim_refresh_tensor": (C.c_int, [vp, C.c_int, vp]),
+        "bez_sim_get_episode_tensor": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "bez_sim_set_actor_root_state_tensor_indexed": (C.c_int, [vp, fp, vp, i32, vp]),
         "bez_sim_set_dof_state_tensor_indexed": (C.c_int, [vp, fp, vp, i32, vp]),
         "bez_sim_set_dof_position_target_tensor": (C.c_int, [vp, fp, vp]),
@@ -72,7 +73,7 @@ EXPORTS = ["bez_sim_default_config", "bez_sim_create", "bez_sim_destroy", "bez_s
            "bez_sim_set_net_contact_force_tensor", "bez_sim_set_prev_lin_vel_tensor", "bez_sim_set_goal_tensor", "bez_sim_set_flags",
            "bez_sim_set_obs_calls", "bez_sim_pre_physics", "bez_sim_simulate", "bez_sim_post_physics", "bez_sim_observe_reward", "bez_sim_step",
            "bez_sim_step_many", "bez_sim_reset_indexed", "bez_sim_set_env_params", "bez_sim_get_env_params", "bez_sim_set_randomization", "bez_sim_dr_prelaunch", "bez_sim_dr_step_args", "bez_sim_dr_cancel", "bez_sim_action_noise_source", "bez_sim_add_dr_noise", "bez_sim_seed", "bez_sim_time_steps",
-           "bez_sim_calibrate", "bez_sim_health"]
+           "bez_sim_calibrate", "bez_sim_health", "bez_sim_get_episode_tensor"]
 # (the bez_ppo_* entry points of the same library are bound in ppo/fused.py)
 
 
@@ -135,18 +136,26 @@ class BezSim:
             raise BezSimError("expected %d elements, got %d" % (numel, t.numel()))
         return C.c_void_p(t.data_ptr())
 
-    def tensor(self, which):
-        """Zero-copy torch view of a sim-owned buffer (gymtorch.wrap_tensor)."""
-        if which not in self._views:
+    def _wrap(self, key, getter, which):
+        if key not in self._views:
             p = C.c_void_p()
             shape = (C.c_int64 * 3)()
             nd, dt = C.c_int(), C.c_int()
-            self._check(self.lib.bez_sim_get_tensor(self.h, which, C.byref(p), shape, C.byref(nd), C.byref(dt)))
+            self._check(getter(self.h, which, C.byref(p), shape, C.byref(nd), C.byref(dt)))
             shp = [int(shape[i]) for i in range(nd.value)]
-            view = _DevView(p.value, shp, "<f4" if dt.value == abi.DTYPE_F32 else "<i8", self)
+            view = _DevView(p.value, shp, {abi.DTYPE_F32: "<f4", abi.DTYPE_I64: "<i8", abi.DTYPE_I32: "<i4"}[dt.value], self)
             with torch.cuda.device(self.device):
-                self._views[which] = torch.as_tensor(view, device=self.device)
-        return self._views[which]
+                self._views[key] = torch.as_tensor(view, device=self.device)
+        return self._views[key]
+
+    def tensor(self, which):
+        """Zero-copy torch view of a sim-owned buffer (gymtorch.wrap_tensor)."""
+        return self._wrap(which, self.lib.bez_sim_get_tensor, which)
+
+    def episode_tensor(self, which):
+        """Zero-copy, always-live torch view of an episode statistic (abi.EPISODE_*): END_BITS (N,) int32, END_COUNTS (8, N) int64
+        [cause][env] (never cleared by the library: take deltas), REWARD_TERMS (8, N) float32 [slot][env] (the caller zeroes it)."""
+        return self._wrap(("episode", int(which)), self.lib.bez_sim_get_episode_tensor, which)
 
     def refresh(self, which):
         self._check(self.lib.bez_sim_refresh_tensor(self.h, which, self._stream()))

@@ -134,6 +134,12 @@ class VecTask(Env):
         self.randomize_buf = s.tensor(abi.TENSOR_RANDOMIZE_BUF)
         self.nonfinite_buf = s.tensor(abi.TENSOR_NONFINITE_COUNT)  # trips of the non-finite guard per env (abi.FLAG_NONFINITE_GUARD)
         self.health_buf = s.tensor(abi.TENSOR_HEALTH)              # the sim's health word (abi.HEALTH_* bits)
+        # why episodes end (abi.END_*): this step's cause bits per env, ended episodes per deciding cause [cause][env] (never cleared),
+        # and with env.debug.rewards (abi.FLAG_REWARD_TERMS) the sums of the reward's terms [slot][env] (zeroed by their consumer)
+        self.episode_end_bits = s.episode_tensor(abi.EPISODE_END_BITS)
+        self.episode_end_counts = s.episode_tensor(abi.EPISODE_END_COUNTS)
+        self.reward_terms_buf = s.episode_tensor(abi.EPISODE_REWARD_TERMS)
+        self.reward_terms_on = bool(int(s.cfg.flags) & abi.FLAG_REWARD_TERMS)
         self.extras = {}
 
     def get_state(self):

@@ -78,5 +78,13 @@ class RLGPUAlgoObserver:
             out["scalars"] = {"scores/mean": [mean, row.get("frame")], "scores/iter": [mean, row.get("epoch")], "scores/time": [mean, row.get("time")]}
         if "nonfinite_resets" in row:   # envs the simulator's non-finite guard reset during the epoch (this rank)
             out.setdefault("scalars", {})["env/nonfinite_resets"] = [row["nonfinite_resets"], row.get("frame")]
+        if "episode_ends" in row:       # why the epoch's episodes ended (this rank): each deciding cause's share of them
+            ends = row["episode_ends"]
+            tot = sum(ends.values())
+            for cause, k in ends.items():
+                out.setdefault("scalars", {})["episode_ends/%s" % cause] = [k / tot if tot else 0.0, row.get("frame")]
+        if "reward_terms" in row:       # env.debug.rewards: each reward term's mean per env-step (include/bez_sim.h slot table)
+            for slot, v in row["reward_terms"].items():
+                out.setdefault("scalars", {})["rewards/%s" % slot] = [v, row.get("frame")]
         self.f.write(json.dumps(out) + "\n")
         self.f.flush()

@@ -114,6 +114,48 @@ extern "C" {
                                          two sums (the pose error, a chain's joint velocities): a finite value so large \
                                          that one of them overflows trips too. */
 
+#define BEZ_FLAG_REWARD_TERMS 16384u /* env.debug.rewards: every launch with post-physics bookkeeping adds each env's reward, split into its \
+                                       terms, to BEZ_EPISODE_REWARD_TERMS (bez_sim_get_episode_tensor).  Not set by \
+                                       bez_sim_default_config; bez_sim_set_flags may toggle it.  No other output changes. */
+
+/* Why an episode ended: cause code k has bit (1 << k) in BEZ_EPISODE_END_BITS.  A test "fires" exactly where the reward sets
+ * reset_buf = 1.
+ *   k  name                     bez_kick                          bez_walk                    bez_orient
+ *   0  BEZ_END_CARRIED          reset_buf was already 1 when the reward was computed (bez_sim_observe_reward only: every
+ *                               launch with bookkeeping performs that reset first)
+ *   1  BEZ_END_FALL             torso z < 0.275                   up_proj < 0.7               up_proj < 0.7
+ *   2  BEZ_END_OUT_OF_BOUNDS    torso > 0.5 m from its start      never                       torso > 0.3 m from its start
+ *   3  BEZ_END_OFF_COURSE       goal-angle difference > 1.5708    heading error > 1.5708      never
+ *   4  BEZ_END_GOAL             ball within 0.05 of the goal      state == 4                  state == 4
+ *   5  BEZ_END_TIMEOUT          progress >= max_episode_length    same                        same
+ *   6  BEZ_END_NONFINITE        the non-finite guard tripped the env (BEZ_FLAG_NONFINITE_GUARD): replaces every other bit
+ *   7  (reserved)
+ * The DECIDING cause of an ended episode is the last test that fired in the reference's order -- the one whose reward stands:
+ *   bez_kick   fall, out of bounds, goal angle, goal, timeout
+ *   bez_walk   fall, goal, heading, timeout
+ *   bez_orient fall, goal, drift, timeout
+ * CARRIED decides only when no test fired; NONFINITE always decides. */
+#define BEZ_END_CARRIED 0
+#define BEZ_END_FALL 1
+#define BEZ_END_OUT_OF_BOUNDS 2
+#define BEZ_END_OFF_COURSE 3
+#define BEZ_END_GOAL 4
+#define BEZ_END_TIMEOUT 5
+#define BEZ_END_NONFINITE 6
+#define BEZ_END_CAUSES 8
+
+/* Slots of BEZ_EPISODE_REWARD_TERMS.  On a step where no test fired the slots sum to rew; on a step where one fired, slot 5 holds
+ * the reward the deciding test assigned and every other slot is 0.  Over any run, the sum of all slots is the sum of rew.
+ *   slot  bez_kick (kick_env.py:1224-1391)      bez_walk (walk_env.py:826-1031)        bez_orient (orient_env.py:843-1018)
+ *   0     0.1 ball_fwd                          0                                      -0.5 |ang_goal|        (ang_goal >= 0.05)
+ *   1     0.05 vel_fwd    (before the kick)     10 vel_fwd       (goal dist >= 0.05)   0
+ *   2     -|0.325 - z|                          -|1 - up_proj|                         -|1 - up_proj|
+ *   3     -0.05 |(v,w)|   (after the kick)      -0.05 |(v,w)|    (goal dist < 0.05)    -0.05 |(v,w)|          (ang_goal < 0.05)
+ *   4     -0.05 |q - q0|  (after the kick)      -0.25 |q - q0| far, -0.05 |q - q0| near  -0.0025 |q - q0| far, -0.05 |q - q0| near
+ *   5     terminal reward                       terminal reward                        terminal reward
+ *   6, 7  0                                     0                                      0
+ * ("after the kick": the ball is more than 0.3 m from its start; |q - q0|: the joints' distance from their default position) */
+
 /* Bits of the health word (BEZ_TENSOR_HEALTH, bez_sim_health): set on the device, cleared only by the caller. */
 #define BEZ_HEALTH_NONFINITE 1u    /* an env tripped the non-finite guard since the word was last cleared */
 #define BEZ_HEALTH_SPIN_TIMEOUT 2u /* an LDS hand-over wait of the 8-role-wave kernel gave up after its bound (the step went on with \
@@ -194,7 +236,18 @@ enum BezTensor {
   BEZ_TENSOR_HEALTH = 16,           /* i64 (1)        health word: BEZ_HEALTH_* bits (read outside the hot loop: bez_sim_health) */
   BEZ_TENSOR_COUNT = 17
 };
-enum BezDtype { BEZ_DTYPE_F32 = 0, BEZ_DTYPE_I64 = 1 };
+enum BezDtype { BEZ_DTYPE_F32 = 0, BEZ_DTYPE_I64 = 1, BEZ_DTYPE_I32 = 2 };
+
+/* Episode statistics (bez_sim_get_episode_tensor): zeroed at create, always live (no bez_sim_refresh_tensor), writable views. */
+enum BezEpisodeTensor {
+  BEZ_EPISODE_END_BITS = 0,     /* i32 (N)    this launch's BEZ_END_* bits per env: nonzero exactly where reset_buf == 1.  Written by
+                                                every launch with post-physics bookkeeping and by bez_sim_observe_reward */
+  BEZ_EPISODE_END_COUNTS = 1,   /* i64 (8,N)  [cause][env]: ended episodes per deciding cause, one per ended episode in launches with
+                                                bookkeeping (not bez_sim_observe_reward).  Never cleared by the library: take deltas */
+  BEZ_EPISODE_REWARD_TERMS = 2, /* f32 (8,N)  [slot][env]: sums of the reward's terms (BEZ_FLAG_REWARD_TERMS; slot table above) since
+                                                the caller last zeroed it, in launches with bookkeeping */
+  BEZ_EPISODE_TENSORS = 3
+};
 
 /* gym.create_sim + create_env/create_actor loop + prepare_sim + allocate_buffers
  * (vec_task.py:174-193, kick_env.py:240-408) followed by KickEnv.__init__'s reset_idx(all)
@@ -206,6 +259,8 @@ const char* bez_sim_last_error(const BezSim* sim); /* sim may be NULL: last crea
 /* gymtorch.wrap_tensor(gym.acquire_*_tensor(sim)): device pointer + shape of a sim-owned
  * buffer.  shape has `*ndim` valid entries. */
 int bez_sim_get_tensor(BezSim* sim, int which, void** dev_ptr, int64_t shape[3], int* ndim, int* dtype);
+/* The same for the episode statistics: `which` is a BezEpisodeTensor. */
+int bez_sim_get_episode_tensor(BezSim* sim, int which, void** dev_ptr, int64_t shape[3], int* ndim, int* dtype);
 
 /* gym.refresh_{actor_root_state,dof_state,rigid_body_state,net_contact_force}_tensor
  * (kick_env.py:750-753): materialise the Isaac-layout tensor from the SoA state. */

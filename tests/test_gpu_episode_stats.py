@@ -1,0 +1,309 @@
+"""Why episodes end, on the GPU (include/bez_sim.h: BEZ_END_*, BezEpisodeTensor, BEZ_FLAG_REWARD_TERMS): the step kernels' cause bits
+against the numpy restatement (tests/test_episode_stats_cpu.py) on the golden sets and along random rollouts, one scripted env per cause
+in one sim, the reward-term sums, bit-identical outputs with the flag on and off, and the PPO epoch row."""
+import numpy as np
+import pytest
+import torch
+
+from bez_isaacgym_amd import abi
+from tests.test_episode_stats_cpu import GOLDEN_SETS, end_causes, golden_inputs, kick_params, task_params
+
+pytestmark = pytest.mark.gpu
+
+KERNELS = ("lane", "ws8", "ws8q")
+TASKS = {"kick": abi.TASK_KICK, "walk": abi.TASK_WALK, "orient": abi.TASK_ORIENT}
+
+
+def _cfg(n, task=abi.TASK_KICK, cleats=False, terms=False, seed=11):
+    c = abi.default_config(n, seed=seed)
+    c.task = task
+    if task != abi.TASK_KICK:   # bez_walk.yaml / bez_orient.yaml (tests/test_tasks.py make_cfg)
+        c.max_episode_length = 600
+        c.goal[:] = [2.0, 0.0]
+        c.goal_angle = 1.5708
+    if cleats:
+        c.flags |= abi.FLAG_CLEATS
+    if terms:
+        c.flags |= abi.FLAG_REWARD_TERMS
+    return c
+
+
+def _sim(monkeypatch, n, kernel, task=abi.TASK_KICK, variant="default", terms=False, seed=11):
+    from bez_isaacgym_amd.sim import BezSim
+    monkeypatch.setenv("BEZ_SIM_KERNEL", kernel)   # read once, at bez_sim_create
+    s = BezSim(_cfg(n, task, cleats=variant == "cleats", terms=terms, seed=seed), 0)
+    if variant == "randomised":
+        from bez_isaacgym_amd.utils.config import load_config
+        params = load_config(["task=bez_kick"], resolve=True)["task"]["task"]["randomization_params"]
+        s.set_flags(int(s.cfg.flags) | abi.FLAG_OBS_NOISE_IN_STEP)
+        s.set_randomization(abi.dr_config_from_params(params))
+    return s
+
+
+def _np(t):
+    torch.cuda.synchronize()
+    return t.detach().cpu().numpy().copy()
+
+
+def _bits(s):
+    return _np(s.episode_tensor(abi.EPISODE_END_BITS)).astype(np.int64)
+
+
+def _counts(s):
+    return _np(s.episode_tensor(abi.EPISODE_END_COUNTS))
+
+
+def _state_inputs(s):
+    """The restatement's inputs from the refreshed state after a step (the reward saw reset_buf 0: the launch performed that reset)."""
+    n, na = s.num_envs, s.num_actors
+    root = _np(s.refresh(abi.TENSOR_ROOT_STATE)).reshape(n, na, 13)
+    dof = _np(s.refresh(abi.TENSOR_DOF_STATE)).reshape(n, 18, 2)
+    x = dict(root=root[:, 0, 0:3], q=root[:, 0, 3:7], v=root[:, 0, 7:10], w=root[:, 0, 10:13], dof=dof[:, :, 0],
+             progress=_np(s.tensor(abi.TENSOR_PROGRESS)), reset=np.zeros(n, np.int64))
+    if na == 2:
+        x.update(ball=root[:, 1, 0:3], ball_v=root[:, 1, 7:10])
+    else:
+        x.update(goal=_np(s.refresh(abi.TENSOR_GOAL)))
+    return x
+
+
+def _params_of(s):
+    return kick_params(int(s.cfg.max_episode_length)) if s.has_ball else task_params(int(s.cfg.max_episode_length), float(s.cfg.goal_angle))
+
+
+def _actions(rng, n, k=1):
+    return torch.from_numpy(rng.uniform(-1, 1, (k * n, 18)).astype(np.float32)).cuda().reshape(-1).contiguous()
+
+
+# ---- 1. the golden sets through bez_sim_observe_reward: the bits equal the restatement's; nothing is counted
+@pytest.mark.parametrize("kernel", KERNELS)
+@pytest.mark.parametrize("task,tag", GOLDEN_SETS)
+def test_golden_bits(monkeypatch, kernel, task, tag):
+    from tests.golden_checks import FLAG_ALIAS, _inject
+    from tests.sim_adapter import SimAdapter
+    monkeypatch.setenv("BEZ_SIM_KERNEL", kernel)
+    t, x, prm, rew, rst = golden_inputs(task, tag)
+    n = len(rew)
+    if task == "kick":
+        b = SimAdapter(abi.default_config(n))
+        b.set_flags(FLAG_ALIAS); b.set_obs_calls(1)
+        _inject(b, root_pos=x["root"], quat=x["q"], vel=x["v"], ang=x["w"], dof_pos=x["dof"], ball=x["ball"], ball_v=x["ball_v"],
+                reset=x["reset"], progress=x["progress"])
+    else:
+        b = SimAdapter(_cfg(n, t))
+        b.set_obs_calls(1)
+        root = np.zeros((n, 13), np.float32)
+        root[:, 0:3] = x["root"]; root[:, 3:7] = x["q"]; root[:, 7:10] = x["v"]; root[:, 10:13] = x["w"]
+        b.set_root_states(root)
+        dof = np.zeros((n, 18, 2), np.float32); dof[:, :, 0] = x["dof"]
+        b.set_dof_state(dof.reshape(-1, 2))
+        b.set_goal(x["goal"]); b.set_reset(x["reset"]); b.set_progress(x["progress"])
+    b.observe_reward()
+    bits = _bits(b.sim)
+    np.testing.assert_array_equal(bits, end_causes(t, x, prm)["bits"])
+    np.testing.assert_array_equal(bits != 0, b.reset_buf == 1)
+    assert _counts(b.sim).sum() == 0   # bez_sim_observe_reward does not count
+
+
+# ---- 2. one scripted env per cause in one sim
+SCRIPT = {abi.TASK_KICK: {1: abi.END_FALL, 2: abi.END_OUT_OF_BOUNDS, 3: abi.END_OFF_COURSE, 4: abi.END_GOAL, 5: abi.END_TIMEOUT,
+                          6: abi.END_NONFINITE},
+          abi.TASK_WALK: {1: abi.END_FALL, 3: abi.END_OFF_COURSE, 4: abi.END_GOAL, 5: abi.END_TIMEOUT, 6: abi.END_NONFINITE},
+          abi.TASK_ORIENT: {1: abi.END_FALL, 2: abi.END_OUT_OF_BOUNDS, 4: abi.END_GOAL, 5: abi.END_TIMEOUT, 6: abi.END_NONFINITE}}
+
+
+def _quat_mul(a, b):   # xyzw
+    ax, ay, az, aw = a
+    bx, by, bz, bw = b
+    return np.array([aw * bx + ax * bw + ay * bz - az * by, aw * by - ax * bz + ay * bw + az * bx,
+                     aw * bz + ax * by - ay * bx + az * bw, aw * bw - ax * bx - ay * by - az * bz], np.float32)
+
+
+def _script(s, task):
+    """Injects, into a settled sim, the state that makes env k end by cause SCRIPT[task][k] in the next step, and nothing else."""
+    n, na = s.num_envs, s.num_actors
+    dev = s.device
+    if task == abi.TASK_WALK:   # one known goal for every env (the OFF_COURSE env stands beyond it)
+        s.set_goal_tensor(torch.tensor([[1.0, 0.5]] * n, dtype=torch.float32, device=dev).reshape(-1).contiguous())
+    root = _np(s.refresh(abi.TENSOR_ROOT_STATE)).reshape(n, na, 13)
+    dof = _np(s.refresh(abi.TENSOR_DOF_STATE)).reshape(n, 18, 2)
+    for e, cause in SCRIPT[task].items():
+        r = root[e, 0]
+        if cause == abi.END_FALL:   # lying on its side in the air: torso z 0.25 < 0.275, up_proj 0 < 0.7; one step of free fall
+            r[2] = 0.25
+            r[3:7] = [np.sin(np.pi / 4), 0.0, 0.0, np.cos(np.pi / 4)]
+            r[7:13] = 0.0
+        elif cause == abi.END_OUT_OF_BOUNDS:   # the standing robot 1 m from its start
+            r[0] += 1.0
+        elif cause == abi.END_OFF_COURSE and task == abi.TASK_KICK:   # the ball beyond the goal: goal-angle difference ~ pi
+            root[e, 1, 0:2] = [2.5, 0.0]
+            root[e, 1, 7:13] = 0.0
+        elif cause == abi.END_OFF_COURSE:   # walk: the robot beyond its goal (1, 0.5): heading error ~ pi
+            r[0:2] = [2.0, 1.0]
+        elif cause == abi.END_GOAL and task == abi.TASK_KICK:   # the ball 2 cm short of the goal
+            root[e, 1, 0:2] = [1.48, 0.0]
+            root[e, 1, 7:13] = 0.0
+        elif cause == abi.END_GOAL:   # at rest in its settled pose, 2 cm from the walk goal / 0.3 rad past the orient heading
+            r[7:13] = 0.0
+            dof[e, :, 1] = 0.0
+            if task == abi.TASK_WALK:
+                r[0:2] = [1.0, 0.5]
+            else:
+                yaw = 1.5708 + 0.3
+                r[3:7] = _quat_mul(np.array([0, 0, np.sin(yaw / 2), np.cos(yaw / 2)], np.float32), r[3:7])
+        elif cause == abi.END_NONFINITE:
+            dof[e, 7, 1] = np.nan
+    s.set_actor_root_state_tensor_indexed(torch.from_numpy(root.reshape(-1, 13)).to(dev).reshape(-1).contiguous(),
+                                          torch.arange(n * na, dtype=torch.int32, device=dev))
+    s.set_dof_state_tensor_indexed(torch.from_numpy(dof.reshape(-1, 2)).to(dev).reshape(-1).contiguous(),
+                                   torch.arange(0, n * na, na, dtype=torch.int32, device=dev))
+    if task == abi.TASK_WALK:   # the GOAL env's goal: 2 cm ahead, on the ray from the origin through it (no heading error)
+        g = _np(s.refresh(abi.TENSOR_GOAL)).reshape(n, 2)
+        g[4] = [1.02, 0.51]
+        s.set_goal_tensor(torch.from_numpy(g).to(dev).reshape(-1).contiguous())
+    e_to = [e for e, c in SCRIPT[task].items() if c == abi.END_TIMEOUT][0]
+    s.tensor(abi.TENSOR_PROGRESS)[e_to] = int(s.cfg.max_episode_length) - 1
+
+
+@pytest.mark.parametrize("variant", ["default", "cleats", "randomised"])
+@pytest.mark.parametrize("task", list(TASKS))
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_scripted_causes(monkeypatch, kernel, task, variant):
+    t = TASKS[task]
+    n = 16
+    s = _sim(monkeypatch, n, kernel, t, variant)
+    zero = torch.zeros(n * 18, dtype=torch.float32, device=s.device)
+    for _ in range(30):   # settle: zero actions hold the default pose
+        s.step(zero)
+    before = _counts(s)
+    _script(s, t)
+    s.step(zero)
+    bits, counts = _bits(s), _counts(s) - before
+    want_bits = np.zeros(n, np.int64)
+    want_counts = np.zeros((abi.END_CAUSES, n), np.int64)
+    for e, cause in SCRIPT[t].items():
+        want_bits[e] = 1 << cause
+        want_counts[cause, e] = 1
+    np.testing.assert_array_equal(bits, want_bits, err_msg="cause bits after the scripted step (restatement on the stored state: %r)"
+                                  % end_causes(t, _state_inputs(s), _params_of(s))["bits"].tolist())
+    np.testing.assert_array_equal(counts, want_counts)
+    np.testing.assert_array_equal(_np(s.tensor(abi.TENSOR_RESET)), (want_bits != 0).astype(np.int64))
+    s.step(zero)   # the ordinary reset of the ended envs
+    np.testing.assert_array_equal(_bits(s), 0)
+    np.testing.assert_array_equal(_np(s.tensor(abi.TENSOR_RESET)), 0)
+    np.testing.assert_array_equal(_counts(s) - before, want_counts)
+
+
+# ---- 3. random rollouts: bits <=> reset, count deltas == resets, bits == the restatement on the terminal state
+ROLLOUTS = [(k, "kick") for k in KERNELS] + [("ws8q", "walk"), ("ws8q", "orient")]
+
+
+@pytest.mark.parametrize("kernel,task", ROLLOUTS)
+def test_rollout_bits_counts_and_restatement(monkeypatch, kernel, task):
+    t = TASKS[task]
+    n, steps, chunk = 4096, 300, 20
+    A = _sim(monkeypatch, n, kernel, t, seed=5)
+    B = _sim(monkeypatch, n, kernel, t, seed=5)   # the same steps through bez_sim_step_many
+    rng = np.random.default_rng(3)
+    acts = [_actions(rng, n) for _ in range(steps)]
+    prm = _params_of(A)
+    seen = _counts(A)
+    excluded = resets_total = 0
+    for i, a in enumerate(acts):
+        A.step(a)
+        bits, reset = _bits(A), _np(A.tensor(abi.TENSOR_RESET))
+        np.testing.assert_array_equal(bits != 0, reset == 1, err_msg="step %d" % i)
+        c = _counts(A)
+        assert (c - seen).sum() == reset.sum(), i
+        assert ((c - seen) >= 0).all()
+        seen = c
+        resets_total += int(reset.sum())
+        out = end_causes(t, _state_inputs(A), prm)
+        ok = out["margin"] > 1e-5
+        excluded += int((~ok).sum())
+        np.testing.assert_array_equal(bits[ok], out["bits"][ok], err_msg="step %d" % i)
+        if (i + 1) % chunk == 0:
+            B.step_many(torch.cat(acts[i + 1 - chunk:i + 1]), chunk)
+            np.testing.assert_array_equal(_bits(B), bits)
+            np.testing.assert_array_equal(_counts(B), c)
+    print("%s %s: %d resets, %d env-steps excluded within 1e-5 of a threshold" % (kernel, task, resets_total, excluded))
+    assert resets_total > 0
+
+
+# ---- 4. the reward-term split: outputs unchanged with the flag, the slots sum to the reward
+@pytest.mark.parametrize("variant", ["default", "randomised"])
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_reward_terms_twin(monkeypatch, kernel, variant):
+    from tests.test_gpu_nonfinite_guard import _snap
+    n, steps = 4096, 200
+    on = _sim(monkeypatch, n, kernel, variant=variant, terms=True)
+    off = _sim(monkeypatch, n, kernel, variant=variant, terms=False)
+    rng = np.random.default_rng(9)
+    rew_sum = np.zeros(n)
+    rew_abs = np.zeros(n)
+    for _ in range(steps):
+        a = _actions(rng, n)
+        on.step(a); off.step(a)
+        r = _np(on.tensor(abi.TENSOR_REW)).astype(np.float64)
+        rew_sum += r
+        rew_abs += np.abs(r)
+    a, b = _snap(on), _snap(off)
+    for w in a:
+        np.testing.assert_array_equal(a[w], b[w], err_msg="tensor %d differs with BEZ_FLAG_REWARD_TERMS" % w)
+    np.testing.assert_array_equal(_bits(on), _bits(off))
+    np.testing.assert_array_equal(_counts(on), _counts(off))
+    terms = _np(on.episode_tensor(abi.EPISODE_REWARD_TERMS)).astype(np.float64)
+    assert terms.shape == (8, n) and (terms[6:] == 0).all()
+    assert (_np(off.episode_tensor(abi.EPISODE_REWARD_TERMS)) == 0).all()
+    # per env, over the run: the slots sum to the rewards (fp32 sums of <= 200 terms each; absolute floor for near-zero sums)
+    np.testing.assert_allclose(terms.sum(0), rew_sum, rtol=1e-5, atol=1e-5 * rew_abs.max())
+    # toggled off, nothing more is added; the consumer's zeroing sticks
+    on.episode_tensor(abi.EPISODE_REWARD_TERMS).zero_()
+    on.set_flags(int(on.cfg.flags) & ~abi.FLAG_REWARD_TERMS | (abi.FLAG_OBS_NOISE_IN_STEP if variant == "randomised" else 0))
+    on.step(_actions(rng, n))
+    assert (_np(on.episode_tensor(abi.EPISODE_REWARD_TERMS)) == 0).all()
+
+
+# ---- 5. PPO (4 epochs: the capturing one, then 3 eager or pipelined): each epoch row's episode_ends add up to the finished episodes
+#         its ep_stats counted
+@pytest.mark.parametrize("pipelined", [False, True], ids=["train_epoch", "pipelined"])
+def test_ppo_epoch_rows(pipelined):
+    from bez_isaacgym_amd.ppo.a2c_continuous import A2CAgent
+    from bez_isaacgym_amd.utils.config import load_config
+    from bez_isaacgym_amd.utils.rlgames_utils import RLGPUEnv, get_rlgames_env_creator
+    N = 1024
+    cfg = load_config(["task=bez_kick", "num_envs=%d" % N, "headless=True"])
+    cfg["task"]["seed"] = 42
+    cfg["task"]["env"]["debug"]["rewards"] = True
+    venv = RLGPUEnv("rlgpu", N, env_creator=get_rlgames_env_creator(cfg["task"], "bez_kick", "cuda:0", "cuda:0", 0, True))
+    assert venv.env.reward_terms_on
+    params = cfg["train"]["params"]
+    params["config"].update(minibatch_size=4096, save_frequency=0, save_best_after=10 ** 9)
+    a = A2CAgent(params, venv, "cuda:0")
+    finished = []
+    orig = a._drain_episode_stats
+
+    def spy(host=None, zero=True):
+        finished.append(int(round(host[0] if host is not None else a.ep_stats[0].item())))
+        return orig(host, zero)
+    a._drain_episode_stats = spy
+    a.obs = a.env_reset()
+    rows = [a.train_epoch()]   # (the first epoch captures the graphs; the pipelined form needs them)
+    if pipelined:
+        pending = None
+        for _ in range(3):
+            ticket = a.train_epoch_launch()
+            assert ticket is not None
+            if pending is not None:
+                rows.append(a.train_epoch_finish(pending))
+            pending = ticket
+        rows.append(a.train_epoch_finish(pending))
+    else:
+        rows += [a.train_epoch() for _ in range(3)]
+    a.release_env()
+    assert len(rows) == len(finished) == 4
+    for row, fin in zip(rows, finished):
+        assert sum(row["episode_ends"].values()) == fin, (row["episode_ends"], finished)
+        terms = row["reward_terms"]
+        assert sorted(terms) == list(range(8)) and all(np.isfinite(v) for v in terms.values())
+    assert sum(finished) > 0

@@ -49,43 +49,43 @@ def evaluate(player, overrides=None, n=4096, steps=900, seed=1, flags=None, devi
     sim = BezSim(cfg, device)
     dev = sim.device
     obs = sim.tensor(abi.TENSOR_OBS); rew = sim.tensor(abi.TENSOR_REW); rst = sim.tensor(abi.TENSOR_RESET)
-    prog = sim.tensor(abi.TENSOR_PROGRESS)
+    bits = sim.episode_tensor(abi.EPISODE_END_BITS); counts = sim.episode_tensor(abi.EPISODE_END_COUNTS)
     sim.step(torch.zeros(n * 18, device=dev))
+    counts0 = counts.sum(1)
     ret = torch.zeros(n, device=dev); length = torch.zeros(n, device=dev)
-    acc = dict(episodes=0, ret=0.0, len=0.0, goal=0, timeout=0, fall=0, oob=0, angle=0, goal_len=0.0)
+    # per-episode sums on the device: no host sync inside the loop.  Why an episode ended comes from the simulator's own per-cause counters
+    # (the deciding test, in the reward's order: include/bez_sim.h BEZ_END_*); the goal-angle ends' ball at the goal line from its bits
+    acc = torch.zeros(4, device=dev, dtype=torch.float64)   # episodes, returns, lengths, lengths of goal-decided episodes
+    late = (1 << abi.END_TIMEOUT) | (1 << abi.END_NONFINITE)
     osum = torch.zeros(54, device=dev, dtype=torch.float64); osq = torch.zeros(54, device=dev, dtype=torch.float64); ocount = 0
-    miss_y, miss_v = [], []  # where / how fast the ball passes the goal line when an episode ends by the goal-angle test
+    miss = torch.full((steps, 2, n), float("nan"), device=dev)   # |ball y| and ball speed where an episode ended by the goal-angle test
     for t in range(steps):
         a = player.get_action(obs)
         if collect_obs:
             o64 = obs.double(); osum += o64.sum(0); osq += (o64 * o64).sum(0); ocount += n
         sim.step(a.reshape(-1).contiguous())
         ret += rew; length += 1
-        done = rst > 0
-        if bool(done.any()):
-            root = sim.refresh(abi.TENSOR_ROOT_STATE).view(n, 2, 13)
-            d = done.nonzero().squeeze(-1)
-            r, z = rew[d], root[d, 0, 2]
-            xy = torch.linalg.norm(root[d, 0, :2] - torch.tensor(list(cfg.bez_init[:2]), device=dev), dim=1)
-            goal = r > 1.0
-            tmo = (~goal) & (prog[d] >= cfg.max_episode_length)
-            fall = (~goal) & (~tmo) & (z < 0.275)
-            oob = (~goal) & (~tmo) & (~fall) & (xy > 0.5)
-            acc["episodes"] += int(d.numel()); acc["ret"] += float(ret[d].sum()); acc["len"] += float(length[d].sum())
-            acc["goal"] += int(goal.sum()); acc["timeout"] += int(tmo.sum()); acc["fall"] += int(fall.sum()); acc["oob"] += int(oob.sum())
-            acc["angle"] += int(d.numel()) - int(goal.sum() + tmo.sum() + fall.sum() + oob.sum())
-            acc["goal_len"] += float(length[d][goal].sum())
-            ang = (~goal) & (~tmo) & (~fall) & (~oob)
-            if bool(ang.any()):
-                miss_y.append(root[d, 1, 1][ang].cpu()); miss_v.append(torch.linalg.norm(root[d, 1, 7:9][ang], dim=1).cpu())
-            ret[d] = 0; length[d] = 0
-    torch.cuda.synchronize()
-    e = max(acc["episodes"], 1)
-    out = dict(episodes=acc["episodes"], goal_rate=acc["goal"] / e, mean_return=acc["ret"] / e, mean_length=acc["len"] / e,
-               goal_length=acc["goal_len"] / max(acc["goal"], 1),
-               reasons={k: acc[k] for k in ("goal", "fall", "oob", "angle", "timeout")})
+        done = (rst > 0).double()
+        b = bits.long()
+        goal = ((b & (1 << abi.END_GOAL)) != 0) & ((b & late) == 0)
+        ang = ((b & (1 << abi.END_OFF_COURSE)) != 0) & ((b & (late | (1 << abi.END_GOAL))) == 0)
+        acc += torch.stack([done.sum(), (ret * done).sum(), (length * done).sum(), (length * goal.double()).sum()])
+        root = sim.refresh(abi.TENSOR_ROOT_STATE).view(n, 2, 13)
+        miss[t, 0] = torch.where(ang, root[:, 1, 1].abs(), miss[t, 0])
+        miss[t, 1] = torch.where(ang, torch.linalg.norm(root[:, 1, 7:9], dim=1), miss[t, 1])
+        ret *= 1 - done; length *= 1 - done
+    ends = (counts.sum(1) - counts0).tolist()
+    acc = acc.tolist()
+    e = max(int(acc[0]), 1)
+    out = dict(episodes=int(acc[0]), goal_rate=ends[abi.END_GOAL] / e, mean_return=acc[1] / e, mean_length=acc[2] / e,
+               goal_length=acc[3] / max(ends[abi.END_GOAL], 1),
+               reasons=dict(goal=ends[abi.END_GOAL], fall=ends[abi.END_FALL], oob=ends[abi.END_OUT_OF_BOUNDS], angle=ends[abi.END_OFF_COURSE],
+                            timeout=ends[abi.END_TIMEOUT]))
+    mm = miss.permute(1, 0, 2).reshape(2, -1).cpu().numpy()
+    keep = ~np.isnan(mm[0])
+    miss_y, miss_v = ([mm[0][keep]], [mm[1][keep]]) if keep.any() else ([], [])
     if miss_y:
-        my, mv = torch.cat(miss_y).abs().numpy(), torch.cat(miss_v).numpy()
+        my, mv = np.concatenate(miss_y), np.concatenate(miss_v)
         out["angle_miss_abs_y_m"] = {"p10": float(np.percentile(my, 10)), "p50": float(np.percentile(my, 50)), "p90": float(np.percentile(my, 90))}
         out["angle_miss_ball_speed"] = {"p10": float(np.percentile(mv, 10)), "p50": float(np.percentile(mv, 50)), "p90": float(np.percentile(mv, 90))}
     if collect_obs:
