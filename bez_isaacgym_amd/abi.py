@@ -30,6 +30,8 @@ FLAG_ALL_GROUND_SHAPES = 2048   # scenario harness: ground contact at every coll
 FLAG_FIX_BASE = 4096            # urdfAsset.fixBaseLink: the torso welded to the world
 FLAG_NONFINITE_GUARD = 8192     # per-env non-finite guard of the post-physics (on by default; include/bez_sim.h)
 FLAG_REWARD_TERMS = 16384       # env.debug.rewards: per-env sums of the reward's terms (EPISODE_REWARD_TERMS; off by default)
+SPACE_ENV = 0                   # bez_sim_apply_body_forces: world axes / world points (gymapi.ENV_SPACE)
+SPACE_LOCAL = 1                 # the body's own frame (gymapi.LOCAL_SPACE)
 HEALTH_NONFINITE = 1            # health word bits (TENSOR_HEALTH, BezSim.health)
 HEALTH_SPIN_TIMEOUT = 2
 TASK_KICK, TASK_WALK, TASK_ORIENT = 0, 1, 2
@@ -254,3 +256,17 @@ def config_from_task_cfg(cfg, seed=42, env_id_offset=0, strict_reference_quirks=
     if env.get("urdfAsset", {}).get("fixBaseLink", False):  # kick_env.py:287
         c.flags |= FLAG_FIX_BASE
     return c
+
+
+def body_force_space(space):
+    """SPACE_ENV / SPACE_LOCAL from the int or from "env" / "local" (any case); anything else raises ValueError."""
+    if isinstance(space, str):
+        key = space.strip().lower()
+        if key in ("env", "env_space"):
+            return SPACE_ENV
+        if key in ("local", "local_space"):
+            return SPACE_LOCAL
+        raise ValueError("space must be 'env' or 'local', got %r" % space)
+    if isinstance(space, bool) or not isinstance(space, int) or space not in (SPACE_ENV, SPACE_LOCAL):
+        raise ValueError("space must be SPACE_ENV (0) or SPACE_LOCAL (1), got %r" % (space,))
+    return int(space)

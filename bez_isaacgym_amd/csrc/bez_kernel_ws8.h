@@ -286,9 +286,10 @@ BEZ_DEV void load_targets(const Params& P, const float* lds, int lane, int e, fl
 }
 
 // ------------------------------------------------------------------------------------------------ roles
-template <int FIRST, bool PRE, bool POST, bool DR, bool CL>
+template <int FIRST, bool PRE, bool POST, bool DR, bool CL, bool EXT = false>
 BEZ_DEV void leg_role(const Params& P, float* lds, int lane, int e, bool active, int side) {
   constexpr int LEN = 6;
+  const bool xp = EXT && ext_pending(P, e);   // external wrenches pending for this env (EXT instantiations)
   float q[LEN], qd[LEN], target[LEN];
   {
     float kps[LEN], kds[LEN], ms[LEN], lo[LEN], hi[LEN];  // (re-fetched inside the substep loop)
@@ -320,7 +321,7 @@ BEZ_DEV void leg_role(const Params& P, float* lds, int lane, int e, bool active,
     BallSel sel;
     sel.link = -1; sel.depth = 0.f; sel.n = sel.P = sel.f0p = sel.x = sel.xb = mk(0, 0, 0); sel.A = sym3zero();
     M3 Eend; V3 rend; SV Vend, Vsel = svzero();
-    ws_chain_pass1<FIRST, LEN, true, CL, false, BEZ_W8_LEG_BAR>(P, D, ms, R, q, qd, LI, pAl, Sl, cbl, Eend, rend, Vend, sel, Vsel, s > 0);  // B5 of the previous substep inside
+    ws_chain_pass1<FIRST, LEN, true, CL, false, BEZ_W8_LEG_BAR, EXT>(P, D, ms, R, q, qd, LI, pAl, Sl, cbl, Eend, rend, Vend, sel, Vsel, s > 0, e, xp);  // B5 of the previous substep inside
     if (!CL) {  // this leg's foot box as a ball candidate (the ball's new state was published at the barrier inside pass 1)
       BallSel fs;
       fs.link = -1; fs.depth = 0.f; fs.n = fs.P = fs.f0p = fs.x = fs.xb = mk(0, 0, 0); fs.A = sym3zero();
@@ -409,6 +410,10 @@ BEZ_DEV void leg_role(const Params& P, float* lds, int lane, int e, bool active,
     ws_barrier();  // B4
     WS_STAMP(side, 8 + 8 * s);
   }
+  if (EXT && xp && active) {   // this leg's wrenches were for this launch only
+#pragma unroll 1
+    for (int i = 0; i < LEN; ++i) ext_clear(P, e, FIRST + i);
+  }
   // joint-side post-physics in the window of the root's last ball update (needs nothing the ball publishes)
   ws_chain_epilogue<(FIRST == 5 ? 0 : 1), POST>(P, lds, lane, e, active, do_reset, episode, q, qd, target);
   WS_STAMP(side, 21);
@@ -417,17 +422,17 @@ BEZ_DEV void leg_role(const Params& P, float* lds, int lane, int e, bool active,
 }
 
 // A 2-link chain (head / one arm) owned by a role: its state and the three passes, split at the barriers by the caller.
-template <int FIRST, int BLOCK_IA, bool CL>
+template <int FIRST, int BLOCK_IA, bool CL, bool EXT = false>
 struct Chain2 {
   float q[2], qd[2], target[2], kps[2], kds[2], ms[2], lo[2], hi[2];
   P3 p3[2];
   BodyContact bcn;
   Sym6 IAc; SV pAc;  // the chain's contribution as seen by the torso (also stored to its X_IA block)
-  BEZ_DEV void up(const Params& P, const ChainDyn& D, float* lds, int lane) {  // passes 1 + 2, contribution -> X_IA block
+  BEZ_DEV void up(const Params& P, const ChainDyn& D, float* lds, int lane, int e = 0, bool xp = false) {  // passes 1 + 2, contribution -> X_IA block
     RootView R = load_root_view(lds, lane);
     BallSel nosel; nosel.link = -1; nosel.depth = 0.f; nosel.n = nosel.P = nosel.f0p = nosel.x = nosel.xb = mk(0, 0, 0); nosel.A = sym3zero();
     LinkInertia LI[2]; SV pAl[2], Sl[2], cbl[2]; M3 Ee; V3 re; SV Ve, Vs = svzero();
-    ws_chain_pass1<FIRST, 2, false, CL>(P, D, ms, R, q, qd, LI, pAl, Sl, cbl, Ee, re, Ve, nosel, Vs);
+    ws_chain_pass1<FIRST, 2, false, CL, false, -1, EXT>(P, D, ms, R, q, qd, LI, pAl, Sl, cbl, Ee, re, Ve, nosel, Vs, false, e, xp);
     Sym6 Kc = sym6zero(); SV pc = svzero();
     ws_ground_points<FIRST + 1, CL>(P, D.mu, R.root_z, Ee, re, Ve, Kc, pc);
     Sym6 IA = sym6zero(); SV pA = svzero();
@@ -435,6 +440,9 @@ struct Chain2 {
     bcn = body_contact_of(Kc, pc);
     IAc = IA; pAc = pA;
     xs_store_sym6(lds, lane, X_IA + BLOCK_IA * 27, IA, pA);
+  }
+  BEZ_DEV void ext_done(const Params& P, int e, bool xp, bool active) {   // the chain's wrenches were for this launch only
+    if (EXT && xp && active) { ext_clear(P, e, FIRST); ext_clear(P, e, FIRST + 1); }
   }
   BEZ_DEV void down(const Params& P, float* lds, int lane, bool keep, bool first) {  // pass 3 + the chain-end contact row
     BallSel nosel; nosel.link = -1; nosel.depth = 0.f; nosel.n = nosel.P = nosel.f0p = nosel.x = nosel.xb = mk(0, 0, 0); nosel.A = sym3zero();
@@ -445,9 +453,10 @@ struct Chain2 {
   }
 };
 
-template <bool PRE, bool POST, bool DR, bool CL>
+template <bool PRE, bool POST, bool DR, bool CL, bool EXT = false>
 BEZ_DEV void head_role(const Params& P, float* lds, int lane, int e, bool active) {
-  Chain2<1, 2, CL> C;
+  Chain2<1, 2, CL, EXT> C;
+  const bool xp = EXT && ext_pending(P, e);
   load_joints<1, 2, DR>(P, e, C.q, C.qd, C.kps, C.kds, C.ms, C.lo, C.hi);
   const ChainDyn D = load_chain_dyn<DR>(P, e);
   const bool do_reset = POST && P.reset[e] != 0;
@@ -471,7 +480,7 @@ BEZ_DEV void head_role(const Params& P, float* lds, int lane, int e, bool active
     }
     WS_STAMP(2, 2 + 8 * s);
     ws_barrier();  // B1  (X_IA is free from here on: the staged actions have been consumed)
-    C.up(P, in_loop(D), lds, lane);
+    C.up(P, in_loop(D), lds, lane, e, xp);
     WS_STAMP(2, 4 + 8 * s);
     ws_barrier();  // B1c: head and arm blocks are in LDS (role 4 sums them into block 2 before B2)
     ws_barrier();  // B2
@@ -479,6 +488,7 @@ BEZ_DEV void head_role(const Params& P, float* lds, int lane, int e, bool active
     C.down(P, lds, lane, keep, first);
     ws_barrier();  // B4
   }
+  C.ext_done(P, e, xp, active);
   ws_chain_epilogue<2, POST>(P, lds, lane, e, active, do_reset, episode, C.q, C.qd, C.target);
   WS_STAMP(2, 21);
   ws_barrier();  // B5 of the last substep
@@ -487,10 +497,11 @@ BEZ_DEV void head_role(const Params& P, float* lds, int lane, int e, bool active
 // roles 4 / 5: the deepest ball<->leg-box candidate of one leg from this wave's own forward kinematics of that leg (window of
 // the leg's pass 1), then the arm of the same side as a chain of its own (window of the leg's pass 2); role 4 finally adds the head and
 // right-arm blocks to its own and leaves the sum in block 2, so that the root role reads three blocks.
-template <int LEG_FIRST, int ARM_FIRST, bool PRE, bool POST, bool DR, bool CL>
+template <int LEG_FIRST, int ARM_FIRST, bool PRE, bool POST, bool DR, bool CL, bool EXT = false>
 BEZ_DEV void cand_arm_role(const Params& P, float* lds, int lane, int e, bool active, int side) {
   constexpr int ROLE = LEG_FIRST == 5 ? 4 : 5;
-  Chain2<ARM_FIRST, 3 + (LEG_FIRST == 5 ? 0 : 1), CL> C;
+  Chain2<ARM_FIRST, 3 + (LEG_FIRST == 5 ? 0 : 1), CL, EXT> C;
+  const bool xp = EXT && ext_pending(P, e);
   load_joints<ARM_FIRST, 2, DR>(P, e, C.q, C.qd, C.kps, C.kds, C.ms, C.lo, C.hi);
   const ChainDyn D = load_chain_dyn<DR>(P, e);
   const bool do_reset = POST && P.reset[e] != 0;
@@ -514,7 +525,7 @@ BEZ_DEV void cand_arm_role(const Params& P, float* lds, int lane, int e, bool ac
 #if BEZ_WS_SUB == 4
     if constexpr (!CL && !DR) wq_produce_packages<LEG_FIRST>(P, in_loop(D).g, lds, lane, side, s + 1);   // the hip links' packages of this side's leg
 #endif
-    C.up(P, in_loop(D), lds, lane);
+    C.up(P, in_loop(D), lds, lane, e, xp);
     WS_STAMP(ROLE, 4 + 8 * s);
     ws_barrier();  // B1c: head and arm blocks are in LDS
     if (ROLE == 4) {
@@ -535,6 +546,7 @@ BEZ_DEV void cand_arm_role(const Params& P, float* lds, int lane, int e, bool ac
     C.down(P, lds, lane, keep, first);
     ws_barrier();  // B4
   }
+  C.ext_done(P, e, xp, active);
   ws_chain_epilogue<ROLE, POST>(P, lds, lane, e, active, do_reset, episode, C.q, C.qd, C.target);
   WS_STAMP(ROLE, 21);
   ws_barrier();  // B5 of the last substep
@@ -656,9 +668,10 @@ BEZ_DEV void self_role(const Params& P, float* lds, int lane, int e, bool active
   ws_barrier();  // B5 of the last substep
 }
 
-template <bool PRE, bool POST, bool DR, bool CL>
+template <bool PRE, bool POST, bool DR, bool CL, bool EXT = false>
 BEZ_DEV void root_role(const Params& P, float* lds, int lane, int e, bool active) {
   const int n = P.n;
+  const bool xp = EXT && ext_pending(P, e);   // external wrenches pending: the torso's and the ball's are this role's
   float* st = P.state;
   auto ld = [&](int f) { return st[(size_t)f * n + e]; };
   V3 root_pos = mk(ld(F_ROOT_POS), ld(F_ROOT_POS + 1), ld(F_ROOT_POS + 2));
@@ -700,7 +713,10 @@ BEZ_DEV void root_role(const Params& P, float* lds, int lane, int e, bool active
     V3 fl = xs_load_v3(lds, lane, X_FL), xb = xs_load_v3(lds, lane, X_FL + 3);
     pin(fl); pin(xb);  // loaded values, not a select between an LDS and a private address (that would put fl_t / sel in scratch)
     if (torso_hit) { fl = fl_t; xb = sel.xb; }
-    SV ab = ball_minv(ball, svzero() - ball.pb - wrench_at(xb, fl));
+    // (+ the ball's external wrench about its centre, resolved with the pose the substep started from, as the one-lane kernel does)
+    SV fb_ext = svzero();
+    if constexpr (EXT) { if (xp) fb_ext = ext_wrench(P, e, BEZ_NL, quat_to_mat(bq[0], bq[1], bq[2], bq[3]), mk(0, 0, 0)); }
+    SV ab = ball_minv(ball, fb_ext - ball.pb - wrench_at(xb, fl));
     if (keep) {
       V3 fb = -cf_along(P, fl, sel.n);
       if (ball.ground) fb = fb + cf_ground(P, hit_force(P, ball.ghit, ab));
@@ -747,6 +763,7 @@ BEZ_DEV void root_role(const Params& P, float* lds, int lane, int e, bool active
     Sym6 IA0 = sym6zero(); SV pA0;
     LinkInertia I0;
     link_inertia<0, CL>(ms0, D.g, E0, mk(0, 0, 0), V0, I0, pA0);
+    if constexpr (EXT) { if (xp) pA0 = pA0 - ext_wrench(P, e, 0, E0, mk(0, 0, 0)); }
     Sym6 Kc = sym6zero(); SV pc = svzero();
     ws_ground_points<0, CL>(P, D.mu, root_pos.z, E0, mk(0, 0, 0), V0, Kc, pc);
 #if BEZ_WS_SUB == 4
@@ -884,6 +901,8 @@ BEZ_DEV void root_role(const Params& P, float* lds, int lane, int e, bool active
   // this barrier; ws_barrier() itself does not wait for outstanding global loads (vmcnt), so the two words are only rewritten here,
   // behind the last barrier -- no reliance on the memory pipeline serving another wave's earlier load before this store.
   if (POST && active && new_episode) P.episode[e] = (lean_ends<DR, CL>() ? episode0 : P.episode[e]) + 1;
+  // the torso's and the ball's wrenches, then the env's pending word: every role has consumed that word before this barrier
+  if (EXT && xp && active) { ext_clear(P, e, 0); ext_clear(P, e, BEZ_NL); P.ext[(size_t)EXT_FLAG * n + e] = 0.f; }
   if (POST) {
     const float pn = (((XS(X_PSUM + 2) + XS(X_PSUM + 4)) + XS(X_PSUM + 5)) + XS(X_PSUM + 0)) + XS(X_PSUM + 1);
     OrnOut orn; orn.ux = orn.uy = orn.gn = orn.ang_goal = 0.f;
@@ -916,7 +935,8 @@ BEZ_DEV void root_role(const Params& P, float* lds, int lane, int e, bool active
 }
 
 // ---- the kernel.  grid = ceil(N / 64) workgroups of 512 threads.
-template <bool PRE, bool POST, bool DR, bool CL>
+// EXT: the instantiation that reads (and, behind the last substep, clears) the pending external wrenches of bez_sim_apply_body_forces
+template <bool PRE, bool POST, bool DR, bool CL, bool EXT = false>
 __global__ __launch_bounds__(WS_BLOCK) void step_kernel_ws8(Params P) {
   __shared__ __attribute__((aligned(16))) float lds[WS_LDS_FLOATS];
   const int tid = threadIdx.x;
@@ -958,21 +978,21 @@ __global__ __launch_bounds__(WS_BLOCK) void step_kernel_ws8(Params P) {
   }
   WS_STAMP(role, 18);
 #ifdef BEZ_AB_ONLY_ROLE   // offline diagnostics (tools/role_resources.sh): the register / spill figures of ONE role's code; never launched
-  if (BEZ_AB_ONLY_ROLE == 0) leg_role<5, PRE, POST, DR, CL>(P, lds, lane, e, active, 0);
-  if (BEZ_AB_ONLY_ROLE == 1) leg_role<13, PRE, POST, DR, CL>(P, lds, lane, e, active, 1);
-  if (BEZ_AB_ONLY_ROLE == 2) head_role<PRE, POST, DR, CL>(P, lds, lane, e, active);
-  if (BEZ_AB_ONLY_ROLE == 3) root_role<PRE, POST, DR, CL>(P, lds, lane, e, active);
-  if (BEZ_AB_ONLY_ROLE == 4) cand_arm_role<5, 3, PRE, POST, DR, CL>(P, lds, lane, e, active, 0);
-  if (BEZ_AB_ONLY_ROLE == 5) cand_arm_role<13, 11, PRE, POST, DR, CL>(P, lds, lane, e, active, 1);
+  if (BEZ_AB_ONLY_ROLE == 0) leg_role<5, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 0);
+  if (BEZ_AB_ONLY_ROLE == 1) leg_role<13, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 1);
+  if (BEZ_AB_ONLY_ROLE == 2) head_role<PRE, POST, DR, CL, EXT>(P, lds, lane, e, active);
+  if (BEZ_AB_ONLY_ROLE == 3) root_role<PRE, POST, DR, CL, EXT>(P, lds, lane, e, active);
+  if (BEZ_AB_ONLY_ROLE == 4) cand_arm_role<5, 3, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 0);
+  if (BEZ_AB_ONLY_ROLE == 5) cand_arm_role<13, 11, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 1);
   if (BEZ_AB_ONLY_ROLE == 6) self_role<0, POST, DR, CL>(P, lds, lane, e, active);
   if (BEZ_AB_ONLY_ROLE == 7) self_role<1, POST, DR, CL>(P, lds, lane, e, active);
 #else
-  if (role == 0) leg_role<5, PRE, POST, DR, CL>(P, lds, lane, e, active, 0);
-  else if (role == 1) leg_role<13, PRE, POST, DR, CL>(P, lds, lane, e, active, 1);
-  else if (role == 2) head_role<PRE, POST, DR, CL>(P, lds, lane, e, active);
-  else if (role == 3) root_role<PRE, POST, DR, CL>(P, lds, lane, e, active);
-  else if (role == 4) cand_arm_role<5, 3, PRE, POST, DR, CL>(P, lds, lane, e, active, 0);
-  else if (role == 5) cand_arm_role<13, 11, PRE, POST, DR, CL>(P, lds, lane, e, active, 1);
+  if (role == 0) leg_role<5, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 0);
+  else if (role == 1) leg_role<13, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 1);
+  else if (role == 2) head_role<PRE, POST, DR, CL, EXT>(P, lds, lane, e, active);
+  else if (role == 3) root_role<PRE, POST, DR, CL, EXT>(P, lds, lane, e, active);
+  else if (role == 4) cand_arm_role<5, 3, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 0);
+  else if (role == 5) cand_arm_role<13, 11, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 1);
   else if (role == 6) self_role<0, POST, DR, CL>(P, lds, lane, e, active);
   else self_role<1, POST, DR, CL>(P, lds, lane, e, active);
 #endif

@@ -97,6 +97,8 @@ struct Params {
   // the episode statistics, one allocation (one kernel-argument pointer: the 8-role-wave kernels are short of scalar registers):
   // (8,N) i64 BEZ_EPISODE_END_COUNTS [cause][env], then (8,N) f32 BEZ_EPISODE_REWARD_TERMS [slot][env], then (N) i32 BEZ_EPISODE_END_BITS
   unsigned long long* episode_stats;
+  // the pending external wrenches of bez_sim_apply_body_forces (read and cleared by the EXT kernel instantiations only; below)
+  float* ext;
 };
 BEZ_DEV unsigned long long* end_counts_of(const Params& P) { return P.episode_stats; }
 BEZ_DEV float* reward_terms_of(const Params& P) { return reinterpret_cast<float*>(P.episode_stats + (size_t)BEZ_END_CAUSES * P.n); }
@@ -146,6 +148,37 @@ BEZ_DEV void episode_end_store(const Params& P, int e, uint32_t bits, float rew,
     for (int k = 0; k < 5; ++k)
       if (terms[k] != 0.f) unsafeAtomicAdd(reward_terms_of(P) + (size_t)k * n + e, terms[k]);
   }
+}
+
+// ---- external wrenches (bez_sim_apply_body_forces).  Pending buffer P.ext, SoA [link][component][env] for the 19 links and the ball
+// (link BEZ_NL), then one word per env that is nonzero when the env has anything pending.  Per link, as bez_sim_apply_body_forces left
+// them: F (world axes, 3), T (world axes, 3) and M = sum_i p_i F_i^T (9, row-major), p_i = the point of application in the link frame
+// (the ball: its own frame about its centre).  With the link's current frame (E, r about the torso origin O, world axes) the wrench
+// about O is (T + r x F + sum_i (E p_i) x F_i, F), and sum_i (E p_i) x F_i is the axial vector of the antisymmetric part of E M:
+// the point of application moves with its body while F stays fixed in world axes.
+constexpr int EXT_LINKS = BEZ_NL + 1, EXT_COMP = 15, EXT_FLAG = EXT_LINKS * EXT_COMP, EXT_WORDS = EXT_FLAG + 1;
+BEZ_DEV bool ext_pending(const Params& P, int e) { return P.ext[(size_t)EXT_FLAG * P.n + e] != 0.f; }
+// (the env index is made opaque per call: otherwise the compiler hoists the 15 loads per link out of the substep loop, where nothing
+// writes global memory, and keeps them live across the physics -- hundreds of spilled VGPRs in the 8-role-wave kernels)
+BEZ_DEV SV ext_wrench(const Params& P, int e, int l, const M3& E, V3 r) {
+  const size_t n = (size_t)P.n;
+  asm volatile("" : "+v"(e));
+  const float* x = P.ext + (size_t)l * EXT_COMP * n + e;
+  const V3 F = mk(x[0], x[n], x[2 * n]), T = mk(x[3 * n], x[4 * n], x[5 * n]);
+  float M[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) M[k] = x[(6 + k) * n];
+  // N = E M: only the off-diagonal entries enter the axial vector
+  auto N = [&](float e0, float e1, float e2, int b) { return fmaf(e0, M[b], fmaf(e1, M[3 + b], e2 * M[6 + b])); };
+  const V3 m = mk(N(E.m10, E.m11, E.m12, 2) - N(E.m20, E.m21, E.m22, 1), N(E.m20, E.m21, E.m22, 0) - N(E.m00, E.m01, E.m02, 2),
+                  N(E.m00, E.m01, E.m02, 1) - N(E.m10, E.m11, E.m12, 0));
+  return mksv(T + cross(r, F) + m, F);
+}
+// the link's entries back to zero, after the launch's last substep (the thread that read them: program order)
+BEZ_DEV void ext_clear(const Params& P, int e, int l) {
+  float* x = P.ext + (size_t)l * EXT_COMP * P.n + e;
+#pragma unroll
+  for (int k = 0; k < EXT_COMP; ++k) x[(size_t)k * P.n] = 0.f;
 }
 
 // the goal an env reset by this launch receives (bez_walk / bez_orient)
@@ -744,9 +777,10 @@ BEZ_DEV void static_for(F&& f) { static_for_impl(std::make_integer_sequence<int,
 
 // ---- passes 1+2 of one serial chain FIRST..FIRST+LEN-1 hanging off the torso.  Accumulates the chain's
 // articulated inertia / bias into the torso's (IA0, pA0) and stages pass-3 data in LDS.
-template <int FIRST, int LEN, bool CL>
+template <int FIRST, int LEN, bool CL, bool EXT = false>
 BEZ_DEV void chain_up(const Params& P, const EnvDyn& D, const EnvState& S, const float* target, const M3& E0, SV V0,
-                      const BallBody& ball, V3 bc, BallSel& sel, const SV* selfw, Sym6& IA0, SV& pA0, SV& pS0, SelfSums& Z, float* lds, int lane, bool keep, int e) {
+                      const BallBody& ball, V3 bc, BallSel& sel, const SV* selfw, Sym6& IA0, SV& pA0, SV& pS0, SelfSums& Z, float* lds, int lane, bool keep, int e,
+                      bool xp = false) {
   LinkInertia LI[LEN];
   constexpr bool LEG = (FIRST == 5 || FIRST == 13);
   M3 Ecalf = E0; V3 rcalf = mk(0, 0, 0);   // BEZ_FLAG_ANKLE_STOP: the calf's frame, kept from pass 1 (legs only)
@@ -760,6 +794,7 @@ BEZ_DEV void chain_up(const Params& P, const EnvDyn& D, const EnvState& S, const
     constexpr int L = FIRST + i;
     link_kinematics<L>(S.q[L - 1], S.qd[L - 1], E, r, V, Sl[i], cbl[i], quirk_rz<CL>(P.flags));
     link_inertia<L, CL>(D.mass_scale[L], D.g, E, r, V, LI[i], pAl[i]);
+    if constexpr (EXT) { if (xp) pAl[i] = pAl[i] - ext_wrench(P, e, L, E, r); }   // external wrench: a bias force of the link (bez_sim_apply_body_forces)
     if constexpr (link_has_box(L)) {
       if (sel.link == L) ball_link_contact(P, D.mu, S.ball_ang, S.ball_lin, ball, bc, V, sel);
     }
@@ -942,8 +977,10 @@ BEZ_DEV void quat_integrate(float q[4], V3 w, float h) {
 
 // ---- one substep of the articulated-body dynamics for this lane's env.  When `keep` the net contact force per body of
 // this substep is accumulated (`first`: it starts the mean): foot rows in `co`, all other rows in HBM.
-template <bool CL>
-BEZ_DEV void substep(const Params& P, const EnvDyn& D, EnvState& S, const float* target, CfOut& co, float* lds, int lane, bool keep, bool first, int e) {
+// EXT: `xp` = this env has external wrenches pending (bez_sim_apply_body_forces): they enter every link's bias force and the ball's.
+template <bool CL, bool EXT = false>
+BEZ_DEV void substep(const Params& P, const EnvDyn& D, EnvState& S, const float* target, CfOut& co, float* lds, int lane, bool keep, bool first, int e,
+                     bool xp = false) {
   const M3 E0 = quat_to_mat(S.rq[0], S.rq[1], S.rq[2], S.rq[3]);
   const SV V0 = mksv(S.root_ang, S.root_lin);
   const V3 bc = S.ball_pos - S.root_pos;  // ball centre rel. O
@@ -991,6 +1028,7 @@ BEZ_DEV void substep(const Params& P, const EnvDyn& D, EnvState& S, const float*
   {
     LinkInertia I0;
     link_inertia<0, CL>(D.mass_scale[0], D.g, E0, mk(0, 0, 0), V0, I0, pA0);
+    if constexpr (EXT) { if (xp) pA0 = pA0 - ext_wrench(P, e, 0, E0, mk(0, 0, 0)); }
     add_link_inertia(IA0, I0);
     link_ground_points<0, CL>(P, D.mu, S.root_pos.z, E0, mk(0, 0, 0), V0, IA0, pA0, lds, lane, keep);
     if (sel.link == 0) {
@@ -999,11 +1037,11 @@ BEZ_DEV void substep(const Params& P, const EnvDyn& D, EnvState& S, const float*
     }
   }
   SV pS0 = svzero(); SelfSums Z; Z.am = Z.as = 0.f; Z.f2 = selff2;
-  chain_up<1, 2, CL>(P, D, S, target, E0, V0, ball, bc, sel, selfw, IA0, pA0, pS0, Z, lds, lane, keep, e);    // neck, head
-  chain_up<3, 2, CL>(P, D, S, target, E0, V0, ball, bc, sel, selfw, IA0, pA0, pS0, Z, lds, lane, keep, e);    // left arm
-  chain_up<5, 6, CL>(P, D, S, target, E0, V0, ball, bc, sel, selfw, IA0, pA0, pS0, Z, lds, lane, keep, e);    // left leg
-  chain_up<11, 2, CL>(P, D, S, target, E0, V0, ball, bc, sel, selfw, IA0, pA0, pS0, Z, lds, lane, keep, e);   // right arm
-  chain_up<13, 6, CL>(P, D, S, target, E0, V0, ball, bc, sel, selfw, IA0, pA0, pS0, Z, lds, lane, keep, e);   // right leg
+  chain_up<1, 2, CL, EXT>(P, D, S, target, E0, V0, ball, bc, sel, selfw, IA0, pA0, pS0, Z, lds, lane, keep, e, xp);    // neck, head
+  chain_up<3, 2, CL, EXT>(P, D, S, target, E0, V0, ball, bc, sel, selfw, IA0, pA0, pS0, Z, lds, lane, keep, e, xp);    // left arm
+  chain_up<5, 6, CL, EXT>(P, D, S, target, E0, V0, ball, bc, sel, selfw, IA0, pA0, pS0, Z, lds, lane, keep, e, xp);    // left leg
+  chain_up<11, 2, CL, EXT>(P, D, S, target, E0, V0, ball, bc, sel, selfw, IA0, pA0, pS0, Z, lds, lane, keep, e, xp);   // right arm
+  chain_up<13, 6, CL, EXT>(P, D, S, target, E0, V0, ball, bc, sel, selfw, IA0, pA0, pS0, Z, lds, lane, keep, e, xp);   // right leg
   // the leg<->leg contacts' common scale (known before the root solve), then their share of the torso's bias
   const float sc = self_scale(P, Z);
   pA0 = pA0 + pS0 * sc;
@@ -1022,8 +1060,11 @@ BEZ_DEV void substep(const Params& P, const EnvDyn& D, EnvState& S, const float*
   chain_down<5, 6, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e);
   chain_down<11, 2, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e);
   chain_down<13, 6, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e);
-  // (f) ball: Mb ab = -pb - Jb^T fl
-  SV ab = ball_minv(ball, svzero() - ball.pb - wrench_at(sel.xb, fl));
+  // (f) ball: Mb ab = -pb - Jb^T fl (+ its external wrench about the centre: the contact operands above did not foresee it, as they do
+  //     not foresee the leg<->leg forces)
+  SV fb_ext = svzero();
+  if constexpr (EXT) { if (xp) fb_ext = ext_wrench(P, e, BEZ_NL, quat_to_mat(S.bq[0], S.bq[1], S.bq[2], S.bq[3]), mk(0, 0, 0)); }
+  SV ab = ball_minv(ball, fb_ext - ball.pb - wrench_at(sel.xb, fl));
   if (keep) {
     V3 fb = -cf_along(P, fl, sel.n);
     if (ball.ground) fb = fb + cf_ground(P, hit_force(P, ball.ghit, ab));
@@ -1266,7 +1307,9 @@ BEZ_DEV void env_observe_reward(const Params& P, const EnvState& S, CfOut& co, f
 }
 
 // ---- the fused kernel: PRE (targets) / SIM (substeps) / POST (bookkeeping, reset, obs, reward)
-template <bool PRE, bool SIM, bool POST, bool DR, bool CL>
+// EXT (with SIM): the instantiation that reads the pending external wrenches of bez_sim_apply_body_forces and clears them after the
+// last substep (a sim runs these once it has called that function: bez_sim.hip)
+template <bool PRE, bool SIM, bool POST, bool DR, bool CL, bool EXT = false>
 __global__ __launch_bounds__(BLOCK) void step_kernel(Params P) {
   __shared__ float lds[SIM ? LDS_SLOTS * BLOCK : 1];
   const int lane = threadIdx.x;
@@ -1328,9 +1371,15 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(Params P) {
       }
     }
     const bool last_only = (P.flags & BEZ_FLAG_CF_LAST_SUBSTEP) != 0;
+    const bool xp = EXT && ext_pending(P, e);
     for (int s = 0; s < P.substeps; ++s) {
       const bool last = (s == P.substeps - 1);
-      substep<CL>(P, D, S, target, co, lds, lane, last_only ? last : true, last_only ? true : (s == 0), e);
+      substep<CL, EXT>(P, D, S, target, co, lds, lane, last_only ? last : true, last_only ? true : (s == 0), e, xp);
+    }
+    if (EXT && xp) {   // the wrenches were for this launch only
+#pragma unroll 1
+      for (int l = 0; l < EXT_LINKS; ++l) ext_clear(P, e, l);
+      P.ext[(size_t)EXT_FLAG * n + e] = 0.f;
     }
   } else if (POST && !CL) {
     co.lf = mk(co.base[(size_t)(BEZ_LFOOT_BODY * 3 + 0) * n], co.base[(size_t)(BEZ_LFOOT_BODY * 3 + 1) * n], co.base[(size_t)(BEZ_LFOOT_BODY * 3 + 2) * n]);

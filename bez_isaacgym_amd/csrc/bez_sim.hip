@@ -77,6 +77,11 @@ struct BezSim {
   unsigned long long* health = nullptr;  // BEZ_HEALTH_* bits (BEZ_TENSOR_HEALTH)
   unsigned long long* episode_stats = nullptr;  // one allocation: (8,N) i64 BEZ_EPISODE_END_COUNTS, (8,N) f32 BEZ_EPISODE_REWARD_TERMS,
                                                 // (N) i32 BEZ_EPISODE_END_BITS (bez_kernels.h end_counts_of / reward_terms_of / end_bits_of)
+  // external wrenches (bez_sim_apply_body_forces): the pending buffer (bez_kernels.h EXT_*: [link][component][env] + one word per env),
+  // allocated by the first call, which also switches every later physics launch of this sim to the EXT kernel instantiations (sticky:
+  // a graph captured after it keeps consuming what later apply calls leave)
+  float* ext = nullptr;
+  bool ext_on = false;
 };
 
 namespace {
@@ -222,6 +227,7 @@ Params make_params(const BezSim* s, const float* actions) {
   P.nonfinite = s->nonfinite; P.health = s->health;
   P.episode_stats = s->episode_stats;
   P.xhit = (c.flags & BEZ_FLAG_ALL_GROUND_SHAPES) ? s->xhit : nullptr;
+  P.ext = s->ext;
   return P;
 }
 bool has_dr(const BezSim* s) {
@@ -375,6 +381,65 @@ __global__ void set_target_indexed_kernel(float* __restrict__ st, const float* _
   st[(size_t)(F_TARGET + j) * n + e] = src[(size_t)e * BEZ_ND + j];
 }
 
+// ---- bez_sim_apply_body_forces: one thread per env turns the Isaac-layout inputs of its env into the pending per-link wrenches (bez_kernels.h
+// ext_wrench): forward kinematics of the current state for the link frames, LOCAL vectors and every point of application resolved now,
+// fixed bodies folded into their links, everything ADDED to what earlier calls left (read-modify-write by the env's one thread).
+template <bool CL>
+__global__ void ext_prepare_kernel(const float* __restrict__ st, float* __restrict__ ext, const float* __restrict__ F, const float* __restrict__ T,
+                                   const float* __restrict__ X, int local, int n, int has_ball, uint32_t flags) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  EnvState S;
+  load_state(st, n, e, S);
+  M3 E[BEZ_NL]; V3 r[BEZ_NL];
+  E[0] = quat_to_mat(S.rq[0], S.rq[1], S.rq[2], S.rq[3]);
+  r[0] = mk(0, 0, 0);
+  {
+    SV V[BEZ_NL];
+    V[0] = svzero();
+    static_for<BEZ_NL - 1>([&](auto I) {
+      constexpr int L = 1 + decltype(I)::value;
+      constexpr int p = BEZ_LINK_PARENT[L];
+      E[L] = E[p]; r[L] = r[p]; V[L] = V[p];
+      SV Sj, cb;
+      link_kinematics<L>(S.q[L - 1], 0.f, E[L], r[L], V[L], Sj, cb, quirk_rz<CL>(flags));
+    });
+  }
+  constexpr int NB = nb_of<CL>();
+  const int nbe = NB + (has_ball ? 1 : 0);
+  bool any = false;
+  // adds (force fw, torque tw, point p in the frame of link l) to link l's entries
+  auto add = [&](int l, V3 fw, V3 tw, V3 p) {
+    float* x = ext + (size_t)l * EXT_COMP * n + e;
+    const float v[EXT_COMP] = {fw.x, fw.y, fw.z, tw.x, tw.y, tw.z, p.x * fw.x, p.x * fw.y, p.x * fw.z, p.y * fw.x, p.y * fw.y, p.y * fw.z,
+                               p.z * fw.x, p.z * fw.y, p.z * fw.z};
+#pragma unroll
+    for (int k = 0; k < EXT_COMP; ++k) x[(size_t)k * n] += v[k];
+  };
+  auto in3 = [&](const float* a, int b) { const float* q = a + ((size_t)e * nbe + b) * 3; return mk(q[0], q[1], q[2]); };
+  for (int b = 0; b < nbe; ++b) {
+    const V3 f = F ? in3(F, b) : mk(0, 0, 0), t = T ? in3(T, b) : mk(0, 0, 0);
+    if (!(f.x != 0.f || f.y != 0.f || f.z != 0.f || t.x != 0.f || t.y != 0.f || t.z != 0.f)) continue;   // (a NaN is != 0: it goes in)
+    any = true;
+    if (b < NB) {   // a robot body: its link's frame, its origin's offset in that frame, its own centre of mass
+      const int l = CL ? BEZ_BODY_LINK_CL[b] : BEZ_BODY_LINK[b];
+      const double* o = CL ? BEZ_BODY_OFFSET_CL[b] : BEZ_BODY_OFFSET[b];
+      const double* c = CL ? BEZ_BODY_COM_CL[b] : BEZ_BODY_COM[b];
+      const V3 off = mk((float)o[0], (float)o[1], (float)o[2]);
+      V3 p;
+      if (!X) p = off + mk((float)c[0], (float)c[1], (float)c[2]);
+      else if (local) p = off + in3(X, b);
+      else p = mulT(E[l], in3(X, b) - S.root_pos - r[l]);
+      add(l, local ? mul(E[l], f) : f, local ? mul(E[l], t) : t, p);
+    } else {        // the ball: its own frame about its centre
+      const M3 Rb = quat_to_mat(S.bq[0], S.bq[1], S.bq[2], S.bq[3]);
+      const V3 p = !X ? mk(0, 0, 0) : (local ? in3(X, b) : mulT(Rb, in3(X, b) - S.ball_pos));
+      add(BEZ_NL, local ? mul(Rb, f) : f, local ? mul(Rb, t) : t, p);
+    }
+  }
+  if (any) ext[(size_t)EXT_FLAG * n + e] = 1.f;
+}
+
 // Kernel choice for launches that include the physics, fixed per sim at bez_sim_create from BEZ_SIM_KERNEL: "ws8q" = the 8-role-wave
 // kernel in its lane-group form (four lanes per env, 16-env workgroups: bez_step_ws8q.hip), "ws8" = the one-lane form (bez_kernel_ws8.h,
 // 64-env workgroups), "lane" = the one-env-per-lane reference kernel (bez_kernels.h).  Unset: by size -- the lane-group form while its
@@ -432,15 +497,15 @@ int launch_step(BezSim* s, const float* actions, hipStream_t stream, bool obs_on
     // configuration 0.8 % (26.56 -> 26.78 us, same box: six more spilled VGPRs in a kernel at its 256-register ceiling)
     // (the same holds for the scenario harness's contact variants, BEZ_FLAG_ALL_GROUND_SHAPES / BEZ_FLAG_ANKLE_STOP: one-env-per-lane kernel only)
     if (s->kernel != 2 && !(s->cfg.flags & (BEZ_FLAG_FIX_BASE | BEZ_FLAG_ALL_GROUND_SHAPES | BEZ_FLAG_ANKLE_STOP))) {
-      if (s->kernel == 3 || (s->kernel == 0 && s->n <= s->quad_max_envs)) bez::launch_step_ws8q(P, PRE, dr, s->cleats, stream);
-      else bez::launch_step_ws8(P, PRE, dr, s->cleats, stream);
+      if (s->kernel == 3 || (s->kernel == 0 && s->n <= s->quad_max_envs)) bez::launch_step_ws8q(P, PRE, dr, s->cleats, stream, s->ext_on);
+      else bez::launch_step_ws8(P, PRE, dr, s->cleats, stream, s->ext_on);
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) return fail(s, -2, "step_kernel_ws launch", e);
       if (POST) s->obs_calls += 1;
       return 0;
     }
   }
-  bez::launch_step_lane(P, PRE, SIM, POST, dr, s->cleats, stream);
+  bez::launch_step_lane(P, PRE, SIM, POST, dr, s->cleats, stream, s->ext_on);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(s, -2, "step kernel launch", e);
   if (POST) s->obs_calls += 1;
@@ -497,7 +562,7 @@ int bez_sim_destroy(BezSim* s) {
   (void)hipSetDevice(s->device);
   void* bufs[] = {s->state, s->obs, s->rew, s->reset, s->progress, s->timeout, s->episode, s->root_states, s->dof_state,
                   s->rigid_body, s->contact, s->targets_aos, s->prev_aos, s->feet_aos, s->goal_aos, s->goal_draw_dev, s->post_calls_dev, s->randomize, s->dr_state, s->dr_snap, s->dr_pack, s->xhit,
-                  s->nonfinite, s->health, s->episode_stats};
+                  s->nonfinite, s->health, s->episode_stats, s->ext};
   for (void* b : bufs) if (b) (void)hipFree(b);
   for (int i = 0; i < BEZ_PARAM_COUNT; ++i) if (s->dr[i]) (void)hipFree(s->dr[i]);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
@@ -913,6 +978,24 @@ int bez_sim_health(BezSim* s, uint64_t* bits, int32_t clear, void* stream_) {
   HIP_TRY(s, hipStreamSynchronize(stream));
   *bits = (uint64_t)h;
   return 0;
+}
+
+int bez_sim_apply_body_forces(BezSim* s, const float* forces_dev, const float* torques_dev, const float* positions_dev, int32_t space, void* stream_) {
+  if (!s) return -1;
+  if (space != BEZ_SPACE_ENV && space != BEZ_SPACE_LOCAL) return fail(s, -1, "bez_sim_apply_body_forces: space must be BEZ_SPACE_ENV or BEZ_SPACE_LOCAL");
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!s->ext) {   // first call: the pending buffer (zeroed in stream order), and the switch to the EXT kernels for the rest of the sim's life
+    const size_t bytes = (size_t)EXT_WORDS * s->n * sizeof(float);
+    HIP_TRY(s, hipMalloc((void**)&s->ext, bytes));
+    HIP_TRY(s, hipMemsetAsync(s->ext, 0, bytes, stream));
+    s->ext_on = true;
+  }
+  if (!forces_dev && !torques_dev) return 0;
+  const dim3 grid((unsigned)((s->n + 63) / 64)), block(64);
+  if (s->cleats) hipLaunchKernelGGL(ext_prepare_kernel<true>, grid, block, 0, stream, s->state, s->ext, forces_dev, torques_dev, positions_dev, (int)space, s->n, (int)s->has_ball, s->cfg.flags);
+  else hipLaunchKernelGGL(ext_prepare_kernel<false>, grid, block, 0, stream, s->state, s->ext, forces_dev, torques_dev, positions_dev, (int)space, s->n, (int)s->has_ball, s->cfg.flags);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(s, -2, "ext_prepare_kernel launch", e);
 }
 
 int bez_sim_seed(BezSim* s, uint64_t seed) { if (!s) return -1; s->cfg.seed = seed; s->dr_prelaunched = false; return 0; }

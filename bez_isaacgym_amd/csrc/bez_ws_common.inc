@@ -136,9 +136,11 @@ struct ChainDyn { float mu; V3 g; };
 // IAo/pAo), the pass-3 operands p3[LEN], the contact rows of the chain-end link, and (legs) the ball/box candidate.
 // BAR_AFTER >= 0: a workgroup barrier is executed after that link when `bar` is set (the 8-wave kernel's deferred ball update
 // meets the other roles there)
-template <int FIRST, int LEN, bool LEG, bool CL, bool BOX = LEG, int BAR_AFTER = -1>
+// EXT: `xp` = env e has external wrenches pending (bez_sim_apply_body_forces): each link's enters its bias force here, in every substep
+template <int FIRST, int LEN, bool LEG, bool CL, bool BOX = LEG, int BAR_AFTER = -1, bool EXT = false>
 BEZ_DEV void ws_chain_pass1(const Params& P, const ChainDyn& D, const float* ms, const RootView& R, const float* q, const float* qd,
-                            LinkInertia* LI, SV* pAl, SV* Sl, SV* cbl, M3& Eend, V3& rend, SV& Vend, BallSel& sel, SV& Vsel, bool bar = false) {
+                            LinkInertia* LI, SV* pAl, SV* Sl, SV* cbl, M3& Eend, V3& rend, SV& Vend, BallSel& sel, SV& Vsel, bool bar = false,
+                            int e = 0, bool xp = false) {
   M3 E = R.E0;
   V3 r = mk(0, 0, 0);
   SV V = R.V0;
@@ -147,6 +149,7 @@ BEZ_DEV void ws_chain_pass1(const Params& P, const ChainDyn& D, const float* ms,
     constexpr int L = FIRST + i;
     link_kinematics<L>(q[i], qd[i], E, r, V, Sl[i], cbl[i], quirk_rz<CL>(P.flags));
     link_inertia<L, CL>(ms[i], D.g, E, r, V, LI[i], pAl[i]);
+    if constexpr (EXT) { if (xp) pAl[i] = pAl[i] - ext_wrench(P, e, L, E, r); }
     if constexpr (i == BAR_AFTER) { if (bar) ws_barrier(); }
     if constexpr (BOX && link_has_box(L)) {
       test_box<link_box(L)>(E, r, R.bc, sel);

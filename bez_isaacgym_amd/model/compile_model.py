@@ -290,6 +290,7 @@ def build(urdf=None, cleats=False, box=False):
         "num_bodies": len(bodies), "num_links": 19, "num_dofs": 18,
         "body_names": names, "dof_names": dof_names,
         "body_link": link_of_body, "body_offset": body_off,
+        "body_com": [[float(x) for x in links[b["name"]]["com"]] for b in bodies],  # URDF inertial origin of each rigid body, body frame
         "links": [{
             "name": d["name"], "body": d["body"], "parent": d["parent"], "axis": d["axis"], "xyz": d["xyz"],
             "mass": d["mass"], "com": d["com"].tolist(),
@@ -358,6 +359,8 @@ def emit_header(m, mc=None, mb=None, mbc=None):
     o.append("BEZ_TBL double BEZ_LINK_INERTIA[BEZ_NL][6] = {%s};" % ", ".join(arr(l["inertia"]) for l in L))
     o.append("BEZ_TBL int BEZ_BODY_LINK[BEZ_NB] = {%s};" % ", ".join(str(x) for x in m["body_link"]))
     o.append("BEZ_TBL double BEZ_BODY_OFFSET[BEZ_NB][3] = {%s};" % ", ".join(arr(x) for x in m["body_offset"]))
+    o.append("/* centre of mass of each rigid body (URDF inertial origin, body frame): where an external force acts by default */")
+    o.append("BEZ_TBL double BEZ_BODY_COM[BEZ_NB][3] = {%s};" % ", ".join(arr(x) for x in m["body_com"]))
     o.append("BEZ_TBL double BEZ_DOF_LOWER[BEZ_ND] = %s;" % arr(m["dof_lower"]))
     o.append("BEZ_TBL double BEZ_DOF_UPPER[BEZ_ND] = %s;" % arr(m["dof_upper"]))
     o.append("BEZ_TBL double BEZ_DOF_DEFAULT[BEZ_ND] = %s;" % arr(m["dof_default"]))
@@ -384,6 +387,7 @@ def emit_header(m, mc=None, mb=None, mbc=None):
         o.append("BEZ_TBL double BEZ_LINK_INERTIA_CL[BEZ_NL][6] = {%s};" % ", ".join(arr(l["inertia"]) for l in LC))
         o.append("BEZ_TBL int BEZ_BODY_LINK_CL[BEZ_NB_CL] = {%s};" % ", ".join(str(x) for x in mc["body_link"]))
         o.append("BEZ_TBL double BEZ_BODY_OFFSET_CL[BEZ_NB_CL][3] = {%s};" % ", ".join(arr(x) for x in mc["body_offset"]))
+        o.append("BEZ_TBL double BEZ_BODY_COM_CL[BEZ_NB_CL][3] = {%s};" % ", ".join(arr(x) for x in mc["body_com"]))
         o.append("BEZ_TBL double BEZ_PT_POS_CL[BEZ_NPT][3] = {%s};" % ", ".join(arr(p["p"]) for p in mc["ground_points"]))
         o.append("BEZ_TBL int BEZ_PT_BODY_CL[BEZ_NPT] = {%s};" % ", ".join(str(p["body"]) for p in mc["ground_points"]))
     o.append("/* leg self-collision capsules (link-local segment p0-p1, radius) and the left x right pair list */")
@@ -450,7 +454,7 @@ def emit_header(m, mc=None, mb=None, mbc=None):
 def main():
     m = build()
     mc = build(os.path.join(REF, "resources/assets/bez/model/soccerbot_stl_sensor.urdf"), cleats=True)
-    m["cleats"] = {k: mc[k] for k in ("num_bodies", "body_names", "body_link", "body_offset", "links", "ground_points", "total_mass")}
+    m["cleats"] = {k: mc[k] for k in ("num_bodies", "body_names", "body_link", "body_offset", "body_com", "links", "ground_points", "total_mass")}
     mb = build(os.path.join(REF, "resources/assets/bez/model/soccerbot_box.urdf"), box=True)
     mbc = build(os.path.join(REF, "resources/assets/bez/model/soccerbot_box_sensor.urdf"), cleats=True, box=True)
     m["box_asset"] = {"ground_points": mb["ground_points"], "torso_box": mb["boxes"][-1],

@@ -59,6 +59,7 @@ def load_library():
         "bez_sim_health": (C.c_int, [vp, C.POINTER(u64), i32, vp]),
         "bez_sim_calibrate": (C.c_int, [vp, u64, i32, vp]),
         "bez_sim_time_steps": (C.c_int, [vp, fp, i32, vp, C.POINTER(C.c_float)]),
+        "bez_sim_apply_body_forces": (C.c_int, [vp, fp, fp, fp, i32, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -73,7 +74,7 @@ EXPORTS = ["bez_sim_default_config", "bez_sim_create", "bez_sim_destroy", "bez_s
            "bez_sim_set_net_contact_force_tensor", "bez_sim_set_prev_lin_vel_tensor", "bez_sim_set_goal_tensor", "bez_sim_set_flags",
            "bez_sim_set_obs_calls", "bez_sim_pre_physics", "bez_sim_simulate", "bez_sim_post_physics", "bez_sim_observe_reward", "bez_sim_step",
            "bez_sim_step_many", "bez_sim_reset_indexed", "bez_sim_set_env_params", "bez_sim_get_env_params", "bez_sim_set_randomization", "bez_sim_dr_prelaunch", "bez_sim_dr_step_args", "bez_sim_dr_cancel", "bez_sim_action_noise_source", "bez_sim_add_dr_noise", "bez_sim_seed", "bez_sim_time_steps",
-           "bez_sim_calibrate", "bez_sim_health", "bez_sim_get_episode_tensor"]
+           "bez_sim_calibrate", "bez_sim_health", "bez_sim_get_episode_tensor", "bez_sim_apply_body_forces"]
 # (the bez_ppo_* entry points of the same library are bound in ppo/fused.py)
 
 
@@ -193,6 +194,26 @@ class BezSim:
 
     def set_flags(self, flags):
         self._check(self.lib.bez_sim_set_flags(self.h, int(flags)))
+
+    # ---- gym.apply_rigid_body_force_tensors / apply_rigid_body_force_at_pos_tensors
+    def apply_body_forces(self, forces=None, torques=None, positions=None, space=abi.SPACE_ENV):
+        """External forces / torques on the rigid bodies for the NEXT physics launch only (include/bez_sim.h: bez_sim_apply_body_forces).
+        Each tensor: float32 on the sim's device, contiguous, (N*B, 3) or (N, B, 3) in RIGID_BODY_STATE order, or None.  `space`:
+        abi.SPACE_ENV / abi.SPACE_LOCAL or "env" / "local".  Everything is checked before the library is called."""
+        space = abi.body_force_space(space)
+        n = self.num_envs * self.num_bodies * 3
+        ptrs = []
+        for name, t in (("forces", forces), ("torques", torques), ("positions", positions)):
+            if t is None:
+                ptrs.append(None)
+                continue
+            if not isinstance(t, torch.Tensor):
+                raise BezSimError("%s: expected a torch tensor, got %s" % (name, type(t).__name__))
+            if tuple(t.shape) not in ((self.num_envs * self.num_bodies, 3), (self.num_envs, self.num_bodies, 3)):
+                raise BezSimError("%s: expected shape (%d, 3) or (%d, %d, 3), got %s" % (name, self.num_envs * self.num_bodies, self.num_envs,
+                                                                                         self.num_bodies, tuple(t.shape)))
+            ptrs.append(self._ptr(t, torch.float32, n))
+        self._check(self.lib.bez_sim_apply_body_forces(self.h, ptrs[0], ptrs[1], ptrs[2], space, self._stream()))
 
     # ---- the non-finite guard (abi.FLAG_NONFINITE_GUARD)
     def health(self, clear=False):

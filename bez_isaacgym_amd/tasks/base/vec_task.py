@@ -204,6 +204,20 @@ class VecTask(Env):
     def get_number_of_agents(self):
         return self.num_agents
 
+    # ---- external forces: gym.apply_rigid_body_force_tensors / gym.apply_rigid_body_force_at_pos_tensors.  Tensors (N*B, 3) or (N, B, 3)
+    # float32 on the sim's device in RIGID_BODY_STATE order; space "env" / "local" (or abi.SPACE_ENV / abi.SPACE_LOCAL).  They act during
+    # the next physics launch only (with controlFrequencyInv = k: the first of the k simulate calls) and several calls add up
+    # (include/bez_sim.h: bez_sim_apply_body_forces).
+    def apply_rigid_body_force_tensors(self, forces=None, torques=None, space="env"):
+        """Forces at each body's centre of mass and torques on the bodies."""
+        self.sim.apply_body_forces(forces=forces, torques=torques, positions=None, space=space)
+        return True
+
+    def apply_rigid_body_force_at_pos_tensors(self, forces, positions=None, space="env"):
+        """Forces at the given points (world coordinates in "env" space, body frame in "local" space; None = the centres of mass)."""
+        self.sim.apply_body_forces(forces=forces, torques=None, positions=positions, space=space)
+        return True
+
     # ---- domain randomisation (vec_task.py:505-725), device-side: bez_sim_set_randomization
     # ---- hooks for a trainer that drives the randomised env at full speed (ppo/a2c_continuous.py): both default to "the env does it"
     external_action_noise = False   # True: the caller adds the action noise itself (action_noise_source), step() must not add it again

@@ -303,6 +303,29 @@ int bez_sim_step_many(BezSim* sim, const float* actions_dev, int32_t n_steps, vo
 /* KickEnv.reset_idx (kick_env.py:779-850) for the env ids in env_ids_dev. */
 int bez_sim_reset_indexed(BezSim* sim, const int32_t* env_ids_dev, int32_t n, void* stream);
 
+/* gym.apply_rigid_body_force_tensors / gym.apply_rigid_body_force_at_pos_tensors: external forces and torques on the rigid bodies,
+ * for the NEXT physics launch (bez_sim_simulate, bez_sim_step, the first step of bez_sim_step_many) only -- they act through all of
+ * its substeps and are then cleared on the device.  Several calls before one launch add up.
+ *   forces_dev / torques_dev / positions_dev: fp32 (N*B, 3) in RIGID_BODY_STATE order (B = 22 for bez_kick, 21 for bez_walk /
+ *   bez_orient; 30 / 29 with cleats); any of them may be NULL (no force / no torque / forces at each body's centre of mass).
+ *   space: BEZ_SPACE_ENV -- vectors in world axes (each env is its own world), points in world coordinates;
+ *          BEZ_SPACE_LOCAL -- vectors and points in the body's own frame.
+ * Resolution: a force or torque given in world axes stays fixed in world axes across the substeps.  A BEZ_SPACE_LOCAL force or torque
+ * and every point of application are resolved ONCE, in this call, against the body poses then on `stream` (the state the launches
+ * enqueued before it leave); from there the world-axis vector stays fixed and the point moves with its body.  A force at a point acts
+ * on the body as that force at the body's centre of mass plus its moment.  Fixed bodies (imu_link, camera, the cleats) add their wrench
+ * to the dynamic link they are merged into.  Centres of mass: each rigid body's own URDF inertial origin (BEZ_BODY_COM).
+ * The NET_CONTACT_FORCE rows, the feet flags and the reward terms stay contact-only; a non-finite input makes the env's state
+ * non-finite, which the non-finite guard handles as any other (BEZ_FLAG_NONFINITE_GUARD).
+ * The first call switches the sim, for the rest of its life, to step-kernel instantiations that read the pending wrenches (a captured
+ * graph keeps the kernels it was captured with; a sim that never calls this launches the kernels it always did).  The call allocates
+ * its buffer on first use; after that it allocates nothing, never synchronises and reads no device data on the host: it can be
+ * captured into a HIP graph. */
+#define BEZ_SPACE_ENV 0
+#define BEZ_SPACE_LOCAL 1
+int bez_sim_apply_body_forces(BezSim* sim, const float* forces_dev, const float* torques_dev, const float* positions_dev, int32_t space,
+                              void* stream);
+
 /* Domain randomisation parameters (vec_task.py:505-725 -> per-env arrays read by the kernel).
  * values_dev: (N, count) fp32 where count is fixed per param; NULL restores the default. */
 enum BezEnvParam {
