@@ -30,6 +30,13 @@ FLAG_ALL_GROUND_SHAPES = 2048   # scenario harness: ground contact at every coll
 FLAG_FIX_BASE = 4096            # urdfAsset.fixBaseLink: the torso welded to the world
 FLAG_NONFINITE_GUARD = 8192     # per-env non-finite guard of the post-physics (on by default; include/bez_sim.h)
 FLAG_REWARD_TERMS = 16384       # env.debug.rewards: per-env sums of the reward's terms (EPISODE_REWARD_TERMS; off by default)
+FLAG_DOF_FORCE = 32768          # env.enableDofForceSensors: the step kernels record joint forces / drive torques / actuator status (off by default)
+# actuator tensors (include/bez_sim.h BezActuatorTensor, BezSim.actuator_tensor), DOF_STATE order, present with FLAG_DOF_FORCE only
+ACTUATOR_DOF_FORCE, ACTUATOR_DRIVE_TORQUE, ACTUATOR_STATUS, ACTUATOR_TENSORS = range(4)
+ACTUATOR_SATURATED_POS, ACTUATOR_SATURATED_NEG, ACTUATOR_LOCKED_POS, ACTUATOR_LOCKED_NEG = 1, 2, 4, 8
+ACTUATOR_SATURATED = ACTUATOR_SATURATED_POS | ACTUATOR_SATURATED_NEG
+ACTUATOR_LOCKED = ACTUATOR_LOCKED_POS | ACTUATOR_LOCKED_NEG
+DOF_FORCE_KEY = "env.enableDofForceSensors"   # this build's task key for FLAG_DOF_FORCE (default False)
 SPACE_ENV = 0                   # bez_sim_apply_body_forces: world axes / world points (gymapi.ENV_SPACE)
 SPACE_LOCAL = 1                 # the body's own frame (gymapi.LOCAL_SPACE)
 HEALTH_NONFINITE = 1            # health word bits (TENSOR_HEALTH, BezSim.health)
@@ -216,6 +223,10 @@ def refuse_unmodelled(cfg):
     # k simulate calls per env step, taken by KickEnv._fused_step through the split entry points
     cfi = int(env.get("controlFrequencyInv", 1))
     no(cfi < 1, "env.controlFrequencyInv", cfi, "must be >= 1")
+    # this build's key for gym.enable_actor_dof_force_sensors: a switch, nothing else
+    dfs = env.get("enableDofForceSensors", False)
+    if not isinstance(dfs, bool):
+        raise ValueError("task config: %s = %r must be True or False" % (DOF_FORCE_KEY, dfs))
 
 
 def config_from_task_cfg(cfg, seed=42, env_id_offset=0, strict_reference_quirks=True, task="bez_kick"):
@@ -249,6 +260,8 @@ def config_from_task_cfg(cfg, seed=42, env_id_offset=0, strict_reference_quirks=
         c.flags |= FLAG_NONFINITE_GUARD
     if (env.get("debug") or {}).get("rewards", False):  # bez_kick.yaml:125-126 env.debug.rewards: the reward's terms per env (kick_env.py:584-600)
         c.flags |= FLAG_REWARD_TERMS
+    if env.get("enableDofForceSensors", False):  # not a key of the reference's yaml (it enables the sensors in code, kick_env.py:368,375)
+        c.flags |= FLAG_DOF_FORCE
     if env.get("asset", {}).get("cleats", False):
         c.flags |= FLAG_CLEATS
     if not env.get("asset", {}).get("stl", True):  # kick_env.py:266-276: soccerbot_box*.urdf
@@ -256,6 +269,18 @@ def config_from_task_cfg(cfg, seed=42, env_id_offset=0, strict_reference_quirks=
     if env.get("urdfAsset", {}).get("fixBaseLink", False):  # kick_env.py:287
         c.flags |= FLAG_FIX_BASE
     return c
+
+
+def actuator_tensor_id(which):
+    """ACTUATOR_DOF_FORCE / ACTUATOR_DRIVE_TORQUE / ACTUATOR_STATUS from the int or from "dof_force" / "drive_torque" / "status"."""
+    names = {"dof_force": ACTUATOR_DOF_FORCE, "drive_torque": ACTUATOR_DRIVE_TORQUE, "status": ACTUATOR_STATUS}
+    if isinstance(which, str):
+        if which.strip().lower() not in names:
+            raise ValueError("actuator tensor must be one of %s, got %r" % (sorted(names), which))
+        return names[which.strip().lower()]
+    if isinstance(which, bool) or not isinstance(which, int) or not 0 <= which < ACTUATOR_TENSORS:
+        raise ValueError("actuator tensor id must be in [0, %d), got %r" % (ACTUATOR_TENSORS, which))
+    return int(which)
 
 
 def body_force_space(space):

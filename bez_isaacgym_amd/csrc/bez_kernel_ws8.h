@@ -354,19 +354,25 @@ BEZ_DEV void leg_role(const Params& P, float* lds, int lane, int e, bool active,
     const Quad Q = quad_of(lane);
     P3q p3[LEN];
     V3 pA;
+#ifdef BEZ_DOF_FORCE
+    uint32_t dfw = 0u;   // the joints' decision bits (actuator record)
+#endif
     {
       Blk M;
-      wq_chain_pass2<FIRST, LEN, (!CL && !DR)>(P, Q, lds, lane, side, s + 1, kps, kds, lo, hi, q, qd, target, LI, pAl, Sl, cbl, Kc, pc, mine, sel, p3, M, pA);
+      wq_chain_pass2<FIRST, LEN, (!CL && !DR)>(P, Q, lds, lane, side, s + 1, kps, kds, lo, hi, q, qd, target, LI, pAl, Sl, cbl, Kc, pc, mine, sel, p3, M, pA BEZ_DF_WORD_ARG);
 #pragma unroll
       for (int i = 0; i < 9; ++i) XS(X_IA + side * 27 + i) = M.m[i];   // the block, in the quad's layout (wq_add_leg_block)
     }
     WS_STAMP(side, 24 + s);
     ws_barrier();  // B1c: both helper parts' leg<->leg contact wrenches are in LDS
-    const float sc = wq_chain_self_correction<LEN, CL>(P, Q, lds, lane, side, s + 1, p3, pA, X_IA + side * 27 + 9);
+    const float sc = wq_chain_self_correction<LEN, CL>(P, Q, lds, lane, side, s + 1, p3, pA, X_IA + side * 27 + 9 BEZ_DF_WORD_ARG);
 #else
     P3 p3[LEN];
     Sym6 IA = sym6zero(); SV pA = svzero();
-    ws_chain_pass2<FIRST, LEN, true>(P, D, kps, kds, lo, hi, q, qd, target, LI, pAl, Sl, cbl, Kc, pc, mine, sel, p3, IA, pA);
+#ifdef BEZ_DOF_FORCE
+    uint32_t dfw = 0u;   // the joints' decision bits (actuator record)
+#endif
+    ws_chain_pass2<FIRST, LEN, true>(P, D, kps, kds, lo, hi, q, qd, target, LI, pAl, Sl, cbl, Kc, pc, mine, sel, p3, IA, pA BEZ_DF_WORD_ARG);
     {  // the chain's articulated inertia goes to its X_IA block NOW (free since B1: the staged actions are consumed): 21 registers
        // less across the barrier and the correction below; the bias follows once the leg<->leg share is in it
       const float* f = (const float*)&IA;
@@ -375,7 +381,7 @@ BEZ_DEV void leg_role(const Params& P, float* lds, int lane, int e, bool active,
     }
     WS_STAMP(side, 24 + s);
     ws_barrier();  // B1c: both helper parts' leg<->leg contact wrenches are in LDS
-    const float sc = ws_chain_self_correction<LEN, CL>(P, lds, lane, side, s + 1, p3, pA);   // (stores the bias part of the chain's X_IA block)
+    const float sc = ws_chain_self_correction<LEN, CL>(P, lds, lane, side, s + 1, p3, pA BEZ_DF_WORD_ARG);   // (stores the bias part of the chain's X_IA block)
 #endif
     WS_STAMP(side, 4 + 8 * s);
     ws_barrier();  // B2
@@ -387,12 +393,23 @@ BEZ_DEV void leg_role(const Params& P, float* lds, int lane, int e, bool active,
 #pragma unroll
     for (int i = 0; i < LEN; ++i) { q[i] = XS(X_LEGQ + side * 12 + i); qd[i] = XS(X_LEGQ + side * 12 + 6 + i); }
     V3 fl = mk(0, 0, 0), fend = mk(0, 0, 0);
+#ifdef BEZ_DOF_FORCE
+    if (DR) {   // the per-env gains and limits again, in front of their second use (as in front of pass 2: not kept alive across the barriers)
+      int ei = e;
+      asm volatile("" : "+v"(ei));
+      load_joint_params<FIRST, LEN, DR>(P, ei, kps, kds, ms, lo, hi);
+    }
+#define BEZ_DF_P3_ARGS , dfw, kps, kds, lo, hi, target, e, s, active
+#else
+#define BEZ_DF_P3_ARGS
+#endif
 #if BEZ_WS_SUB == 4
-    SV aend = wq_chain_pass3<FIRST, LEN, CL>(P, Q, p3, q, qd, mine, sel, fl, fend, lds, lane, keep, first, sc);
+    SV aend = wq_chain_pass3<FIRST, LEN, CL>(P, Q, p3, q, qd, mine, sel, fl, fend, lds, lane, keep, first, sc BEZ_DF_P3_ARGS);
 #else
     SV a0 = xs_load_sv(lds, lane, X_A0);
-    SV aend = ws_chain_pass3<FIRST, LEN, true, CL>(P, a0, p3, q, qd, mine, sel, fl, fend, lds, lane, keep, first, sc);
+    SV aend = ws_chain_pass3<FIRST, LEN, true, CL>(P, a0, p3, q, qd, mine, sel, fl, fend, lds, lane, keep, first, sc BEZ_DF_P3_ARGS);
 #endif
+#undef BEZ_DF_P3_ARGS
     if (mine && sel.link >= 0) { xs_store_v3(lds, lane, X_FL, fl); xs_store_v3(lds, lane, X_FL + 3, sel.xb); }
     if (keep) {
       if constexpr (CL) {  // the foot plate only feels the ball / the other leg; the ground acts on the four cleats
@@ -426,6 +443,9 @@ template <int FIRST, int BLOCK_IA, bool CL, bool EXT = false>
 struct Chain2 {
   float q[2], qd[2], target[2], kps[2], kds[2], ms[2], lo[2], hi[2];
   P3 p3[2];
+#ifdef BEZ_DOF_FORCE
+  uint32_t dfw;   // the two joints' decision bits (actuator record)
+#endif
   BodyContact bcn;
   Sym6 IAc; SV pAc;  // the chain's contribution as seen by the torso (also stored to its X_IA block)
   BEZ_DEV void up(const Params& P, const ChainDyn& D, float* lds, int lane, int e = 0, bool xp = false) {  // passes 1 + 2, contribution -> X_IA block
@@ -436,7 +456,10 @@ struct Chain2 {
     Sym6 Kc = sym6zero(); SV pc = svzero();
     ws_ground_points<FIRST + 1, CL>(P, D.mu, R.root_z, Ee, re, Ve, Kc, pc);
     Sym6 IA = sym6zero(); SV pA = svzero();
-    ws_chain_pass2<FIRST, 2, false>(P, D, kps, kds, lo, hi, q, qd, target, LI, pAl, Sl, cbl, Kc, pc, false, nosel, p3, IA, pA);
+#ifdef BEZ_DOF_FORCE
+    dfw = 0u;
+#endif
+    ws_chain_pass2<FIRST, 2, false>(P, D, kps, kds, lo, hi, q, qd, target, LI, pAl, Sl, cbl, Kc, pc, false, nosel, p3, IA, pA BEZ_DF_WORD_ARG);
     bcn = body_contact_of(Kc, pc);
     IAc = IA; pAc = pA;
     xs_store_sym6(lds, lane, X_IA + BLOCK_IA * 27, IA, pA);
@@ -444,11 +467,20 @@ struct Chain2 {
   BEZ_DEV void ext_done(const Params& P, int e, bool xp, bool active) {   // the chain's wrenches were for this launch only
     if (EXT && xp && active) { ext_clear(P, e, FIRST); ext_clear(P, e, FIRST + 1); }
   }
-  BEZ_DEV void down(const Params& P, float* lds, int lane, bool keep, bool first) {  // pass 3 + the chain-end contact row
+#ifdef BEZ_DOF_FORCE
+#define BEZ_DF_C2_PARAMS , int e, int sub, bool active
+#define BEZ_DF_C2_ARGS , e, s, active
+#define BEZ_DF_C2_P3 , dfw, kps, kds, lo, hi, target, e, sub, active
+#else
+#define BEZ_DF_C2_PARAMS
+#define BEZ_DF_C2_ARGS
+#define BEZ_DF_C2_P3
+#endif
+  BEZ_DEV void down(const Params& P, float* lds, int lane, bool keep, bool first BEZ_DF_C2_PARAMS) {  // pass 3 + the chain-end contact row
     BallSel nosel; nosel.link = -1; nosel.depth = 0.f; nosel.n = nosel.P = nosel.f0p = nosel.x = nosel.xb = mk(0, 0, 0); nosel.A = sym3zero();
     SV a0 = xs_load_sv(lds, lane, X_A0);
     V3 fl = mk(0, 0, 0), fend = mk(0, 0, 0);
-    SV ae = ws_chain_pass3<FIRST, 2, false, CL>(P, a0, p3, q, qd, false, nosel, fl, fend, lds, lane, keep, first);
+    SV ae = ws_chain_pass3<FIRST, 2, false, CL>(P, a0, p3, q, qd, false, nosel, fl, fend, lds, lane, keep, first, 0.f BEZ_DF_C2_P3);
     if (keep) ws_cf_acc(lds, lane, link_body<CL>(FIRST + 1), cf_ground(P, body_contact_force(bcn, ae)), P.cf_w, first);
   }
 };
@@ -485,7 +517,7 @@ BEZ_DEV void head_role(const Params& P, float* lds, int lane, int e, bool active
     ws_barrier();  // B1c: head and arm blocks are in LDS (role 4 sums them into block 2 before B2)
     ws_barrier();  // B2
     ws_barrier();  // B3
-    C.down(P, lds, lane, keep, first);
+    C.down(P, lds, lane, keep, first BEZ_DF_C2_ARGS);
     ws_barrier();  // B4
   }
   C.ext_done(P, e, xp, active);
@@ -543,7 +575,7 @@ BEZ_DEV void cand_arm_role(const Params& P, float* lds, int lane, int e, bool ac
     }
     ws_barrier();  // B2
     ws_barrier();  // B3
-    C.down(P, lds, lane, keep, first);
+    C.down(P, lds, lane, keep, first BEZ_DF_C2_ARGS);
     ws_barrier();  // B4
   }
   C.ext_done(P, e, xp, active);
@@ -937,7 +969,11 @@ BEZ_DEV void root_role(const Params& P, float* lds, int lane, int e, bool active
 // ---- the kernel.  grid = ceil(N / 64) workgroups of 512 threads.
 // EXT: the instantiation that reads (and, behind the last substep, clears) the pending external wrenches of bez_sim_apply_body_forces
 template <bool PRE, bool POST, bool DR, bool CL, bool EXT = false>
+#ifdef BEZ_DOF_FORCE
+__global__ __launch_bounds__(WS_BLOCK) void step_kernel_ws8(ParamsDF P) {
+#else
 __global__ __launch_bounds__(WS_BLOCK) void step_kernel_ws8(Params P) {
+#endif
   __shared__ __attribute__((aligned(16))) float lds[WS_LDS_FLOATS];
   const int tid = threadIdx.x;
   const int lane = tid & 63;

@@ -36,7 +36,11 @@ enum : int {
 };
 
 // ---- LDS slots per lane
+#ifdef BEZ_DOF_FORCE
+constexpr int P3_STRIDE = 23;                       // ... + the actuator record's decision word, reaction constant / ankle-stop torque, ankle-stop stiffness (df_record)
+#else
 constexpr int P3_STRIDE = 20;                       // UD(6) uD(1) S(6) cb(6) per joint + the leg<->leg contacts' share of uD (1)
+#endif
 constexpr int LDS_P3 = 0;                           // 18 joints
 constexpr int LDS_HIT = LDS_P3 + BEZ_ND * P3_STRIDE;  // ground-point records, 8 floats each
 constexpr int HIT_STRIDE = 8;                       // x(3) fn0 kn ct ftx0 fty0
@@ -305,6 +309,47 @@ struct EnvDyn {
   V3 g;
   float kp_scale[BEZ_ND], kd_scale[BEZ_ND], mass_scale[BEZ_NL], lo[BEZ_ND], hi[BEZ_ND];
 };
+
+#ifdef BEZ_DOF_FORCE
+// ---- actuator record (BEZ_FLAG_DOF_FORCE; include/bez_sim.h "Actuator tensors").  The translation units built with BEZ_DOF_FORCE
+// (bez_step_*_df.hip) compile the same kernels under other names with this code in them; their kernel argument is a Params with the raw
+// buffer behind it: [substep][quantity: drive torque, net joint force, status word][dof][env], written by the env's owning lane right
+// behind pass 3 of each joint (plain stores, nothing loaded or waited for); bez_sim_refresh_actuator_tensors reduces it.
+struct ParamsDF : Params { float* dof_force; };
+BEZ_DEV float* df_buf(const Params& P) { return static_cast<const ParamsDF&>(P).dof_force; }
+// the decision word pass 2 hands to pass 3 (the status bits of BEZ_ACTUATOR_STATUS)
+constexpr uint32_t DF_SAT_POS = 1u, DF_SAT_NEG = 2u, DF_LOCK_POS = 4u, DF_LOCK_NEG = 8u, DF_LOCK = DF_LOCK_POS | DF_LOCK_NEG;
+// One joint, one substep.  (q0, qd0) = the joint state at the start of the substep, qdd = the acceleration pass 3 solved;
+// react = the constraint's reaction S.pA + U.(a_parent + c) + (J + armature) qdd of a speed-limit-locked joint (formed by the caller from
+// pass 2's quantities); stop_tau / stop_k = the ankle stop's explicit torque and implicit stiffness on this joint (0 elsewhere).
+BEZ_DEV void df_record(const Params& P, int e, int sub, int d, uint32_t bits, float kp_scale, float kd_scale, float lo, float hi, float q0, float qd0, float target,
+                       float qdd, float react, float stop_tau = 0.f, float stop_k = 0.f) {
+  const float vn = fmaf(P.h, qdd, qd0), qn = fmaf(P.h, vn, q0);   // the integrator's own expressions: bit for bit the stored state
+  const float kp = P.kp * kp_scale, kdm = P.kd * kd_scale;
+  float drive = fmaf(kp, target - qn, -kdm * vn);
+  drive = (bits & DF_SAT_POS) ? P.effort : ((bits & DF_SAT_NEG) ? -P.effort : drive);
+  const float cf = P.jfric * frcp(fmaxf(fabsf(qd0), P.jf_veps));
+  float tl = fmaf(-stop_k, qdd, stop_tau);
+  if (q0 < lo) tl += fmaf(P.lim_k, lo - qn, -P.lim_d * vn);
+  else if (q0 > hi) tl += fmaf(P.lim_k, hi - qn, -P.lim_d * vn);
+  const float net = (bits & DF_LOCK) ? react : fmaf(-cf, vn, drive) + tl;
+  asm volatile("" : "+v"(e));   // the store addresses are formed here, not carried through the physics
+  const size_t n = (size_t)P.n;
+  float* o = df_buf(P) + ((size_t)sub * 3 * BEZ_ND + d) * n + e;
+  o[0] = drive; o[(size_t)BEZ_ND * n] = net; o[(size_t)2 * BEZ_ND * n] = __uint_as_float(bits);
+}
+#define BEZ_DF_JOINT_OUT , uint32_t& dfb, float& dfc0
+#define BEZ_DF_STOP_PARAMS float stop_tau, float stop_k, uint32_t& dfb, float& dfc0
+#define BEZ_DF_SUB_PARAM , int sub = 0
+#define BEZ_DF_DOWN_PARAMS , const EnvDyn& D, const float* target, int sub
+#define BEZ_DF_DOWN_ARGS , D, target, sub
+#else
+#define BEZ_DF_JOINT_OUT
+#define BEZ_DF_STOP_PARAMS float stop_tau = 0.f, float stop_k = 0.f
+#define BEZ_DF_SUB_PARAM
+#define BEZ_DF_DOWN_PARAMS
+#define BEZ_DF_DOWN_ARGS
+#endif
 
 // ---- contact: implicit spring-damper at a point against the ground plane z = 0.
 // Folds the point's implicit stiffness into (IA, pA) of its body and returns the hit record.
@@ -699,7 +744,7 @@ BEZ_DEV constexpr bool link_has_xpoints(int l) {
 // acceleration that puts it ON the limit -- same recursion, and the reaction reaches the parent through pA (oracle: dynamics_x).
 template <int L>
 BEZ_DEV void joint_terms(const Params& P, float kp_scale, float kd_scale, float lo, float hi, float q, float qd, float target, const Sym6& IA, SV pA,
-                         SV S, SV cb, SV& U, float& g, float& w, float& qdd_hp, float stop_tau = 0.f, float stop_k = 0.f) {
+                         SV S, SV cb, SV& U, float& g, float& w, float& qdd_hp, BEZ_DF_STOP_PARAMS) {
   U = mul(IA, S);
   float J = dot(S, U) + P.armature;
   float kp = P.kp * kp_scale, kdm = P.kd * kd_scale;
@@ -727,6 +772,11 @@ BEZ_DEV void joint_terms(const Params& P, float kp_scale, float kd_scale, float 
   const float ahi = (P.vel_limit - qd) * P.inv_h, alo = (-P.vel_limit - qd) * P.inv_h;
   const float fix = fminf(fmaxf(qdd_hp, alo), ahi);
   const bool lock = fix != qdd_hp;
+#ifdef BEZ_DOF_FORCE
+  // the decisions of this joint, and the part of a locked joint's reaction that is known here: S.pA + (J + armature) qdd (the caller adds U.(a_parent + c))
+  dfb = (tau_drive > P.effort ? DF_SAT_POS : 0u) | (tau_drive < -P.effort ? DF_SAT_NEG : 0u) | (lock ? (fix > qdd_hp ? DF_LOCK_NEG : DF_LOCK_POS) : 0u);
+  dfc0 = fmaf(J, fix, sp);
+#endif
   w = lock ? fix : w; g = lock ? 0.f : g; qdd_hp = fix;
 }
 
@@ -734,7 +784,7 @@ BEZ_DEV void joint_terms(const Params& P, float kp_scale, float kd_scale, float 
 // ucb = (IA S).cb across a quad of lanes; the same arithmetic in the same order as above.
 template <int L>
 BEZ_DEV void joint_scalar(const Params& P, float kp_scale, float kd_scale, float lo, float hi, float q, float qd, float target, float Jraw, float sp, float ucb,
-                          float& g, float& w, float& qdd_hp) {
+                          float& g, float& w, float& qdd_hp BEZ_DF_JOINT_OUT) {
   float J = Jraw + P.armature;
   float kp = P.kp * kp_scale, kdm = P.kd * kd_scale;
   float tau_pd0 = fmaf(kp, target - q - P.h * qd, -kdm * qd);
@@ -757,6 +807,11 @@ BEZ_DEV void joint_scalar(const Params& P, float kp_scale, float kd_scale, float
   const float ahi = (P.vel_limit - qd) * P.inv_h, alo = (-P.vel_limit - qd) * P.inv_h;
   const float fix = fminf(fmaxf(qdd_hp, alo), ahi);
   const bool lock = fix != qdd_hp;
+#ifdef BEZ_DOF_FORCE
+  // the decisions of this joint, and the part of a locked joint's reaction that is known here: S.pA + (J + armature) qdd (the caller adds U.(a_parent + c))
+  dfb = (tau_drive > P.effort ? DF_SAT_POS : 0u) | (tau_drive < -P.effort ? DF_SAT_NEG : 0u) | (lock ? (fix > qdd_hp ? DF_LOCK_NEG : DF_LOCK_POS) : 0u);
+  dfc0 = fmaf(J, fix, sp);
+#endif
   w = lock ? fix : w; g = lock ? 0.f : g; qdd_hp = fix;
 }
 
@@ -857,8 +912,15 @@ BEZ_DEV void chain_up(const Params& P, const EnvDyn& D, const EnvState& S, const
     }
     if constexpr (!CL && link_has_xpoints(L)) { if (P.xhit) link_xpoints_fold<L>(P, e, IA, pA); }
     SV U; float Dinv, uD, qhp;
+#ifdef BEZ_DOF_FORCE
+    uint32_t dfb; float dfc0;
+    const float dstop_tau = (LEG && i >= 4) ? stop_tau[i >= 4 ? i - 4 : 0] : 0.f, dstop_k = (LEG && i >= 4) ? stop_k[i >= 4 ? i - 4 : 0] : 0.f;
+    joint_terms<L>(P, D.kp_scale[L - 1], D.kd_scale[L - 1], D.lo[L - 1], D.hi[L - 1], S.q[L - 1], S.qd[L - 1], target[L - 1], IA, pA, Sl[i], cbl[i], U,
+                   Dinv, uD, qhp, dstop_tau, dstop_k, dfb, dfc0);
+#else
     joint_terms<L>(P, D.kp_scale[L - 1], D.kd_scale[L - 1], D.lo[L - 1], D.hi[L - 1], S.q[L - 1], S.qd[L - 1], target[L - 1], IA, pA, Sl[i], cbl[i], U,
                    Dinv, uD, qhp, (LEG && i >= 4) ? stop_tau[i >= 4 ? i - 4 : 0] : 0.f, (LEG && i >= 4) ? stop_k[i >= 4 ? i - 4 : 0] : 0.f);
+#endif
     SV UD = U * Dinv;
     const float duD = -dot(Sl[i], pS) * Dinv;
     if constexpr (FIRST == 5 || FIRST == 13) {   // only the legs carry leg<->leg contacts
@@ -871,6 +933,15 @@ BEZ_DEV void chain_up(const Params& P, const EnvDyn& D, const EnvState& S, const
     p3[7 * BLOCK] = Sl[i].a.x; p3[8 * BLOCK] = Sl[i].a.y; p3[9 * BLOCK] = Sl[i].a.z; p3[10 * BLOCK] = Sl[i].l.x; p3[11 * BLOCK] = Sl[i].l.y; p3[12 * BLOCK] = Sl[i].l.z;
     p3[13 * BLOCK] = cbl[i].a.x; p3[14 * BLOCK] = cbl[i].a.y; p3[15 * BLOCK] = cbl[i].a.z; p3[16 * BLOCK] = cbl[i].l.x; p3[17 * BLOCK] = cbl[i].l.y; p3[18 * BLOCK] = cbl[i].l.z;
     p3[19 * BLOCK] = duD;
+#ifdef BEZ_DOF_FORCE
+    // actuator record: a locked joint (1/D = 0: the six U/D slots and the contacts' share would hold zeros) hands pass 3 U itself and
+    // S.pS instead -- chain_down reads them as zeros for the dynamics -- with its decision word and the reaction's known part
+    if (dfb & DF_LOCK) {
+      p3[0 * BLOCK] = U.a.x; p3[1 * BLOCK] = U.a.y; p3[2 * BLOCK] = U.a.z; p3[3 * BLOCK] = U.l.x; p3[4 * BLOCK] = U.l.y; p3[5 * BLOCK] = U.l.z;
+      p3[19 * BLOCK] = dot(Sl[i], pS);
+    }
+    p3[20 * BLOCK] = __uint_as_float(dfb); p3[21 * BLOCK] = (dfb & DF_LOCK) ? dfc0 : dstop_tau; p3[22 * BLOCK] = dstop_k;
+#endif
     // Ia = IA - U U^T / D ;  pa = pA + Ia c + U u / D
     add_outer(IA, U, -Dinv);
     pA = pA + mul(IA, cbl[i]) + U * uD;
@@ -885,7 +956,7 @@ BEZ_DEV void chain_up(const Params& P, const EnvDyn& D, const EnvState& S, const
 // place (semi-implicit Euler) and resolves contact forces on the way.  sc = the leg<->leg contacts' common scale.
 template <int FIRST, int LEN, bool CL>
 BEZ_DEV void chain_down(const Params& P, EnvState& S, SV a0, float sc, BallSel& sel, const V3* selfcf, V3& ball_link_force, CfOut& co, const float* lds,
-                        int lane, bool keep, bool first, int e) {
+                        int lane, bool keep, bool first, int e BEZ_DF_DOWN_PARAMS) {
   SV a = a0;
   constexpr int Lend = FIRST + LEN - 1;
   constexpr bool LEG = (FIRST == 5 || FIRST == 13);
@@ -901,7 +972,18 @@ BEZ_DEV void chain_down(const Params& P, EnvState& S, SV a0, float sc, BallSel& 
     SV Sj = mksv(mk(p3[7 * BLOCK], p3[8 * BLOCK], p3[9 * BLOCK]), mk(p3[10 * BLOCK], p3[11 * BLOCK], p3[12 * BLOCK]));
     SV cb = mksv(mk(p3[13 * BLOCK], p3[14 * BLOCK], p3[15 * BLOCK]), mk(p3[16 * BLOCK], p3[17 * BLOCK], p3[18 * BLOCK]));
     SV ap = a + cb;
+#ifdef BEZ_DOF_FORCE
+    const uint32_t dfb = __float_as_uint(p3[20 * BLOCK]);
+    const float dUa = dot(UD, ap);   // a locked joint's slots hold U: U.(a_parent + c), the rest of its reaction
+    float qdd = (dfb & DF_LOCK) ? p3[6 * BLOCK] : uD - dUa;
+    {
+      const bool lk = (dfb & DF_LOCK) != 0u;
+      df_record(P, e, sub, L - 1, dfb, D.kp_scale[L - 1], D.kd_scale[L - 1], D.lo[L - 1], D.hi[L - 1], S.q[L - 1], S.qd[L - 1], target[L - 1], qdd,
+                fmaf(sc, p3[19 * BLOCK], p3[21 * BLOCK] + dUa), lk ? 0.f : p3[21 * BLOCK], lk ? 0.f : p3[22 * BLOCK]);
+    }
+#else
     float qdd = uD - dot(UD, ap);
+#endif
     a = ap + Sj * qdd;
     float v = fmaf(P.h, qdd, S.qd[L - 1]);   // the speed limit is inside the dynamics (joint_terms): no rate is edited here
     S.qd[L - 1] = v;
@@ -980,7 +1062,7 @@ BEZ_DEV void quat_integrate(float q[4], V3 w, float h) {
 // EXT: `xp` = this env has external wrenches pending (bez_sim_apply_body_forces): they enter every link's bias force and the ball's.
 template <bool CL, bool EXT = false>
 BEZ_DEV void substep(const Params& P, const EnvDyn& D, EnvState& S, const float* target, CfOut& co, float* lds, int lane, bool keep, bool first, int e,
-                     bool xp = false) {
+                     bool xp = false BEZ_DF_SUB_PARAM) {
   const M3 E0 = quat_to_mat(S.rq[0], S.rq[1], S.rq[2], S.rq[3]);
   const SV V0 = mksv(S.root_ang, S.root_lin);
   const V3 bc = S.ball_pos - S.root_pos;  // ball centre rel. O
@@ -1055,11 +1137,11 @@ BEZ_DEV void substep(const Params& P, const EnvDyn& D, EnvState& S, const float*
     if (sel.link == 0) { fl = sel.f0p - mul(sel.A, point_of(a0, sel.x)); f0 = cf_along(P, fl, sel.n); }
     if (keep) cf_accum(co, 0, f0 + cf_ground(P, link_ground_forces<0>(P, a0, lds, lane)), P.cf_w, first);
   }
-  chain_down<1, 2, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e);
-  chain_down<3, 2, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e);
-  chain_down<5, 6, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e);
-  chain_down<11, 2, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e);
-  chain_down<13, 6, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e);
+  chain_down<1, 2, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e BEZ_DF_DOWN_ARGS);
+  chain_down<3, 2, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e BEZ_DF_DOWN_ARGS);
+  chain_down<5, 6, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e BEZ_DF_DOWN_ARGS);
+  chain_down<11, 2, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e BEZ_DF_DOWN_ARGS);
+  chain_down<13, 6, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e BEZ_DF_DOWN_ARGS);
   // (f) ball: Mb ab = -pb - Jb^T fl (+ its external wrench about the centre: the contact operands above did not foresee it, as they do
   //     not foresee the leg<->leg forces)
   SV fb_ext = svzero();
@@ -1310,7 +1392,11 @@ BEZ_DEV void env_observe_reward(const Params& P, const EnvState& S, CfOut& co, f
 // EXT (with SIM): the instantiation that reads the pending external wrenches of bez_sim_apply_body_forces and clears them after the
 // last substep (a sim runs these once it has called that function: bez_sim.hip)
 template <bool PRE, bool SIM, bool POST, bool DR, bool CL, bool EXT = false>
+#ifdef BEZ_DOF_FORCE
+__global__ __launch_bounds__(BLOCK) void step_kernel(ParamsDF P) {
+#else
 __global__ __launch_bounds__(BLOCK) void step_kernel(Params P) {
+#endif
   __shared__ float lds[SIM ? LDS_SLOTS * BLOCK : 1];
   const int lane = threadIdx.x;
   const int e = blockIdx.x * BLOCK + lane;
@@ -1374,7 +1460,11 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(Params P) {
     const bool xp = EXT && ext_pending(P, e);
     for (int s = 0; s < P.substeps; ++s) {
       const bool last = (s == P.substeps - 1);
+#ifdef BEZ_DOF_FORCE
+      substep<CL, EXT>(P, D, S, target, co, lds, lane, last_only ? last : true, last_only ? true : (s == 0), e, xp, s);
+#else
       substep<CL, EXT>(P, D, S, target, co, lds, lane, last_only ? last : true, last_only ? true : (s == 0), e, xp);
+#endif
     }
     if (EXT && xp) {   // the wrenches were for this launch only
 #pragma unroll 1

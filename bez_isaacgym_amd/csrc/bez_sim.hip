@@ -13,6 +13,7 @@
 #include "bez_kernels.h"
 #include "bez_dr_step.h"
 #include "bez_launch.h"
+#include "bez_launch_df.h"
 
 using namespace bez;
 
@@ -82,6 +83,10 @@ struct BezSim {
   // a graph captured after it keeps consuming what later apply calls leave)
   float* ext = nullptr;
   bool ext_on = false;
+  // actuator tensors (BEZ_FLAG_DOF_FORCE), one allocation made when the flag is first set: the raw record of the step kernels
+  // [substep][3][dof][env] (bez_kernels.h df_record), then the three Isaac-layout tensors bez_sim_refresh_actuator_tensors fills
+  float* df_raw = nullptr;
+  float* df_out = nullptr;   // (N*18) net joint force, (N*18) drive torque, (N*18) i32 status
 };
 
 namespace {
@@ -440,6 +445,36 @@ __global__ void ext_prepare_kernel(const float* __restrict__ st, float* __restri
   if (any) ext[(size_t)EXT_FLAG * n + e] = 1.f;
 }
 
+// bez_sim_refresh_actuator_tensors: mean over the substeps of the two torques, OR of the status words, non-finite -> 0, [dof][env] -> (N*18)
+__global__ void refresh_actuator_kernel(const float* __restrict__ raw, float* __restrict__ out, int n, int substeps) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n * BEZ_ND) return;
+  const int d = t / n, e = t % n;   // (coalesced reads of the record; the stores are strided by 18 words)
+  const size_t plane = (size_t)BEZ_ND * n;
+  float drive = 0.f, net = 0.f;
+  uint32_t bits = 0u;
+  for (int s = 0; s < substeps; ++s) {
+    const float* r = raw + (size_t)s * 3 * plane + (size_t)d * n + e;
+    drive += r[0]; net += r[plane]; bits |= __float_as_uint(r[2 * plane]);
+  }
+  const float w = 1.0f / (float)substeps;
+  const size_t o = (size_t)e * BEZ_ND + d, total = (size_t)n * BEZ_ND;
+  out[o] = finite_or(net * w, 0.f);
+  out[total + o] = finite_or(drive * w, 0.f);
+  reinterpret_cast<int32_t*>(out)[2 * total + o] = (int32_t)(bits & 15u);
+}
+// the flag's buffers, on first use
+int ensure_actuator_buffers(BezSim* s) {
+  if (s->df_raw) return 0;
+  (void)hipSetDevice(s->device);
+  const size_t plane = (size_t)s->n * BEZ_ND, raw = (size_t)s->cfg.substeps * 3 * plane, bytes = (raw + 3 * plane) * sizeof(float);
+  hipError_t e = hipMalloc((void**)&s->df_raw, bytes);
+  if (e == hipSuccess) e = hipMemset(s->df_raw, 0, bytes);
+  if (e != hipSuccess) { s->df_raw = nullptr; return fail(s, -4, "hipMalloc (actuator tensors)", e); }
+  s->df_out = s->df_raw + raw;
+  return 0;
+}
+
 // Kernel choice for launches that include the physics, fixed per sim at bez_sim_create from BEZ_SIM_KERNEL: "ws8q" = the 8-role-wave
 // kernel in its lane-group form (four lanes per env, 16-env workgroups: bez_step_ws8q.hip), "ws8" = the one-lane form (bez_kernel_ws8.h,
 // 64-env workgroups), "lane" = the one-env-per-lane reference kernel (bez_kernels.h).  Unset: by size -- the lane-group form while its
@@ -496,8 +531,12 @@ int launch_step(BezSim* s, const float* actions, hipStream_t stream, bool obs_on
     // one-env-per-lane kernel, which carries the "root acceleration = 0" branch; in the 8-role-wave kernel that branch costs the default
     // configuration 0.8 % (26.56 -> 26.78 us, same box: six more spilled VGPRs in a kernel at its 256-register ceiling)
     // (the same holds for the scenario harness's contact variants, BEZ_FLAG_ALL_GROUND_SHAPES / BEZ_FLAG_ANKLE_STOP: one-env-per-lane kernel only)
+    const bool df = (s->cfg.flags & BEZ_FLAG_DOF_FORCE) != 0u;   // the recording instantiations (bez_step_*_df.hip)
     if (s->kernel != 2 && !(s->cfg.flags & (BEZ_FLAG_FIX_BASE | BEZ_FLAG_ALL_GROUND_SHAPES | BEZ_FLAG_ANKLE_STOP))) {
-      if (s->kernel == 3 || (s->kernel == 0 && s->n <= s->quad_max_envs)) bez::launch_step_ws8q(P, PRE, dr, s->cleats, stream, s->ext_on);
+      const bool quad = s->kernel == 3 || (s->kernel == 0 && s->n <= s->quad_max_envs);
+      if (df && quad) bez::launch_step_ws8q_df(P, s->df_raw, PRE, dr, s->cleats, stream, s->ext_on);
+      else if (df) bez::launch_step_ws8_df(P, s->df_raw, PRE, dr, s->cleats, stream, s->ext_on);
+      else if (quad) bez::launch_step_ws8q(P, PRE, dr, s->cleats, stream, s->ext_on);
       else bez::launch_step_ws8(P, PRE, dr, s->cleats, stream, s->ext_on);
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) return fail(s, -2, "step_kernel_ws launch", e);
@@ -505,7 +544,11 @@ int launch_step(BezSim* s, const float* actions, hipStream_t stream, bool obs_on
       return 0;
     }
   }
-  bez::launch_step_lane(P, PRE, SIM, POST, dr, s->cleats, stream, s->ext_on);
+  bool recorded = false;
+  if constexpr (SIM && PRE == POST) {
+    if (s->cfg.flags & BEZ_FLAG_DOF_FORCE) { bez::launch_step_lane_df(P, s->df_raw, PRE, dr, s->cleats, stream, s->ext_on); recorded = true; }
+  }
+  if (!recorded) bez::launch_step_lane(P, PRE, SIM, POST, dr, s->cleats, stream, s->ext_on);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(s, -2, "step kernel launch", e);
   if (POST) s->obs_calls += 1;
@@ -553,6 +596,10 @@ static const char* oracle_only(uint32_t flags, const float* tune) {
   // (round 6: the scenario harness's two contact variants run on the one-env-per-lane kernel -- for the asset they are defined for)
   if ((flags & (BEZ_FLAG_ANKLE_STOP | BEZ_FLAG_ALL_GROUND_SHAPES)) && (flags & (BEZ_FLAG_CLEATS | BEZ_FLAG_BOX_ASSET)))
     return "BEZ_FLAG_ANKLE_STOP / BEZ_FLAG_ALL_GROUND_SHAPES are defined for soccerbot_stl.urdf without cleats only (as in the CPU oracle); this asset has no kernel for them";
+  // the actuator record of the scenario harness's two contact variants has no known-answer test yet (the ankle stop is a coupled limit of two
+  // joints; the extra ground shapes only add link forces): refused rather than reported unchecked
+  if ((flags & BEZ_FLAG_DOF_FORCE) && (flags & (BEZ_FLAG_ANKLE_STOP | BEZ_FLAG_ALL_GROUND_SHAPES)))
+    return "BEZ_FLAG_DOF_FORCE with BEZ_FLAG_ANKLE_STOP / BEZ_FLAG_ALL_GROUND_SHAPES: the joint forces of these scenario variants are not validated; not served";
   if (tune) for (int i = 0; i < 24; ++i) if (tune[i] != 0.f) return "BezSimConfig.tune[]: knobs of the oracle-only solver variants; must be 0 for libbez_sim.so";
   return nullptr;
 }
@@ -562,7 +609,7 @@ int bez_sim_destroy(BezSim* s) {
   (void)hipSetDevice(s->device);
   void* bufs[] = {s->state, s->obs, s->rew, s->reset, s->progress, s->timeout, s->episode, s->root_states, s->dof_state,
                   s->rigid_body, s->contact, s->targets_aos, s->prev_aos, s->feet_aos, s->goal_aos, s->goal_draw_dev, s->post_calls_dev, s->randomize, s->dr_state, s->dr_snap, s->dr_pack, s->xhit,
-                  s->nonfinite, s->health, s->episode_stats, s->ext};
+                  s->nonfinite, s->health, s->episode_stats, s->ext, s->df_raw};
   for (void* b : bufs) if (b) (void)hipFree(b);
   for (int i = 0; i < BEZ_PARAM_COUNT; ++i) if (s->dr[i]) (void)hipFree(s->dr[i]);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
@@ -622,6 +669,9 @@ int bez_sim_create(const BezSimConfig* cfg, int device_id, BezSim** out) {
     e = hipMalloc((void**)&s->xhit, n * BEZ_NXPT * 8 * sizeof(float));
     if (e == hipSuccess) e = hipMemset(s->xhit, 0, n * BEZ_NXPT * 8 * sizeof(float));
     if (e != hipSuccess) { int rc = fail(nullptr, -4, "hipMalloc", e); bez_sim_destroy(s); return rc; }
+  }
+  if (cfg->flags & BEZ_FLAG_DOF_FORCE) {
+    if (int rc = ensure_actuator_buffers(s)) { g_create_error = s->err; bez_sim_destroy(s); return rc; }
   }
   (void)hipEventCreate(&s->ev0);
   (void)hipEventCreate(&s->ev1);
@@ -752,8 +802,32 @@ int bez_sim_set_flags(BezSim* s, uint32_t flags) {
     HIP_TRY(s, hipMalloc((void**)&s->xhit, (size_t)s->cfg.num_envs * BEZ_NXPT * 8 * sizeof(float)));
     HIP_TRY(s, hipMemset(s->xhit, 0, (size_t)s->cfg.num_envs * BEZ_NXPT * 8 * sizeof(float)));
   }
+  if (merged & BEZ_FLAG_DOF_FORCE) {
+    if (int rc = ensure_actuator_buffers(s)) return rc;
+  }
   s->cfg.flags = merged;
   return 0;
+}
+
+int bez_sim_get_actuator_tensor(BezSim* s, int which, void** dev_ptr, int64_t shape[3], int* ndim, int* dtype) {
+  if (!s || !dev_ptr || !shape || !ndim || !dtype) return fail(s, -1, "bez_sim_get_actuator_tensor: null argument");
+  if (!(s->cfg.flags & BEZ_FLAG_DOF_FORCE) || !s->df_out) return fail(s, -1, "bez_sim_get_actuator_tensor: BEZ_FLAG_DOF_FORCE is not set (the step kernels record no joint forces without it)");
+  const size_t total = (size_t)s->n * BEZ_ND;
+  shape[0] = (int64_t)total; shape[1] = shape[2] = 0; *ndim = 1;
+  switch (which) {
+    case BEZ_ACTUATOR_DOF_FORCE: *dev_ptr = s->df_out; *dtype = BEZ_DTYPE_F32; break;
+    case BEZ_ACTUATOR_DRIVE_TORQUE: *dev_ptr = s->df_out + total; *dtype = BEZ_DTYPE_F32; break;
+    case BEZ_ACTUATOR_STATUS: *dev_ptr = s->df_out + 2 * total; *dtype = BEZ_DTYPE_I32; break;
+    default: return fail(s, -1, "bez_sim_get_actuator_tensor: unknown tensor id");
+  }
+  return 0;
+}
+int bez_sim_refresh_actuator_tensors(BezSim* s, void* stream) {
+  if (!s) return -1;
+  if (!(s->cfg.flags & BEZ_FLAG_DOF_FORCE) || !s->df_raw) return fail(s, -1, "bez_sim_refresh_actuator_tensors: BEZ_FLAG_DOF_FORCE is not set (the step kernels record no joint forces without it)");
+  hipLaunchKernelGGL(refresh_actuator_kernel, dim3(((size_t)s->n * BEZ_ND + TB - 1) / TB), dim3(TB), 0, (hipStream_t)stream, s->df_raw, s->df_out, s->n, s->cfg.substeps);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(s, -2, "refresh_actuator launch", e);
 }
 int bez_sim_set_obs_calls(BezSim* s, int64_t calls) { if (!s) return -1; s->obs_calls = calls; return 0; }
 

@@ -428,6 +428,7 @@ class A2CAgent:
         self._nf_seen = self._nonfinite_buf.sum().reshape(1) if self._nonfinite_buf is not None else None
         # why episodes end (abi.END_*): the env's per-cause counters and, with env.debug.rewards, its reward-term sums, folded into the same
         # report (slots _ENDS_SLOT.. / _TERMS_SLOT..) the same way
+        self._act_env = genv if getattr(genv, "dof_force_on", False) else None   # env.enableDofForceSensors: the epoch row gains `actuators`
         self._end_counts = getattr(genv, "episode_end_counts", None)
         self._terms_buf = getattr(genv, "reward_terms_buf", None) if getattr(genv, "reward_terms_on", False) else None
         self._end_seen = self._end_counts.sum(1) if self._end_counts is not None else None
@@ -1467,6 +1468,38 @@ class A2CAgent:
             row["reward_terms"] = {k: v[abi.END_CAUSES + k] / steps for k in range(abi.REWARD_TERM_SLOTS)}
         return row
 
+    # ---- env.enableDofForceSensors (abi.FLAG_DOF_FORCE): the actuators of the rollout's last step, once per epoch
+    _ACT_SLOT = 40   # fp64 words 40-43 of the epoch report (free between the KL accumulators and the episode statistics)
+    ACTUATOR_NAMES = ("mean_abs_drive_torque", "saturated_share", "locked_share", "mean_positive_power")
+
+    def _act_in_report(self):
+        return self._report is not None and self.mb is not None and 12 + self.mini_epochs <= 2 * self._ACT_SLOT
+
+    def _fold_actuators(self):
+        """Device side, at the end of an epoch (the env has not stepped since the rollout's last step): one refresh of the actuator tensors
+        and one small reduction over that step's N x 16 driven joint samples (the head DOFs 0, 1 are never driven) -- mean |tau_drive|,
+        saturated share, locked share, mean positive mechanical power max(tau_drive * qd, 0).  Returns None without the env's flag or where
+        the four numbers went into the epoch report (read with it: no host sync of their own); else a (4,) fp64 tensor."""
+        env = self._act_env
+        if env is None:
+            return None
+        drive, status, qd = env.actuator_snapshot()
+        drive, status, qd = drive[:, 2:], status[:, 2:], qd[:, 2:]
+        packed = self._act_in_report()
+        out = self._report[self._ACT_SLOT:self._ACT_SLOT + 4] if packed else torch.zeros(4, dtype=torch.float64, device=drive.device)
+        vals = torch.stack([drive.abs().mean(dtype=torch.float64), ((status & abi.ACTUATOR_SATURATED) != 0).to(torch.float64).mean(),
+                            ((status & abi.ACTUATOR_LOCKED) != 0).to(torch.float64).mean(),
+                            (drive * qd).clamp_min(0).mean(dtype=torch.float64)])
+        out.copy_(vals)
+        return None if packed else out
+
+    def _actuators_row(self, v, rep=None):
+        """The epoch row's `actuators` entry (nothing without the env's flag: the row keeps exactly the keys it had)"""
+        if self._act_env is None:
+            return {}
+        v = rep[self._ACT_SLOT:self._ACT_SLOT + 4].tolist() if v is None else v.tolist()
+        return dict(actuators=dict(zip(self.ACTUATOR_NAMES, (float(x) for x in v))))
+
     def _ends_from_report(self, rep):
         return rep[self._ENDS_SLOT:self._TERMS_SLOT + abi.END_CAUSES].tolist() if self._end_counts is not None and self._ends_in_report() else None
 
@@ -1484,6 +1517,7 @@ class A2CAgent:
             ev[2].record()
             guard = self._fold_guard()
             ends = self._fold_episode_stats()
+            acts = self._fold_actuators()
             rep = self._report.cpu()     # the epoch's host sync
             nf, health = (int(guard[0]), int(guard[1])) if guard is not None else self._guard_from_report(rep)
             ends = self._ends_from_report(rep) if ends is None else ends.tolist()
@@ -1503,6 +1537,7 @@ class A2CAgent:
             self.run_update()
             guard = self._fold_guard()
             ends = self._fold_episode_stats()
+            acts, rep = self._fold_actuators(), None
             if guard is not None and self.device.type == "cuda" and self._nonfinite_buf is not None:
                 # the guard's two numbers and the episode statistics ride on the learning-rate read: still the epoch's only other host sync
                 v = torch.cat([self.lr_t.reshape(1).double(), guard[0].double().reshape(1).to(self.device),
@@ -1522,12 +1557,15 @@ class A2CAgent:
             a_l, c_l = (self.loss_acc / (self.mini_epochs * self.num_minibatches)).tolist()
             self._drain_episode_stats()
             t_total = time.perf_counter() - t0
+        if acts is None and self._act_env is not None and rep is None:   # (unpacked path with the numbers in the report after all)
+            rep = self._report.cpu()
         self._eager_epochs += 1
         self.epoch_num += 1
         self.frame += self.batch_size * self.world
         self._weights_sig = self._weights_signature()   # whatever this epoch's own optimiser steps did to the versions is not "external"
         return dict(play_time=t_play, update_time=t_total - t_play, total_time=t_total, kl=sum(kls) / len(kls),
-                    a_loss=a_l, c_loss=c_l, lr=self.last_lr, nonfinite_resets=nf, sim_health=health, **self._episode_stats_row(ends))
+                    a_loss=a_l, c_loss=c_l, lr=self.last_lr, nonfinite_resets=nf, sim_health=health, **self._episode_stats_row(ends),
+                    **self._actuators_row(acts, rep))
 
     # ---- pipelined epochs: the host reads epoch k's report while epoch k + 1 is already queued.  train_epoch() ends in the epoch's one
     # device-to-host copy and only then launches the next rollout: between the two the GPU waits for the host (wake-up from the copy, the
@@ -1563,6 +1601,7 @@ class A2CAgent:
             ev[2].record()
         st["guard"] = self._fold_guard()   # (None: folded into the report copied below)
         st["ends"] = self._fold_episode_stats()   # (same)
+        st["acts"] = self._fold_actuators()       # (same)
         st["host"].copy_(self._report, non_blocking=True)
         self.ep_stats.zero_()            # (stream order: behind the copy, in front of the next rollout's first count)
         st["done"].record()
@@ -1600,7 +1639,8 @@ class A2CAgent:
             self._play_share = dev_play / max(dev_play + dev_upd, 1e-9)
         t_play = t_total * getattr(self, "_play_share", 0.35)
         return dict(play_time=t_play, update_time=t_total - t_play, total_time=t_total, kl=sum(kls) / len(kls), a_loss=a_l, c_loss=c_l,
-                    lr=self.last_lr, epoch=st["epoch"], frame=st["frame"], nonfinite_resets=nf, sim_health=health, **self._episode_stats_row(ends))
+                    lr=self.last_lr, epoch=st["epoch"], frame=st["frame"], nonfinite_resets=nf, sim_health=health, **self._episode_stats_row(ends),
+                    **self._actuators_row(st.get("acts"), rep))
 
     def release_env(self):
         """Hands the env back to other consumers: lean stepping off, so env.net_contact_forces / feet / prev_lin_vel are

@@ -60,6 +60,8 @@ def load_library():
         "bez_sim_calibrate": (C.c_int, [vp, u64, i32, vp]),
         "bez_sim_time_steps": (C.c_int, [vp, fp, i32, vp, C.POINTER(C.c_float)]),
         "bez_sim_apply_body_forces": (C.c_int, [vp, fp, fp, fp, i32, vp]),
+        "bez_sim_get_actuator_tensor": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "bez_sim_refresh_actuator_tensors": (C.c_int, [vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -74,7 +76,8 @@ EXPORTS = ["bez_sim_default_config", "bez_sim_create", "bez_sim_destroy", "bez_s
            "bez_sim_set_net_contact_force_tensor", "bez_sim_set_prev_lin_vel_tensor", "bez_sim_set_goal_tensor", "bez_sim_set_flags",
            "bez_sim_set_obs_calls", "bez_sim_pre_physics", "bez_sim_simulate", "bez_sim_post_physics", "bez_sim_observe_reward", "bez_sim_step",
            "bez_sim_step_many", "bez_sim_reset_indexed", "bez_sim_set_env_params", "bez_sim_get_env_params", "bez_sim_set_randomization", "bez_sim_dr_prelaunch", "bez_sim_dr_step_args", "bez_sim_dr_cancel", "bez_sim_action_noise_source", "bez_sim_add_dr_noise", "bez_sim_seed", "bez_sim_time_steps",
-           "bez_sim_calibrate", "bez_sim_health", "bez_sim_get_episode_tensor", "bez_sim_apply_body_forces"]
+           "bez_sim_calibrate", "bez_sim_health", "bez_sim_get_episode_tensor", "bez_sim_apply_body_forces",
+           "bez_sim_get_actuator_tensor", "bez_sim_refresh_actuator_tensors"]
 # (the bez_ppo_* entry points of the same library are bound in ppo/fused.py)
 
 
@@ -90,6 +93,8 @@ class _DevView:
 
 class BezSim:
     """One simulator instance on one GPU (one per process / rank)."""
+
+    _flags_set = None   # the flags the library holds after the last set_flags(); None: cfg.flags as created
 
     def __init__(self, cfg: abi.BezSimConfig, device_id: int = 0):
         if not torch.cuda.is_available():
@@ -158,6 +163,29 @@ class BezSim:
         [cause][env] (never cleared by the library: take deltas), REWARD_TERMS (8, N) float32 [slot][env] (the caller zeroes it)."""
         return self._wrap(("episode", int(which)), self.lib.bez_sim_get_episode_tensor, which)
 
+    # ---- gym.acquire_dof_force_tensor / refresh_dof_force_tensor (abi.FLAG_DOF_FORCE)
+    @property
+    def dof_force_enabled(self):
+        flags = int(self.cfg.flags) if self._flags_set is None else self._flags_set
+        return bool(flags & abi.FLAG_DOF_FORCE)
+
+    def _need_dof_force(self, what):
+        if not self.dof_force_enabled:
+            raise BezSimError("%s needs abi.FLAG_DOF_FORCE (task key %s: True): without it the step kernels record no joint forces"
+                              % (what, abi.DOF_FORCE_KEY))
+
+    def actuator_tensor(self, which):
+        """Zero-copy torch view of an actuator tensor (abi.ACTUATOR_* or "dof_force" / "drive_torque" / "status"), shape (N*18,) in
+        DOF_STATE order: DOF_FORCE and DRIVE_TORQUE float32, STATUS int32.  Filled by refresh_actuator_tensors()."""
+        which = abi.actuator_tensor_id(which)
+        self._need_dof_force("actuator_tensor()")
+        return self._wrap(("actuator", which), self.lib.bez_sim_get_actuator_tensor, which)
+
+    def refresh_actuator_tensors(self):
+        """gym.refresh_dof_force_tensor: materialises the three actuator tensors from what the last physics launch recorded."""
+        self._need_dof_force("refresh_actuator_tensors()")
+        self._check(self.lib.bez_sim_refresh_actuator_tensors(self.h, self._stream()))
+
     def refresh(self, which):
         self._check(self.lib.bez_sim_refresh_tensor(self.h, which, self._stream()))
         return self.tensor(which)
@@ -194,6 +222,8 @@ class BezSim:
 
     def set_flags(self, flags):
         self._check(self.lib.bez_sim_set_flags(self.h, int(flags)))
+        asset = abi.FLAG_CLEATS | abi.FLAG_BOX_ASSET   # (the library keeps the creation value of the asset bits)
+        self._flags_set = (int(flags) & ~asset) | (int(self.cfg.flags) & asset)   # cfg.flags stays the caller's: callers restore flags from it
 
     # ---- gym.apply_rigid_body_force_tensors / apply_rigid_body_force_at_pos_tensors
     def apply_body_forces(self, forces=None, torques=None, positions=None, space=abi.SPACE_ENV):

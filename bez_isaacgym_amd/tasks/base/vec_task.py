@@ -140,7 +140,40 @@ class VecTask(Env):
         self.episode_end_counts = s.episode_tensor(abi.EPISODE_END_COUNTS)
         self.reward_terms_buf = s.episode_tensor(abi.EPISODE_REWARD_TERMS)
         self.reward_terms_on = bool(int(s.cfg.flags) & abi.FLAG_REWARD_TERMS)
+        # gym.acquire_dof_force_tensor (env.enableDofForceSensors / abi.FLAG_DOF_FORCE): (N, 18) views of the sim's actuator tensors,
+        # filled by refresh_dof_force_tensor(); without the key the three properties below raise and say why
+        self.dof_force_on = bool(int(s.cfg.flags) & abi.FLAG_DOF_FORCE)
+        self._dof_force_views = None
+        if self.dof_force_on:
+            self._dof_force_views = tuple(s.actuator_tensor(k).view(self.num_envs, abi.NUM_DOFS)
+                                          for k in (abi.ACTUATOR_DOF_FORCE, abi.ACTUATOR_DRIVE_TORQUE, abi.ACTUATOR_STATUS))
         self.extras = {}
+
+    def _dof_force_view(self, k, name):
+        views = self.__dict__.get("_dof_force_views")
+        if views is None:
+            from ... import abi
+            raise AttributeError("%s exists only with the task key %s: True (abi.FLAG_DOF_FORCE): without it the step kernels "
+                                 "record no joint forces" % (name, abi.DOF_FORCE_KEY))
+        return views[k]
+
+    dof_force_tensor = property(lambda self: self._dof_force_view(0, "dof_force_tensor"), doc="(N, 18) f32 net joint force (Isaac's DOF force)")
+    dof_drive_torque = property(lambda self: self._dof_force_view(1, "dof_drive_torque"), doc="(N, 18) f32 drive torque")
+    dof_status = property(lambda self: self._dof_force_view(2, "dof_status"), doc="(N, 18) i32 abi.ACTUATOR_* status bits")
+
+    def refresh_dof_force_tensor(self):
+        """gym.refresh_dof_force_tensor: fills dof_force_tensor / dof_drive_torque / dof_status from the last physics launch."""
+        self._dof_force_view(0, "refresh_dof_force_tensor()")
+        self.sim.refresh_actuator_tensors()
+        return True
+
+    def actuator_snapshot(self):
+        """(drive torque, status, joint velocity), each (N, 18), of the last physics launch: one refresh of the actuator tensors and one of
+        DOF_STATE (the PPO loop's per-epoch actuator statistics)."""
+        from ... import abi
+        self.refresh_dof_force_tensor()
+        qd = self.sim.refresh(abi.TENSOR_DOF_STATE).view(self.num_envs, abi.NUM_DOFS, 2)[:, :, 1]
+        return self.dof_drive_torque, self.dof_status, qd
 
     def get_state(self):
         return torch.clamp(self.states_buf, -self.clip_obs, self.clip_obs).to(self.rl_device)

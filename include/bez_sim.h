@@ -118,6 +118,16 @@ extern "C" {
                                        terms, to BEZ_EPISODE_REWARD_TERMS (bez_sim_get_episode_tensor).  Not set by \
                                        bez_sim_default_config; bez_sim_set_flags may toggle it.  No other output changes. */
 
+#define BEZ_FLAG_DOF_FORCE 32768u /* gym.enable_actor_dof_force_sensors (kick_env.py:368,375, walk_env.py:300, orient_env.py:302): every launch that \
+                                     contains physics (bez_sim_simulate, bez_sim_step, bez_sim_step_many) records each joint's drive torque, net joint \
+                                     force and actuator status ("Actuator tensors" below: bez_sim_get_actuator_tensor, \
+                                     bez_sim_refresh_actuator_tensors).  Off by default; accepted by bez_sim_create and bez_sim_set_flags (the first \
+                                     use allocates the tensors).  Without it the library launches the kernels it always did and allocates nothing; \
+                                     with it the step kernels are other instantiations that compute the same state, observations, rewards and \
+                                     contact rows bit for bit.  A captured graph keeps the kernels it was captured with: set the flag BEFORE \
+                                     capturing.  Not served together with BEZ_FLAG_ANKLE_STOP / BEZ_FLAG_ALL_GROUND_SHAPES (rc -5: the joint forces \
+                                     of these two scenario variants have no validation yet). */
+
 /* Why an episode ended: cause code k has bit (1 << k) in BEZ_EPISODE_END_BITS.  A test "fires" exactly where the reward sets
  * reset_buf = 1.
  *   k  name                     bez_kick                          bez_walk                    bez_orient
@@ -249,6 +259,36 @@ enum BezEpisodeTensor {
   BEZ_EPISODE_TENSORS = 3
 };
 
+/* Actuator tensors (BEZ_FLAG_DOF_FORCE; bez_sim_get_actuator_tensor), all in DOF_STATE order (env-major, 18 DOFs per env).
+ * Per DOF d and substep, with h the substep, (q, qd) the joint state at its start, qdd the acceleration the substep solves,
+ * qd+ = qd + h qdd and q+ = q + h qd+ (the state the substep leaves):
+ *   drive torque  tau_drive = +-effort where the substep's saturation predictor clamped the drive, else the PD law at the end-of-substep
+ *                 state, kp_d (target - q+) - kd_d qd+ (kp_d, kd_d include the env's BEZ_PARAM_KP_SCALE / BEZ_PARAM_KD_SCALE); on a joint locked
+ *                 on its speed limit the same, with the prescribed qdd.
+ *   net joint force  tau_net = everything the joint mechanism applies about its axis.  Unlocked joint: tau_drive - cf qd+ + tau_limit(q+, qd+),
+ *                 cf = joint_friction / max(|qd|, jfric_veps) the regularised friction coefficient of the substep, tau_limit the joint-limit
+ *                 spring-damper limit_k (bound - q+) - limit_d qd+ where q was beyond the bound at the start of the substep (with
+ *                 BEZ_FLAG_ANKLE_STOP also the calf <-> foot-plate contact's share on the two ankle joints).  Locked joint: the reaction of the
+ *                 constraint, the force that produces the prescribed qdd: S.pA + U.(a_parent + c) + (J + armature) qdd in the quantities of
+ *                 the articulated-body recursion.  In both cases tau_net - armature qdd is what an inverse dynamics (RNEA) of the rigid links
+ *                 finds at the joint; ground, ball, leg <-> leg contacts and external wrenches are link forces, not joint forces.
+ *                 The head DOFs (never driven: their actions are zeroed) report what the same formulas give.
+ *   status        bit 0 / 1: a substep saturated the drive at +effort / -effort; bit 2 / 3: a substep locked the joint on +vel_limit / -vel_limit.
+ * A launch reports the MEAN over its substeps of tau_drive and tau_net (as NET_CONTACT_FORCE is the mean over the substeps) and the OR of
+ * the status bits; bez_sim_step_many leaves its last step's values.  The values describe the physics that ran in the launch whether or not the
+ * env was reset behind it: an env whose progress_buf is 0 after bez_sim_step was reset, and its row describes the discarded step.  A
+ * non-finite entry is written as 0 (the state's own non-finite values are the non-finite guard's business). */
+enum BezActuatorTensor {
+  BEZ_ACTUATOR_DOF_FORCE = 0,    /* f32 (N*18)  tau_net: gym.acquire_dof_force_tensor */
+  BEZ_ACTUATOR_DRIVE_TORQUE = 1, /* f32 (N*18)  tau_drive */
+  BEZ_ACTUATOR_STATUS = 2,       /* i32 (N*18)  BEZ_ACTUATOR_* status bits */
+  BEZ_ACTUATOR_TENSORS = 3
+};
+#define BEZ_ACTUATOR_SATURATED_POS 1
+#define BEZ_ACTUATOR_SATURATED_NEG 2
+#define BEZ_ACTUATOR_LOCKED_POS 4
+#define BEZ_ACTUATOR_LOCKED_NEG 8
+
 /* gym.create_sim + create_env/create_actor loop + prepare_sim + allocate_buffers
  * (vec_task.py:174-193, kick_env.py:240-408) followed by KickEnv.__init__'s reset_idx(all)
  * (kick_env.py:238): every env starts from its first reset draw with reset_buf = 0. */
@@ -261,6 +301,12 @@ const char* bez_sim_last_error(const BezSim* sim); /* sim may be NULL: last crea
 int bez_sim_get_tensor(BezSim* sim, int which, void** dev_ptr, int64_t shape[3], int* ndim, int* dtype);
 /* The same for the episode statistics: `which` is a BezEpisodeTensor. */
 int bez_sim_get_episode_tensor(BezSim* sim, int which, void** dev_ptr, int64_t shape[3], int* ndim, int* dtype);
+
+/* The actuator tensors: `which` is a BezActuatorTensor.  Without BEZ_FLAG_DOF_FORCE: an error (rc -1) with a message, not zeros. */
+int bez_sim_get_actuator_tensor(BezSim* sim, int which, void** dev_ptr, int64_t shape[3], int* ndim, int* dtype);
+/* gym.refresh_dof_force_tensor: materialises the three actuator tensors from what the last physics launch recorded (one small kernel
+ * on `stream`; captures into a HIP graph).  Without BEZ_FLAG_DOF_FORCE: rc -1 with a message. */
+int bez_sim_refresh_actuator_tensors(BezSim* sim, void* stream);
 
 /* gym.refresh_{actor_root_state,dof_state,rigid_body_state,net_contact_force}_tensor
  * (kick_env.py:750-753): materialise the Isaac-layout tensor from the SoA state. */
