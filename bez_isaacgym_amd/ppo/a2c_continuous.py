@@ -337,6 +337,31 @@ class _CpuLr:
         return float(self.value)
 
 
+class EpochReport:
+    """Layout of the epoch report: the one fp64 buffer that holds everything the host reads back per epoch.
+    fields[name] = (dtype the buffer is viewed as, offset, length), both in elements of that dtype.  The optional sections start behind
+    the KL accumulators, at word 40 (a 64-word report) for every mini_epochs <= 68; beyond that they move up and the report grows."""
+
+    def __init__(self, mini_epochs):
+        f64, f32, x = torch.float64, torch.float32, max(40, (13 + mini_epochs) // 2)
+        self.fields = dict(ep_stats=(f64, 0, 3),   # finished episodes, sum of returns, sum of lengths: accumulated on the device (no .nonzero() / .tolist() inside the rollout)
+                           lr=(f32, 8, 1), loss=(f32, 10, 2), kl=(f32, 12, mini_epochs),   # loss | kl: neighbours, zeroed by one fill
+                           actuators=(f64, x, 4),                                # A2CAgent.ACTUATOR_NAMES (env.enableDofForceSensors)
+                           episode_ends=(f64, x + 6, abi.END_CAUSES),            # episodes ended in the epoch, per deciding cause
+                           reward_terms=(f64, x + 6 + abi.END_CAUSES, abi.REWARD_TERM_SLOTS),   # env.debug.rewards: the reward's term sums
+                           nonfinite=(f64, x + 22, 1), health=(f64, x + 23, 1))  # the non-finite guard's trips and health word
+        spans = sorted((o * t.itemsize, (o + n) * t.itemsize, k) for k, (t, o, n) in self.fields.items())
+        assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])), ("epoch report fields overlap", spans)
+        assert self.fields["loss"][1] + 2 == self.fields["kl"][1]
+        self.words = -(-spans[-1][1] // 8)
+
+    def view(self, buf, name, last=None):
+        """The slice of `buf` (the report or a host copy of it) that holds field `name`, or the fields from `name` to `last`"""
+        t, o, _ = self.fields[name]
+        _, o1, n1 = self.fields[last or name]
+        return buf.view(t)[o:o1 + n1]
+
+
 class A2CAgent:
     """Continuous-action PPO agent.  `vec_env` needs step(actions)->(obs_dict, rew, done, info), reset()->obs_dict."""
 
@@ -411,23 +436,23 @@ class A2CAgent:
         self.value_mean_std = RunningMeanStd((1,)).to(self.device) if self.normalize_value else None
         on_gpu = self.device.type == "cuda"
         # lr lives on the device so that the adaptive-KL rule needs no host sync and the update can be graph-captured
-        # One 512-byte device buffer holds everything the host reads back per epoch -- episode statistics (3 fp64), learning rate, loss and KL
-        # accumulators (fp32 views) -- so an epoch ends with ONE device-to-host copy instead of four reads with a host round trip each
-        # (~30 us of idle GPU apiece between the replayed graphs)
-        self._report = torch.zeros(64, device=self.device, dtype=torch.float64) if on_gpu else None
-        if on_gpu:
-            self.lr_t = self._report.view(torch.float32)[8]
-            self.lr_t.fill_(self.last_lr)
-        else:
-            self.lr_t = torch.tensor(self.last_lr, device=self.device, dtype=torch.float32)
+        # One 512-byte device buffer (EpochReport) holds everything the host reads back per epoch -- episode statistics, learning rate, loss
+        # and KL accumulators, the optional sections of _fold_report -- so an epoch ends with ONE device-to-host copy instead of four reads
+        # with a host round trip each (~30 us of idle GPU apiece between the replayed graphs)
+        self._layout = EpochReport(self.mini_epochs)
+        self._report = torch.zeros(self._layout.words, device=self.device, dtype=torch.float64)
+        field = lambda *names: self._layout.view(self._report, *names)
+        self.ep_stats, self.loss_acc, self.kl_acc, self._upd_sums = field("ep_stats"), field("loss"), field("kl"), field("loss", "kl")
+        self.lr_t = field("lr")[0]   # (CPU: replaced by the _CpuLr wrapper below)
+        self.lr_t.fill_(self.last_lr)
         # the simulator's non-finite guard (abi.FLAG_NONFINITE_GUARD): its per-env trip counters and health word, folded into the same
-        # epoch report (slots _NF_SLOT / _HEALTH_SLOT, written by two small eager launches behind the update: no host sync, graphs unchanged)
+        # epoch report (by two small eager launches behind the update: no host sync, graphs unchanged)
         genv = getattr(vec_env, "env", vec_env)
         self._nonfinite_buf = getattr(genv, "nonfinite_buf", None)
         self._health_buf = getattr(genv, "health_buf", None)
         self._nf_seen = self._nonfinite_buf.sum().reshape(1) if self._nonfinite_buf is not None else None
         # why episodes end (abi.END_*): the env's per-cause counters and, with env.debug.rewards, its reward-term sums, folded into the same
-        # report (slots _ENDS_SLOT.. / _TERMS_SLOT..) the same way
+        # report the same way
         self._act_env = genv if getattr(genv, "dof_force_on", False) else None   # env.enableDofForceSensors: the epoch row gains `actuators`
         self._end_counts = getattr(genv, "episode_end_counts", None)
         self._terms_buf = getattr(genv, "reward_terms_buf", None) if getattr(genv, "reward_terms_on", False) else None
@@ -578,14 +603,6 @@ class A2CAgent:
             for k_mb, k_ds in (("obs", "obs"), ("act", "actions"), ("mu", "mu"), ("sigma", "sigma")):
                 self.mb[k_mb] = ds[k_ds].view(N, H, -1).transpose(0, 1)
             self.mb["neglogp"] = ds["old_logp"].view(N, H).transpose(0, 1)
-        # episode statistics accumulated on the device (no .nonzero()/.tolist() inside the rollout)
-        if self._report is not None and 12 + self.mini_epochs <= 2 * self._report.numel():   # views of the epoch report (see __init__)
-            f32 = self._report.view(torch.float32)
-            self.ep_stats, self.loss_acc, self.kl_acc = self._report[0:3], f32[10:12], f32[12:12 + self.mini_epochs]
-        else:
-            self.ep_stats = torch.zeros(3, device=dev, dtype=torch.float64)  # [finished episodes, sum of returns, sum of lengths]
-            self.kl_acc = torch.zeros(self.mini_epochs, device=dev)
-            self.loss_acc = torch.zeros(2, device=dev)
         # the epoch's data-only moments in ONE fp64 buffer = one all-reduce per epoch when data parallel: the
         # observation moments of every minibatch (rl_games updates the input normaliser at every minibatch forward, and what
         # it adds depends on the dataset alone, not on the weights), then the moments of the values and of the returns
@@ -1312,13 +1329,7 @@ class A2CAgent:
         return mb
 
     def _zero_update_sums(self):
-        acc = getattr(self, "_upd_sums", None)
-        if acc is None and self._report is not None and self.loss_acc.data_ptr() + 8 == self.kl_acc.data_ptr():
-            acc = self._upd_sums = self._report.view(torch.float32)[10:12 + self.mini_epochs]   # loss_acc | kl_acc: neighbours in the epoch report, one fill
-        if acc is not None:
-            acc.zero_()
-        else:
-            self.kl_acc.zero_(); self.loss_acc.zero_()
+        self._upd_sums.zero_()   # loss_acc | kl_acc: neighbours in the epoch report, one fill
 
     def _update_impl(self):
         """mini_epochs x num_minibatches optimiser steps + the adaptive LR rule, all on the device."""
@@ -1393,10 +1404,10 @@ class A2CAgent:
         else:
             self._g_update.replay()
 
-    def _drain_episode_stats(self, host=None, zero=True):
-        """Finished-episode count / return / length sums of this epoch's rollout (host = the values already read back with the epoch
-        report; None: one device->host read of its own).  zero False: the caller has cleared the device sums already (pipelined epochs)."""
-        cnt, rsum, lsum = self.ep_stats.tolist() if host is None else host
+    def _drain_episode_stats(self, host, zero=True):
+        """Finished-episode count / return / length sums of this epoch's rollout (host = the values read back with the epoch report).
+        zero False: the caller has cleared the device sums already (pipelined epochs)."""
+        cnt, rsum, lsum = host
         if zero:
             self.ep_stats.zero_()
         if cnt > 0:
@@ -1408,105 +1419,62 @@ class A2CAgent:
             self.game_rewards = [sum(r for _, r, _ in self._ep_hist) / tot]
             self.game_lengths = [sum(l for _, _, l in self._ep_hist) / tot]
 
-    _NF_SLOT, _HEALTH_SLOT = 62, 63   # fp64 words of the epoch report (the KL accumulators end at fp32 12 + mini_epochs)
-
-    def _guard_in_report(self):
-        return self._report is not None and 12 + self.mini_epochs <= 2 * self._NF_SLOT
-
-    def _fold_guard(self):
-        """Device side, at the end of an epoch: the trips of this epoch (increments of the env's counters since the last call) and the
-        health word into the epoch report.  Returns None there; without the packed report: (trips, health) as tensors, or ints without counters."""
-        nf, hw = self._nonfinite_buf, self._health_buf
-        if nf is None:
-            return None if self._guard_in_report() and self.mb is not None else (0, 0)
-        tot = nf.sum().reshape(1)
-        delta = tot - self._nf_seen
-        self._nf_seen.copy_(tot)
-        if self._guard_in_report() and self.mb is not None:
-            self._report[self._NF_SLOT:self._NF_SLOT + 1].copy_(delta)
-            if hw is not None:
-                self._report[self._HEALTH_SLOT:self._HEALTH_SLOT + 1].copy_(hw.reshape(1))
-            return None
-        return delta, (hw.reshape(-1)[0] if hw is not None else torch.zeros((), dtype=torch.int64, device=delta.device))
-
-    def _guard_from_report(self, rep):
-        return (int(rep[self._NF_SLOT]), int(rep[self._HEALTH_SLOT])) if self._guard_in_report() else (0, 0)
-
-    _ENDS_SLOT, _TERMS_SLOT = 46, 54   # fp64 words 46-53: ended episodes per cause, 54-61: reward-term sums (below the guard's 62-63)
-
-    def _ends_in_report(self):
-        return self._report is not None and self.mb is not None and 12 + self.mini_epochs <= 2 * self._ENDS_SLOT
-
-    def _fold_episode_stats(self):
-        """Device side, at the end of an epoch: the episodes that ended during it per deciding cause (increments of the env's counters since
-        the last call) and, with env.debug.rewards, the sums of the reward's terms (the env's buffer is zeroed behind the read).  Returns
-        None where they went into the epoch report; else one (16,) fp64 tensor [8 cause deltas, 8 term sums], or None without counters."""
-        cnt = self._end_counts
-        if cnt is None:
-            return None
-        packed = self._ends_in_report()
-        if packed:
-            out = self._report[self._ENDS_SLOT:self._TERMS_SLOT + abi.END_CAUSES]
-        else:
-            out = torch.zeros(2 * abi.END_CAUSES, dtype=torch.float64, device=cnt.device)
-        tot = cnt.sum(1)
-        torch.sub(tot, self._end_seen, out=out[:abi.END_CAUSES])
-        self._end_seen.copy_(tot)
-        if self._terms_buf is not None:
-            torch.sum(self._terms_buf, 1, dtype=torch.float64, out=out[abi.END_CAUSES:])
-            self._terms_buf.zero_()
-        return None if packed else out
-
-    def _episode_stats_row(self, v):
-        """The epoch row's entries from the 16 host values of _fold_episode_stats (None: no counters): episode_ends {cause: count} and,
-        with env.debug.rewards, reward_terms {slot: mean per env-step}.  Per rank, like nonfinite_resets."""
-        if v is None or self._end_counts is None:
-            return {}
-        row = dict(episode_ends={abi.END_NAMES[k]: int(round(v[k])) for k in range(abi.END_CAUSES - 1)})
-        if self._terms_buf is not None:
-            steps = max(self.batch_size, 1)
-            row["reward_terms"] = {k: v[abi.END_CAUSES + k] / steps for k in range(abi.REWARD_TERM_SLOTS)}
-        return row
-
-    # ---- env.enableDofForceSensors (abi.FLAG_DOF_FORCE): the actuators of the rollout's last step, once per epoch
-    _ACT_SLOT = 40   # fp64 words 40-43 of the epoch report (free between the KL accumulators and the episode statistics)
     ACTUATOR_NAMES = ("mean_abs_drive_torque", "saturated_share", "locked_share", "mean_positive_power")
 
-    def _act_in_report(self):
-        return self._report is not None and self.mb is not None and 12 + self.mini_epochs <= 2 * self._ACT_SLOT
+    def _fold_report(self):
+        """Device side, at the end of an epoch, behind the update: the optional sections into their slices of the epoch report (read with it:
+        no host sync of their own).  A section whose env attribute is absent writes nothing."""
+        out = lambda name: self._layout.view(self._report, name)
+        nf, hw, cnt, env = self._nonfinite_buf, self._health_buf, self._end_counts, self._act_env
+        if nf is not None:   # the guard's trips of this epoch (increments of the env's counters since the last call) and its health word
+            tot = nf.sum().reshape(1)
+            delta = tot - self._nf_seen
+            self._nf_seen.copy_(tot)
+            out("nonfinite").copy_(delta)
+            if hw is not None:
+                out("health").copy_(hw.reshape(1))
+        if cnt is not None:  # the episodes that ended during the epoch per deciding cause (increments, likewise) ...
+            tot = cnt.sum(1)
+            torch.sub(tot, self._end_seen, out=out("episode_ends"))
+            self._end_seen.copy_(tot)
+            if self._terms_buf is not None:   # ... and, with env.debug.rewards, the sums of the reward's terms (zeroed behind the read)
+                torch.sum(self._terms_buf, 1, dtype=torch.float64, out=out("reward_terms"))
+                self._terms_buf.zero_()
+        if env is not None:
+            # env.enableDofForceSensors (abi.FLAG_DOF_FORCE; the env has not stepped since the rollout's last step): one refresh of the actuator
+            # tensors and one small reduction over that step's N x 16 driven joint samples (the head DOFs 0, 1 are never driven) -- mean
+            # |tau_drive|, saturated share, locked share, mean positive mechanical power max(tau_drive * qd, 0)
+            drive, status, qd = (t[:, 2:] for t in env.actuator_snapshot())
+            out("actuators").copy_(torch.stack([drive.abs().mean(dtype=torch.float64),
+                                                ((status & abi.ACTUATOR_SATURATED) != 0).to(torch.float64).mean(),
+                                                ((status & abi.ACTUATOR_LOCKED) != 0).to(torch.float64).mean(),
+                                                (drive * qd).clamp_min(0).mean(dtype=torch.float64)]))
 
-    def _fold_actuators(self):
-        """Device side, at the end of an epoch (the env has not stepped since the rollout's last step): one refresh of the actuator tensors
-        and one small reduction over that step's N x 16 driven joint samples (the head DOFs 0, 1 are never driven) -- mean |tau_drive|,
-        saturated share, locked share, mean positive mechanical power max(tau_drive * qd, 0).  Returns None without the env's flag or where
-        the four numbers went into the epoch report (read with it: no host sync of their own); else a (4,) fp64 tensor."""
-        env = self._act_env
-        if env is None:
-            return None
-        drive, status, qd = env.actuator_snapshot()
-        drive, status, qd = drive[:, 2:], status[:, 2:], qd[:, 2:]
-        packed = self._act_in_report()
-        out = self._report[self._ACT_SLOT:self._ACT_SLOT + 4] if packed else torch.zeros(4, dtype=torch.float64, device=drive.device)
-        vals = torch.stack([drive.abs().mean(dtype=torch.float64), ((status & abi.ACTUATOR_SATURATED) != 0).to(torch.float64).mean(),
-                            ((status & abi.ACTUATOR_LOCKED) != 0).to(torch.float64).mean(),
-                            (drive * qd).clamp_min(0).mean(dtype=torch.float64)])
-        out.copy_(vals)
-        return None if packed else out
-
-    def _actuators_row(self, v, rep=None):
-        """The epoch row's `actuators` entry (nothing without the env's flag: the row keeps exactly the keys it had)"""
-        if self._act_env is None:
-            return {}
-        v = rep[self._ACT_SLOT:self._ACT_SLOT + 4].tolist() if v is None else v.tolist()
-        return dict(actuators=dict(zip(self.ACTUATOR_NAMES, (float(x) for x in v))))
-
-    def _ends_from_report(self, rep):
-        return rep[self._ENDS_SLOT:self._TERMS_SLOT + abi.END_CAUSES].tolist() if self._end_counts is not None and self._ends_in_report() else None
+    def _row_from_report(self, rep, zero=True):
+        """The epoch row's entries from a host copy of the epoch report (per rank); feeds the episode history (zero: see _drain_episode_stats).
+        episode_ends {cause: count}, reward_terms {slot: mean per env-step} and actuators appear only with their env attribute."""
+        get = lambda name: self._layout.view(rep, name)
+        self._drain_episode_stats(get("ep_stats").tolist(), zero)
+        self.last_lr = float(get("lr")[0]) if self.device.type == "cuda" else self.lr_t.item()
+        kls = get("kl").tolist()
+        a_l, c_l = (get("loss") / (self.mini_epochs * self.num_minibatches)).tolist()
+        row = dict(kl=sum(kls) / len(kls), a_loss=a_l, c_loss=c_l, lr=self.last_lr,
+                   nonfinite_resets=int(get("nonfinite")[0]), sim_health=int(get("health")[0]))
+        if self._end_counts is not None:
+            ends = get("episode_ends").tolist()
+            row["episode_ends"] = {abi.END_NAMES[k]: int(round(ends[k])) for k in range(abi.END_CAUSES - 1)}
+            if self._terms_buf is not None:
+                steps = max(self.batch_size, 1)
+                row["reward_terms"] = {k: v / steps for k, v in enumerate(get("reward_terms").tolist())}
+        if self._act_env is not None:
+            row["actuators"] = dict(zip(self.ACTUATOR_NAMES, get("actuators").tolist()))
+        return row
 
     def train_epoch(self):
         t0 = time.perf_counter()
-        packed = self._report is not None and self.mb is not None and self.ep_stats.data_ptr() == self._report.data_ptr()
-        if packed:
+        on_gpu = self.device.type == "cuda"
+        events = on_gpu and self.mb is not None
+        if events:
             # no host synchronisation between the rollout and the update: their shares of the epoch come from HIP events, resolved at
             # the epoch's ONE device-to-host copy
             ev = self._epoch_events = getattr(self, "_epoch_events", None) or [torch.cuda.Event(enable_timing=True) for _ in range(3)]
@@ -1515,67 +1483,32 @@ class A2CAgent:
             ev[1].record()
             self.run_update()
             ev[2].record()
-            guard = self._fold_guard()
-            ends = self._fold_episode_stats()
-            acts = self._fold_actuators()
-            rep = self._report.cpu()     # the epoch's host sync
-            nf, health = (int(guard[0]), int(guard[1])) if guard is not None else self._guard_from_report(rep)
-            ends = self._ends_from_report(rep) if ends is None else ends.tolist()
-            f32 = rep.view(torch.float32)
-            self.last_lr = float(f32[8])
-            kls = f32[12:12 + self.mini_epochs].tolist()
-            a_l, c_l = (f32[10:12] / (self.mini_epochs * self.num_minibatches)).tolist()
-            self._drain_episode_stats(rep[0:3].tolist())
-            t_total = time.perf_counter() - t0
-            dev_play, dev_upd = ev[0].elapsed_time(ev[1]) * 1e-3, ev[1].elapsed_time(ev[2]) * 1e-3
-            t_play = t_total * dev_play / max(dev_play + dev_upd, 1e-9)   # the wall time split as the device time was
-        else:
+        else:   # CPU, or the epoch that allocates the rollout buffers: the wall clock
             self.play_steps()
-            if self.device.type == "cuda":
+            if on_gpu:
                 torch.cuda.synchronize()
             t_play = time.perf_counter() - t0
             self.run_update()
-            guard = self._fold_guard()
-            ends = self._fold_episode_stats()
-            acts, rep = self._fold_actuators(), None
-            if guard is not None and self.device.type == "cuda" and self._nonfinite_buf is not None:
-                # the guard's two numbers and the episode statistics ride on the learning-rate read: still the epoch's only other host sync
-                v = torch.cat([self.lr_t.reshape(1).double(), guard[0].double().reshape(1).to(self.device),
-                               guard[1].double().reshape(1).to(self.device)] + ([ends] if ends is not None else [])).cpu().tolist()
-                self.last_lr, nf, health = float(v[0]), int(v[1]), int(v[2])
-                ends = v[3:] if ends is not None else None
-            else:
-                self.last_lr = float(self.lr_t.item())  # the epoch's only other host sync
-                if guard is not None:
-                    nf, health = int(guard[0]), int(guard[1])
-                    ends = ends.tolist() if ends is not None else None
-                else:
-                    rep = self._report.cpu()
-                    nf, health = self._guard_from_report(rep)
-                    ends = self._ends_from_report(rep) if ends is None else ends.tolist()
-            kls = self.kl_acc.tolist()
-            a_l, c_l = (self.loss_acc / (self.mini_epochs * self.num_minibatches)).tolist()
-            self._drain_episode_stats()
-            t_total = time.perf_counter() - t0
-        if acts is None and self._act_env is not None and rep is None:   # (unpacked path with the numbers in the report after all)
-            rep = self._report.cpu()
+        self._fold_report()
+        row = self._row_from_report(self._report.cpu() if on_gpu else self._report.clone())   # (.cpu(): the epoch's host sync)
+        t_total = time.perf_counter() - t0
+        if events:
+            dev_play, dev_upd = ev[0].elapsed_time(ev[1]) * 1e-3, ev[1].elapsed_time(ev[2]) * 1e-3
+            t_play = t_total * dev_play / max(dev_play + dev_upd, 1e-9)   # the wall time split as the device time was
         self._eager_epochs += 1
         self.epoch_num += 1
         self.frame += self.batch_size * self.world
         self._weights_sig = self._weights_signature()   # whatever this epoch's own optimiser steps did to the versions is not "external"
-        return dict(play_time=t_play, update_time=t_total - t_play, total_time=t_total, kl=sum(kls) / len(kls),
-                    a_loss=a_l, c_loss=c_l, lr=self.last_lr, nonfinite_resets=nf, sim_health=health, **self._episode_stats_row(ends),
-                    **self._actuators_row(acts, rep))
+        return dict(play_time=t_play, update_time=t_total - t_play, total_time=t_total, **row)
 
     # ---- pipelined epochs: the host reads epoch k's report while epoch k + 1 is already queued.  train_epoch() ends in the epoch's one
     # device-to-host copy and only then launches the next rollout: between the two the GPU waits for the host (wake-up from the copy, the
     # report, the next epoch's fills / noise / graph launch) -- ~120 us of a 3.9 ms epoch in the kernel trace.  Here the report goes to a pinned
     # buffer behind the epoch's kernels (two slots), the device sums are cleared in stream order, and the caller collects the report one epoch late.
     def train_epoch_launch(self):
-        """Queues one epoch (rollout + update + the copy of its report) and returns a ticket for train_epoch_finish(); None where the epoch
-        report is not packed (CPU, unfused paths): the caller then uses train_epoch()."""
-        packed = self._report is not None and self.mb is not None and self.ep_stats.data_ptr() == self._report.data_ptr()
-        if not packed or self.device.type != "cuda":
+        """Queues one epoch (rollout + update + the copy of its report) and returns a ticket for train_epoch_finish(); None on the CPU and
+        before the rollout buffers exist: the caller then uses train_epoch()."""
+        if self.device.type != "cuda" or self.mb is None:
             return None
         pipe = getattr(self, "_pipe", None)
         if pipe is None:
@@ -1599,9 +1532,7 @@ class A2CAgent:
         self.run_update()
         if timed:
             ev[2].record()
-        st["guard"] = self._fold_guard()   # (None: folded into the report copied below)
-        st["ends"] = self._fold_episode_stats()   # (same)
-        st["acts"] = self._fold_actuators()       # (same)
+        self._fold_report()
         st["host"].copy_(self._report, non_blocking=True)
         self.ep_stats.zero_()            # (stream order: behind the copy, in front of the next rollout's first count)
         st["done"].record()
@@ -1620,16 +1551,7 @@ class A2CAgent:
         assert st["busy"]
         st["done"].synchronize()
         st["busy"] = False
-        rep = st["host"]
-        f32 = rep.view(torch.float32)
-        self.last_lr = float(f32[8])
-        kls = f32[12:12 + self.mini_epochs].tolist()
-        a_l, c_l = (f32[10:12] / (self.mini_epochs * self.num_minibatches)).tolist()
-        self._drain_episode_stats(rep[0:3].tolist(), zero=False)
-        g = st.get("guard")
-        nf, health = (int(g[0]), int(g[1])) if g is not None else self._guard_from_report(rep)
-        ends = st.get("ends")
-        ends = self._ends_from_report(rep) if ends is None else ends.tolist()
+        row = self._row_from_report(st["host"], zero=False)
         now = time.perf_counter()
         t_total = now - max(st["t0"], getattr(self, "_pipe_last_report", 0.0))
         self._pipe_last_report = now
@@ -1638,9 +1560,7 @@ class A2CAgent:
             dev_play, dev_upd = ev[0].elapsed_time(ev[1]) * 1e-3, ev[1].elapsed_time(ev[2]) * 1e-3
             self._play_share = dev_play / max(dev_play + dev_upd, 1e-9)
         t_play = t_total * getattr(self, "_play_share", 0.35)
-        return dict(play_time=t_play, update_time=t_total - t_play, total_time=t_total, kl=sum(kls) / len(kls), a_loss=a_l, c_loss=c_l,
-                    lr=self.last_lr, epoch=st["epoch"], frame=st["frame"], nonfinite_resets=nf, sim_health=health, **self._episode_stats_row(ends),
-                    **self._actuators_row(st.get("acts"), rep))
+        return dict(play_time=t_play, update_time=t_total - t_play, total_time=t_total, **row, epoch=st["epoch"], frame=st["frame"])
 
     def release_env(self):
         """Hands the env back to other consumers: lean stepping off, so env.net_contact_forces / feet / prev_lin_vel are

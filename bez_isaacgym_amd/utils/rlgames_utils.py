@@ -86,7 +86,7 @@ class RLGPUAlgoObserver:
         if "reward_terms" in row:       # env.debug.rewards: each reward term's mean per env-step (include/bez_sim.h slot table)
             for slot, v in row["reward_terms"].items():
                 out.setdefault("scalars", {})["rewards/%s" % slot] = [v, row.get("frame")]
-        if "actuators" in row:          # env.enableDofForceSensors: the actuators of the rollout's last step (a2c_continuous._fold_actuators)
+        if "actuators" in row:          # env.enableDofForceSensors: the actuators of the rollout's last step (a2c_continuous._fold_report)
             for name, v in row["actuators"].items():
                 out.setdefault("scalars", {})["actuators/%s" % name] = [v, row.get("frame")]
         self.f.write(json.dumps(out) + "\n")

@@ -89,6 +89,54 @@ def test_learns_toy_env_and_checkpoint_roundtrip(tmp_path):
     assert other.epoch_num == agent.epoch_num and other.frame == agent.frame
 
 
+def test_epoch_report_layout_is_pinned_and_grows_with_mini_epochs():
+    """EpochReport: for mini_epochs <= 68 the offsets and the 64-word size are the ones every earlier version used; beyond, the fields behind
+    the KL accumulators move up -- no two fields share a byte, every field lies inside the buffer -- and the epoch row keeps its keys."""
+    from bez_isaacgym_amd import abi
+    from bez_isaacgym_amd.ppo.a2c_continuous import EpochReport
+    names = ("ep_stats", "lr", "loss", "kl", "actuators", "episode_ends", "reward_terms", "nonfinite", "health")
+    for me in (1, 5, 68, 69, 200):
+        lay = EpochReport(me)
+        assert tuple(lay.fields) == names
+        assert [lay.fields[k][2] for k in names] == [3, 1, 2, me, 4, abi.END_CAUSES, abi.REWARD_TERM_SLOTS, 1, 1]
+        assert [lay.fields[k][0] for k in names] == [torch.float64] + 3 * [torch.float32] + 5 * [torch.float64]
+        if me <= 68:
+            assert [lay.fields[k][1] for k in names] == [0, 8, 10, 12, 40, 46, 54, 62, 63] and lay.words == 64
+        spans = sorted((o * t.itemsize, (o + n) * t.itemsize) for t, o, n in lay.fields.values())
+        assert spans[0][0] == 0 and spans[-1][1] <= 8 * lay.words
+        assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])), (me, spans)
+        assert lay.fields["loss"][1] + 2 == lay.fields["kl"][1]     # neighbours: one fill zeroes both
+        # the same through the views the trainer uses: a mark written into every field survives the writes into all the others
+        buf = torch.zeros(lay.words, dtype=torch.float64)
+        for i, k in enumerate(names):
+            assert lay.view(buf, k).numel() == lay.fields[k][2]
+            lay.view(buf, k).fill_(i + 1)
+        assert all((lay.view(buf, k) == i + 1).all() for i, k in enumerate(names))
+        assert lay.view(buf, "loss", "kl").numel() == 2 + me
+
+    from tests.test_dof_force_cpu import _ActuatorFakeEnv
+    from tests.test_episode_stats_cpu import _CountingFakeEnv
+    from tests.test_nonfinite_guard_cpu import _GuardedFakeEnv
+
+    class _Actuators(_ActuatorFakeEnv, FakeVecEnv):
+        pass
+    for make in (lambda: _GuardedFakeEnv(16, seed=7, trips={2: {3: 1}}), lambda: _CountingFakeEnv(16, seed=7, terms=True),
+                 lambda: _Actuators(16, seed=7)):
+        rows = {}
+        for me in (5, 69):
+            p = _params(16, 64, horizon=4)
+            p["config"]["mini_epochs"] = me
+            agent = A2CAgent(p, make(), "cpu")
+            assert agent._report.numel() == (64 if me == 5 else 65) and agent.kl_acc.numel() == me
+            agent.obs = agent.env_reset()
+            rows[me] = [agent.train_epoch() for _ in range(2)]
+        assert all(set(a) == set(b) for a, b in zip(rows[5], rows[69])), (sorted(rows[5][0]), sorted(rows[69][0]))
+        a, b = rows[5][0], rows[69][0]   # the first rollout does not depend on the update: the same numbers, wherever the fields lie
+        for k in ("nonfinite_resets", "sim_health", "episode_ends", "reward_terms", "actuators"):
+            assert a.get(k) == b.get(k), k
+    assert rows[5][0]["actuators"] and "episode_ends" not in rows[5][0]
+
+
 def _dp_worker(rank, world, port, out):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
