@@ -2,13 +2,14 @@
 // layout kernels (Isaac AoS tensors <-> the simulator's SoA state).  gfx950 only.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <cstdlib>
 #include <new>
 #include <string>
-
-#include <cstdlib>
+#include <vector>
 
 #include "bez_kernels.h"
 #include "bez_dr_step.h"
@@ -20,11 +21,6 @@ using namespace bez;
 namespace {
 
 thread_local std::string g_create_error;
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
 
 }  // namespace
 
@@ -41,7 +37,8 @@ struct BezSim {
   int quad_max_envs = 4096;  // 16 envs x the device's CUs: up to here the lane-group form runs in one round of workgroups
   int nb = BEZ_NB, nbe = BEZ_NBE, nobs = BEZ_NUM_OBS, nact = 2;  // robot bodies, exported body rows, obs width, actors per env
   std::string err;
-  // sim-owned device memory
+  // sim-owned device memory: every buffer is made by dev_alloc_zeroed, which records its slot here; bez_sim_destroy frees the list
+  std::vector<void**> owned;
   float* state = nullptr;       // SoA [F_COUNT][N]
   float* obs = nullptr;         // (N,54)
   float* rew = nullptr;         // (N)
@@ -65,6 +62,7 @@ struct BezSim {
   BezDrConfig drc = {};
   int64_t* randomize = nullptr;   // (N) randomize_buf, vec_task.py:247
   DrState* dr_state = nullptr;  // device: frame counter, frame of the last non-env randomisation, noise parameters
+  float* dr_noise = nullptr;    // = dr_state->noise (BEZ_TENSOR_DR_NOISE)
   DrSnap* dr_snap = nullptr;    // device: the action-noise parameters / frame the NEXT step's action noise uses (written by the step kernels)
   float4* dr_pack = nullptr;    // device (N,18): {kp scale, kd scale, lower, upper} per joint, kept equal to the four dr[] arrays (null while none of them exists)
   bool gravity_uniform = false; // every row of dr[GRAVITY] holds the same vector (written by the randomisation kernel, not by the user)
@@ -98,11 +96,38 @@ int fail(BezSim* s, int code, const char* what, hipError_t e = hipSuccess) {
   if (s) s->err = buf; else g_create_error = buf;
   return code;
 }
-#define HIP_TRY(s, call)                                              \
-  do {                                                                \
-    hipError_t _e = (call);                                           \
-    if (_e != hipSuccess) return fail((s), -2, #call, _e);            \
-  } while (0)
+#define HIP_TRY(s, call) do { hipError_t _e = (call); if (_e != hipSuccess) return fail((s), -2, #call, _e); } while (0)
+#define RC_TRY(call) do { if (int _rc = (call)) return _rc; } while (0)
+
+// The one owner of device memory: allocates `bytes` into *slot, zeroes them (in stream order on `stream`; before the call returns
+// without one) and records the slot in s->owned.  dev_free releases a buffer before the sim ends; bez_sim_destroy releases the rest.
+template <typename T>
+int dev_alloc_zeroed(BezSim* s, T** slot, size_t bytes, hipStream_t stream = nullptr) {
+  void* p = nullptr;
+  hipError_t e = hipMalloc(&p, bytes);
+  if (e != hipSuccess) return fail(s, -4, "hipMalloc", e);
+  *slot = (T*)p;
+  s->owned.push_back((void**)slot);
+  e = stream ? hipMemsetAsync(p, 0, bytes, stream) : hipMemset(p, 0, bytes);
+  return e == hipSuccess ? 0 : fail(s, -2, "hipMemset", e);
+}
+template <typename T>
+void dev_free(BezSim* s, T** slot) {
+  s->owned.erase(std::remove(s->owned.begin(), s->owned.end(), (void**)slot), s->owned.end());
+  (void)hipFree(*slot);
+  *slot = nullptr;
+}
+
+// The one checked launch: `total` elements, one per thread, in workgroups of THREADS; an error becomes rc -2 and "<kernel> launch".
+constexpr int TB = 256;
+template <int THREADS, typename... P, typename... A>
+int launch_checked(BezSim* s, const char* what, void (*kernel)(P...), size_t total, hipStream_t stream, A... args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((total + THREADS - 1) / THREADS)), dim3(THREADS), 0, stream, static_cast<P>(args)...);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(s, -2, what, e);
+}
+#define LAUNCH(s, kernel, total, stream, ...) launch_checked<TB>((s), #kernel " launch", kernel, (total), (stream), __VA_ARGS__)
+#define LAUNCH_PER_ENV(s, kernel, stream, ...) launch_checked<64>((s), #kernel " launch", kernel, (size_t)(s)->n, (stream), __VA_ARGS__)
 
 // host copy of the reset-noise Philox (bez_kernels.h) for the per-call goal draw
 void philox_host(uint32_t c[4], uint32_t k0, uint32_t k1) {
@@ -171,14 +196,13 @@ __global__ void dr_repack_kernel(float4* pack, const float* kp, const float* kd,
 int repack_dr(BezSim* s, hipStream_t stream) {
   const bool any = s->dr[BEZ_PARAM_KP_SCALE] || s->dr[BEZ_PARAM_KD_SCALE] || s->dr[BEZ_PARAM_DOF_LOWER] || s->dr[BEZ_PARAM_DOF_UPPER];
   if (!any) {
-    if (s->dr_pack) { if (hipStreamSynchronize(stream) != hipSuccess) return -2; (void)hipFree(s->dr_pack); s->dr_pack = nullptr; }
+    if (s->dr_pack) { HIP_TRY(s, hipStreamSynchronize(stream)); dev_free(s, &s->dr_pack); }
     return 0;
   }
   const size_t total = (size_t)s->n * BEZ_ND;
-  if (!s->dr_pack && hipMalloc((void**)&s->dr_pack, total * sizeof(float4)) != hipSuccess) return -4;
-  hipLaunchKernelGGL(dr_repack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, s->dr_pack, s->dr[BEZ_PARAM_KP_SCALE], s->dr[BEZ_PARAM_KD_SCALE],
-                     s->dr[BEZ_PARAM_DOF_LOWER], s->dr[BEZ_PARAM_DOF_UPPER], total);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
+  if (!s->dr_pack) RC_TRY(dev_alloc_zeroed(s, &s->dr_pack, total * sizeof(float4), stream));
+  return LAUNCH(s, dr_repack_kernel, total, stream, s->dr_pack, s->dr[BEZ_PARAM_KP_SCALE], s->dr[BEZ_PARAM_KD_SCALE], s->dr[BEZ_PARAM_DOF_LOWER],
+                s->dr[BEZ_PARAM_DOF_UPPER], total);
 }
 
 DrArgs make_dr_args(const BezSim* s, bool first) {
@@ -239,10 +263,8 @@ bool has_dr(const BezSim* s) {
   for (int i = 0; i < BEZ_PARAM_COUNT; ++i) if (s->dr[i]) return true;
   return false;
 }
-int grid_for(int n) { return (n + BLOCK - 1) / BLOCK; }
 
 // ---------------------------------------------------------------- layout kernels
-constexpr int TB = 256;
 
 // KickEnv.reset_idx for listed envs (or all when ids == nullptr)
 __global__ void reset_kernel(Params P, const int32_t* ids, int count) {
@@ -317,6 +339,30 @@ BEZ_DEV void mat_to_quat(const M3& R, float q[4]) {
   }
 }
 
+// Forward kinematics of one env's link frames: orientation E[l] and origin r[l] (relative to the root's position) of every link, and
+// WITH_VEL the spatial velocities V[l] (without: V is scratch, the joints stand still)
+template <bool CL, bool WITH_VEL>
+BEZ_DEV void link_frames(const EnvState& S, uint32_t flags, M3 (&E)[BEZ_NL], V3 (&r)[BEZ_NL], SV (&V)[BEZ_NL]) {
+  E[0] = quat_to_mat(S.rq[0], S.rq[1], S.rq[2], S.rq[3]);
+  r[0] = mk(0, 0, 0);
+  V[0] = WITH_VEL ? mksv(S.root_ang, S.root_lin) : svzero();
+  static_for<BEZ_NL - 1>([&](auto I) {
+    constexpr int L = 1 + decltype(I)::value;
+    constexpr int p = BEZ_LINK_PARENT[L];
+    E[L] = E[p]; r[L] = r[p]; V[L] = V[p];
+    SV Sj, cb;
+    link_kinematics<L>(S.q[L - 1], WITH_VEL ? S.qd[L - 1] : 0.f, E[L], r[L], V[L], Sj, cb, quirk_rz<CL>(flags));
+  });
+}
+// Robot body b of the asset: the link it is fixed to, its origin's offset in that link's frame, its centre of mass in its own frame
+struct BodyFrame { int link; V3 off, com; };
+template <bool CL>
+BEZ_DEV BodyFrame body_frame(int b) {
+  const double* o = CL ? BEZ_BODY_OFFSET_CL[b] : BEZ_BODY_OFFSET[b];
+  const double* c = CL ? BEZ_BODY_COM_CL[b] : BEZ_BODY_COM[b];
+  return {CL ? BEZ_BODY_LINK_CL[b] : BEZ_BODY_LINK[b], mk((float)o[0], (float)o[1], (float)o[2]), mk((float)c[0], (float)c[1], (float)c[2])};
+}
+
 // gym.refresh_rigid_body_state_tensor: forward kinematics of all 21 robot bodies + the ball row
 template <bool CL>
 __global__ void refresh_rigid_body_kernel(const float* __restrict__ st, float* __restrict__ out, int n, int has_ball, uint32_t flags) {
@@ -325,24 +371,13 @@ __global__ void refresh_rigid_body_kernel(const float* __restrict__ st, float* _
   EnvState S;
   load_state(st, n, e, S);
   M3 E[BEZ_NL]; V3 r[BEZ_NL]; SV V[BEZ_NL];
-  E[0] = quat_to_mat(S.rq[0], S.rq[1], S.rq[2], S.rq[3]);
-  r[0] = mk(0, 0, 0);
-  V[0] = mksv(S.root_ang, S.root_lin);
-  static_for<BEZ_NL - 1>([&](auto I) {
-    constexpr int L = 1 + decltype(I)::value;
-    constexpr int p = BEZ_LINK_PARENT[L];
-    E[L] = E[p]; r[L] = r[p]; V[L] = V[p];
-    SV Sj, cb;
-    link_kinematics<L>(S.q[L - 1], S.qd[L - 1], E[L], r[L], V[L], Sj, cb, quirk_rz<CL>(flags));
-  });
+  link_frames<CL, true>(S, flags, E, r, V);
   constexpr int NB = nb_of<CL>();
   const int nbe = NB + (has_ball ? 1 : 0);
   static_for<NB>([&](auto I) {
-    constexpr int b = decltype(I)::value;
-    constexpr int l = CL ? BEZ_BODY_LINK_CL[b] : BEZ_BODY_LINK[b];
-    V3 off = CL ? mk((float)BEZ_BODY_OFFSET_CL[b][0], (float)BEZ_BODY_OFFSET_CL[b][1], (float)BEZ_BODY_OFFSET_CL[b][2])
-                : mk((float)BEZ_BODY_OFFSET[b < BEZ_NB ? b : 0][0], (float)BEZ_BODY_OFFSET[b < BEZ_NB ? b : 0][1], (float)BEZ_BODY_OFFSET[b < BEZ_NB ? b : 0][2]);
-    V3 x = r[l] + mul(E[l], off);
+    const BodyFrame f = body_frame<CL>(decltype(I)::value);
+    const int b = decltype(I)::value, l = f.link;
+    V3 x = r[l] + mul(E[l], f.off);
     V3 vel = point_of(V[l], x);
     float q[4];
     mat_to_quat(E[l], q);
@@ -396,20 +431,8 @@ __global__ void ext_prepare_kernel(const float* __restrict__ st, float* __restri
   if (e >= n) return;
   EnvState S;
   load_state(st, n, e, S);
-  M3 E[BEZ_NL]; V3 r[BEZ_NL];
-  E[0] = quat_to_mat(S.rq[0], S.rq[1], S.rq[2], S.rq[3]);
-  r[0] = mk(0, 0, 0);
-  {
-    SV V[BEZ_NL];
-    V[0] = svzero();
-    static_for<BEZ_NL - 1>([&](auto I) {
-      constexpr int L = 1 + decltype(I)::value;
-      constexpr int p = BEZ_LINK_PARENT[L];
-      E[L] = E[p]; r[L] = r[p]; V[L] = V[p];
-      SV Sj, cb;
-      link_kinematics<L>(S.q[L - 1], 0.f, E[L], r[L], V[L], Sj, cb, quirk_rz<CL>(flags));
-    });
-  }
+  M3 E[BEZ_NL]; V3 r[BEZ_NL]; SV V[BEZ_NL];
+  link_frames<CL, false>(S, flags, E, r, V);
   constexpr int NB = nb_of<CL>();
   const int nbe = NB + (has_ball ? 1 : 0);
   bool any = false;
@@ -427,13 +450,11 @@ __global__ void ext_prepare_kernel(const float* __restrict__ st, float* __restri
     if (!(f.x != 0.f || f.y != 0.f || f.z != 0.f || t.x != 0.f || t.y != 0.f || t.z != 0.f)) continue;   // (a NaN is != 0: it goes in)
     any = true;
     if (b < NB) {   // a robot body: its link's frame, its origin's offset in that frame, its own centre of mass
-      const int l = CL ? BEZ_BODY_LINK_CL[b] : BEZ_BODY_LINK[b];
-      const double* o = CL ? BEZ_BODY_OFFSET_CL[b] : BEZ_BODY_OFFSET[b];
-      const double* c = CL ? BEZ_BODY_COM_CL[b] : BEZ_BODY_COM[b];
-      const V3 off = mk((float)o[0], (float)o[1], (float)o[2]);
+      const BodyFrame bf = body_frame<CL>(b);
+      const int l = bf.link;
       V3 p;
-      if (!X) p = off + mk((float)c[0], (float)c[1], (float)c[2]);
-      else if (local) p = off + in3(X, b);
+      if (!X) p = bf.off + bf.com;
+      else if (local) p = bf.off + in3(X, b);
       else p = mulT(E[l], in3(X, b) - S.root_pos - r[l]);
       add(l, local ? mul(E[l], f) : f, local ? mul(E[l], t) : t, p);
     } else {        // the ball: its own frame about its centre
@@ -463,16 +484,72 @@ __global__ void refresh_actuator_kernel(const float* __restrict__ raw, float* __
   out[total + o] = finite_or(drive * w, 0.f);
   reinterpret_cast<int32_t*>(out)[2 * total + o] = (int32_t)(bits & 15u);
 }
-// the flag's buffers, on first use
-int ensure_actuator_buffers(BezSim* s) {
-  if (s->df_raw) return 0;
+// the buffers that only a flag needs, on its first use (bez_sim_create and bez_sim_set_flags)
+int ensure_flag_buffers(BezSim* s, uint32_t flags) {
   (void)hipSetDevice(s->device);
-  const size_t plane = (size_t)s->n * BEZ_ND, raw = (size_t)s->cfg.substeps * 3 * plane, bytes = (raw + 3 * plane) * sizeof(float);
-  hipError_t e = hipMalloc((void**)&s->df_raw, bytes);
-  if (e == hipSuccess) e = hipMemset(s->df_raw, 0, bytes);
-  if (e != hipSuccess) { s->df_raw = nullptr; return fail(s, -4, "hipMalloc (actuator tensors)", e); }
-  s->df_out = s->df_raw + raw;
+  if ((flags & BEZ_FLAG_ALL_GROUND_SHAPES) && !s->xhit) RC_TRY(dev_alloc_zeroed(s, &s->xhit, (size_t)s->n * BEZ_NXPT * 8 * sizeof(float)));
+  if ((flags & BEZ_FLAG_DOF_FORCE) && !s->df_raw) {
+    const size_t plane = (size_t)s->n * BEZ_ND, raw = (size_t)s->cfg.substeps * 3 * plane;
+    RC_TRY(dev_alloc_zeroed(s, &s->df_raw, (raw + 3 * plane) * sizeof(float)));
+    s->df_out = s->df_raw + raw;
+  }
   return 0;
+}
+
+// ---------------------------------------------------------------- the tensor table: all the host side knows about a BezTensor.  A new tensor
+// is one BezSim member, one enum value in include/bez_sim.h and one row here; create, get_tensor, refresh_tensor and the dense setters read it.
+enum : int { PER_ENV = -1, PER_ACTOR = -2, PER_BODY = -3, PER_DOF = -4 };   // row rules: N, N * actors, N * exported bodies, N * 18 (>= 0: that many)
+constexpr int COLS_OBS = -1;                                                // column rule: the task's observation width
+enum Refresh { LIVE, ROWS, ROOT_KERNEL, DOF_KERNEL, RIGID_BODY_KERNEL };    // LIVE: written in place, a refresh is a no-op
+struct TensorRow {
+  int id;                      // its own index (checked below)
+  void** (*slot)(BezSim*);     // the member that holds it
+  int dtype, rows, cols;       // shape (rows, cols); cols 0: one-dimensional
+  bool alloc;                  // bez_sim_create allocates it, for the largest layout (2 actors, BEZ_NBE_MAX bodies, BEZ_NUM_OBS columns)
+  Refresh refresh;
+  int field0;                  // ROWS: the env's row is the state fields field0 .. field0 + (elements per env) - 1
+};
+#define SLOT(member) [](BezSim* s) -> void** { return (void**)&s->member; }
+constexpr TensorRow TENSORS[] = {
+    {BEZ_TENSOR_ROOT_STATE, SLOT(root_states), BEZ_DTYPE_F32, PER_ACTOR, 13, true, ROOT_KERNEL, 0},
+    {BEZ_TENSOR_DOF_STATE, SLOT(dof_state), BEZ_DTYPE_F32, PER_DOF, 2, true, DOF_KERNEL, 0},
+    {BEZ_TENSOR_RIGID_BODY_STATE, SLOT(rigid_body), BEZ_DTYPE_F32, PER_BODY, 13, true, RIGID_BODY_KERNEL, 0},
+    {BEZ_TENSOR_NET_CONTACT_FORCE, SLOT(contact), BEZ_DTYPE_F32, PER_BODY, 3, true, ROWS, F_CF},
+    {BEZ_TENSOR_OBS, SLOT(obs), BEZ_DTYPE_F32, PER_ENV, COLS_OBS, true, LIVE, 0},
+    {BEZ_TENSOR_REW, SLOT(rew), BEZ_DTYPE_F32, PER_ENV, 0, true, LIVE, 0},
+    {BEZ_TENSOR_RESET, SLOT(reset), BEZ_DTYPE_I64, PER_ENV, 0, true, LIVE, 0},
+    {BEZ_TENSOR_PROGRESS, SLOT(progress), BEZ_DTYPE_I64, PER_ENV, 0, true, LIVE, 0},
+    {BEZ_TENSOR_TIMEOUT, SLOT(timeout), BEZ_DTYPE_I64, PER_ENV, 0, true, LIVE, 0},
+    {BEZ_TENSOR_DOF_TARGET, SLOT(targets_aos), BEZ_DTYPE_F32, PER_ENV, BEZ_ND, true, ROWS, F_TARGET},
+    {BEZ_TENSOR_PREV_LIN_VEL, SLOT(prev_aos), BEZ_DTYPE_F32, PER_ENV, 3, true, ROWS, F_PREV},
+    {BEZ_TENSOR_FEET, SLOT(feet_aos), BEZ_DTYPE_F32, PER_ENV, 8, true, ROWS, F_FEET},
+    {BEZ_TENSOR_GOAL, SLOT(goal_aos), BEZ_DTYPE_F32, PER_ENV, 2, true, ROWS, F_GOAL},
+    {BEZ_TENSOR_RANDOMIZE_BUF, SLOT(randomize), BEZ_DTYPE_I64, PER_ENV, 0, true, LIVE, 0},
+    {BEZ_TENSOR_DR_NOISE, SLOT(dr_noise), BEZ_DTYPE_F32, 4, 0, false, LIVE, 0},   // (inside dr_state)
+    {BEZ_TENSOR_NONFINITE_COUNT, SLOT(nonfinite), BEZ_DTYPE_I64, PER_ENV, 0, true, LIVE, 0},
+    {BEZ_TENSOR_HEALTH, SLOT(health), BEZ_DTYPE_I64, 1, 0, true, LIVE, 0},
+};
+#undef SLOT
+constexpr bool tensor_ids_in_order() {
+  for (int i = 0; i < BEZ_TENSOR_COUNT; ++i) if (TENSORS[i].id != i) return false;
+  return true;
+}
+static_assert(sizeof(TENSORS) / sizeof(TENSORS[0]) == BEZ_TENSOR_COUNT && tensor_ids_in_order(), "one TENSORS row per BezTensor, in enum order");
+
+// shape of tensor t in this sim -- or, `largest`, in the largest layout any sim has (what bez_sim_create allocates); returns the element count
+size_t tensor_shape(const BezSim* s, const TensorRow& t, int64_t shape[2], bool largest = false) {
+  const int64_t n = s->n, per_env = t.rows == PER_ACTOR ? (largest ? BEZ_NUM_ACTORS : s->nact) : t.rows == PER_BODY ? (largest ? BEZ_NBE_MAX : s->nbe) : t.rows == PER_DOF ? BEZ_ND : 1;
+  shape[0] = t.rows < 0 ? n * per_env : t.rows;
+  shape[1] = t.cols == COLS_OBS ? (largest ? BEZ_NUM_OBS : s->nobs) : t.cols;
+  return (size_t)(shape[0] * (shape[1] ? shape[1] : 1));
+}
+size_t tensor_numel(const BezSim* s, const TensorRow& t, bool largest = false) { int64_t shape[2]; return tensor_shape(s, t, shape, largest); }
+
+// the dense setters: an Isaac-layout (N, width) tensor back into the state fields its refresh reads
+int scatter_rows(BezSim* s, int which, const float* src, void* stream, const char* bad_argument) {
+  if (!s || !src) return fail(s, -1, bad_argument);
+  const size_t total = tensor_numel(s, TENSORS[which]);
+  return LAUNCH(s, scatter_rows_kernel, total, (hipStream_t)stream, s->state, src, s->n, TENSORS[which].field0, (int)(total / s->n));
 }
 
 // Kernel choice for launches that include the physics, fixed per sim at bez_sim_create from BEZ_SIM_KERNEL: "ws8q" = the 8-role-wave
@@ -607,15 +684,36 @@ static const char* oracle_only(uint32_t flags, const float* tune) {
 int bez_sim_destroy(BezSim* s) {
   if (!s) return 0;
   (void)hipSetDevice(s->device);
-  void* bufs[] = {s->state, s->obs, s->rew, s->reset, s->progress, s->timeout, s->episode, s->root_states, s->dof_state,
-                  s->rigid_body, s->contact, s->targets_aos, s->prev_aos, s->feet_aos, s->goal_aos, s->goal_draw_dev, s->post_calls_dev, s->randomize, s->dr_state, s->dr_snap, s->dr_pack, s->xhit,
-                  s->nonfinite, s->health, s->episode_stats, s->ext, s->df_raw};
-  for (void* b : bufs) if (b) (void)hipFree(b);
-  for (int i = 0; i < BEZ_PARAM_COUNT; ++i) if (s->dr[i]) (void)hipFree(s->dr[i]);
+  for (void** slot : s->owned) (void)hipFree(*slot);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
   delete s;
   return 0;
+}
+
+// the device side of bez_sim_create: every buffer, then the state after KickEnv.__init__.  On an error the caller destroys the sim.
+static int sim_init(BezSim* s) {
+  const size_t n = (size_t)s->n;
+  for (const TensorRow& t : TENSORS)
+    if (t.alloc) RC_TRY(dev_alloc_zeroed(s, t.slot(s), tensor_numel(s, t, true) * (t.dtype == BEZ_DTYPE_I64 ? 8 : 4)));
+  RC_TRY(dev_alloc_zeroed(s, &s->state, n * F_COUNT * sizeof(float)));
+  RC_TRY(dev_alloc_zeroed(s, &s->episode, n * sizeof(uint32_t)));
+  RC_TRY(dev_alloc_zeroed(s, &s->goal_draw_dev, 2 * sizeof(float)));
+  RC_TRY(dev_alloc_zeroed(s, &s->post_calls_dev, sizeof(unsigned long long)));
+  RC_TRY(dev_alloc_zeroed(s, &s->dr_state, sizeof(DrState)));
+  s->dr_noise = s->dr_state->noise;
+  RC_TRY(dev_alloc_zeroed(s, &s->dr_snap, sizeof(DrSnap)));
+  RC_TRY(dev_alloc_zeroed(s, &s->episode_stats, BEZ_END_CAUSES * n * (sizeof(int64_t) + sizeof(float)) + n * sizeof(int32_t)));
+  RC_TRY(ensure_flag_buffers(s, s->cfg.flags));
+  (void)hipEventCreate(&s->ev0);
+  (void)hipEventCreate(&s->ev1);
+  // state after KickEnv.__init__: allocate_buffers (vec_task.py:226-249) then reset_idx(all) (kick_env.py:238)
+  Params P = make_params(s, nullptr);
+  goal_draw(s->cfg.seed, s->reset_calls++, 1, P.goal_draw);  // the reset_idx(all) that ends Kick/Walk/OrientEnv.__init__
+  RC_TRY(LAUNCH(s, init_misc_kernel, n, nullptr, s->state, s->n, s->cfg.goal[0], s->cfg.goal[1]));
+  RC_TRY(LAUNCH(s, reset_kernel, n, nullptr, P, (const int32_t*)nullptr, s->n));
+  const hipError_t e = hipDeviceSynchronize();
+  return e == hipSuccess ? 0 : fail(s, -2, "init kernels", e);
 }
 
 int bez_sim_create(const BezSimConfig* cfg, int device_id, BezSim** out) {
@@ -647,69 +745,17 @@ int bez_sim_create(const BezSimConfig* cfg, int device_id, BezSim** out) {
   s->nact = s->has_ball ? 2 : 1;
   s->nobs = s->has_ball ? BEZ_NUM_OBS : BEZ_NUM_OBS_WALK;      // walk_env.py:104
   if (!s->has_ball) { s->cfg.ball_init[0] = 1000.0f; s->cfg.ball_init[1] = 0.0f; s->cfg.ball_init[2] = (float)BEZ_BALL_RADIUS; }  // parked out of reach
-  const size_t n = (size_t)s->n;
-  struct { void** p; size_t bytes; } allocs[] = {
-      {(void**)&s->state, n * F_COUNT * sizeof(float)}, {(void**)&s->obs, n * BEZ_NUM_OBS * sizeof(float)},
-      {(void**)&s->rew, n * sizeof(float)}, {(void**)&s->reset, n * sizeof(int64_t)}, {(void**)&s->progress, n * sizeof(int64_t)},
-      {(void**)&s->timeout, n * sizeof(int64_t)}, {(void**)&s->episode, n * sizeof(uint32_t)},
-      {(void**)&s->root_states, n * 26 * sizeof(float)}, {(void**)&s->dof_state, n * BEZ_ND * 2 * sizeof(float)},
-      {(void**)&s->rigid_body, n * BEZ_NBE_MAX * 13 * sizeof(float)}, {(void**)&s->contact, n * BEZ_NBE_MAX * 3 * sizeof(float)},
-      {(void**)&s->targets_aos, n * BEZ_ND * sizeof(float)}, {(void**)&s->prev_aos, n * 3 * sizeof(float)},
-      {(void**)&s->feet_aos, n * 8 * sizeof(float)}, {(void**)&s->goal_aos, n * 2 * sizeof(float)},
-      {(void**)&s->goal_draw_dev, 2 * sizeof(float)}, {(void**)&s->post_calls_dev, sizeof(unsigned long long)},
-      {(void**)&s->randomize, n * sizeof(int64_t)}, {(void**)&s->dr_state, sizeof(DrState)}, {(void**)&s->dr_snap, sizeof(DrSnap)},
-      {(void**)&s->nonfinite, n * sizeof(int64_t)}, {(void**)&s->health, sizeof(unsigned long long)},
-      {(void**)&s->episode_stats, BEZ_END_CAUSES * n * (sizeof(int64_t) + sizeof(float)) + n * sizeof(int32_t)}};
-  for (auto& a : allocs) {
-    e = hipMalloc(a.p, a.bytes);
-    if (e == hipSuccess) e = hipMemset(*a.p, 0, a.bytes);
-    if (e != hipSuccess) { int rc = fail(nullptr, -4, "hipMalloc", e); bez_sim_destroy(s); return rc; }
-  }
-  if (cfg->flags & BEZ_FLAG_ALL_GROUND_SHAPES) {   // records of the extra ground points (one-env-per-lane kernel)
-    e = hipMalloc((void**)&s->xhit, n * BEZ_NXPT * 8 * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(s->xhit, 0, n * BEZ_NXPT * 8 * sizeof(float));
-    if (e != hipSuccess) { int rc = fail(nullptr, -4, "hipMalloc", e); bez_sim_destroy(s); return rc; }
-  }
-  if (cfg->flags & BEZ_FLAG_DOF_FORCE) {
-    if (int rc = ensure_actuator_buffers(s)) { g_create_error = s->err; bez_sim_destroy(s); return rc; }
-  }
-  (void)hipEventCreate(&s->ev0);
-  (void)hipEventCreate(&s->ev1);
-  // state after KickEnv.__init__: allocate_buffers (vec_task.py:226-249) then reset_idx(all) (kick_env.py:238)
-  Params P = make_params(s, nullptr);
-  goal_draw(s->cfg.seed, s->reset_calls++, 1, P.goal_draw);  // the reset_idx(all) that ends Kick/Walk/OrientEnv.__init__
-  hipLaunchKernelGGL(init_misc_kernel, dim3((s->n + TB - 1) / TB), dim3(TB), 0, 0, s->state, s->n, s->cfg.goal[0], s->cfg.goal[1]);
-  hipLaunchKernelGGL(reset_kernel, dim3((s->n + TB - 1) / TB), dim3(TB), 0, 0, P, (const int32_t*)nullptr, s->n);
-  e = hipDeviceSynchronize();
-  if (e != hipSuccess) { int rc = fail(nullptr, -2, "init kernels", e); bez_sim_destroy(s); return rc; }
+  if (int rc = sim_init(s)) { g_create_error = s->err; bez_sim_destroy(s); return rc; }
   *out = s;
   return 0;
 }
 
 int bez_sim_get_tensor(BezSim* s, int which, void** dev_ptr, int64_t shape[3], int* ndim, int* dtype) {
   if (!s || !dev_ptr || !shape || !ndim || !dtype) return fail(s, -1, "bez_sim_get_tensor: null argument");
-  const int64_t n = s->n;
-  *dtype = BEZ_DTYPE_F32;
-  switch (which) {
-    case BEZ_TENSOR_ROOT_STATE: *dev_ptr = s->root_states; shape[0] = n * s->nact; shape[1] = 13; *ndim = 2; break;
-    case BEZ_TENSOR_DOF_STATE: *dev_ptr = s->dof_state; shape[0] = n * BEZ_ND; shape[1] = 2; *ndim = 2; break;
-    case BEZ_TENSOR_RIGID_BODY_STATE: *dev_ptr = s->rigid_body; shape[0] = n * s->nbe; shape[1] = 13; *ndim = 2; break;
-    case BEZ_TENSOR_NET_CONTACT_FORCE: *dev_ptr = s->contact; shape[0] = n * s->nbe; shape[1] = 3; *ndim = 2; break;
-    case BEZ_TENSOR_OBS: *dev_ptr = s->obs; shape[0] = n; shape[1] = s->nobs; *ndim = 2; break;
-    case BEZ_TENSOR_REW: *dev_ptr = s->rew; shape[0] = n; *ndim = 1; break;
-    case BEZ_TENSOR_RESET: *dev_ptr = s->reset; shape[0] = n; *ndim = 1; *dtype = BEZ_DTYPE_I64; break;
-    case BEZ_TENSOR_PROGRESS: *dev_ptr = s->progress; shape[0] = n; *ndim = 1; *dtype = BEZ_DTYPE_I64; break;
-    case BEZ_TENSOR_TIMEOUT: *dev_ptr = s->timeout; shape[0] = n; *ndim = 1; *dtype = BEZ_DTYPE_I64; break;
-    case BEZ_TENSOR_DOF_TARGET: *dev_ptr = s->targets_aos; shape[0] = n; shape[1] = BEZ_ND; *ndim = 2; break;
-    case BEZ_TENSOR_PREV_LIN_VEL: *dev_ptr = s->prev_aos; shape[0] = n; shape[1] = 3; *ndim = 2; break;
-    case BEZ_TENSOR_FEET: *dev_ptr = s->feet_aos; shape[0] = n; shape[1] = 8; *ndim = 2; break;
-    case BEZ_TENSOR_GOAL: *dev_ptr = s->goal_aos; shape[0] = n; shape[1] = 2; *ndim = 2; break;
-    case BEZ_TENSOR_RANDOMIZE_BUF: *dev_ptr = s->randomize; shape[0] = n; *ndim = 1; *dtype = BEZ_DTYPE_I64; break;
-    case BEZ_TENSOR_DR_NOISE: *dev_ptr = s->dr_state->noise; shape[0] = 4; *ndim = 1; break;
-    case BEZ_TENSOR_NONFINITE_COUNT: *dev_ptr = s->nonfinite; shape[0] = n; *ndim = 1; *dtype = BEZ_DTYPE_I64; break;
-    case BEZ_TENSOR_HEALTH: *dev_ptr = s->health; shape[0] = 1; *ndim = 1; *dtype = BEZ_DTYPE_I64; break;
-    default: return fail(s, -1, "bez_sim_get_tensor: unknown tensor id");
-  }
+  if (which < 0 || which >= BEZ_TENSOR_COUNT) return fail(s, -1, "bez_sim_get_tensor: unknown tensor id");
+  const TensorRow& t = TENSORS[which];
+  *dev_ptr = *t.slot(s); *dtype = t.dtype; *ndim = t.cols ? 2 : 1;
+  tensor_shape(s, t, shape);
   return 0;
 }
 
@@ -729,82 +775,54 @@ int bez_sim_get_episode_tensor(BezSim* s, int which, void** dev_ptr, int64_t sha
 int bez_sim_refresh_tensor(BezSim* s, int which, void* stream_) {
   if (!s) return -1;
   hipStream_t stream = (hipStream_t)stream_;
+  if (which < 0 || which >= BEZ_TENSOR_COUNT) return fail(s, -1, "bez_sim_refresh_tensor: unknown tensor id");
+  const TensorRow& t = TENSORS[which];
   const int n = s->n;
-  auto blocks = [](size_t total) { return dim3((unsigned)((total + TB - 1) / TB)); };
-  switch (which) {
-    case BEZ_TENSOR_ROOT_STATE: hipLaunchKernelGGL(refresh_root_kernel, blocks((size_t)n * 13 * s->nact), dim3(TB), 0, stream, s->state, s->root_states, n, s->nact); break;
-    case BEZ_TENSOR_DOF_STATE: hipLaunchKernelGGL(refresh_dof_kernel, blocks((size_t)n * BEZ_ND * 2), dim3(TB), 0, stream, s->state, s->dof_state, n); break;
-    case BEZ_TENSOR_RIGID_BODY_STATE:
-      if (s->cleats) hipLaunchKernelGGL(refresh_rigid_body_kernel<true>, dim3((n + 63) / 64), dim3(64), 0, stream, s->state, s->rigid_body, n, (int)s->has_ball, s->cfg.flags);
-      else hipLaunchKernelGGL(refresh_rigid_body_kernel<false>, dim3((n + 63) / 64), dim3(64), 0, stream, s->state, s->rigid_body, n, (int)s->has_ball, s->cfg.flags);
-      break;
-    case BEZ_TENSOR_NET_CONTACT_FORCE: hipLaunchKernelGGL(refresh_rows_kernel, blocks((size_t)n * s->nbe * 3), dim3(TB), 0, stream, s->state, s->contact, n, (int)F_CF, s->nbe * 3); break;
-    case BEZ_TENSOR_DOF_TARGET: hipLaunchKernelGGL(refresh_rows_kernel, blocks((size_t)n * BEZ_ND), dim3(TB), 0, stream, s->state, s->targets_aos, n, (int)F_TARGET, BEZ_ND); break;
-    case BEZ_TENSOR_PREV_LIN_VEL: hipLaunchKernelGGL(refresh_rows_kernel, blocks((size_t)n * 3), dim3(TB), 0, stream, s->state, s->prev_aos, n, (int)F_PREV, 3); break;
-    case BEZ_TENSOR_FEET: hipLaunchKernelGGL(refresh_rows_kernel, blocks((size_t)n * 8), dim3(TB), 0, stream, s->state, s->feet_aos, n, (int)F_FEET, 8); break;
-    case BEZ_TENSOR_GOAL: hipLaunchKernelGGL(refresh_rows_kernel, blocks((size_t)n * 2), dim3(TB), 0, stream, s->state, s->goal_aos, n, (int)F_GOAL, 2); break;
-    case BEZ_TENSOR_OBS: case BEZ_TENSOR_REW: case BEZ_TENSOR_RESET: case BEZ_TENSOR_PROGRESS: case BEZ_TENSOR_TIMEOUT:
-    case BEZ_TENSOR_NONFINITE_COUNT: case BEZ_TENSOR_HEALTH: break;  // always live
-    default: return fail(s, -1, "bez_sim_refresh_tensor: unknown tensor id");
+  const size_t total = tensor_numel(s, t);
+  float* out = (float*)*t.slot(s);
+  switch (t.refresh) {
+    case LIVE: return 0;
+    case ROWS: return LAUNCH(s, refresh_rows_kernel, total, stream, s->state, out, n, t.field0, (int)(total / n));
+    case ROOT_KERNEL: return LAUNCH(s, refresh_root_kernel, total, stream, s->state, out, n, s->nact);
+    case DOF_KERNEL: return LAUNCH(s, refresh_dof_kernel, total, stream, s->state, out, n);
+    case RIGID_BODY_KERNEL:
+      return s->cleats ? LAUNCH_PER_ENV(s, refresh_rigid_body_kernel<true>, stream, s->state, out, n, (int)s->has_ball, s->cfg.flags)
+                       : LAUNCH_PER_ENV(s, refresh_rigid_body_kernel<false>, stream, s->state, out, n, (int)s->has_ball, s->cfg.flags);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(s, -2, "refresh kernel launch", e);
   return 0;
 }
 
 int bez_sim_set_actor_root_state_tensor_indexed(BezSim* s, const float* root_states_dev, const int32_t* ids, int32_t count, void* stream) {
   if (!s || !root_states_dev || (!ids && count > 0) || count < 0) return fail(s, -1, "set_actor_root_state_tensor_indexed: bad argument");
   if (count == 0) return 0;
-  hipLaunchKernelGGL(set_root_indexed_kernel, dim3(((size_t)count * 13 + TB - 1) / TB), dim3(TB), 0, (hipStream_t)stream, s->state, root_states_dev, ids, count, s->n, s->nact);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(s, -2, "set_root_indexed launch", e);
+  return LAUNCH(s, set_root_indexed_kernel, (size_t)count * 13, (hipStream_t)stream, s->state, root_states_dev, ids, count, s->n, s->nact);
 }
 int bez_sim_set_dof_state_tensor_indexed(BezSim* s, const float* dof_state_dev, const int32_t* ids, int32_t count, void* stream) {
   if (!s || !dof_state_dev || (!ids && count > 0) || count < 0) return fail(s, -1, "set_dof_state_tensor_indexed: bad argument");
   if (count == 0) return 0;
-  hipLaunchKernelGGL(set_dof_indexed_kernel, dim3(((size_t)count * BEZ_ND * 2 + TB - 1) / TB), dim3(TB), 0, (hipStream_t)stream, s->state, dof_state_dev, ids, count, s->n, s->nact);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(s, -2, "set_dof_indexed launch", e);
+  return LAUNCH(s, set_dof_indexed_kernel, (size_t)count * BEZ_ND * 2, (hipStream_t)stream, s->state, dof_state_dev, ids, count, s->n, s->nact);
 }
 int bez_sim_set_dof_position_target_tensor(BezSim* s, const float* targets_dev, void* stream) {
-  if (!s || !targets_dev) return fail(s, -1, "set_dof_position_target_tensor: bad argument");
-  hipLaunchKernelGGL(scatter_rows_kernel, dim3(((size_t)s->n * BEZ_ND + TB - 1) / TB), dim3(TB), 0, (hipStream_t)stream, s->state, targets_dev, s->n, (int)F_TARGET, BEZ_ND);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(s, -2, "set_target launch", e);
+  return scatter_rows(s, BEZ_TENSOR_DOF_TARGET, targets_dev, stream, "set_dof_position_target_tensor: bad argument");
 }
 int bez_sim_set_dof_position_target_tensor_indexed(BezSim* s, const float* targets_dev, const int32_t* ids, int32_t count, void* stream) {
   if (!s || !targets_dev || (!ids && count > 0) || count < 0) return fail(s, -1, "set_dof_position_target_tensor_indexed: bad argument");
   if (count == 0) return 0;
-  hipLaunchKernelGGL(set_target_indexed_kernel, dim3(((size_t)count * BEZ_ND + TB - 1) / TB), dim3(TB), 0, (hipStream_t)stream, s->state, targets_dev, ids, count, s->n, s->nact);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(s, -2, "set_target_indexed launch", e);
+  return LAUNCH(s, set_target_indexed_kernel, (size_t)count * BEZ_ND, (hipStream_t)stream, s->state, targets_dev, ids, count, s->n, s->nact);
 }
 int bez_sim_set_net_contact_force_tensor(BezSim* s, const float* forces_dev, void* stream) {
-  if (!s || !forces_dev) return fail(s, -1, "set_net_contact_force_tensor: bad argument");
-  hipLaunchKernelGGL(scatter_rows_kernel, dim3(((size_t)s->n * s->nbe * 3 + TB - 1) / TB), dim3(TB), 0, (hipStream_t)stream, s->state, forces_dev, s->n, (int)F_CF, s->nbe * 3);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(s, -2, "set_contact launch", e);
+  return scatter_rows(s, BEZ_TENSOR_NET_CONTACT_FORCE, forces_dev, stream, "set_net_contact_force_tensor: bad argument");
 }
 /* test hook used by the parity tests: writes prev_lin_vel (N,3) */
 int bez_sim_set_prev_lin_vel_tensor(BezSim* s, const float* prev_dev, void* stream) {
-  if (!s || !prev_dev) return fail(s, -1, "set_prev_lin_vel_tensor: bad argument");
-  hipLaunchKernelGGL(scatter_rows_kernel, dim3(((size_t)s->n * 3 + TB - 1) / TB), dim3(TB), 0, (hipStream_t)stream, s->state, prev_dev, s->n, (int)F_PREV, 3);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(s, -2, "set_prev launch", e);
+  return scatter_rows(s, BEZ_TENSOR_PREV_LIN_VEL, prev_dev, stream, "set_prev_lin_vel_tensor: bad argument");
 }
 int bez_sim_set_flags(BezSim* s, uint32_t flags) {
   if (!s) return -1;
   const uint32_t asset = BEZ_FLAG_CLEATS | BEZ_FLAG_BOX_ASSET;  // the asset is fixed at creation (buffer shapes, kernel variant)
   const uint32_t merged = (flags & ~asset) | (s->cfg.flags & asset);
   if (const char* why = oracle_only(merged, nullptr)) return fail(s, -5, why);
-  if ((merged & BEZ_FLAG_ALL_GROUND_SHAPES) && !s->xhit) {
-    (void)hipSetDevice(s->device);
-    HIP_TRY(s, hipMalloc((void**)&s->xhit, (size_t)s->cfg.num_envs * BEZ_NXPT * 8 * sizeof(float)));
-    HIP_TRY(s, hipMemset(s->xhit, 0, (size_t)s->cfg.num_envs * BEZ_NXPT * 8 * sizeof(float)));
-  }
-  if (merged & BEZ_FLAG_DOF_FORCE) {
-    if (int rc = ensure_actuator_buffers(s)) return rc;
-  }
+  RC_TRY(ensure_flag_buffers(s, merged));
   s->cfg.flags = merged;
   return 0;
 }
@@ -825,9 +843,7 @@ int bez_sim_get_actuator_tensor(BezSim* s, int which, void** dev_ptr, int64_t sh
 int bez_sim_refresh_actuator_tensors(BezSim* s, void* stream) {
   if (!s) return -1;
   if (!(s->cfg.flags & BEZ_FLAG_DOF_FORCE) || !s->df_raw) return fail(s, -1, "bez_sim_refresh_actuator_tensors: BEZ_FLAG_DOF_FORCE is not set (the step kernels record no joint forces without it)");
-  hipLaunchKernelGGL(refresh_actuator_kernel, dim3(((size_t)s->n * BEZ_ND + TB - 1) / TB), dim3(TB), 0, (hipStream_t)stream, s->df_raw, s->df_out, s->n, s->cfg.substeps);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(s, -2, "refresh_actuator launch", e);
+  return LAUNCH(s, refresh_actuator_kernel, (size_t)s->n * BEZ_ND, (hipStream_t)stream, s->df_raw, s->df_out, s->n, s->cfg.substeps);
 }
 int bez_sim_set_obs_calls(BezSim* s, int64_t calls) { if (!s) return -1; s->obs_calls = calls; return 0; }
 
@@ -850,10 +866,7 @@ int bez_sim_observe_reward(BezSim* s, void* stream) {
 }
 /* (N,2) per-env goal of bez_walk (test hook; walk_env.py:143,570-575) */
 int bez_sim_set_goal_tensor(BezSim* s, const float* goal_dev, void* stream) {
-  if (!s || !goal_dev) return fail(s, -1, "set_goal_tensor: bad argument");
-  hipLaunchKernelGGL(scatter_rows_kernel, dim3(((size_t)s->n * 2 + TB - 1) / TB), dim3(TB), 0, (hipStream_t)stream, s->state, goal_dev, s->n, (int)F_GOAL, 2);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(s, -2, "set_goal launch", e);
+  return scatter_rows(s, BEZ_TENSOR_GOAL, goal_dev, stream, "set_goal_tensor: bad argument");
 }
 int bez_sim_step(BezSim* s, const float* actions_dev, void* stream) {
   if (!s || !actions_dev) return fail(s, -1, "bez_sim_step: bad argument");
@@ -886,55 +899,52 @@ int bez_sim_reset_indexed(BezSim* s, const int32_t* env_ids_dev, int32_t count, 
   if (count == 0) return 0;
   Params P = make_params(s, nullptr);
   goal_draw(s->cfg.seed, s->reset_calls++, 1, P.goal_draw);
-  hipLaunchKernelGGL(reset_kernel, dim3((count + TB - 1) / TB), dim3(TB), 0, (hipStream_t)stream, P, env_ids_dev, count);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(s, -2, "reset launch", e);
+  return LAUNCH(s, reset_kernel, (size_t)count, (hipStream_t)stream, P, env_ids_dev, count);
 }
+
+// (N, width) of every BezEnvParam (abi.PARAM_WIDTH is the Python mirror)
+static constexpr int PARAM_WIDTH[BEZ_PARAM_COUNT] = {1, BEZ_ND, BEZ_ND, BEZ_NL, 3, BEZ_ND, BEZ_ND};
 
 int bez_sim_set_env_params(BezSim* s, int param, const float* values_dev, void* stream) {
   if (!s || param < 0 || param >= BEZ_PARAM_COUNT) return fail(s, -1, "bez_sim_set_env_params: bad argument");
-  static const int width[BEZ_PARAM_COUNT] = {1, BEZ_ND, BEZ_ND, BEZ_NL, 3, BEZ_ND, BEZ_ND};
   const bool packed = param == BEZ_PARAM_KP_SCALE || param == BEZ_PARAM_KD_SCALE || param == BEZ_PARAM_DOF_LOWER || param == BEZ_PARAM_DOF_UPPER;
   if (param == BEZ_PARAM_GRAVITY) s->gravity_uniform = false;   // rows written from outside may differ from env to env
   if (!values_dev) {
-    if (s->dr[param]) { HIP_TRY(s, hipStreamSynchronize((hipStream_t)stream)); (void)hipFree(s->dr[param]); s->dr[param] = nullptr; }
-    if (packed && repack_dr(s, (hipStream_t)stream)) return fail(s, -2, "bez_sim_set_env_params: repack");
-    return 0;
+    if (s->dr[param]) { HIP_TRY(s, hipStreamSynchronize((hipStream_t)stream)); dev_free(s, &s->dr[param]); }
+  } else {
+    const size_t bytes = (size_t)s->n * PARAM_WIDTH[param] * sizeof(float);
+    if (!s->dr[param]) RC_TRY(dev_alloc_zeroed(s, &s->dr[param], bytes, (hipStream_t)stream));
+    HIP_TRY(s, hipMemcpyAsync(s->dr[param], values_dev, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   }
-  size_t bytes = (size_t)s->n * width[param] * sizeof(float);
-  if (!s->dr[param]) HIP_TRY(s, hipMalloc((void**)&s->dr[param], bytes));
-  HIP_TRY(s, hipMemcpyAsync(s->dr[param], values_dev, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   if (packed && repack_dr(s, (hipStream_t)stream)) return fail(s, -2, "bez_sim_set_env_params: repack");
   return 0;
 }
 
-__global__ void fill_rows_kernel(float* out, const float* row, int width, size_t total) {
+struct ParamRow { float v[BEZ_NL]; };   // the widest row, passed to the kernel by value
+__global__ void fill_rows_kernel(float* out, ParamRow row, int width, size_t total) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < total) out[i] = row[i % width];
+  if (i < total) out[i] = row.v[i % width];
 }
-
-int bez_sim_get_env_params(BezSim* s, int param, float* out_dev, void* stream_) {
-  if (!s || !out_dev || param < 0 || param >= BEZ_PARAM_COUNT) return fail(s, -1, "bez_sim_get_env_params: bad argument");
-  static const int width[BEZ_PARAM_COUNT] = {1, BEZ_ND, BEZ_ND, BEZ_NL, 3, BEZ_ND, BEZ_ND};
-  hipStream_t stream = (hipStream_t)stream_;
-  const size_t total = (size_t)s->n * width[param];
-  if (s->dr[param]) { HIP_TRY(s, hipMemcpyAsync(out_dev, s->dr[param], total * sizeof(float), hipMemcpyDeviceToDevice, stream)); return 0; }
-  float row[BEZ_NL];
-  for (int k = 0; k < width[param]; ++k) {
+// the default rows of a parameter (what the step uses while the parameter is not set): only enqueues work on `stream`
+static int fill_default_params(BezSim* s, int param, float* out_dev, hipStream_t stream) {
+  const int width = PARAM_WIDTH[param];
+  ParamRow row = {};
+  for (int k = 0; k < width; ++k) {
     switch (param) {
-      case BEZ_PARAM_FRICTION: row[k] = s->cfg.plane_friction; break;
-      case BEZ_PARAM_GRAVITY: row[k] = s->cfg.gravity[k]; break;
-      case BEZ_PARAM_DOF_LOWER: row[k] = (float)BEZ_DOF_LOWER[k]; break;
-      case BEZ_PARAM_DOF_UPPER: row[k] = (float)BEZ_DOF_UPPER[k]; break;
-      default: row[k] = 1.0f; break;
+      case BEZ_PARAM_FRICTION: row.v[k] = s->cfg.plane_friction; break;
+      case BEZ_PARAM_GRAVITY: row.v[k] = s->cfg.gravity[k]; break;
+      case BEZ_PARAM_DOF_LOWER: row.v[k] = (float)BEZ_DOF_LOWER[k]; break;
+      case BEZ_PARAM_DOF_UPPER: row.v[k] = (float)BEZ_DOF_UPPER[k]; break;
+      default: row.v[k] = 1.0f; break;
     }
   }
-  float* row_dev = nullptr;
-  HIP_TRY(s, hipMalloc((void**)&row_dev, sizeof(row)));
-  HIP_TRY(s, hipMemcpy(row_dev, row, sizeof(row), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(fill_rows_kernel, dim3((unsigned)((total + TB - 1) / TB)), dim3(TB), 0, stream, out_dev, row_dev, width[param], total);
-  HIP_TRY(s, hipStreamSynchronize(stream));
-  (void)hipFree(row_dev);
+  return LAUNCH(s, fill_rows_kernel, (size_t)s->n * width, stream, out_dev, row, width, (size_t)s->n * width);
+}
+
+int bez_sim_get_env_params(BezSim* s, int param, float* out_dev, void* stream) {
+  if (!s || !out_dev || param < 0 || param >= BEZ_PARAM_COUNT) return fail(s, -1, "bez_sim_get_env_params: bad argument");
+  if (!s->dr[param]) return fill_default_params(s, param, out_dev, (hipStream_t)stream);
+  HIP_TRY(s, hipMemcpyAsync(out_dev, s->dr[param], (size_t)s->n * PARAM_WIDTH[param] * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return 0;
 }
 
@@ -943,11 +953,7 @@ int bez_sim_add_dr_noise(BezSim* s, const float* x_dev, float* y_dev, int64_t n,
   if (n == 0) return 0;
   if (which == 0 && x_dev == s->obs && y_dev == s->obs && s->obs_noise_applied) return 0;   // the step kernel already added it (BEZ_FLAG_OBS_NOISE_IN_STEP)
   const long long quads = (n + 3) / 4;
-  hipLaunchKernelGGL(dr_noise_kernel, dim3((unsigned)((quads + TB - 1) / TB)), dim3(TB), 0, (hipStream_t)stream_, x_dev, y_dev, (long long)n, s->dr_state, s->dr_snap, (int)which,
-                     s->cfg.seed, s->cfg.env_id_offset);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(s, -2, "dr_noise_kernel launch", e);
-  return 0;
+  return LAUNCH(s, dr_noise_kernel, (size_t)quads, (hipStream_t)stream_, x_dev, y_dev, (long long)n, s->dr_state, s->dr_snap, (int)which, s->cfg.seed, s->cfg.env_id_offset);
 }
 
 /* The randomisation kernel of the COMING control step, now, on `stream` (the step then skips its own): the caller may overlap it with
@@ -999,14 +1005,10 @@ int bez_sim_set_randomization(BezSim* s, const BezDrConfig* dr, void* stream_) {
   const struct { int param; int on; } need[] = {{BEZ_PARAM_FRICTION, dr->friction.enabled}, {BEZ_PARAM_KP_SCALE, dr->stiffness.enabled},
                                                 {BEZ_PARAM_KD_SCALE, dr->damping.enabled}, {BEZ_PARAM_DOF_LOWER, dr->lower.enabled},
                                                 {BEZ_PARAM_DOF_UPPER, dr->upper.enabled}, {BEZ_PARAM_GRAVITY, dr->gravity.enabled}};
-  static const int width[BEZ_PARAM_COUNT] = {1, BEZ_ND, BEZ_ND, BEZ_NL, 3, BEZ_ND, BEZ_ND};
   for (const auto& nd : need) {
     if (!nd.on || s->dr[nd.param]) continue;
-    float* buf = nullptr;
-    HIP_TRY(s, hipMalloc((void**)&buf, (size_t)s->n * width[nd.param] * sizeof(float)));
-    int rc = bez_sim_get_env_params(s, nd.param, buf, stream_);
-    if (rc) { (void)hipFree(buf); return rc; }
-    s->dr[nd.param] = buf;
+    RC_TRY(dev_alloc_zeroed(s, &s->dr[nd.param], (size_t)s->n * PARAM_WIDTH[nd.param] * sizeof(float), stream));
+    if (int rc = fill_default_params(s, nd.param, s->dr[nd.param], stream)) { dev_free(s, &s->dr[nd.param]); return rc; }
   }
   HIP_TRY(s, hipMemsetAsync(s->dr_state, 0, sizeof(DrState), stream));
   s->dr_on = true;
@@ -1024,10 +1026,9 @@ int bez_sim_set_randomization(BezSim* s, const BezDrConfig* dr, void* stream_) {
 #ifdef BEZ_WS_STAMPS
 /* diagnostic build only: run one fused step and return the 8 x 32 s_memtime stamps (roles x phase boundaries) of workgroup 0 */
 int bez_sim_debug_stamps(BezSim* s, const float* actions_dev, unsigned long long* out_host) {
-  if (!s->stamps) { HIP_TRY(s, hipMalloc((void**)&s->stamps, 256 * sizeof(unsigned long long))); }
+  if (!s->stamps) RC_TRY(dev_alloc_zeroed(s, &s->stamps, 256 * sizeof(unsigned long long)));
   HIP_TRY(s, hipMemset(s->stamps, 0, 256 * sizeof(unsigned long long)));
-  int rc = bez_sim_step(s, actions_dev, nullptr);
-  if (rc) return rc;
+  RC_TRY(bez_sim_step(s, actions_dev, nullptr));
   HIP_TRY(s, hipDeviceSynchronize());
   HIP_TRY(s, hipMemcpy(out_host, s->stamps, 256 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return 0;
@@ -1059,17 +1060,12 @@ int bez_sim_apply_body_forces(BezSim* s, const float* forces_dev, const float* t
   if (space != BEZ_SPACE_ENV && space != BEZ_SPACE_LOCAL) return fail(s, -1, "bez_sim_apply_body_forces: space must be BEZ_SPACE_ENV or BEZ_SPACE_LOCAL");
   hipStream_t stream = (hipStream_t)stream_;
   if (!s->ext) {   // first call: the pending buffer (zeroed in stream order), and the switch to the EXT kernels for the rest of the sim's life
-    const size_t bytes = (size_t)EXT_WORDS * s->n * sizeof(float);
-    HIP_TRY(s, hipMalloc((void**)&s->ext, bytes));
-    HIP_TRY(s, hipMemsetAsync(s->ext, 0, bytes, stream));
+    RC_TRY(dev_alloc_zeroed(s, &s->ext, (size_t)EXT_WORDS * s->n * sizeof(float), stream));
     s->ext_on = true;
   }
   if (!forces_dev && !torques_dev) return 0;
-  const dim3 grid((unsigned)((s->n + 63) / 64)), block(64);
-  if (s->cleats) hipLaunchKernelGGL(ext_prepare_kernel<true>, grid, block, 0, stream, s->state, s->ext, forces_dev, torques_dev, positions_dev, (int)space, s->n, (int)s->has_ball, s->cfg.flags);
-  else hipLaunchKernelGGL(ext_prepare_kernel<false>, grid, block, 0, stream, s->state, s->ext, forces_dev, torques_dev, positions_dev, (int)space, s->n, (int)s->has_ball, s->cfg.flags);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(s, -2, "ext_prepare_kernel launch", e);
+  return s->cleats ? LAUNCH_PER_ENV(s, ext_prepare_kernel<true>, stream, s->state, s->ext, forces_dev, torques_dev, positions_dev, (int)space, s->n, (int)s->has_ball, s->cfg.flags)
+                   : LAUNCH_PER_ENV(s, ext_prepare_kernel<false>, stream, s->state, s->ext, forces_dev, torques_dev, positions_dev, (int)space, s->n, (int)s->has_ball, s->cfg.flags);
 }
 
 int bez_sim_seed(BezSim* s, uint64_t seed) { if (!s) return -1; s->cfg.seed = seed; s->dr_prelaunched = false; return 0; }

@@ -16,6 +16,51 @@ class BezSimError(RuntimeError):
     pass
 
 
+vp, i32, i64, u32, u64, fp = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_void_p
+# (restype, argtypes) of every bez_sim_* entry point of include/bez_sim.h (the bez_ppo_* ones of the same library: ppo/fused.py)
+SIGS = {
+    "bez_sim_default_config": (C.c_int, [C.POINTER(abi.BezSimConfig), i32]),
+    "bez_sim_create": (C.c_int, [C.POINTER(abi.BezSimConfig), C.c_int, C.POINTER(vp)]),
+    "bez_sim_destroy": (C.c_int, [vp]),
+    "bez_sim_last_error": (C.c_char_p, [vp]),
+    "bez_sim_get_tensor": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bez_sim_refresh_tensor": (C.c_int, [vp, C.c_int, vp]),
+    "bez_sim_get_episode_tensor": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bez_sim_set_actor_root_state_tensor_indexed": (C.c_int, [vp, fp, vp, i32, vp]),
+    "bez_sim_set_dof_state_tensor_indexed": (C.c_int, [vp, fp, vp, i32, vp]),
+    "bez_sim_set_dof_position_target_tensor": (C.c_int, [vp, fp, vp]),
+    "bez_sim_set_dof_position_target_tensor_indexed": (C.c_int, [vp, fp, vp, i32, vp]),
+    "bez_sim_set_net_contact_force_tensor": (C.c_int, [vp, fp, vp]),
+    "bez_sim_set_prev_lin_vel_tensor": (C.c_int, [vp, fp, vp]),
+    "bez_sim_set_goal_tensor": (C.c_int, [vp, fp, vp]),
+    "bez_sim_set_flags": (C.c_int, [vp, u32]),
+    "bez_sim_set_obs_calls": (C.c_int, [vp, i64]),
+    "bez_sim_pre_physics": (C.c_int, [vp, fp, vp]),
+    "bez_sim_simulate": (C.c_int, [vp, vp]),
+    "bez_sim_post_physics": (C.c_int, [vp, vp]),
+    "bez_sim_observe_reward": (C.c_int, [vp, vp]),
+    "bez_sim_step": (C.c_int, [vp, fp, vp]),
+    "bez_sim_step_many": (C.c_int, [vp, fp, i32, vp]),
+    "bez_sim_reset_indexed": (C.c_int, [vp, vp, i32, vp]),
+    "bez_sim_set_env_params": (C.c_int, [vp, C.c_int, fp, vp]),
+    "bez_sim_get_env_params": (C.c_int, [vp, C.c_int, fp, vp]),
+    "bez_sim_set_randomization": (C.c_int, [vp, C.POINTER(abi.BezDrConfig), vp]),
+    "bez_sim_dr_prelaunch": (C.c_int, [vp, vp]),
+    "bez_sim_dr_step_args": (C.c_int, [vp, vp, i32]),
+    "bez_sim_dr_cancel": (C.c_int, [vp]),
+    "bez_sim_action_noise_source": (C.c_int, [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(i64)]),
+    "bez_sim_add_dr_noise": (C.c_int, [vp, fp, fp, i64, i32, vp]),
+    "bez_sim_seed": (C.c_int, [vp, u64]),
+    "bez_sim_health": (C.c_int, [vp, C.POINTER(u64), i32, vp]),
+    "bez_sim_calibrate": (C.c_int, [vp, u64, i32, vp]),
+    "bez_sim_time_steps": (C.c_int, [vp, fp, i32, vp, C.POINTER(C.c_float)]),
+    "bez_sim_apply_body_forces": (C.c_int, [vp, fp, fp, fp, i32, vp]),
+    "bez_sim_get_actuator_tensor": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bez_sim_refresh_actuator_tensors": (C.c_int, [vp, vp]),
+}
+EXPORTS = list(SIGS)
+
+
 def load_library():
     """dlopen libbez_sim.so and declare every entry point of include/bez_sim.h."""
     global _LIB
@@ -26,59 +71,11 @@ def load_library():
         raise BezSimError("libbez_sim.so not built (%s): run `python -m bez_isaacgym_amd.build` -- "
                           "the HIP extension is required, there is no fallback path" % path)
     lib = C.CDLL(path)
-    vp, i32, i64, u32, u64, fp = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_void_p
-    sigs = {
-        "bez_sim_default_config": (C.c_int, [C.POINTER(abi.BezSimConfig), i32]),
-        "bez_sim_create": (C.c_int, [C.POINTER(abi.BezSimConfig), C.c_int, C.POINTER(vp)]),
-        "bez_sim_destroy": (C.c_int, [vp]),
-        "bez_sim_last_error": (C.c_char_p, [vp]),
-        "bez_sim_get_tensor": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-        "bez_sim_refresh_tensor": (C.c_int, [vp, C.c_int, vp]),
-        "bez_sim_get_episode_tensor": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-        "bez_sim_set_actor_root_state_tensor_indexed": (C.c_int, [vp, fp, vp, i32, vp]),
-        "bez_sim_set_dof_state_tensor_indexed": (C.c_int, [vp, fp, vp, i32, vp]),
-        "bez_sim_set_dof_position_target_tensor": (C.c_int, [vp, fp, vp]),
-        "bez_sim_set_dof_position_target_tensor_indexed": (C.c_int, [vp, fp, vp, i32, vp]),
-        "bez_sim_set_net_contact_force_tensor": (C.c_int, [vp, fp, vp]),
-        "bez_sim_set_prev_lin_vel_tensor": (C.c_int, [vp, fp, vp]),
-        "bez_sim_set_goal_tensor": (C.c_int, [vp, fp, vp]),
-        "bez_sim_set_flags": (C.c_int, [vp, u32]),
-        "bez_sim_set_obs_calls": (C.c_int, [vp, i64]),
-        "bez_sim_pre_physics": (C.c_int, [vp, fp, vp]),
-        "bez_sim_simulate": (C.c_int, [vp, vp]),
-        "bez_sim_post_physics": (C.c_int, [vp, vp]),
-        "bez_sim_observe_reward": (C.c_int, [vp, vp]),
-        "bez_sim_step": (C.c_int, [vp, fp, vp]),
-        "bez_sim_step_many": (C.c_int, [vp, fp, i32, vp]),
-        "bez_sim_reset_indexed": (C.c_int, [vp, vp, i32, vp]),
-        "bez_sim_set_env_params": (C.c_int, [vp, C.c_int, fp, vp]),
-        "bez_sim_get_env_params": (C.c_int, [vp, C.c_int, fp, vp]),
-        "bez_sim_set_randomization": (C.c_int, [vp, C.POINTER(abi.BezDrConfig), vp]),
-        "bez_sim_add_dr_noise": (C.c_int, [vp, fp, fp, i64, i32, vp]),
-        "bez_sim_seed": (C.c_int, [vp, u64]),
-        "bez_sim_health": (C.c_int, [vp, C.POINTER(u64), i32, vp]),
-        "bez_sim_calibrate": (C.c_int, [vp, u64, i32, vp]),
-        "bez_sim_time_steps": (C.c_int, [vp, fp, i32, vp, C.POINTER(C.c_float)]),
-        "bez_sim_apply_body_forces": (C.c_int, [vp, fp, fp, fp, i32, vp]),
-        "bez_sim_get_actuator_tensor": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-        "bez_sim_refresh_actuator_tensors": (C.c_int, [vp, vp]),
-    }
-    for name, (res, args) in sigs.items():
+    for name, (res, args) in SIGS.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     _LIB = lib
     return lib
-
-
-EXPORTS = ["bez_sim_default_config", "bez_sim_create", "bez_sim_destroy", "bez_sim_last_error", "bez_sim_get_tensor",
-           "bez_sim_refresh_tensor", "bez_sim_set_actor_root_state_tensor_indexed", "bez_sim_set_dof_state_tensor_indexed",
-           "bez_sim_set_dof_position_target_tensor", "bez_sim_set_dof_position_target_tensor_indexed",
-           "bez_sim_set_net_contact_force_tensor", "bez_sim_set_prev_lin_vel_tensor", "bez_sim_set_goal_tensor", "bez_sim_set_flags",
-           "bez_sim_set_obs_calls", "bez_sim_pre_physics", "bez_sim_simulate", "bez_sim_post_physics", "bez_sim_observe_reward", "bez_sim_step",
-           "bez_sim_step_many", "bez_sim_reset_indexed", "bez_sim_set_env_params", "bez_sim_get_env_params", "bez_sim_set_randomization", "bez_sim_dr_prelaunch", "bez_sim_dr_step_args", "bez_sim_dr_cancel", "bez_sim_action_noise_source", "bez_sim_add_dr_noise", "bez_sim_seed", "bez_sim_time_steps",
-           "bez_sim_calibrate", "bez_sim_health", "bez_sim_get_episode_tensor", "bez_sim_apply_body_forces",
-           "bez_sim_get_actuator_tensor", "bez_sim_refresh_actuator_tensors"]
-# (the bez_ppo_* entry points of the same library are bound in ppo/fused.py)
 
 
 class _DevView:
@@ -105,15 +102,17 @@ class BezSim:
         self.device = torch.device("cuda", self.device_id)
         self.num_envs = int(cfg.num_envs)
         self.has_ball = int(cfg.task) == abi.TASK_KICK
-        self.num_actors = 2 if self.has_ball else 1
-        self.num_bodies = (29 if int(cfg.flags) & abi.FLAG_CLEATS else 21) + (1 if self.has_ball else 0)
-        self.num_obs = 54 if self.has_ball else 52
         h = C.c_void_p()
         rc = self.lib.bez_sim_create(C.byref(cfg), self.device_id, C.byref(h))
         if rc != 0:
             raise BezSimError("bez_sim_create failed (%d): %s" % (rc, self.lib.bez_sim_last_error(None).decode()))
         self.h = h
         self._views = {}
+        # the layout is the library's: shapes as bez_sim_get_tensor reports them for this task and asset
+        self._shape = {w: self._describe(self.lib.bez_sim_get_tensor, w)[1] for w in range(abi.TENSOR_COUNT)}
+        self.num_actors = self._shape[abi.TENSOR_ROOT_STATE][0] // self.num_envs
+        self.num_bodies = self._shape[abi.TENSOR_RIGID_BODY_STATE][0] // self.num_envs
+        self.num_obs = self._shape[abi.TENSOR_OBS][1]
 
     def close(self):
         if getattr(self, "h", None):
@@ -142,14 +141,16 @@ class BezSim:
             raise BezSimError("expected %d elements, got %d" % (numel, t.numel()))
         return C.c_void_p(t.data_ptr())
 
+    def _describe(self, getter, which):
+        """(device pointer, shape, typestr) of a sim-owned buffer"""
+        p, shape, nd, dt = C.c_void_p(), (C.c_int64 * 3)(), C.c_int(), C.c_int()
+        self._check(getter(self.h, which, C.byref(p), shape, C.byref(nd), C.byref(dt)))
+        return p.value, tuple(int(shape[i]) for i in range(nd.value)), {abi.DTYPE_F32: "<f4", abi.DTYPE_I64: "<i8", abi.DTYPE_I32: "<i4"}[dt.value]
+
     def _wrap(self, key, getter, which):
         if key not in self._views:
-            p = C.c_void_p()
-            shape = (C.c_int64 * 3)()
-            nd, dt = C.c_int(), C.c_int()
-            self._check(getter(self.h, which, C.byref(p), shape, C.byref(nd), C.byref(dt)))
-            shp = [int(shape[i]) for i in range(nd.value)]
-            view = _DevView(p.value, shp, {abi.DTYPE_F32: "<f4", abi.DTYPE_I64: "<i8", abi.DTYPE_I32: "<i4"}[dt.value], self)
+            p, shp, typestr = self._describe(getter, which)
+            view = _DevView(p, shp, typestr, self)
             with torch.cuda.device(self.device):
                 self._views[key] = torch.as_tensor(view, device=self.device)
         return self._views[key]
@@ -190,35 +191,33 @@ class BezSim:
         self._check(self.lib.bez_sim_refresh_tensor(self.h, which, self._stream()))
         return self.tensor(which)
 
-    # ---- gym.set_* equivalents
+    # ---- gym.set_* equivalents: `src` is the full tensor in the layout of tensor `which`; actor_ids picks the rows an indexed setter takes
+    def _set(self, fn, which, src, actor_ids=None):
+        args = [self._ptr(src, torch.float32, torch.Size(self._shape[which]).numel())]
+        if actor_ids is not None:
+            args += [self._ptr(actor_ids, torch.int32), actor_ids.numel()]
+        self._check(fn(self.h, *args, self._stream()))
+
     def set_actor_root_state_tensor_indexed(self, root_states, actor_ids):
-        self._check(self.lib.bez_sim_set_actor_root_state_tensor_indexed(
-            self.h, self._ptr(root_states, torch.float32, self.num_envs * 13 * self.num_actors), self._ptr(actor_ids, torch.int32),
-            actor_ids.numel(), self._stream()))
+        self._set(self.lib.bez_sim_set_actor_root_state_tensor_indexed, abi.TENSOR_ROOT_STATE, root_states, actor_ids)
 
     def set_dof_state_tensor_indexed(self, dof_state, actor_ids):
-        self._check(self.lib.bez_sim_set_dof_state_tensor_indexed(
-            self.h, self._ptr(dof_state, torch.float32, self.num_envs * 36), self._ptr(actor_ids, torch.int32),
-            actor_ids.numel(), self._stream()))
+        self._set(self.lib.bez_sim_set_dof_state_tensor_indexed, abi.TENSOR_DOF_STATE, dof_state, actor_ids)
 
     def set_dof_position_target_tensor(self, targets):
-        self._check(self.lib.bez_sim_set_dof_position_target_tensor(
-            self.h, self._ptr(targets, torch.float32, self.num_envs * 18), self._stream()))
+        self._set(self.lib.bez_sim_set_dof_position_target_tensor, abi.TENSOR_DOF_TARGET, targets)
 
     def set_dof_position_target_tensor_indexed(self, targets, actor_ids):
-        self._check(self.lib.bez_sim_set_dof_position_target_tensor_indexed(
-            self.h, self._ptr(targets, torch.float32, self.num_envs * 18), self._ptr(actor_ids, torch.int32),
-            actor_ids.numel(), self._stream()))
+        self._set(self.lib.bez_sim_set_dof_position_target_tensor_indexed, abi.TENSOR_DOF_TARGET, targets, actor_ids)
 
     def set_net_contact_force_tensor(self, forces):
-        self._check(self.lib.bez_sim_set_net_contact_force_tensor(
-            self.h, self._ptr(forces, torch.float32, self.num_envs * self.num_bodies * 3), self._stream()))
+        self._set(self.lib.bez_sim_set_net_contact_force_tensor, abi.TENSOR_NET_CONTACT_FORCE, forces)
 
     def set_prev_lin_vel_tensor(self, prev):
-        self._check(self.lib.bez_sim_set_prev_lin_vel_tensor(self.h, self._ptr(prev, torch.float32, self.num_envs * 3), self._stream()))
+        self._set(self.lib.bez_sim_set_prev_lin_vel_tensor, abi.TENSOR_PREV_LIN_VEL, prev)
 
     def set_goal_tensor(self, goal):
-        self._check(self.lib.bez_sim_set_goal_tensor(self.h, self._ptr(goal, torch.float32, self.num_envs * 2), self._stream()))
+        self._set(self.lib.bez_sim_set_goal_tensor, abi.TENSOR_GOAL, goal)
 
     def set_flags(self, flags):
         self._check(self.lib.bez_sim_set_flags(self.h, int(flags)))
@@ -262,7 +261,7 @@ class BezSim:
 
     # ---- the path
     def pre_physics(self, actions):
-        self._check(self.lib.bez_sim_pre_physics(self.h, self._ptr(actions, torch.float32, self.num_envs * 18), self._stream()))
+        self._check(self.lib.bez_sim_pre_physics(self.h, self._ptr(actions, torch.float32, self.num_envs * abi.NUM_DOFS), self._stream()))
 
     def simulate(self):
         self._check(self.lib.bez_sim_simulate(self.h, self._stream()))
@@ -274,15 +273,15 @@ class BezSim:
         self._check(self.lib.bez_sim_observe_reward(self.h, self._stream()))
 
     def step(self, actions):
-        self._check(self.lib.bez_sim_step(self.h, self._ptr(actions, torch.float32, self.num_envs * 18), self._stream()))
+        self._check(self.lib.bez_sim_step(self.h, self._ptr(actions, torch.float32, self.num_envs * abi.NUM_DOFS), self._stream()))
 
     def step_many(self, actions, n_steps):
-        self._check(self.lib.bez_sim_step_many(self.h, self._ptr(actions, torch.float32, n_steps * self.num_envs * 18),
+        self._check(self.lib.bez_sim_step_many(self.h, self._ptr(actions, torch.float32, n_steps * self.num_envs * abi.NUM_DOFS),
                                                n_steps, self._stream()))
 
     def time_steps(self, actions, n_steps):
         ms = C.c_float()
-        self._check(self.lib.bez_sim_time_steps(self.h, self._ptr(actions, torch.float32, n_steps * self.num_envs * 18),
+        self._check(self.lib.bez_sim_time_steps(self.h, self._ptr(actions, torch.float32, n_steps * self.num_envs * abi.NUM_DOFS),
                                                 n_steps, self._stream(), C.byref(ms)))
         return float(ms.value)
 
@@ -290,11 +289,8 @@ class BezSim:
         self._check(self.lib.bez_sim_reset_indexed(self.h, self._ptr(env_ids, torch.int32), env_ids.numel(), self._stream()))
 
     def set_env_params(self, param, values):
-        if values is None:
-            self._check(self.lib.bez_sim_set_env_params(self.h, param, None, self._stream()))
-        else:
-            self._check(self.lib.bez_sim_set_env_params(
-                self.h, param, self._ptr(values, torch.float32, self.num_envs * abi.PARAM_WIDTH[param]), self._stream()))
+        ptr = None if values is None else self._ptr(values, torch.float32, self.num_envs * abi.PARAM_WIDTH[param])
+        self._check(self.lib.bez_sim_set_env_params(self.h, param, ptr, self._stream()))
 
     def get_env_params(self, param):
         """current (N, width) array of a domain-randomisation parameter (defaults where never set)"""

@@ -309,7 +309,9 @@ int bez_sim_get_actuator_tensor(BezSim* sim, int which, void** dev_ptr, int64_t 
 int bez_sim_refresh_actuator_tensors(BezSim* sim, void* stream);
 
 /* gym.refresh_{actor_root_state,dof_state,rigid_body_state,net_contact_force}_tensor
- * (kick_env.py:750-753): materialise the Isaac-layout tensor from the SoA state. */
+ * (kick_env.py:750-753): materialise the Isaac-layout tensor from the SoA state.  ROOT_STATE, DOF_STATE, RIGID_BODY_STATE,
+ * NET_CONTACT_FORCE, DOF_TARGET, PREV_LIN_VEL, FEET and GOAL need it; every other BezTensor is always live (the kernels
+ * write it in place) and its refresh is a successful no-op.  An id outside the enum: rc -1. */
 int bez_sim_refresh_tensor(BezSim* sim, int which, void* stream);
 
 /* gym.set_actor_root_state_tensor_indexed (kick_env.py:831-837): teleport the actors listed in

@@ -41,6 +41,17 @@ def test_exports_match_header(lib):
     assert lib.bez_ppo_abi_version() == PPO_ABI_VERSION == int(re.search(r"#define BEZ_PPO_ABI_VERSION (\d+)", hdr).group(1))
 
 
+def test_every_export_has_an_explicit_signature(lib):
+    """no entry point is left to ctypes' guesses (int arguments, int result): each name in EXPORTS carries the argtypes and restype
+    its row of sim.SIGS declares"""
+    from bez_isaacgym_amd.sim import EXPORTS, SIGS
+    assert len(EXPORTS) == len(set(EXPORTS)) == len(SIGS)
+    for name in EXPORTS:
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and fn.restype is not None, name
+        assert fn.restype is SIGS[name][0] and list(fn.argtypes) == list(SIGS[name][1]), name
+
+
 def test_default_config_matches_python(lib):
     c = abi.BezSimConfig()
     assert lib.bez_sim_default_config(C.byref(c), 4096) == 0

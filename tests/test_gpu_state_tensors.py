@@ -10,7 +10,10 @@ an outlier budget.
     all-actor, ball-actor and invalid id sets; after every call every refreshable tensor is snapshot and only the intended rows may
     change.
   * reset_indexed against Oracle.reset_idx, bit for bit (partial, unsorted, overlapping, with invalid ids for the HIP side only).
-  * get_env_params / set_env_params: the default rows, set -> get, set None -> the defaults again (the packed per-joint copy included).
+  * get_env_params / set_env_params: the default rows, set -> get, set None -> the defaults again (the packed per-joint copy included);
+    the default rows also from a side stream with one synchronisation at the end (the call only enqueues work).
+  * every BezTensor id: the header's dtype and shape per task and asset, a refresh that succeeds and returns the same memory.
+  * create / destroy over the lazily allocated buffers leaves the free device memory where it was.
 """
 import numpy as np
 import pytest
@@ -121,6 +124,46 @@ def test_rigid_body_refresh_against_fp64_references(gen, asset, task):
             np.testing.assert_array_equal(rb[:, nb], ball[:n])
         sim.close()
     print("worst error / bar:", {k: v for k, v in report.items() if k[1] == NMAX})
+
+
+# ---------------------------------------------------------------- the tensor table: every id, its documented dtype and shape
+
+def _documented_tensors(n, nact, nbe, nobs):
+    """dtype and shape of every BezTensor as include/bez_sim.h documents them beside the enum (A actors, B bodies, OBS width)"""
+    f32, i64 = torch.float32, torch.int64
+    return {abi.TENSOR_ROOT_STATE: (f32, (n * nact, 13)), abi.TENSOR_DOF_STATE: (f32, (n * 18, 2)),
+            abi.TENSOR_RIGID_BODY_STATE: (f32, (n * nbe, 13)), abi.TENSOR_NET_CONTACT_FORCE: (f32, (n * nbe, 3)),
+            abi.TENSOR_OBS: (f32, (n, nobs)), abi.TENSOR_REW: (f32, (n,)), abi.TENSOR_RESET: (i64, (n,)),
+            abi.TENSOR_PROGRESS: (i64, (n,)), abi.TENSOR_TIMEOUT: (i64, (n,)), abi.TENSOR_DOF_TARGET: (f32, (n, 18)),
+            abi.TENSOR_PREV_LIN_VEL: (f32, (n, 3)), abi.TENSOR_FEET: (f32, (n, 8)), abi.TENSOR_GOAL: (f32, (n, 2)),
+            abi.TENSOR_RANDOMIZE_BUF: (i64, (n,)), abi.TENSOR_DR_NOISE: (f32, (4,)), abi.TENSOR_NONFINITE_COUNT: (i64, (n,)),
+            abi.TENSOR_HEALTH: (i64, (1,))}
+
+
+@pytest.mark.parametrize("task", ["bez_kick", "bez_walk", "bez_orient"])
+@pytest.mark.parametrize("asset", ["default", "cleats"])
+def test_every_tensor_id_has_its_documented_layout_and_refreshes(asset, task):
+    """tensor(id) for every id below TENSOR_COUNT: the header's dtype and shape for this task and asset; refresh(id) succeeds -- a no-op
+    for the always-live ones, TENSOR_RANDOMIZE_BUF and TENSOR_DR_NOISE included -- and hands back a view of the same memory; the
+    first id past the table is an error for both"""
+    from bez_isaacgym_amd.sim import BezSimError
+    n = 3
+    sim = _sim(make_cfg(n, task=task, seed=2, **ASSETS[asset]))
+    kick = task == "bez_kick"
+    nact, nbe, nobs = (2 if kick else 1), (29 if asset == "cleats" else 21) + (1 if kick else 0), (54 if kick else 52)
+    assert (sim.num_actors, sim.num_bodies, sim.num_obs) == (nact, nbe, nobs)
+    doc = _documented_tensors(n, nact, nbe, nobs)
+    assert sorted(doc) == list(range(abi.TENSOR_COUNT))
+    for which in range(abi.TENSOR_COUNT):
+        t = sim.tensor(which)
+        assert (t.dtype, tuple(t.shape)) == doc[which] and t.is_contiguous() and t.data_ptr() != 0, which
+        r = sim.refresh(which)
+        assert r.data_ptr() == t.data_ptr() and (r.dtype, tuple(r.shape)) == doc[which], which
+    torch.cuda.synchronize()
+    for call in (sim.tensor, sim.refresh):
+        with pytest.raises(BezSimError):
+            call(abi.TENSOR_COUNT)
+    sim.close()
 
 
 # ---------------------------------------------------------------- setters: bit for bit against a numpy model of the contract
@@ -311,7 +354,8 @@ def _default_rows(cfg, n):
 @pytest.mark.parametrize("n", [1, 257])
 def test_env_params_defaults_round_trip_and_unset(n):
     """for every PARAM_*: before any set, get returns the default rows (the config's friction and gravity, unit scales, the URDF's
-    joint limits in fp32 -- the oracle's too); set -> get is bit-exact; set None -> the default rows again"""
+    joint limits in fp32 -- the oracle's too); set -> get is bit-exact; set None -> the default rows again; and the default rows of all
+    seven read back to back on a side stream, with nothing but one device synchronisation at the end"""
     from oracle.bez_oracle import Oracle
     cfg = make_cfg(n, seed=4)
     sim, o = _sim(cfg), Oracle(make_cfg(n, seed=4))
@@ -329,7 +373,60 @@ def test_env_params_defaults_round_trip_and_unset(n):
             np.testing.assert_array_equal(_bits(_host(sim.get_env_params(p))), _bits(v), err_msg="set -> get of param %d" % p)
         sim.set_env_params(p, None)
         np.testing.assert_array_equal(_bits(_host(sim.get_env_params(p))), _bits(dflt[p]), err_msg="set None of param %d" % p)
+    # the default rows only enqueue work: all seven on a side stream with no synchronisation in between, then one for the device
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        got = [sim.get_env_params(p) for p in range(abi.PARAM_COUNT)]
+    torch.cuda.synchronize()
+    for p in range(abi.PARAM_COUNT):
+        np.testing.assert_array_equal(_bits(got[p].cpu().numpy()), _bits(dflt[p]), err_msg="side-stream default rows of param %d" % p)
     sim.close()
+
+
+def test_destroy_returns_every_buffer():
+    """every lazily allocated buffer has the sim as its owner: after one create / destroy per flag combination -- the actuator record,
+    the extra ground points set through set_flags, a randomisation set then unset, the external-wrench buffer -- the free device
+    memory is back at its starting value within the allocator's granularity, which is what a plain create / destroy pair moves it by.
+    (A first, unmeasured pass loads the code objects of the kernel variants these sims launch and fills torch's own pool.)"""
+    from bez_isaacgym_amd.utils.config import load_config
+    n = 65
+    dr = abi.dr_config_from_params(load_config(["task=bez_kick"], resolve=True)["task"]["task"]["randomization_params"])
+    act, forces = torch.zeros(n * 18, device="cuda:0"), torch.ones(n * 22, 3, device="cuda:0")
+
+    def free():
+        torch.cuda.synchronize()
+        return torch.cuda.mem_get_info(0)[0]
+
+    def create_use_destroy(flags, use):
+        cfg = make_cfg(n, seed=1)
+        cfg.flags |= flags
+        sim = _sim(cfg)
+        use(sim)
+        sim.step(act)
+        torch.cuda.synchronize()
+        sim.close()
+
+    def randomise_and_unset(sim):
+        sim.set_randomization(dr)
+        sim.step(act)
+        sim.set_randomization(None)
+        for p in range(abi.PARAM_COUNT):
+            sim.set_env_params(p, None)
+
+    def every_combination():
+        create_use_destroy(abi.FLAG_DOF_FORCE, lambda sim: (sim.step(act), sim.refresh_actuator_tensors()))
+        create_use_destroy(0, lambda sim: sim.set_flags(int(sim.cfg.flags) | abi.FLAG_ALL_GROUND_SHAPES))
+        create_use_destroy(0, randomise_and_unset)
+        create_use_destroy(0, lambda sim: sim.apply_body_forces(forces=forces))
+
+    every_combination()
+    start = free()
+    _sim(make_cfg(n, seed=1)).close()
+    granularity = abs(free() - start)
+    every_combination()
+    end = free()
+    print("free device memory: %d before, %d after, granularity %d" % (start, end, granularity))
+    assert abs(end - start) <= granularity, (start, end, granularity)
 
 
 def _step_outputs(sim, act):
