@@ -322,6 +322,15 @@ def swap_and_flatten01(x):
     return x.transpose(0, 1).reshape(s[0] * s[1], *s[2:])
 
 
+def policy_kernel_gate(obs_dim, widths, act_dim):
+    """Which one-launch MFMA policy kernels take an MLP of hidden `widths` on `obs_dim` observations with `act_dim` actions -- the same
+    conditions as the C entry points (csrc/bez_policy.hip fill_args, bez_ppo_policy_forward_train, policy_backward_impl):
+    forward (rollout), train_forward (keeps the activations: half2 stores, even widths) and backward (16-byte fragment reads: >= 32 columns)."""
+    fwd = all(1 <= w <= 416 for w in widths) and 1 <= obs_dim <= 416 and 1 <= act_dim <= 31 and 1 <= len(widths) <= 6
+    even = obs_dim % 2 == 0 and all(w % 2 == 0 for w in widths)
+    return dict(forward=fwd, train_forward=fwd and even, backward=fwd and all(w >= 32 and w % 2 == 0 for w in widths))
+
+
 class _CpuLr:
     """CPU fallback of the device-resident lr tensor (tests): same interface, writes through to the param groups."""
 
@@ -536,14 +545,15 @@ class A2CAgent:
             if self.half_path and c.get("fused_policy_forward", True) and getattr(net, "_p16", None) is not None:
                 nh = len(net._lin) - 2
                 wb = [(net._p16[2 * i], net._p16[2 * i + 1]) for i in range(nh + 2)]
-                if all(w.shape[0] <= 416 for w, _ in wb[:nh]) and obs_dim <= 416 and act_dim <= 31 and nh <= 6:
+                gate = policy_kernel_gate(obs_dim, [w.shape[0] for w, _ in wb[:nh]], act_dim)
+                if gate["forward"]:
                     # fragment-major copies of the weights (coalesced MFMA operand loads), refreshed by one scatter of the fp16 working copy
                     hflat = getattr(self, "_hflat", None)
                     layout = None if hflat is None else [((w.data_ptr() - hflat.data_ptr()) // 2, w.shape[0], w.shape[1]) for w, _ in wb]
                     self._packed = F.PackedWeights(hflat, layout, act_dim) if (hflat is not None and c.get("packed_weights", True)) else None
                     self._policy_fwd = F.PolicyForward(wb[:nh], wb[nh], wb[nh + 1], self.running_mean_std if self.normalize_input else None, self._packed)
                     # ... and the input-gradient chain of the minibatch backward pass as one kernel on transposed copies
-                    if (hflat is not None and c.get("fused_policy_backward", True) and all(32 <= w.shape[0] <= 416 and w.shape[0] % 2 == 0 for w, _ in wb[:nh])):
+                    if hflat is not None and c.get("fused_policy_backward", True) and gate["backward"]:
                         self._policy_bwd = F.PolicyBackward(hflat, layout, act_dim, self._packed)
         if (self._segmented or world > 1 or _dist_on()) and not self.fused:   # (also with dp_capture_collectives: the plain torch path is never captured across ranks)
             self.use_graphs = False  # the plain torch path has collectives in the middle of autograd-heavy code: eager only
@@ -1121,8 +1131,8 @@ class A2CAgent:
             return False
         k, s = obs.shape[0], net._splits
         lin = net._lin
-        return (obs.dtype == torch.float32 and obs.is_contiguous() and s > 1 and k % s == 0 and k // s >= 64 and obs.shape[1] % 2 == 0
-                and all(m.weight.shape[0] % 2 == 0 for m in lin[:-2])
+        return (obs.dtype == torch.float32 and obs.is_contiguous() and s > 1 and k % s == 0 and k // s >= 64
+                and policy_kernel_gate(obs.shape[1], [m.weight.shape[0] for m in lin[:-2]], lin[-2].weight.shape[0])["train_forward"]
                 and all(m.weight.grad is not None and m.bias.grad is not None and m.weight.grad.is_contiguous() and m.bias.grad.is_contiguous() for m in lin))
 
     def _train_bufs(self, k):
