@@ -36,6 +36,10 @@ ACTUATOR_DOF_FORCE, ACTUATOR_DRIVE_TORQUE, ACTUATOR_STATUS, ACTUATOR_TENSORS = r
 ACTUATOR_SATURATED_POS, ACTUATOR_SATURATED_NEG, ACTUATOR_LOCKED_POS, ACTUATOR_LOCKED_NEG = 1, 2, 4, 8
 ACTUATOR_SATURATED = ACTUATOR_SATURATED_POS | ACTUATOR_SATURATED_NEG
 ACTUATOR_LOCKED = ACTUATOR_LOCKED_POS | ACTUATOR_LOCKED_NEG
+# dynamics tensors (include/bez_sim.h BezDynamicsTensor, BezSim.dynamics_tensor): the robot's Jacobian (N*NB, 6, NUM_GEN) and mass matrix
+# (N, NUM_GEN, NUM_GEN) in the generalised velocity [root_lin 3, root_ang 3, qd 18]; allocated on first acquisition
+DYNAMICS_JACOBIAN, DYNAMICS_MASS_MATRIX, DYNAMICS_COUNT = range(3)
+NUM_GEN = 24
 DOF_FORCE_KEY = "env.enableDofForceSensors"   # this build's task key for FLAG_DOF_FORCE (default False)
 SPACE_ENV = 0                   # bez_sim_apply_body_forces: world axes / world points (gymapi.ENV_SPACE)
 SPACE_LOCAL = 1                 # the body's own frame (gymapi.LOCAL_SPACE)
@@ -280,6 +284,18 @@ def actuator_tensor_id(which):
         return names[which.strip().lower()]
     if isinstance(which, bool) or not isinstance(which, int) or not 0 <= which < ACTUATOR_TENSORS:
         raise ValueError("actuator tensor id must be in [0, %d), got %r" % (ACTUATOR_TENSORS, which))
+    return int(which)
+
+
+def dynamics_tensor_id(which):
+    """DYNAMICS_JACOBIAN / DYNAMICS_MASS_MATRIX from the int or from "jacobian" / "mass_matrix"."""
+    names = {"jacobian": DYNAMICS_JACOBIAN, "mass_matrix": DYNAMICS_MASS_MATRIX}
+    if isinstance(which, str):
+        if which.strip().lower() not in names:
+            raise ValueError("dynamics tensor must be one of %s, got %r" % (sorted(names), which))
+        return names[which.strip().lower()]
+    if isinstance(which, bool) or not isinstance(which, int) or not 0 <= which < DYNAMICS_COUNT:
+        raise ValueError("dynamics tensor id must be in [0, %d), got %r" % (DYNAMICS_COUNT, which))
     return int(which)
 
 

@@ -85,6 +85,9 @@ struct BezSim {
   // [substep][3][dof][env] (bez_kernels.h df_record), then the three Isaac-layout tensors bez_sim_refresh_actuator_tensors fills
   float* df_raw = nullptr;
   float* df_out = nullptr;   // (N*18) net joint force, (N*18) drive torque, (N*18) i32 status
+  // dynamics tensors (bez_sim_get_dynamics_tensor allocates each on its first acquisition; bez_sim_refresh_dynamics_tensors fills them)
+  float* jacobian = nullptr;     // (N*nb, 6, 24)
+  float* mass_matrix = nullptr;  // (N, 24, 24)
 };
 
 namespace {
@@ -391,6 +394,148 @@ __global__ void refresh_rigid_body_kernel(const float* __restrict__ st, float* _
   o[0] = S.ball_pos.x; o[1] = S.ball_pos.y; o[2] = S.ball_pos.z;
   o[3] = S.bq[0]; o[4] = S.bq[1]; o[5] = S.bq[2]; o[6] = S.bq[3];
   o[7] = S.ball_lin.x; o[8] = S.ball_lin.y; o[9] = S.ball_lin.z; o[10] = S.ball_ang.x; o[11] = S.ball_ang.y; o[12] = S.ball_ang.z;
+}
+
+// ---- gym.refresh_jacobian_tensors / gym.refresh_mass_matrix_tensors (definitions: include/bez_sim.h "Dynamics tensors").
+// A workgroup takes DYN_TILE consecutive envs.  Phase 1, one lane per env: forward kinematics, then the world joint axes, the joint
+// origins and the body origins (both relative to the root origin) go to LDS, and -- still in that lane -- the composite-rigid-body
+// recursion in the frame link_inertia already uses (world axes about the root origin: composites add up without transforms) leaves
+// every DISTINCT entry of M in LDS.  Phase 2, all lanes: the tile's output range is contiguous (DYN_TILE x nb x 144 floats of J,
+// DYN_TILE x 576 of M), and each lane forms four consecutive elements from LDS and stores them as one float4, so every store
+// instruction of a wave covers 1 KB of consecutive addresses.  Structural zeros and ones are constants, never computed.
+constexpr int DYN_TILE = 16, DYN_THREADS = 256, DYN_NG = 6 + BEZ_ND;
+constexpr int link_depth(int l) { int d = 0; for (; l > 0; l = BEZ_LINK_PARENT[l]) ++d; return d; }
+constexpr int dyn_pair_base(int l) { int s = 0; for (int k = 1; k < l; ++k) s += link_depth(k); return s; }   // (l, its path to the root) starts here
+constexpr uint32_t link_ancestors(int l) { uint32_t m = 0; for (; l > 0; l = BEZ_LINK_PARENT[l]) m |= 1u << l; return m; }   // bit l' : DOF l' - 1 moves link l
+// LDS words of one env: [axis 18x3][joint origin 18x3][body origin nb x 3][the distinct entries of M]
+constexpr int DYN_AX = 0, DYN_RO = 3 * BEZ_ND, DYN_XB = 6 * BEZ_ND, DYN_MS = DYN_XB + 3 * BEZ_NB_CL;
+// entries of M: 0 the constant zero, total mass, h, -h, Ibar (xx yy zz xy xz yz), F_l = I^c_l S_l as [lin; ang] per joint, S_j . F_l per path pair
+constexpr int MS_ZERO = 0, MS_MASS = 1, MS_H = 2, MS_NH = 5, MS_IBAR = 8, MS_F = 14, MS_PAIR = MS_F + 6 * BEZ_ND, MS_COUNT = MS_PAIR + dyn_pair_base(BEZ_NL);
+constexpr int DYN_STRIDE = (DYN_MS + MS_COUNT) | 1;   // odd: the lanes of phase 1 (one env each) write distinct banks
+struct MassSlots { int16_t s[DYN_NG * DYN_NG]; };
+constexpr MassSlots mass_slots() {
+  MassSlots T = {};
+  for (int i = 0; i < DYN_NG * DYN_NG; ++i) T.s[i] = MS_ZERO;
+  const int ibar[3][3] = {{0, 3, 4}, {3, 1, 5}, {4, 5, 2}};
+  // skew(h) = [[0, -hz, hy], [hz, 0, -hx], [-hy, hx, 0]] as (component, negated)
+  const int sk[3][3] = {{-1, MS_NH + 2, MS_H + 1}, {MS_H + 2, -1, MS_NH + 0}, {MS_NH + 1, MS_H + 0, -1}};
+  for (int r = 0; r < 3; ++r) {
+    T.s[r * DYN_NG + r] = MS_MASS;
+    for (int c = 0; c < 3; ++c) {
+      T.s[(3 + r) * DYN_NG + 3 + c] = (int16_t)(MS_IBAR + ibar[r][c]);
+      if (sk[r][c] >= 0) T.s[(3 + r) * DYN_NG + c] = T.s[c * DYN_NG + 3 + r] = (int16_t)sk[r][c];   // ang row, lin column = skew(h); its transpose
+    }
+  }
+  for (int l = 1; l < BEZ_NL; ++l) {
+    for (int k = 0; k < 6; ++k) T.s[(5 + l) * DYN_NG + k] = T.s[k * DYN_NG + 5 + l] = (int16_t)(MS_F + 6 * (l - 1) + k);
+    int p = MS_PAIR + dyn_pair_base(l);
+    for (int j = l; j > 0; j = BEZ_LINK_PARENT[j], ++p) T.s[(5 + l) * DYN_NG + 5 + j] = T.s[(5 + j) * DYN_NG + 5 + l] = (int16_t)p;
+  }
+  return T;
+}
+__device__ const MassSlots MASS_SLOTS = mass_slots();
+struct BodyAncestors { uint32_t m[BEZ_NB_CL]; };
+template <bool CL> constexpr BodyAncestors body_ancestors() {
+  BodyAncestors T = {};
+  for (int b = 0; b < (CL ? BEZ_NB_CL : BEZ_NB); ++b) T.m[b] = link_ancestors(CL ? BEZ_BODY_LINK_CL[b] : BEZ_BODY_LINK[b]);
+  return T;
+}
+template <bool CL> __device__ const BodyAncestors BODY_ANCESTORS = body_ancestors<CL>();
+
+BEZ_DEV float pick(V3 v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
+BEZ_DEV V3 lds3(const float* p) { return mk(p[0], p[1], p[2]); }
+// J[row][col] of a body with origin x (relative to the root origin) whose link has the ancestor set `mask`; L: the env's LDS words
+BEZ_DEV float jacobian_entry(const float* L, uint32_t mask, V3 x, int row, int col) {
+  if (col < 3) return row == col ? 1.f : 0.f;
+  if (col < 6) {
+    if (row >= 3) return row == col ? 1.f : 0.f;
+    const int c = col - 3;                      // -skew(x) = [[0, z, -y], [-z, 0, x], [y, -x, 0]]
+    if (c == row) return 0.f;
+    const float v = pick(x, 3 - row - c);
+    return ((c - row + 3) % 3 == 1) ? v : -v;
+  }
+  const int d = col - 6;
+  if (!((mask >> (d + 1)) & 1u)) return 0.f;
+  const V3 a = lds3(L + DYN_AX + 3 * d);
+  if (row >= 3) return pick(a, row - 3);
+  return pick(cross(a, x - lds3(L + DYN_RO + 3 * d)), row);
+}
+
+template <bool CL>
+__global__ void __launch_bounds__(DYN_THREADS) refresh_dynamics_kernel(const float* __restrict__ st, const float* __restrict__ mass_scale, float* __restrict__ J,
+                                                                       float* __restrict__ M, int n, uint32_t flags, float armature) {
+  __shared__ float lds[DYN_TILE * DYN_STRIDE];
+  constexpr int NB = nb_of<CL>();
+  const int e0 = blockIdx.x * DYN_TILE, ne = min(DYN_TILE, n - e0);
+  if ((int)threadIdx.x < ne) {
+    const int e = e0 + threadIdx.x;
+    float* L = lds + threadIdx.x * DYN_STRIDE;
+    EnvState S;
+    load_state(st, n, e, S);
+    M3 E[BEZ_NL]; V3 r[BEZ_NL]; SV V[BEZ_NL];
+    link_frames<CL, false>(S, flags, E, r, V);
+    auto put3 = [&](int at, V3 v) { L[at] = v.x; L[at + 1] = v.y; L[at + 2] = v.z; };
+    static_for<BEZ_ND>([&](auto I) {   // the joint's axis is the column of its link's frame that the joint rotation leaves alone
+      constexpr int l = 1 + decltype(I)::value;
+      put3(DYN_AX + 3 * (l - 1), col(E[l], axis_index(l)) * axis_sign(l));
+      put3(DYN_RO + 3 * (l - 1), r[l]);
+    });
+    static_for<NB>([&](auto I) {
+      const BodyFrame f = body_frame<CL>(decltype(I)::value);
+      put3(DYN_XB + 3 * decltype(I)::value, r[f.link] + mul(E[f.link], f.off));
+    });
+    if (M) {
+      LinkInertia Ic[BEZ_NL];
+      static_for<BEZ_NL>([&](auto I) {
+        constexpr int l = decltype(I)::value;
+        SV pA;
+        link_inertia<l, CL>(mass_scale ? mass_scale[(size_t)e * BEZ_NL + l] : 1.f, mk(0, 0, 0), E[l], r[l], svzero(), Ic[l], pA);
+      });
+      float* Ms = L + DYN_MS;
+      static_for<BEZ_NL - 1>([&](auto I) {   // leaves first: link l is complete when its turn comes, then joins its parent
+        constexpr int l = BEZ_NL - 1 - decltype(I)::value, p = BEZ_LINK_PARENT[l];
+        const LinkInertia& C = Ic[l];
+        const V3 a = lds3(L + DYN_AX + 3 * (l - 1)), sl = cross(r[l], a);           // S_l = [a; r x a]
+        const V3 Fa = mul(C.Ibar, a) + cross(C.h, sl), Fl = sl * C.m - cross(C.h, a);  // F_l = I^c_l S_l
+        put3(DYN_MS + MS_F + 6 * (l - 1), Fl);
+        put3(DYN_MS + MS_F + 6 * (l - 1) + 3, Fa);
+        int at = MS_PAIR + dyn_pair_base(l);
+        for (int j = l; j > 0; j = BEZ_LINK_PARENT[j], ++at) {
+          const V3 aj = lds3(L + DYN_AX + 3 * (j - 1)), sj = cross(lds3(L + DYN_RO + 3 * (j - 1)), aj);
+          const float v = dot(aj, Fa) + dot(sj, Fl);
+          Ms[at] = j == l ? v + armature : v;
+        }
+        Ic[p].m += C.m; Ic[p].h = Ic[p].h + C.h; add_to(Ic[p].Ibar, C.Ibar);
+      });
+      const LinkInertia& C = Ic[0];
+      Ms[MS_ZERO] = 0.f; Ms[MS_MASS] = C.m;
+      put3(DYN_MS + MS_H, C.h); put3(DYN_MS + MS_NH, -C.h);
+      Ms[MS_IBAR] = C.Ibar.xx; Ms[MS_IBAR + 1] = C.Ibar.yy; Ms[MS_IBAR + 2] = C.Ibar.zz;
+      Ms[MS_IBAR + 3] = C.Ibar.xy; Ms[MS_IBAR + 4] = C.Ibar.xz; Ms[MS_IBAR + 5] = C.Ibar.yz;
+    }
+  }
+  __syncthreads();
+  if (J) {
+    float4* out = reinterpret_cast<float4*>(J + (size_t)e0 * NB * 6 * DYN_NG);
+    const int total = ne * NB * 6 * (DYN_NG / 4);
+    for (int i = threadIdx.x; i < total; i += DYN_THREADS) {
+      const int c4 = i % (DYN_NG / 4), t = i / (DYN_NG / 4), row = t % 6, b = (t / 6) % NB, el = t / (6 * NB);
+      const float* L = lds + el * DYN_STRIDE;
+      const uint32_t mask = BODY_ANCESTORS<CL>.m[b];
+      const V3 x = lds3(L + DYN_XB + 3 * b);
+      out[i] = make_float4(jacobian_entry(L, mask, x, row, 4 * c4), jacobian_entry(L, mask, x, row, 4 * c4 + 1),
+                           jacobian_entry(L, mask, x, row, 4 * c4 + 2), jacobian_entry(L, mask, x, row, 4 * c4 + 3));
+    }
+  }
+  if (M) {
+    float4* out = reinterpret_cast<float4*>(M + (size_t)e0 * DYN_NG * DYN_NG);
+    constexpr int PER_ENV = DYN_NG * DYN_NG / 4;
+    for (int i = threadIdx.x; i < ne * PER_ENV; i += DYN_THREADS) {
+      const float* Ms = lds + (i / PER_ENV) * DYN_STRIDE + DYN_MS;
+      const int16_t* sl = MASS_SLOTS.s + 4 * (i % PER_ENV);
+      out[i] = make_float4(Ms[sl[0]], Ms[sl[1]], Ms[sl[2]], Ms[sl[3]]);
+    }
+  }
 }
 
 // gym.set_actor_root_state_tensor_indexed
@@ -844,6 +989,39 @@ int bez_sim_refresh_actuator_tensors(BezSim* s, void* stream) {
   if (!s) return -1;
   if (!(s->cfg.flags & BEZ_FLAG_DOF_FORCE) || !s->df_raw) return fail(s, -1, "bez_sim_refresh_actuator_tensors: BEZ_FLAG_DOF_FORCE is not set (the step kernels record no joint forces without it)");
   return LAUNCH(s, refresh_actuator_kernel, (size_t)s->n * BEZ_ND, (hipStream_t)stream, s->df_raw, s->df_out, s->n, s->cfg.substeps);
+}
+// ---- dynamics tensors: a table in the manner of TENSORS, with a third dimension and an allocation on first acquisition
+struct DynamicsRow { int id; float** (*slot)(BezSim*); int per_env_bodies; int64_t d1, d2; };   // rows: N x robot bodies, or N
+constexpr DynamicsRow DYNAMICS[] = {
+    {BEZ_DYNAMICS_JACOBIAN, [](BezSim* s) -> float** { return &s->jacobian; }, 1, 6, 6 + BEZ_ND},
+    {BEZ_DYNAMICS_MASS_MATRIX, [](BezSim* s) -> float** { return &s->mass_matrix; }, 0, 6 + BEZ_ND, 6 + BEZ_ND},
+};
+static_assert(sizeof(DYNAMICS) / sizeof(DYNAMICS[0]) == BEZ_DYNAMICS_COUNT && DYNAMICS[1].id == 1, "one DYNAMICS row per BezDynamicsTensor, in enum order");
+
+int bez_sim_get_dynamics_tensor(BezSim* s, int which, void** dev_ptr, int64_t shape[3], int* ndim, int* dtype) {
+  if (!s || !dev_ptr || !shape || !ndim || !dtype) return fail(s, -1, "bez_sim_get_dynamics_tensor: null argument");
+  if (which < 0 || which >= BEZ_DYNAMICS_COUNT) return fail(s, -1, "bez_sim_get_dynamics_tensor: unknown tensor id");
+  const DynamicsRow& t = DYNAMICS[which];
+  shape[0] = (int64_t)s->n * (t.per_env_bodies ? s->nb : 1); shape[1] = t.d1; shape[2] = t.d2;
+  float** slot = t.slot(s);
+  if (!*slot) {   // the acquisition: the one place that allocates (and, through hipMemset, waits)
+    (void)hipSetDevice(s->device);
+    RC_TRY(dev_alloc_zeroed(s, slot, (size_t)(shape[0] * shape[1] * shape[2]) * sizeof(float)));
+  }
+  *dev_ptr = *slot; *ndim = 3; *dtype = BEZ_DTYPE_F32;
+  return 0;
+}
+int bez_sim_refresh_dynamics_tensors(BezSim* s, uint32_t which_mask, void* stream) {
+  if (!s) return -1;
+  if (which_mask == 0u || (which_mask >> BEZ_DYNAMICS_COUNT)) return fail(s, -1, "bez_sim_refresh_dynamics_tensors: which_mask must be a non-empty set of (1u << BezDynamicsTensor) bits");
+  float* J = (which_mask & (1u << BEZ_DYNAMICS_JACOBIAN)) ? s->jacobian : nullptr;
+  float* M = (which_mask & (1u << BEZ_DYNAMICS_MASS_MATRIX)) ? s->mass_matrix : nullptr;
+  if (((which_mask & (1u << BEZ_DYNAMICS_JACOBIAN)) && !J) || ((which_mask & (1u << BEZ_DYNAMICS_MASS_MATRIX)) && !M))
+    return fail(s, -1, "bez_sim_refresh_dynamics_tensors: a requested tensor was never acquired (bez_sim_get_dynamics_tensor allocates it)");
+  const size_t threads = (size_t)((s->n + DYN_TILE - 1) / DYN_TILE) * DYN_THREADS;
+  const float* ms = s->dr[BEZ_PARAM_MASS_SCALE];
+  return s->cleats ? launch_checked<DYN_THREADS>(s, "refresh_dynamics_kernel launch", refresh_dynamics_kernel<true>, threads, (hipStream_t)stream, s->state, ms, J, M, s->n, s->cfg.flags, s->cfg.armature)
+                   : launch_checked<DYN_THREADS>(s, "refresh_dynamics_kernel launch", refresh_dynamics_kernel<false>, threads, (hipStream_t)stream, s->state, ms, J, M, s->n, s->cfg.flags, s->cfg.armature);
 }
 int bez_sim_set_obs_calls(BezSim* s, int64_t calls) { if (!s) return -1; s->obs_calls = calls; return 0; }
 

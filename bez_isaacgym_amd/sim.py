@@ -57,6 +57,8 @@ SIGS = {
     "bez_sim_apply_body_forces": (C.c_int, [vp, fp, fp, fp, i32, vp]),
     "bez_sim_get_actuator_tensor": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bez_sim_refresh_actuator_tensors": (C.c_int, [vp, vp]),
+    "bez_sim_get_dynamics_tensor": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bez_sim_refresh_dynamics_tensors": (C.c_int, [vp, u32, vp]),
 }
 EXPORTS = list(SIGS)
 
@@ -186,6 +188,28 @@ class BezSim:
         """gym.refresh_dof_force_tensor: materialises the three actuator tensors from what the last physics launch recorded."""
         self._need_dof_force("refresh_actuator_tensors()")
         self._check(self.lib.bez_sim_refresh_actuator_tensors(self.h, self._stream()))
+
+    # ---- gym.acquire_jacobian_tensor / acquire_mass_matrix_tensor and their refreshes
+    def dynamics_tensor(self, which):
+        """Zero-copy torch view of a dynamics tensor (abi.DYNAMICS_* or "jacobian" / "mass_matrix"): the Jacobian (N*NB, 6, 24) of the
+        robot's NB bodies, the mass matrix (N, 24, 24), both float32 (definitions: include/bez_sim.h).  The first call for a tensor
+        allocates it; refresh_dynamics_tensors() fills it."""
+        which = abi.dynamics_tensor_id(which)
+        return self._wrap(("dynamics", which), self.lib.bez_sim_get_dynamics_tensor, which)
+
+    def refresh_dynamics_tensors(self, which=None):
+        """gym.refresh_jacobian_tensors / refresh_mass_matrix_tensors in one launch on the current stream.  `which`: one tensor or a
+        sequence of them (ids or names); None: every tensor acquired so far.  A tensor that was never acquired is an error."""
+        if which is None:
+            ids = [k[1] for k in self._views if isinstance(k, tuple) and k[0] == "dynamics"]
+        elif isinstance(which, (str, int)):
+            ids = [abi.dynamics_tensor_id(which)]
+        else:
+            ids = [abi.dynamics_tensor_id(w) for w in which]
+        mask = 0
+        for k in ids:
+            mask |= 1 << k
+        self._check(self.lib.bez_sim_refresh_dynamics_tensors(self.h, mask, self._stream()))
 
     def refresh(self, which):
         self._check(self.lib.bez_sim_refresh_tensor(self.h, which, self._stream()))

@@ -167,6 +167,38 @@ class VecTask(Env):
         self.sim.refresh_actuator_tensors()
         return True
 
+    # ---- gym.acquire_jacobian_tensor / acquire_mass_matrix_tensor (include/bez_sim.h "Dynamics tensors"): allocated by the acquisition
+    def _dynamics_view(self, name):
+        view = self.__dict__.get("_" + name + "_view")
+        if view is None:
+            raise AttributeError("%s exists only after acquire_%s_tensor(): the sim allocates the tensor on its first acquisition" % (name, name))
+        return view
+
+    jacobian = property(lambda self: self._dynamics_view("jacobian"), doc="(N, NB, 6, 24) f32 Jacobian of the robot's bodies")
+    mass_matrix = property(lambda self: self._dynamics_view("mass_matrix"), doc="(N, 24, 24) f32 mass matrix")
+
+    def acquire_jacobian_tensor(self):
+        """gym.acquire_jacobian_tensor (wrapped): the (N, NB, 6, 24) view of the sim's Jacobian, NB = the robot's rigid bodies."""
+        from ... import abi
+        self._jacobian_view = self.sim.dynamics_tensor(abi.DYNAMICS_JACOBIAN).view(self.num_envs, -1, 6, abi.NUM_GEN)
+        return self._jacobian_view
+
+    def acquire_mass_matrix_tensor(self):
+        """gym.acquire_mass_matrix_tensor (wrapped): the (N, 24, 24) view of the sim's mass matrix."""
+        from ... import abi
+        self._mass_matrix_view = self.sim.dynamics_tensor(abi.DYNAMICS_MASS_MATRIX)
+        return self._mass_matrix_view
+
+    def refresh_jacobian_tensors(self):
+        self._dynamics_view("jacobian")
+        self.sim.refresh_dynamics_tensors("jacobian")
+        return True
+
+    def refresh_mass_matrix_tensors(self):
+        self._dynamics_view("mass_matrix")
+        self.sim.refresh_dynamics_tensors("mass_matrix")
+        return True
+
     def actuator_snapshot(self):
         """(drive torque, status, joint velocity), each (N, 18), of the last physics launch: one refresh of the actuator tensors and one of
         DOF_STATE (the PPO loop's per-epoch actuator statistics)."""

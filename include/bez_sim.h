@@ -308,6 +308,35 @@ int bez_sim_get_actuator_tensor(BezSim* sim, int which, void** dev_ptr, int64_t 
  * on `stream`; captures into a HIP graph).  Without BEZ_FLAG_DOF_FORCE: rc -1 with a message. */
 int bez_sim_refresh_actuator_tensors(BezSim* sim, void* stream);
 
+/* Dynamics tensors: gym.acquire_jacobian_tensor / gym.refresh_jacobian_tensors and gym.acquire_mass_matrix_tensor /
+ * gym.refresh_mass_matrix_tensors for the robot actor -- what operational-space and whole-body controllers read.
+ *   Generalised velocity  u = [root_lin(3), root_ang(3), qd(18)]: columns 7:13 of the robot's ROOT_STATE row, then the DOF velocities in
+ *     DOF_STATE order; world (env) axes.  24 = 6 + BEZ_NUM_DOFS entries.
+ *   BEZ_DYNAMICS_JACOBIAN  f32 (N*NB, 6, 24), env-major; NB = 21 robot bodies (29 with cleats) in RIGID_BODY_STATE order.  There is no
+ *     ball row: Isaac's Jacobian is per actor.  Rows 0:3 are the linear velocity of the body's ORIGIN, rows 3:6 its angular velocity,
+ *     world axes, so that J[e,b] @ u[e] == RIGID_BODY_STATE[e,b,7:13].  Column 6+d is non-zero only where link d+1 is the body's link or
+ *     an ancestor of it; there it is [a x (x_b - r_l); a] with a the joint axis in world axes, r_l the joint origin and x_b the body
+ *     origin.  Base block: J[0:3,0:3] = I, J[3:6,3:6] = I, J[3:6,0:3] = 0, J[0:3,3:6] = -skew(x_b - root_pos).  Fixed bodies (imu_link,
+ *     camera, the cleats) use their link's columns with their own origin; the joint origin that soccerbot_box_sensor.urdf moves
+ *     (BEZ_FLAG_BOX_ASSET with BEZ_FLAG_CLEATS) is where the step kernels have it.  The ones and the structural zeros are exact.
+ *   BEZ_DYNAMICS_MASS_MATRIX  f32 (N, 24, 24): the matrix of the kinetic energy in u,
+ *       M = sum over links of J_com^T diag(m I3, I_c in world axes) J_com + armature * diag(0 x 6, 1 x 18),
+ *     so that 1/2 u^T M u = KE + 1/2 armature |qd|^2 (the armature is included because the step's joint-space inertia includes it).
+ *     Link masses and inertias carry the env's BEZ_PARAM_MASS_SCALE row (m and I_c alike, as in the step).  Both triangles are written
+ *     from one computed value: M is bitwise symmetric; M[0:3,0:3] is the total mass times I with exact zeros off the diagonal.
+ *   BEZ_FLAG_FIX_BASE changes no shape (bez_sim_set_flags may flip it while views exist): the fixed-base quantities are the sub-blocks
+ *     J[..., 6:] and M[6:, 6:].  This is the one deliberate deviation from Isaac Gym, whose fixed-base tensors drop the six base columns.
+ *   A non-finite state is written through as it is (the structural zeros and ones stay). */
+enum BezDynamicsTensor { BEZ_DYNAMICS_JACOBIAN = 0, BEZ_DYNAMICS_MASS_MATRIX = 1, BEZ_DYNAMICS_COUNT = 2 };
+/* gym.acquire_jacobian_tensor / gym.acquire_mass_matrix_tensor: `which` is a BezDynamicsTensor; *ndim is 3.  The FIRST call for a tensor
+ * allocates it (12 KB per env for the Jacobian, 2.3 KB for the mass matrix: a sim that never asks allocates nothing), zero-filled;
+ * bez_sim_destroy frees it.  Later calls return the same memory. */
+int bez_sim_get_dynamics_tensor(BezSim* sim, int which, void** dev_ptr, int64_t shape[3], int* ndim, int* dtype);
+/* gym.refresh_jacobian_tensors / gym.refresh_mass_matrix_tensors: ONE kernel launch on `stream` fills the tensors named in which_mask
+ * (bit (1u << which)) from the state as it stands on the stream.  A tensor that was never acquired, a zero mask or an unknown bit:
+ * rc -1 with a message.  The call allocates nothing, never synchronises, reads nothing on the host: it captures into a HIP graph. */
+int bez_sim_refresh_dynamics_tensors(BezSim* sim, uint32_t which_mask, void* stream);
+
 /* gym.refresh_{actor_root_state,dof_state,rigid_body_state,net_contact_force}_tensor
  * (kick_env.py:750-753): materialise the Isaac-layout tensor from the SoA state.  ROOT_STATE, DOF_STATE, RIGID_BODY_STATE,
  * NET_CONTACT_FORCE, DOF_TARGET, PREV_LIN_VEL, FEET and GOAL need it; every other BezTensor is always live (the kernels
