@@ -40,6 +40,9 @@ ACTUATOR_LOCKED = ACTUATOR_LOCKED_POS | ACTUATOR_LOCKED_NEG
 # (N, NUM_GEN, NUM_GEN) in the generalised velocity [root_lin 3, root_ang 3, qd 18]; allocated on first acquisition
 DYNAMICS_JACOBIAN, DYNAMICS_MASS_MATRIX, DYNAMICS_COUNT = range(3)
 NUM_GEN = 24
+# bez_sim_inverse_dynamics (include/bez_sim.h "Inverse dynamics", BezSim.inverse_dynamics): the terms of M(q) udot + h(q, u) to add up
+ID_INERTIA, ID_VELOCITY, ID_GRAVITY = 1, 2, 4
+ID_ALL = 7
 DOF_FORCE_KEY = "env.enableDofForceSensors"   # this build's task key for FLAG_DOF_FORCE (default False)
 SPACE_ENV = 0                   # bez_sim_apply_body_forces: world axes / world points (gymapi.ENV_SPACE)
 SPACE_LOCAL = 1                 # the body's own frame (gymapi.LOCAL_SPACE)

@@ -538,6 +538,115 @@ __global__ void __launch_bounds__(DYN_THREADS) refresh_dynamics_kernel(const flo
   }
 }
 
+// ---- bez_sim_inverse_dynamics (definition: include/bez_sim.h "Inverse dynamics"): recursive Newton-Euler in the frame every bias force
+// here uses (world axes about the root origin), where a subtree's wrench is the plain sum of its links' wrenches.
+// A workgroup is ONE wave and takes ID_TILE consecutive envs.  All lanes bring the tile's udot rows -- one contiguous range -- into LDS
+// with float4 loads; then one lane per env walks the tree CHAIN BY CHAIN: out along a chain (two legs of 6 joints, two arms and the head
+// of 2) keeping per joint only S = [a; r x a] and handing the link's acceleration down, back along it adding up the wrenches and emitting
+// tau = S . F into the udot slot it has just consumed, and the chain's total joins the torso's wrench.  At most six links are live,
+// never the 19 frames of link_frames.  Last, all lanes write the tile's rows as one contiguous range of float4 stores.
+// A term is dropped by zeroing its input (udot, the velocities, g): one code path, and the dropped term's products are exact zeros.
+// The chains are taken last to first and each is summed from its leaf, the order in which refresh_dynamics_kernel adds up the masses.
+constexpr int ID_TILE = 16, ID_THREADS = 64, ID_STRIDE = DYN_NG + 1;   // odd row stride: the lanes' own rows start in distinct LDS banks
+BEZ_DEV SV inertia_times(const LinkInertia& I, SV a) {   // I a = [Ibar a.a + h x a.l ; m a.l - h x a.a]
+  return mksv(mul(I.Ibar, a.a) + cross(I.h, a.l), a.l * I.m - cross(I.h, a.a));
+}
+template <int FIRST, int LEN> constexpr bool is_chain() {
+  if (BEZ_LINK_PARENT[FIRST] != 0) return false;
+  for (int i = 1; i < LEN; ++i) if (BEZ_LINK_PARENT[FIRST + i] != FIRST + i - 1) return false;
+  return FIRST + LEN == BEZ_NL || BEZ_LINK_PARENT[FIRST + LEN] == 0;
+}
+// One link of a chain and, by recursion, the links below it: on the way out the link's frame, velocity and accelerations from its
+// parent's (by value: each level keeps its own) and its own wrenches; on the way back tau = S . F goes to U[5 + L], the slot whose udot
+// the way out consumed, and the subtree's wrenches are returned.  (Plain locals per level, no arrays over the links: the compiler keeps
+// arrays of spatial vectors live as whole register blocks for all five chains at once.)
+// The three terms are carried APART -- the acceleration as aI (from udot) and aV (velocity products), the wrench as i = I aI,
+// v = I aV + v x* I v and g = -I [0; g] -- and meet only in the last two additions of every output element: the wrenches that cancel
+// along a chain to a small joint torque are then rounded within their own term, a term's value does not depend on which other terms
+// were asked for, and all terms together are the fp32 sum (inertia + velocity) + gravity of the three single-term results.
+struct IdCtx { const float* st; const float* mass_scale; int n, e; bool vel; float quirk_z, armature; V3 g; };
+struct IdWrench { SV i, v, g; };
+BEZ_DEV IdWrench operator+(const IdWrench& a, const IdWrench& b) { return {a.i + b.i, a.v + b.v, a.g + b.g}; }
+BEZ_DEV IdWrench id_wrench(const LinkInertia& I, SV aI, SV aV, SV pV, V3 g) {
+  return {inertia_times(I, aI), inertia_times(I, aV) + pV, mksv(-cross(I.h, g), -(g * I.m))};
+}
+BEZ_DEV float id_sum(float i, float v, float g) { return (i + v) + g; }
+template <int L, int END, bool CL>
+BEZ_DEV IdWrench id_links(const IdCtx& C, M3 E, V3 r, SV V, SV aI, SV aV, float* U) {
+  const float q = C.st[(size_t)(F_Q + L - 1) * C.n + C.e], qd = C.vel ? C.st[(size_t)(F_QD + L - 1) * C.n + C.e] : 0.f, qdd = U[5 + L];
+  SV S, cb;
+  link_kinematics<L>(q, qd, E, r, V, S, cb, C.quirk_z);
+  aI = aI + S * qdd; aV = aV + cb;
+  LinkInertia LI; SV pV;
+  link_inertia<L, CL>(C.mass_scale ? C.mass_scale[(size_t)C.e * BEZ_NL + L] : 1.f, mk(0, 0, 0), E, r, V, LI, pV);
+  IdWrench F = id_wrench(LI, aI, aV, pV, C.g);
+  if constexpr (L + 1 < END) F = F + id_links<L + 1, END, CL>(C, E, r, V, aI, aV, U);
+  U[5 + L] = id_sum(fmaf(C.armature, qdd, dot(S, F.i)), dot(S, F.v), dot(S, F.g));
+  return F;
+}
+template <bool CL>
+__global__ void __launch_bounds__(ID_THREADS) inverse_dynamics_kernel(const float* __restrict__ st, const float* __restrict__ mass_scale,
+                                                                      const float* __restrict__ gravity_rows, const float* __restrict__ udot,
+                                                                      float* __restrict__ out, int n, uint32_t flags, uint32_t terms, float armature,
+                                                                      float gx, float gy, float gz) {
+  __shared__ float rows[ID_TILE * ID_STRIDE];
+  const int e0 = blockIdx.x * ID_TILE, ne = min(ID_TILE, n - e0), total = ne * DYN_NG;
+  const bool acc = udot && (terms & BEZ_ID_INERTIA);
+  const bool quads = ((reinterpret_cast<uintptr_t>(udot) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0;   // 96 B rows: the tile's range is as aligned as the base
+  auto slot = [&](int i) -> float& { return rows[(i / DYN_NG) * ID_STRIDE + i % DYN_NG]; };
+  if (!acc) {
+    for (int i = threadIdx.x; i < total; i += ID_THREADS) slot(i) = 0.f;
+  } else if (quads) {
+    const float4* in = reinterpret_cast<const float4*>(udot + (size_t)e0 * DYN_NG);
+    for (int i = threadIdx.x; i < total / 4; i += ID_THREADS) {
+      const float4 v = in[i];
+      slot(4 * i) = v.x; slot(4 * i + 1) = v.y; slot(4 * i + 2) = v.z; slot(4 * i + 3) = v.w;
+    }
+  } else {
+    for (int i = threadIdx.x; i < total; i += ID_THREADS) slot(i) = udot[(size_t)e0 * DYN_NG + i];
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < ne) {
+    const int e = e0 + threadIdx.x;
+    float* U = rows + threadIdx.x * ID_STRIDE;
+    auto ld = [&](int f) { return st[(size_t)f * n + e]; };
+    const bool vel = (terms & BEZ_ID_VELOCITY) != 0;
+    const M3 E0 = quat_to_mat(ld(F_ROOT_QUAT), ld(F_ROOT_QUAT + 1), ld(F_ROOT_QUAT + 2), ld(F_ROOT_QUAT + 3));
+    const SV V0 = vel ? mksv(mk(ld(F_ROOT_ANG), ld(F_ROOT_ANG + 1), ld(F_ROOT_ANG + 2)), mk(ld(F_ROOT_LIN), ld(F_ROOT_LIN + 1), ld(F_ROOT_LIN + 2))) : svzero();
+    V3 g = mk(0, 0, 0);
+    if (terms & BEZ_ID_GRAVITY) g = gravity_rows ? mk(gravity_rows[(size_t)e * 3], gravity_rows[(size_t)e * 3 + 1], gravity_rows[(size_t)e * 3 + 2]) : mk(gx, gy, gz);
+    // spatial acceleration of the torso about the (momentarily fixed) point its origin passes through: [wdot; vdot - w x v]
+    const SV aI0 = mksv(mk(U[3], U[4], U[5]), mk(U[0], U[1], U[2])), aV0 = mksv(mk(0, 0, 0), -cross(V0.a, V0.l));
+    LinkInertia I0; SV pV0;
+    link_inertia<0, CL>(mass_scale ? mass_scale[(size_t)e * BEZ_NL] : 1.f, mk(0, 0, 0), E0, mk(0, 0, 0), V0, I0, pV0);
+    IdWrench F0 = id_wrench(I0, aI0, aV0, pV0, g);
+    // (the env index is made opaque per chain, together with the wrench so far: otherwise every chain's loads are issued up front and
+    // the five chains are interleaved, at the price of their registers)
+    IdCtx C = {st, mass_scale, n, e, vel, quirk_rz<CL>(flags), armature, g};
+    auto chain = [&](auto first, auto len) {
+      constexpr int FIRST = decltype(first)::value, LEN = decltype(len)::value;
+      static_assert(is_chain<FIRST, LEN>(), "not a chain off the torso");
+      asm volatile("" : "+v"(C.e), "+v"(F0.i.l.x));
+      F0 = F0 + id_links<FIRST, FIRST + LEN, CL>(C, E0, mk(0, 0, 0), V0, aI0, aV0, U);
+    };
+    using std::integral_constant;
+    chain(integral_constant<int, 13>{}, integral_constant<int, 6>{});
+    chain(integral_constant<int, 11>{}, integral_constant<int, 2>{});
+    chain(integral_constant<int, 5>{}, integral_constant<int, 6>{});
+    chain(integral_constant<int, 3>{}, integral_constant<int, 2>{});
+    chain(integral_constant<int, 1>{}, integral_constant<int, 2>{});
+    U[0] = id_sum(F0.i.l.x, F0.v.l.x, F0.g.l.x); U[1] = id_sum(F0.i.l.y, F0.v.l.y, F0.g.l.y); U[2] = id_sum(F0.i.l.z, F0.v.l.z, F0.g.l.z);
+    U[3] = id_sum(F0.i.a.x, F0.v.a.x, F0.g.a.x); U[4] = id_sum(F0.i.a.y, F0.v.a.y, F0.g.a.y); U[5] = id_sum(F0.i.a.z, F0.v.a.z, F0.g.a.z);
+  }
+  __syncthreads();
+  if (quads) {
+    float4* o = reinterpret_cast<float4*>(out + (size_t)e0 * DYN_NG);
+    for (int i = threadIdx.x; i < total / 4; i += ID_THREADS) o[i] = make_float4(slot(4 * i), slot(4 * i + 1), slot(4 * i + 2), slot(4 * i + 3));
+  } else {
+    for (int i = threadIdx.x; i < total; i += ID_THREADS) out[(size_t)e0 * DYN_NG + i] = slot(i);
+  }
+}
+
 // gym.set_actor_root_state_tensor_indexed
 __global__ void set_root_indexed_kernel(float* __restrict__ st, const float* __restrict__ src, const int32_t* __restrict__ ids, int count, int n, int nact) {
   int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1022,6 +1131,18 @@ int bez_sim_refresh_dynamics_tensors(BezSim* s, uint32_t which_mask, void* strea
   const float* ms = s->dr[BEZ_PARAM_MASS_SCALE];
   return s->cleats ? launch_checked<DYN_THREADS>(s, "refresh_dynamics_kernel launch", refresh_dynamics_kernel<true>, threads, (hipStream_t)stream, s->state, ms, J, M, s->n, s->cfg.flags, s->cfg.armature)
                    : launch_checked<DYN_THREADS>(s, "refresh_dynamics_kernel launch", refresh_dynamics_kernel<false>, threads, (hipStream_t)stream, s->state, ms, J, M, s->n, s->cfg.flags, s->cfg.armature);
+}
+int bez_sim_inverse_dynamics(BezSim* s, const float* udot_dev, uint32_t terms, float* out_dev, void* stream) {
+  if (!s) return -1;
+  if (terms == 0u || (terms & ~(uint32_t)BEZ_ID_ALL)) return fail(s, -1, "bez_sim_inverse_dynamics: terms must be a non-empty set of BEZ_ID_INERTIA | BEZ_ID_VELOCITY | BEZ_ID_GRAVITY");
+  if (!out_dev) return fail(s, -1, "bez_sim_inverse_dynamics: out_dev is null");
+  const size_t threads = (size_t)((s->n + ID_TILE - 1) / ID_TILE) * ID_THREADS;
+  const float* g = s->cfg.gravity;
+  auto launch = [&](auto kernel) {
+    return launch_checked<ID_THREADS>(s, "inverse_dynamics_kernel launch", kernel, threads, (hipStream_t)stream, s->state, s->dr[BEZ_PARAM_MASS_SCALE],
+                                      s->dr[BEZ_PARAM_GRAVITY], udot_dev, out_dev, s->n, s->cfg.flags, terms, s->cfg.armature, g[0], g[1], g[2]);
+  };
+  return s->cleats ? launch(inverse_dynamics_kernel<true>) : launch(inverse_dynamics_kernel<false>);
 }
 int bez_sim_set_obs_calls(BezSim* s, int64_t calls) { if (!s) return -1; s->obs_calls = calls; return 0; }
 

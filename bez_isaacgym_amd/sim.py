@@ -59,6 +59,7 @@ SIGS = {
     "bez_sim_refresh_actuator_tensors": (C.c_int, [vp, vp]),
     "bez_sim_get_dynamics_tensor": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bez_sim_refresh_dynamics_tensors": (C.c_int, [vp, u32, vp]),
+    "bez_sim_inverse_dynamics": (C.c_int, [vp, fp, u32, fp, vp]),
 }
 EXPORTS = list(SIGS)
 
@@ -210,6 +211,30 @@ class BezSim:
         for k in ids:
             mask |= 1 << k
         self._check(self.lib.bez_sim_refresh_dynamics_tensors(self.h, mask, self._stream()))
+
+    # ---- inverse dynamics: M(q) udot + h(q, u) of the current state without forming M
+    def inverse_dynamics(self, udot=None, terms=abi.ID_ALL, out=None):
+        """(N, 24) float32: the sum of the terms of M udot + h selected by `terms` (abi.ID_INERTIA | ID_VELOCITY | ID_GRAVITY), in the
+        dynamics tensors' coordinates u = [root_lin, root_ang, qd]: rows 0:3 force, 3:6 moment about the root origin (world axes), 6:24
+        joint torques (include/bez_sim.h "Inverse dynamics").  `udot`: (N, 24) float32 on the sim's device, contiguous, or None for zero.
+        `out`: the same kind of tensor to write into; None: one buffer per sim, allocated by the first such call and overwritten by
+        every later one.  One launch on the current stream."""
+        shape = (self.num_envs, abi.NUM_GEN)
+        for name, t in (("udot", udot), ("out", out)):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor):
+                raise BezSimError("%s: expected a torch tensor, got %s" % (name, type(t).__name__))
+            if tuple(t.shape) != shape:
+                raise BezSimError("%s: expected shape %s, got %s" % (name, shape, tuple(t.shape)))
+        if out is None:
+            if getattr(self, "_id_out", None) is None:
+                self._id_out = torch.zeros(shape, device=self.device, dtype=torch.float32)
+            out = self._id_out
+        n = shape[0] * shape[1]
+        self._check(self.lib.bez_sim_inverse_dynamics(self.h, None if udot is None else self._ptr(udot, torch.float32, n), int(terms),
+                                                      self._ptr(out, torch.float32, n), self._stream()))
+        return out
 
     def refresh(self, which):
         self._check(self.lib.bez_sim_refresh_tensor(self.h, which, self._stream()))

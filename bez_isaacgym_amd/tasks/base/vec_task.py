@@ -199,6 +199,22 @@ class VecTask(Env):
         self.sim.refresh_dynamics_tensors("mass_matrix")
         return True
 
+    # ---- inverse dynamics of the current state (include/bez_sim.h "Inverse dynamics"); usable between steps like the refreshes above
+    def inverse_dynamics(self, udot=None, terms=7):
+        """(N, 24): the terms (abi.ID_INERTIA | ID_VELOCITY | ID_GRAVITY; default all) of M(q) udot + h(q, u) in u = [root_lin, root_ang,
+        qd]; udot (N, 24) or None for zero.  The tensor is the sim's one result buffer: the next call overwrites it."""
+        return self.sim.inverse_dynamics(udot, terms)
+
+    def bias_forces(self):
+        """(N, 24): h(q, u), the Coriolis, centrifugal and gravity forces of the current state"""
+        from ... import abi
+        return self.sim.inverse_dynamics(None, abi.ID_VELOCITY | abi.ID_GRAVITY)
+
+    def gravity_forces(self):
+        """(N, 24): the generalised force that holds the robot still against gravity in its current configuration"""
+        from ... import abi
+        return self.sim.inverse_dynamics(None, abi.ID_GRAVITY)
+
     def actuator_snapshot(self):
         """(drive torque, status, joint velocity), each (N, 18), of the last physics launch: one refresh of the actuator tensors and one of
         DOF_STATE (the PPO loop's per-epoch actuator statistics)."""

@@ -337,6 +337,33 @@ int bez_sim_get_dynamics_tensor(BezSim* sim, int which, void** dev_ptr, int64_t 
  * rc -1 with a message.  The call allocates nothing, never synchronises, reads nothing on the host: it captures into a HIP graph. */
 int bez_sim_refresh_dynamics_tensors(BezSim* sim, uint32_t which_mask, void* stream);
 
+/* Inverse dynamics: the left side of the robot's equation of motion
+ *       M(q) udot + h(q, u) = [0 x 6 ; tau_joint] + sum over bodies of J_b^T w_b
+ * by a recursive Newton-Euler pass, without forming M -- what gravity compensation, computed torque and contact-wrench estimation need.
+ *   Coordinates: u = [root_lin(3), root_ang(3), qd(18)] of the dynamics tensors above; udot_dev and out_dev are f32 (N, 24), env-major.
+ *     udot is the time derivative of u: [d/dt root_lin, d/dt root_ang, qdd].  udot_dev == NULL means udot = 0.
+ *   out = the sum of the terms selected in `terms`, evaluated on the state as it stands on `stream`:
+ *     BEZ_ID_INERTIA   M(q) udot, the armature on the 18 joint diagonals as in BEZ_DYNAMICS_MASS_MATRIX;
+ *     BEZ_ID_VELOCITY  the Coriolis and centrifugal forces of the state's u;
+ *     BEZ_ID_GRAVITY   -sum over links of J_com^T m g: the generalised force that holds the robot still against gravity.
+ *     All three: M udot + h.  A term is dropped by zeroing its input, and the terms are evaluated apart and meet only in the last two
+ *     additions of each element: a term's value does not depend on which other terms were asked for, all terms together are the fp32
+ *     sum (inertia + velocity) + gravity of the three single-term results, and the velocity term of a state at rest, the gravity term
+ *     under zero gravity and the inertia term of udot = 0 are exact zeros.
+ *   Rows of out: 0:3 the force in world axes, 3:6 the moment about the root origin in world axes (dual to u: u . out is a power),
+ *     6:24 the joint torques in DOF_STATE order.
+ *   Gravity is what the step would use: the env's BEZ_PARAM_GRAVITY row if set, else cfg.gravity.  Masses and inertias carry the env's
+ *     BEZ_PARAM_MASS_SCALE row.  The asset (cleats, box, the joint origin box + cleats moves) is the step's.  The ball takes no part.
+ *   BEZ_FLAG_FIX_BASE changes nothing: the stored state is evaluated as it is, and rows 0:6 are then the wrench the weld carries.
+ *   A non-finite input is written through.
+ *   One kernel launch.  The call allocates nothing, never synchronises, reads nothing on the host and writes only out_dev: it captures
+ *   into a HIP graph.  terms == 0, an unknown bit or a null out_dev: rc -1 with a message. */
+#define BEZ_ID_INERTIA  1u   /* M(q) udot, armature included as in BEZ_DYNAMICS_MASS_MATRIX */
+#define BEZ_ID_VELOCITY 2u   /* Coriolis / centrifugal forces of the state's u */
+#define BEZ_ID_GRAVITY  4u   /* -sum_l J_com,l^T m_l g: what holds the robot still against gravity */
+#define BEZ_ID_ALL      7u
+int bez_sim_inverse_dynamics(BezSim* sim, const float* udot_dev, uint32_t terms, float* out_dev, void* stream);
+
 /* gym.refresh_{actor_root_state,dof_state,rigid_body_state,net_contact_force}_tensor
  * (kick_env.py:750-753): materialise the Isaac-layout tensor from the SoA state.  ROOT_STATE, DOF_STATE, RIGID_BODY_STATE,
  * NET_CONTACT_FORCE, DOF_TARGET, PREV_LIN_VEL, FEET and GOAL need it; every other BezTensor is always live (the kernels
