@@ -283,3 +283,38 @@ def test_cli_config_contract():
     assert cfg["task"]["sim"]["use_gpu_pipeline"] is False and cfg["task"]["sim"]["physx"]["use_gpu"] is False
     assert cfg["train"]["params"]["config"]["max_epochs"] == 7 and cfg["train"]["params"]["config"]["num_actors"] == 64
     assert cfg["train"]["params"]["config"]["minibatch_size"] == 32768 and cfg["train"]["params"]["config"]["horizon_length"] == 32
+
+
+def test_switch_table_is_pinned_and_read_once():
+    """Every A/B switch of the agent is a row of ONE table (name, default, what it does), read once in __init__: names and defaults are
+    pinned here, bench.py's A/B list is a subset of it, an agent built without overrides holds every switch at its default, and no
+    method behind __init__ reads a switch from the config again."""
+    import inspect
+    import re
+    from bez_isaacgym_amd.ppo import a2c_continuous as m
+    want = dict(hip_graphs="auto", lean_env_step=True, dp_capture_collectives=False, dp_direct_rccl=True, fused_ops=True, half_path=True,
+                wgrad_splits=32, fused_optimizer=True, fused_policy_forward=True, packed_weights=True, fused_policy_backward=True,
+                rollout_into_dataset=True, episode_sum_slots=True, fold_rollout_post=True, fold_action_noise=True, fold_dr_step=True,
+                dr_prelaunch=False, fused_dataset_prep=True, fused_grad_reduce=True, fused_loss_backward=True, fused_wgrad=True,
+                fused_train_forward=True, dp_grid_norm=True, dp_eager_update=False, pipeline_epochs=True)
+    assert [name for name, _, _ in m.SWITCHES] == list(want) and all(isinstance(doc, str) and doc for _, _, doc in m.SWITCHES)
+    for name, default, _ in m.SWITCHES:
+        assert default == want[name] and type(default) is type(want[name]), name
+    # bench.py's own list of A/B names, from its source text
+    bench = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")).read()
+    names = re.search(r'for k in \(([^)]*)\):\s*# A/B switches', bench)
+    ab = re.findall(r'"(\w+)"', names.group(1))
+    assert len(ab) == 9 and set(ab) <= set(want), sorted(set(ab) - set(want))
+    p = _params(16, 64, horizon=4)
+    assert not set(want) & set(p["config"])                     # the shipped YAML overrides none of them ...
+    p["config"]["no_such_switch"] = 1                           # ... and a key the table does not know is ignored
+    agent = A2CAgent(p, FakeVecEnv(16, seed=5), "cpu")
+    assert vars(agent.sw) == want and agent.cfg is p["config"]
+    assert m.read_switches(dict(fold_dr_step=False, dr_prelaunch=True)).__dict__ == dict(want, fold_dr_step=False, dr_prelaunch=True)
+    assert not any(vars(agent.plan).values())                   # nothing of the fused path is planned on the CPU
+    # source level: the config is read in __init__ alone
+    for name, fn in inspect.getmembers(A2CAgent, inspect.isfunction):
+        if name != "__init__":
+            assert not re.search(r"\bcfg\s*\.\s*get\s*\(|\bcfg\s*\[", inspect.getsource(fn)), name
+    src = inspect.getsource(m)
+    assert src.count("cfg.get(") == 1 and "cfg.get(" in inspect.getsource(m.read_switches)
