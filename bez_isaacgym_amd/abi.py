@@ -43,6 +43,10 @@ NUM_GEN = 24
 # bez_sim_inverse_dynamics (include/bez_sim.h "Inverse dynamics", BezSim.inverse_dynamics): the terms of M(q) udot + h(q, u) to add up
 ID_INERTIA, ID_VELOCITY, ID_GRAVITY = 1, 2, 4
 ID_ALL = 7
+# bez_sim_centroidal (include/bez_sim.h "Centroidal dynamics", BezSim.centroidal): the words of a (N, CM_WORDS) state row; the momentum
+# matrix is (N, 6, NUM_GEN) with rows [linear momentum 3; angular momentum about the centre of mass 3]
+CM_WORDS = 16
+CM_COM, CM_COM_VEL, CM_LIN_MOM, CM_ANG_MOM, CM_MASS, CM_KINETIC, CM_POTENTIAL = 0, 3, 6, 9, 12, 13, 14
 DOF_FORCE_KEY = "env.enableDofForceSensors"   # this build's task key for FLAG_DOF_FORCE (default False)
 SPACE_ENV = 0                   # bez_sim_apply_body_forces: world axes / world points (gymapi.ENV_SPACE)
 SPACE_LOCAL = 1                 # the body's own frame (gymapi.LOCAL_SPACE)

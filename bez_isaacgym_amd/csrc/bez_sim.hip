@@ -461,6 +461,13 @@ BEZ_DEV float jacobian_entry(const float* L, uint32_t mask, V3 x, int row, int c
   return pick(cross(a, x - lds3(L + DYN_RO + 3 * d)), row);
 }
 
+// the per-env parameter rows the dynamics kernels share with the step: link l's BEZ_PARAM_MASS_SCALE entry (1 without rows) and the env's
+// BEZ_PARAM_GRAVITY row (the config's vector without rows)
+BEZ_DEV float mass_scale_of(const float* __restrict__ mass_scale, int e, int l) { return mass_scale ? mass_scale[(size_t)e * BEZ_NL + l] : 1.f; }
+BEZ_DEV V3 gravity_of(const float* __restrict__ gravity_rows, int e, float gx, float gy, float gz) {
+  return gravity_rows ? mk(gravity_rows[(size_t)e * 3], gravity_rows[(size_t)e * 3 + 1], gravity_rows[(size_t)e * 3 + 2]) : mk(gx, gy, gz);
+}
+
 template <bool CL>
 __global__ void __launch_bounds__(DYN_THREADS) refresh_dynamics_kernel(const float* __restrict__ st, const float* __restrict__ mass_scale, float* __restrict__ J,
                                                                        float* __restrict__ M, int n, uint32_t flags, float armature) {
@@ -489,7 +496,7 @@ __global__ void __launch_bounds__(DYN_THREADS) refresh_dynamics_kernel(const flo
       static_for<BEZ_NL>([&](auto I) {
         constexpr int l = decltype(I)::value;
         SV pA;
-        link_inertia<l, CL>(mass_scale ? mass_scale[(size_t)e * BEZ_NL + l] : 1.f, mk(0, 0, 0), E[l], r[l], svzero(), Ic[l], pA);
+        link_inertia<l, CL>(mass_scale_of(mass_scale, e, l), mk(0, 0, 0), E[l], r[l], svzero(), Ic[l], pA);
       });
       float* Ms = L + DYN_MS;
       static_for<BEZ_NL - 1>([&](auto I) {   // leaves first: link l is complete when its turn comes, then joins its parent
@@ -578,7 +585,7 @@ BEZ_DEV IdWrench id_links(const IdCtx& C, M3 E, V3 r, SV V, SV aI, SV aV, float*
   link_kinematics<L>(q, qd, E, r, V, S, cb, C.quirk_z);
   aI = aI + S * qdd; aV = aV + cb;
   LinkInertia LI; SV pV;
-  link_inertia<L, CL>(C.mass_scale ? C.mass_scale[(size_t)C.e * BEZ_NL + L] : 1.f, mk(0, 0, 0), E, r, V, LI, pV);
+  link_inertia<L, CL>(mass_scale_of(C.mass_scale, C.e, L), mk(0, 0, 0), E, r, V, LI, pV);
   IdWrench F = id_wrench(LI, aI, aV, pV, C.g);
   if constexpr (L + 1 < END) F = F + id_links<L + 1, END, CL>(C, E, r, V, aI, aV, U);
   U[5 + L] = id_sum(fmaf(C.armature, qdd, dot(S, F.i)), dot(S, F.v), dot(S, F.g));
@@ -614,11 +621,11 @@ __global__ void __launch_bounds__(ID_THREADS) inverse_dynamics_kernel(const floa
     const M3 E0 = quat_to_mat(ld(F_ROOT_QUAT), ld(F_ROOT_QUAT + 1), ld(F_ROOT_QUAT + 2), ld(F_ROOT_QUAT + 3));
     const SV V0 = vel ? mksv(mk(ld(F_ROOT_ANG), ld(F_ROOT_ANG + 1), ld(F_ROOT_ANG + 2)), mk(ld(F_ROOT_LIN), ld(F_ROOT_LIN + 1), ld(F_ROOT_LIN + 2))) : svzero();
     V3 g = mk(0, 0, 0);
-    if (terms & BEZ_ID_GRAVITY) g = gravity_rows ? mk(gravity_rows[(size_t)e * 3], gravity_rows[(size_t)e * 3 + 1], gravity_rows[(size_t)e * 3 + 2]) : mk(gx, gy, gz);
+    if (terms & BEZ_ID_GRAVITY) g = gravity_of(gravity_rows, e, gx, gy, gz);
     // spatial acceleration of the torso about the (momentarily fixed) point its origin passes through: [wdot; vdot - w x v]
     const SV aI0 = mksv(mk(U[3], U[4], U[5]), mk(U[0], U[1], U[2])), aV0 = mksv(mk(0, 0, 0), -cross(V0.a, V0.l));
     LinkInertia I0; SV pV0;
-    link_inertia<0, CL>(mass_scale ? mass_scale[(size_t)e * BEZ_NL] : 1.f, mk(0, 0, 0), E0, mk(0, 0, 0), V0, I0, pV0);
+    link_inertia<0, CL>(mass_scale_of(mass_scale, e, 0), mk(0, 0, 0), E0, mk(0, 0, 0), V0, I0, pV0);
     IdWrench F0 = id_wrench(I0, aI0, aV0, pV0, g);
     // (the env index is made opaque per chain, together with the wrench so far: otherwise every chain's loads are issued up front and
     // the five chains are interleaved, at the price of their registers)
@@ -645,6 +652,106 @@ __global__ void __launch_bounds__(ID_THREADS) inverse_dynamics_kernel(const floa
   } else {
     for (int i = threadIdx.x; i < total; i += ID_THREADS) out[(size_t)e0 * DYN_NG + i] = slot(i);
   }
+}
+
+// ---- bez_sim_centroidal (definition: include/bez_sim.h "Centroidal dynamics"): the composite-rigid-body sums of refresh_dynamics_kernel
+// stopped at rows 0:6 of M -- no path-pair products -- with the moment shifted from the root origin to the centre of mass.
+// A workgroup is ONE wave and takes CM_TILE consecutive envs.  Phase 1, one lane per env, in world axes about the root origin (where the
+// LinkInertia composites add up without transforms): forward kinematics with velocities, the links' inertias, then links 18 -> 1: F_l =
+// I^c_l S_l as [lin; ang] -- column 6 + l - 1 of the momentum map about the root origin -- goes to the env's LDS row where A_G has it, and
+// the composite joins its parent's.  With I^c_0 = {m, h, Ibar} the centre of mass is c = h / m; a second pass over the columns takes
+// c x (linear rows) off the angular rows and adds up the momentum A_G u on the way.  The base block is written from its definition:
+// m I, -skew(h), the constant 0 and I_G = Ibar - m (|c|^2 I - c c^T), six values for nine slots.
+// The kinetic energy is the sum over links of 1/2 V_l . I_l V_l with the link's OWN inertia and spatial velocity (+ 1/2 armature |qd|^2):
+// 19 non-negative terms, equal to 1/2 u^T M u, without the subtree sums that the rows 6:24 of M u would need.
+// Phase 2, all lanes: the tile's rows are two contiguous ranges (CM_TILE x 16 floats of state, CM_TILE x 144 of matrix), stored as float4
+// (pointers that are not 16-byte aligned: a scalar path to the same bits).  Rows of CM_STRIDE words, odd: the lanes of phase 1 write
+// distinct banks.
+constexpr int CM_TILE = 16, CM_THREADS = 64, CM_MATRIX = 6 * DYN_NG, CM_STRIDE = (BEZ_CM_WORDS + CM_MATRIX) | 1;
+static_assert(BEZ_CM_WORDS % 4 == 0 && CM_MATRIX % 4 == 0, "an env's rows are whole float4s: the tile's range is as aligned as the base");
+// the tile's rows of one output: WIDTH floats per env, kept at `rows` (+ CM_STRIDE per env) in LDS, to out[e0 * WIDTH ...]
+template <int WIDTH>
+BEZ_DEV void cm_store_tile(const float* rows, float* __restrict__ out, int e0, int ne) {
+  if (!out) return;
+  auto at = [&](int i) { return rows[(i / WIDTH) * CM_STRIDE + i % WIDTH]; };
+  float* o = out + (size_t)e0 * WIDTH;
+  if ((reinterpret_cast<uintptr_t>(out) & 15u) == 0) {
+    float4* o4 = reinterpret_cast<float4*>(o);
+    for (int i = threadIdx.x; i < ne * (WIDTH / 4); i += CM_THREADS) o4[i] = make_float4(at(4 * i), at(4 * i + 1), at(4 * i + 2), at(4 * i + 3));
+  } else {
+    for (int i = threadIdx.x; i < ne * WIDTH; i += CM_THREADS) o[i] = at(i);
+  }
+}
+template <bool CL>
+__global__ void __launch_bounds__(CM_THREADS) centroidal_kernel(const float* __restrict__ st, const float* __restrict__ mass_scale,
+                                                                const float* __restrict__ gravity_rows, float* __restrict__ state_out,
+                                                                float* __restrict__ matrix_out, int n, uint32_t flags, float armature, float gx, float gy,
+                                                                float gz) {
+  __shared__ float lds[CM_TILE * CM_STRIDE];
+  const int e0 = blockIdx.x * CM_TILE, ne = min(CM_TILE, n - e0);
+  if ((int)threadIdx.x < ne) {
+    const int e = e0 + threadIdx.x;
+    float* W = lds + threadIdx.x * CM_STRIDE;   // the env's state words
+    float* A = W + BEZ_CM_WORDS;                // its A_G, 6 x 24 row-major
+    auto put_col = [&](int row0, int c, V3 v) { A[row0 * DYN_NG + c] = v.x; A[(row0 + 1) * DYN_NG + c] = v.y; A[(row0 + 2) * DYN_NG + c] = v.z; };
+    auto get_col = [&](int row0, int c) { return mk(A[row0 * DYN_NG + c], A[(row0 + 1) * DYN_NG + c], A[(row0 + 2) * DYN_NG + c]); };
+    EnvState S;
+    load_state(st, n, e, S);
+    M3 E[BEZ_NL]; V3 r[BEZ_NL]; SV V[BEZ_NL];
+    link_frames<CL, true>(S, flags, E, r, V);
+    LinkInertia Ic[BEZ_NL];
+    float ke2 = 0.f;   // twice the kinetic energy
+    static_for<BEZ_NL>([&](auto I) {
+      constexpr int l = decltype(I)::value;
+      SV pA;
+      link_inertia<l, CL>(mass_scale_of(mass_scale, e, l), mk(0, 0, 0), E[l], r[l], svzero(), Ic[l], pA);
+      ke2 += dot(V[l], inertia_times(Ic[l], V[l]));
+    });
+    float qd2 = 0.f;
+    static_for<BEZ_NL - 1>([&](auto I) {   // leaves first: link l is complete when its turn comes, then joins its parent
+      constexpr int l = BEZ_NL - 1 - decltype(I)::value, p = BEZ_LINK_PARENT[l];
+      const LinkInertia& C = Ic[l];
+      const V3 a = col(E[l], axis_index(l)) * axis_sign(l);   // the column of the link's frame that the joint rotation leaves alone
+      const SV F = inertia_times(C, mksv(a, cross(r[l], a)));   // F_l = I^c_l S_l, S_l = [a; r x a]
+      put_col(0, 5 + l, F.l);
+      put_col(3, 5 + l, F.a);
+      qd2 = fmaf(S.qd[l - 1], S.qd[l - 1], qd2);
+      Ic[p].m += C.m; Ic[p].h = Ic[p].h + C.h; add_to(Ic[p].Ibar, C.Ibar);
+    });
+    const LinkInertia& C = Ic[0];
+    const float m = C.m;
+    const V3 h = C.h, c = mk(h.x / m, h.y / m, h.z / m), w = S.root_ang;
+    Sym3 G;   // I_G = Ibar - m (|c|^2 I - c c^T): each of the six values is formed once and written to both triangles
+    G.xx = C.Ibar.xx - fmaf(h.y, c.y, h.z * c.z); G.yy = C.Ibar.yy - fmaf(h.x, c.x, h.z * c.z); G.zz = C.Ibar.zz - fmaf(h.x, c.x, h.y * c.y);
+    G.xy = fmaf(h.x, c.y, C.Ibar.xy); G.xz = fmaf(h.x, c.z, C.Ibar.xz); G.yz = fmaf(h.y, c.z, C.Ibar.yz);
+    put_col(0, 0, mk(m, 0.f, 0.f)); put_col(0, 1, mk(0.f, m, 0.f)); put_col(0, 2, mk(0.f, 0.f, m));
+    put_col(0, 3, mk(0.f, -h.z, h.y)); put_col(0, 4, mk(h.z, 0.f, -h.x)); put_col(0, 5, mk(-h.y, h.x, 0.f));   // -skew(h) = -m skew(c)
+    put_col(3, 0, mk(0, 0, 0)); put_col(3, 1, mk(0, 0, 0)); put_col(3, 2, mk(0, 0, 0));
+    put_col(3, 3, mk(G.xx, G.xy, G.xz)); put_col(3, 4, mk(G.xy, G.yy, G.yz)); put_col(3, 5, mk(G.xz, G.yz, G.zz));
+    // the momentum A_G u: the base columns (their structural zeros skipped), then the joints'
+    V3 P = S.root_lin * m - cross(h, w), L = mul(G, w);
+    static_for<BEZ_ND>([&](auto I) {
+      constexpr int d = decltype(I)::value;
+      const V3 Fl = get_col(0, 6 + d), Fg = get_col(3, 6 + d) - cross(c, Fl);
+      put_col(3, 6 + d, Fg);
+      P = fma3(Fl, S.qd[d], P);
+      L = fma3(Fg, S.qd[d], L);
+    });
+    const V3 g = gravity_of(gravity_rows, e, gx, gy, gz), com = S.root_pos + c;
+    W[BEZ_CM_COM] = com.x; W[BEZ_CM_COM + 1] = com.y; W[BEZ_CM_COM + 2] = com.z;
+    // (x + 0.0f is x except that it turns -0.0 into +0.0: a state at rest and a zero gravity row give zeros to the bit)
+    P = P + mk(0.f, 0.f, 0.f); L = L + mk(0.f, 0.f, 0.f);
+    W[BEZ_CM_COM_VEL] = P.x / m; W[BEZ_CM_COM_VEL + 1] = P.y / m; W[BEZ_CM_COM_VEL + 2] = P.z / m;
+    W[BEZ_CM_LIN_MOM] = P.x; W[BEZ_CM_LIN_MOM + 1] = P.y; W[BEZ_CM_LIN_MOM + 2] = P.z;
+    W[BEZ_CM_ANG_MOM] = L.x; W[BEZ_CM_ANG_MOM + 1] = L.y; W[BEZ_CM_ANG_MOM + 2] = L.z;
+    W[BEZ_CM_MASS] = m;
+    W[BEZ_CM_KINETIC] = 0.5f * fmaf(armature, qd2, ke2) + 0.f;
+    W[BEZ_CM_POTENTIAL] = 0.f - m * dot(g, com);
+    W[15] = 0.f;
+  }
+  __syncthreads();
+  cm_store_tile<BEZ_CM_WORDS>(lds, state_out, e0, ne);
+  cm_store_tile<CM_MATRIX>(lds + BEZ_CM_WORDS, matrix_out, e0, ne);
 }
 
 // gym.set_actor_root_state_tensor_indexed
@@ -1143,6 +1250,17 @@ int bez_sim_inverse_dynamics(BezSim* s, const float* udot_dev, uint32_t terms, f
                                       s->dr[BEZ_PARAM_GRAVITY], udot_dev, out_dev, s->n, s->cfg.flags, terms, s->cfg.armature, g[0], g[1], g[2]);
   };
   return s->cleats ? launch(inverse_dynamics_kernel<true>) : launch(inverse_dynamics_kernel<false>);
+}
+int bez_sim_centroidal(BezSim* s, float* state_dev, float* matrix_dev, void* stream) {
+  if (!s) return fail(s, -1, "bez_sim_centroidal: sim is null");
+  if (!state_dev && !matrix_dev) return fail(s, -1, "bez_sim_centroidal: state_dev and matrix_dev are both null (nothing to write)");
+  const size_t threads = (size_t)((s->n + CM_TILE - 1) / CM_TILE) * CM_THREADS;
+  const float* g = s->cfg.gravity;
+  auto launch = [&](auto kernel) {
+    return launch_checked<CM_THREADS>(s, "centroidal_kernel launch", kernel, threads, (hipStream_t)stream, s->state, s->dr[BEZ_PARAM_MASS_SCALE],
+                                      s->dr[BEZ_PARAM_GRAVITY], state_dev, matrix_dev, s->n, s->cfg.flags, s->cfg.armature, g[0], g[1], g[2]);
+  };
+  return s->cleats ? launch(centroidal_kernel<true>) : launch(centroidal_kernel<false>);
 }
 int bez_sim_set_obs_calls(BezSim* s, int64_t calls) { if (!s) return -1; s->obs_calls = calls; return 0; }
 

@@ -60,6 +60,7 @@ SIGS = {
     "bez_sim_get_dynamics_tensor": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bez_sim_refresh_dynamics_tensors": (C.c_int, [vp, u32, vp]),
     "bez_sim_inverse_dynamics": (C.c_int, [vp, fp, u32, fp, vp]),
+    "bez_sim_centroidal": (C.c_int, [vp, fp, fp, vp]),
 }
 EXPORTS = list(SIGS)
 
@@ -235,6 +236,34 @@ class BezSim:
         self._check(self.lib.bez_sim_inverse_dynamics(self.h, None if udot is None else self._ptr(udot, torch.float32, n), int(terms),
                                                       self._ptr(out, torch.float32, n), self._stream()))
         return out
+
+    # ---- centroidal dynamics: centre of mass, momentum about it, the momentum matrix A_G, mechanical energy
+    def centroidal(self, state=None, matrix=None, want_matrix=False):
+        """(state, matrix) of the current state in one launch on the current stream (include/bez_sim.h "Centroidal dynamics").
+        state (N, 16) float32: the abi.CM_* words -- COM 0:3, COM_VEL 3:6, LIN_MOM 6:9, ANG_MOM (about the centre of mass) 9:12, MASS,
+        KINETIC, POTENTIAL.  matrix (N, 6, 24) float32: A_G with matrix @ u == [LIN_MOM; ANG_MOM], u = [root_lin, root_ang, qd]; it is
+        written only when a `matrix` tensor is given or want_matrix is set, and is None in the result otherwise.  `state`, `matrix`:
+        contiguous float32 tensors on the sim's device to write into; None: one buffer of each kind per sim, allocated by the first
+        call that needs it and overwritten by every later one."""
+        shapes = {"state": (self.num_envs, abi.CM_WORDS), "matrix": (self.num_envs, 6, abi.NUM_GEN)}
+        for name, t in (("state", state), ("matrix", matrix)):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor):
+                raise BezSimError("%s: expected a torch tensor, got %s" % (name, type(t).__name__))
+            if tuple(t.shape) != shapes[name]:
+                raise BezSimError("%s: expected shape %s, got %s" % (name, shapes[name], tuple(t.shape)))
+        if state is None:
+            if getattr(self, "_cm_state", None) is None:
+                self._cm_state = torch.zeros(shapes["state"], device=self.device, dtype=torch.float32)
+            state = self._cm_state
+        if matrix is None and want_matrix:
+            if getattr(self, "_cm_matrix", None) is None:
+                self._cm_matrix = torch.zeros(shapes["matrix"], device=self.device, dtype=torch.float32)
+            matrix = self._cm_matrix
+        self._check(self.lib.bez_sim_centroidal(self.h, self._ptr(state, torch.float32, state.numel()),
+                                                None if matrix is None else self._ptr(matrix, torch.float32, matrix.numel()), self._stream()))
+        return state, matrix
 
     def refresh(self, which):
         self._check(self.lib.bez_sim_refresh_tensor(self.h, which, self._stream()))

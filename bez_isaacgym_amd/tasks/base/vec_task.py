@@ -215,6 +215,33 @@ class VecTask(Env):
         from ... import abi
         return self.sim.inverse_dynamics(None, abi.ID_GRAVITY)
 
+    # ---- centroidal dynamics of the current state (include/bez_sim.h "Centroidal dynamics"); each method is one launch, and what it
+    # returns is (a view of) the sim's one result buffer of that kind: the next call overwrites it
+    def centroidal_state(self):
+        """(N, 16): the abi.CM_* words -- COM, COM_VEL, LIN_MOM, ANG_MOM about the centre of mass, MASS, KINETIC, POTENTIAL"""
+        return self.sim.centroidal()[0]
+
+    def center_of_mass(self):
+        """((N, 3) position in env coordinates, (N, 3) velocity) of the robot's centre of mass"""
+        from ... import abi
+        s = self.centroidal_state()
+        return s[:, abi.CM_COM:abi.CM_COM + 3], s[:, abi.CM_COM_VEL:abi.CM_COM_VEL + 3]
+
+    def centroidal_momentum(self):
+        """(N, 6): [linear momentum; angular momentum about the centre of mass], world axes"""
+        from ... import abi
+        return self.centroidal_state()[:, abi.CM_LIN_MOM:abi.CM_LIN_MOM + 6]
+
+    def centroidal_momentum_matrix(self):
+        """(N, 6, 24): A_G with A_G @ u == centroidal_momentum(), u = [root_lin, root_ang, qd]"""
+        return self.sim.centroidal(want_matrix=True)[1]
+
+    def mechanical_energy(self):
+        """((N,) kinetic energy 1/2 u^T M u, (N,) potential energy -m g . com)"""
+        from ... import abi
+        s = self.centroidal_state()
+        return s[:, abi.CM_KINETIC], s[:, abi.CM_POTENTIAL]
+
     def actuator_snapshot(self):
         """(drive torque, status, joint velocity), each (N, 18), of the last physics launch: one refresh of the actuator tensors and one of
         DOF_STATE (the PPO loop's per-epoch actuator statistics)."""

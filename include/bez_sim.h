@@ -364,6 +364,38 @@ int bez_sim_refresh_dynamics_tensors(BezSim* sim, uint32_t which_mask, void* str
 #define BEZ_ID_ALL      7u
 int bez_sim_inverse_dynamics(BezSim* sim, const float* udot_dev, uint32_t terms, float* out_dev, void* stream);
 
+/* Centroidal dynamics: the robot's centre of mass, its momentum about it, the map from u to that momentum, and the mechanical energy --
+ * what balance controllers, capture-point and angular-momentum rewards and energy diagnostics read.
+ *   Coordinates: u = [root_lin(3), root_ang(3), qd(18)] of the dynamics tensors above; world (env) axes throughout.
+ *   state_dev  f32 (N, BEZ_CM_WORDS), env-major, the words named below.  COM is in the coordinates of the ROOT_STATE positions; ANG_MOM is
+ *     taken ABOUT THE CENTRE OF MASS; COM_VEL is LIN_MOM / MASS; KINETIC is 1/2 u^T M u with M of BEZ_DYNAMICS_MASS_MATRIX (the armature
+ *     on the 18 joint diagonals included, as there); POTENTIAL is -MASS * g . COM (zero at the origin of the env's coordinates).
+ *   matrix_dev f32 (N, 6, 24): the centroidal momentum matrix A_G, so that matrix[e] @ u[e] == [LIN_MOM; ANG_MOM]: rows 0:3 the linear
+ *     momentum, rows 3:6 the angular momentum about the centre of mass.  matrix[0:3,0:3] = MASS * I with exact zeros off the diagonal;
+ *     matrix[3:6,0:3] = 0 exactly (the momentum about the centre of mass does not see the root's translation); matrix[3:6,3:6] is the
+ *     centroidal composite inertia, bitwise symmetric; matrix[0:3,3:6] = -MASS * skew(COM - root_pos); column 6+d is [F_lin;
+ *     F_ang - (COM - root_pos) x F_lin] with F = I^c_(d+1) S_(d+1) the composite inertia below joint d times the joint's axis.
+ *   Gravity is what the step would use: the env's BEZ_PARAM_GRAVITY row if set, else cfg.gravity.  Masses and inertias carry the env's
+ *     BEZ_PARAM_MASS_SCALE row.  Fixed bodies (imu, camera, cleats) are in their links; the asset (cleats, box, the joint origin
+ *     box + cleats moves) is the step's.  The ball takes no part.  BEZ_FLAG_FIX_BASE changes nothing: the stored state is evaluated as
+ *     it is.  A non-finite state is written through (the structural zeros stay).
+ *   Zeros are +0.0f to the bit: the structural zeros of the matrix, word 15, COM_VEL / LIN_MOM / ANG_MOM / KINETIC of a state with u = 0 and
+ *     POTENTIAL under a zero gravity row.
+ *   Either pointer may be NULL: that output is not written.  Both NULL, or a NULL sim: rc -1 with a message.
+ *   One kernel launch.  The call allocates nothing, never synchronises, reads nothing on the host and writes only the two outputs: it
+ *   captures into a HIP graph. */
+#define BEZ_CM_WORDS     16  /* floats per env of state_dev */
+#define BEZ_CM_COM        0  /* 0:3   centre of mass, env (world) coordinates, as ROOT_STATE positions */
+#define BEZ_CM_COM_VEL    3  /* 3:6   its velocity = LIN_MOM / MASS */
+#define BEZ_CM_LIN_MOM    6  /* 6:9   sum_l m_l v_com,l, world axes */
+#define BEZ_CM_ANG_MOM    9  /* 9:12  angular momentum ABOUT THE CENTRE OF MASS, world axes */
+#define BEZ_CM_MASS      12  /* total mass (the env's BEZ_PARAM_MASS_SCALE row applied) */
+#define BEZ_CM_KINETIC   13  /* 1/2 u^T M u with M of BEZ_DYNAMICS_MASS_MATRIX (armature included, as there) */
+#define BEZ_CM_POTENTIAL 14  /* -MASS * g . COM, g = the env's BEZ_PARAM_GRAVITY row if set, else cfg.gravity */
+                             /* word 15: 0.0f */
+int bez_sim_centroidal(BezSim* sim, float* state_dev /* (N,16) or NULL */,
+                       float* matrix_dev /* (N,6,24) or NULL */, void* stream);
+
 /* gym.refresh_{actor_root_state,dof_state,rigid_body_state,net_contact_force}_tensor
  * (kick_env.py:750-753): materialise the Isaac-layout tensor from the SoA state.  ROOT_STATE, DOF_STATE, RIGID_BODY_STATE,
  * NET_CONTACT_FORCE, DOF_TARGET, PREV_LIN_VEL, FEET and GOAL need it; every other BezTensor is always live (the kernels

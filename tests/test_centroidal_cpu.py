@@ -1,0 +1,278 @@
+"""CPU: the C ABI declares, lists and exports bez_sim_centroidal; and the reference that pins it on the GPU
+(tests/centroidal_numpy.cm_ref) is what it says it is -- held in fp64 to identities it was not built from (the mass matrix of
+tests/dynamics_numpy.py, the inverse dynamics of tests/inverse_dynamics_numpy.py), on random states of the default, cleats and box
+models -- and notices the mistakes it is there to catch.  The Python layer's argument checks run on a sim without a library."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from bez_isaacgym_amd import abi
+from tests import centroidal_numpy as CM
+from tests import dynamics_numpy as D
+from tests import inverse_dynamics_numpy as ID
+from tests.test_state_tensors_cpu import generate_states
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = open(os.path.join(ROOT, "include", "bez_sim.h")).read()
+ARMATURE = float(abi.default_config(1).armature)
+G = np.array([0.3, -0.2, -9.81])   # not along an axis: a dropped or permuted component shows
+TOL = 1e-9
+NG = 24
+
+
+def centroidal_states(n, seed=31):
+    """the states of tests/test_state_tensors_cpu.generate_states (seams, joint limits, random roots; |w| up to 10 rad/s, |qd| up to
+    20 rad/s) with the root a few metres from the origin, so that COM carries a real offset without drowning it: fp32 (n, 13), (n, 18, 2)"""
+    root, dof, _ = generate_states(n)
+    rng = np.random.default_rng(seed)
+    root = root.copy()
+    root[:, 0:2] = rng.uniform(-3, 3, (n, 2))
+    root[:, 2] = rng.uniform(0.2, 2, n)
+    return root.astype(np.float32), dof.astype(np.float32)
+
+
+def test_abi_declares_lists_and_exports_the_centroidal_call():
+    """the header declares the entry with the issue's signature and the BEZ_CM_* words, equal to abi's and the reference's; sim.EXPORTS
+    and sim.SIGS list it; the built library exports it; BEZ_SIM_ABI_VERSION, BEZ_TENSOR_COUNT and the BezDynamicsTensor enum are untouched"""
+    code = re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S))   # the declarations without their comments
+    assert "int bez_sim_centroidal(BezSim* sim, float* state_dev , float* matrix_dev , void* stream);" in code
+    ids = dict((m.group(1), int(m.group(2))) for m in re.finditer(r"#define BEZ_CM_(\w+)\s+(\d+)\s", HEADER))
+    want = {"WORDS": 16, "COM": 0, "COM_VEL": 3, "LIN_MOM": 6, "ANG_MOM": 9, "MASS": 12, "KINETIC": 13, "POTENTIAL": 14}
+    assert ids == want
+    assert {k: getattr(abi, "CM_" + k) for k in want} == want
+    assert {k: getattr(CM, "CM_" + k) for k in want} == want
+    from bez_isaacgym_amd.build import lib_path
+    from bez_isaacgym_amd.sim import EXPORTS, SIGS
+    assert "bez_sim_centroidal" in EXPORTS
+    assert SIGS["bez_sim_centroidal"] == (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+    assert getattr(C.CDLL(lib_path()), "bez_sim_centroidal") is not None
+    assert int(re.search(r"#define BEZ_SIM_ABI_VERSION (\d+)", HEADER).group(1)) == 5 == abi.ABI_VERSION
+    body = re.search(r"enum BezDynamicsTensor \{(.*?)\};", HEADER, re.S).group(1)
+    assert dict((m.group(1), int(m.group(2))) for m in re.finditer(r"BEZ_DYNAMICS_(\w+) = (\d+)", body)) == {"JACOBIAN": 0, "MASS_MATRIX": 1, "COUNT": 2}
+    assert (abi.DYNAMICS_JACOBIAN, abi.DYNAMICS_MASS_MATRIX, abi.DYNAMICS_COUNT) == (0, 1, 2) and abi.TENSOR_COUNT == 17
+    assert re.search(r"BEZ_TENSOR_COUNT = 17\b", HEADER)
+
+
+# ---------------------------------------------------------------- the reference
+
+N = 24
+
+
+@pytest.fixture(scope="module")
+def cases():
+    """N states with exactly unit quaternions; mass-scale rows (ones for the first third); the default, cleats and box models in turn;
+    the fp64 reference of each"""
+    root, dof = centroidal_states(300)
+    pick = np.concatenate([np.arange(0, 10), np.arange(40, 300, 17)])[:N]
+    root, dof = root[pick].astype(np.float64), dof[pick].astype(np.float64)
+    root[:, 3:7] /= np.linalg.norm(root[:, 3:7], axis=1, keepdims=True)
+    rng = np.random.default_rng(23)
+    scale = rng.uniform(0.5, 1.5, (N, 19))
+    scale[: N // 3] = 1.0
+    udot = rng.uniform(-10, 10, (N, NG))
+    out = []
+    for e in range(N):
+        model = D.model_of(("default", "cleats", "box")[e % 3])
+        c = dict(model=model, root=root[e], dof=dof[e], scale=scale[e], udot=udot[e], u=np.concatenate([root[e, 7:13], dof[e, :, 1]]))
+        c["ref"] = _cm(c)
+        c["M"] = D.M_ref_jtmj(model, root[e, 3:7], dof[e, :, 0], scale[e], ARMATURE)
+        out.append(c)
+    return out
+
+
+def _cm(c, root=None, dof=None, **kw):
+    a = dict(mass_scale=c["scale"][None], gravity=G, armature=ARMATURE)
+    a.update(kw)
+    r = CM.cm_ref(c["model"], ((c["root"] if root is None else root)[None], (c["dof"] if dof is None else dof)[None]), **a)
+    return {k: v[0] for k, v in r.items()}
+
+
+def _words(ref, first, count=3):
+    return ref["state"][first:first + count]
+
+
+def test_momentum_about_the_root_is_rows_0_6_of_the_mass_matrix_times_u(cases):
+    """[p; L_root] == M_ref[0:6, :] @ u, and L_G == L_root - (c - root) x p"""
+    for c in cases:
+        ref, M, u = c["ref"], c["M"], c["u"]
+        want = M[0:6] @ u
+        tol = TOL * (D.scale_of(M)[0:6] @ np.abs(u))
+        got = np.concatenate([_words(ref, CM.CM_LIN_MOM), ref["L_root"]])
+        assert (np.abs(got - want) <= tol).all(), np.abs(got - want).max()
+        shift = np.cross(_words(ref, CM.CM_COM) - c["root"][0:3], _words(ref, CM.CM_LIN_MOM))
+        assert (np.abs(_words(ref, CM.CM_ANG_MOM) - (ref["L_root"] - shift)) <= tol[3:6]).all()
+
+
+def test_kinetic_energy_is_half_u_M_u_and_the_mass_is_M00(cases):
+    for c in cases:
+        ref, M, u = c["ref"], c["M"], c["u"]
+        assert abs(ref["state"][CM.CM_KINETIC] - 0.5 * u @ M @ u) <= TOL * 0.5 * (np.abs(u) @ D.scale_of(M) @ np.abs(u))
+        assert abs(ref["state"][CM.CM_MASS] - M[0, 0]) <= TOL * M[0, 0]
+        assert ref["state"][CM.CM_KINETIC] > 0 and ref["state"][15] == 0.0
+
+
+def test_the_matrix_times_u_is_the_momentum_and_has_the_documented_blocks(cases):
+    """A_G u == [LIN_MOM; ANG_MOM]; the base block is [m I, -m skew(c - root); 0, I_G] with I_G symmetric; COM_VEL = LIN_MOM / MASS"""
+    for c in cases:
+        ref, u = c["ref"], c["u"]
+        A, s = ref["matrix"], ref["state"]
+        m, rel = s[CM.CM_MASS], _words(ref, CM.CM_COM) - c["root"][0:3]
+        size = np.abs(A) @ np.abs(u)
+        assert (np.abs(A @ u - s[CM.CM_LIN_MOM:CM.CM_LIN_MOM + 6]) <= TOL * size).all()
+        assert np.abs(A[0:3, 0:3] - m * np.eye(3)).max() <= TOL * m and np.abs(A[3:6, 0:3]).max() <= TOL * m
+        K = np.array([[0, -rel[2], rel[1]], [rel[2], 0, -rel[0]], [-rel[1], rel[0], 0]])
+        assert np.abs(A[0:3, 3:6] + m * K).max() <= TOL * m
+        assert np.abs(A[3:6, 3:6] - A[3:6, 3:6].T).max() <= TOL * np.abs(A[3:6, 3:6]).max()
+        assert np.linalg.eigvalsh(0.5 * (A[3:6, 3:6] + A[3:6, 3:6].T)).min() > 0
+        assert np.abs(_words(ref, CM.CM_COM_VEL) * m - _words(ref, CM.CM_LIN_MOM)).max() <= TOL * np.abs(_words(ref, CM.CM_LIN_MOM)).max()
+
+
+def _advance(c, t):
+    """(root row, dof) of the state moved for the time t along its own velocity with the acceleration udot: the root origin along
+    root_lin, the orientation about the world-frame angular velocity (xyzw quaternion), u(t) = u + t udot"""
+    root, dof = c["root"].copy(), c["dof"].copy()
+    w = c["root"][10:13]
+    th = np.linalg.norm(w) * t
+    ax = w / np.linalg.norm(w)
+    dx, dy, dz, dw = (*(ax * np.sin(th / 2)), np.cos(th / 2))
+    x, y, z, s = c["root"][3:7]
+    root[3:7] = [dw * x + dx * s + dy * z - dz * y, dw * y - dx * z + dy * s + dz * x, dw * z + dx * y - dy * x + dz * s,
+                 dw * s - dx * x - dy * y - dz * z]
+    root[0:3] = c["root"][0:3] + t * c["root"][7:10]
+    root[7:13] = c["root"][7:13] + t * c["udot"][0:6]
+    dof[:, 0] = c["dof"][:, 0] + t * c["dof"][:, 1]
+    dof[:, 1] = c["dof"][:, 1] + t * c["udot"][6:]
+    return root, dof
+
+
+def test_rate_of_momentum_is_the_base_wrench_of_inverse_dynamics(cases):
+    """d/dt [p; L about the FIXED point the root origin passes through] by central differences along a short fp64 trajectory (velocity u,
+    acceleration udot) equals rows 0:6 of id_ref for the inertia + velocity terms (Newton and Euler for the whole robot).  L about the
+    fixed point is formed from the call's own words: ANG_MOM + (COM - that point) x LIN_MOM.  1e-5 of the size of the terms, as the
+    central-difference checks of tests/test_inverse_dynamics_cpu.py: the step 1e-6 s leaves 1e-16 / 1e-6 = 1e-10 of the momentum in
+    the quotient and a truncation of 4e-10 relative"""
+    dt = 1e-6
+    for c in cases:
+        O = c["root"][0:3]
+
+        def mom(t):
+            s = _cm(c, *_advance(c, t))["state"]
+            return np.concatenate([s[CM.CM_LIN_MOM:CM.CM_LIN_MOM + 3], s[CM.CM_ANG_MOM:CM.CM_ANG_MOM + 3] + np.cross(s[0:3] - O, s[CM.CM_LIN_MOM:CM.CM_LIN_MOM + 3])])
+        rate = (mom(dt) - mom(-dt)) / (2 * dt)
+        a = dict(model=c["model"], quat=c["root"][3:7], v0=c["root"][7:13], q=c["dof"][:, 0], qd=c["dof"][:, 1], gravity=G, mass_scale=c["scale"],
+                 armature=ARMATURE)
+        want = ID.id_ref(udot=c["udot"], terms=ID.ID_INERTIA | ID.ID_VELOCITY, **a)[0:6]
+        size = D.scale_of(c["M"])[0:6] @ np.abs(c["udot"]) + np.abs(ID.id_ref(udot=None, terms=ID.ID_VELOCITY, **a)[0:6]) + np.abs(want)
+        assert (np.abs(rate - want) <= 1e-5 * size).all(), (np.abs(rate - want).max(), size)
+
+
+def test_rate_of_potential_energy_is_the_gravity_power(cases):
+    """d(PE)/dt by central differences == u . (gravity term of id_ref) == -g . LIN_MOM: the identity (b) of
+    tests/test_inverse_dynamics_cpu.py (the gravity term is the force that HOLDS the robot, so its power along u is the rate at which
+    the potential energy rises)"""
+    dt = 1e-6
+    for c in cases:
+        rate = (_cm(c, *_advance(c, dt))["state"][CM.CM_POTENTIAL] - _cm(c, *_advance(c, -dt))["state"][CM.CM_POTENTIAL]) / (2 * dt)
+        gt = ID.id_ref(model=c["model"], quat=c["root"][3:7], v0=c["root"][7:13], q=c["dof"][:, 0], qd=c["dof"][:, 1], udot=None, gravity=G,
+                       mass_scale=c["scale"], armature=ARMATURE, terms=ID.ID_GRAVITY)
+        size = np.abs(c["u"]) @ np.abs(gt)
+        assert abs(rate - c["u"] @ gt) <= 1e-5 * size
+        assert abs(c["u"] @ gt + G @ _words(c["ref"], CM.CM_LIN_MOM)) <= TOL * size
+        s = c["ref"]["state"]
+        assert abs(s[CM.CM_POTENTIAL] + s[CM.CM_MASS] * (G @ s[0:3])) <= TOL * abs(s[CM.CM_POTENTIAL])
+
+
+def _block_errors(a, b):
+    """{block: worst |a - b|} over the state's and the matrix's blocks"""
+    out = {name: float(np.abs(a["state"][..., sl] - b["state"][..., sl]).max()) for name, sl in CM.STATE_BLOCKS}
+    out.update({name: float(np.abs(a["matrix"][..., sl, :] - b["matrix"][..., sl, :]).max()) for name, sl in CM.MATRIX_BLOCKS})
+    return out
+
+
+def test_the_reference_is_sensitive(cases):
+    """one link 1 % heavier, two DOFs swapped, the sign of g flipped: each moves some block of the result by more than 100x the error
+    the fp32 yardstick has in that block -- the error the GPU bars are made of"""
+    for c in cases[:9]:
+        base = c["ref"]
+        y32 = {k: v.astype(np.float64) for k, v in _cm(c, dtype=np.float32).items()}
+        err32 = _block_errors(y32, base)
+        size = _block_errors(base, {k: np.zeros_like(v) for k, v in base.items()})
+        assert all(0 < err32[k] < 1e-4 * size[k] for k in err32 if k != "mass"), (err32, size)
+        heavier = c["scale"].copy(); heavier[9] *= 1.01      # a knee
+        perm = np.arange(18); perm[[7, 8]] = perm[[8, 7]]       # knee <-> ankle pitch of the left leg
+        swapped = _cm(c, dof=c["dof"][perm])
+        swapped["matrix"] = swapped["matrix"].copy()
+        swapped["matrix"][:, 6:] = swapped["matrix"][:, 6:][:, perm]
+        for what, moved, blocks in (("mass", _cm(c, mass_scale=heavier[None]), ("mass", "lin_mom", "ang_mom", "kinetic", "potential", "matrix_lin", "matrix_ang")),
+                                    ("swap", swapped, ("lin_mom", "ang_mom", "kinetic")),   # (the first states have every joint at zero: only the rates differ)
+                                    ("gravity", _cm(c, gravity=-G), ("potential",))):
+            d = _block_errors(moved, base)
+            for k in blocks:
+                assert d[k] > 100 * err32[k], (what, k, d[k], err32[k])
+
+
+# ---------------------------------------------------------------- the Python layer, without a library
+
+class _FakeLib:
+    def __init__(self):
+        self.calls = []
+
+    def bez_sim_centroidal(self, h, state, matrix, stream):
+        self.calls.append((state.value, None if matrix is None else matrix.value))
+        return 0
+
+
+def _bare_sim(n=4):
+    from bez_isaacgym_amd.sim import BezSim
+    s = BezSim.__new__(BezSim)
+    s.lib, s.h, s.num_envs, s.device, s._views = _FakeLib(), None, n, torch.device("cpu"), {}
+    s._stream = lambda: None
+    return s
+
+
+def test_python_argument_errors_and_buffers():
+    from bez_isaacgym_amd.sim import BezSimError
+    n = 4
+    sim = _bare_sim(n)
+    state, matrix = torch.zeros(n, 16), torch.zeros(n, 6, 24)
+    for bad in (dict(state=state[:, :15]), dict(state=state.double()), dict(state=state.t().contiguous().t()), dict(state=state.reshape(-1)),
+                dict(state=state.numpy()), dict(matrix=matrix[:-1]), dict(matrix=matrix.reshape(n, 144)), dict(matrix=matrix.double()),
+                dict(matrix=matrix.transpose(1, 2).contiguous().transpose(1, 2)), dict(matrix=matrix.numpy()),
+                dict(state=state.to("meta")), dict(matrix=matrix.to("meta"))):
+        with pytest.raises(BezSimError):
+            sim.centroidal(**bad)
+    assert sim.lib.calls == []
+    s, m = sim.centroidal()
+    assert m is None and tuple(s.shape) == (n, 16) and s.dtype == torch.float32 and sim.lib.calls[-1] == (s.data_ptr(), None)
+    s2, m2 = sim.centroidal(want_matrix=True)
+    assert s2 is s and tuple(m2.shape) == (n, 6, 24) and sim.lib.calls[-1] == (s.data_ptr(), m2.data_ptr())
+    s3, m3 = sim.centroidal(state, matrix)
+    assert s3 is state and m3 is matrix and sim.lib.calls[-1] == (state.data_ptr(), matrix.data_ptr())
+    assert sim.centroidal(want_matrix=True)[1] is m2       # one buffer of each kind per sim
+
+
+def test_vec_task_wrappers_are_views_of_one_result():
+    from bez_isaacgym_amd.tasks.base.vec_task import VecTask
+
+    class _T(VecTask):
+        def pre_physics_step(self, actions): pass
+        def post_physics_step(self): pass
+    n = 4
+    t = _T.__new__(_T)
+    t.sim = _bare_sim(n)
+    s = t.centroidal_state()
+    s.copy_(torch.arange(n * 16, dtype=torch.float32).view(n, 16))
+    pos, vel = t.center_of_mass()
+    ke, pe = t.mechanical_energy()
+    mom = t.centroidal_momentum()
+    for view, first, width in ((pos, abi.CM_COM, 3), (vel, abi.CM_COM_VEL, 3), (mom, abi.CM_LIN_MOM, 6)):
+        assert tuple(view.shape) == (n, width) and view.data_ptr() == s.data_ptr() + 4 * first and torch.equal(view, s[:, first:first + width])
+    for view, first in ((ke, abi.CM_KINETIC), (pe, abi.CM_POTENTIAL)):
+        assert tuple(view.shape) == (n,) and view.data_ptr() == s.data_ptr() + 4 * first
+    A = t.centroidal_momentum_matrix()
+    assert tuple(A.shape) == (n, 6, 24) and t.sim.lib.calls[-1] == (s.data_ptr(), A.data_ptr())
+    assert len(t.sim.lib.calls) == 5
