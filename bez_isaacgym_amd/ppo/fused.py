@@ -243,7 +243,12 @@ def adam_step(params, grads, exp_avg, exp_avg_sq, steps, lr, betas, eps, weight_
     packed (PackedWeights): its fragment-major copies are written in the same pass (instead of a refresh() launch before the next forward);
     next_rms = (FusedRunningMeanStd, moments): the input normaliser absorbs the NEXT minibatch's moments here (instead of an apply() launch);
     norm_parts: the (blocks, 2) tensor grad_reduce_all() / grad_norm_parts() filled for THIS gradient (norm and non-finite count are then not
-    re-derived); grad_div: the buffer holds the all-reduced SUM over that many ranks (the division rides in the unscale factor)."""
+    re-derived); grad_div: the buffer holds the all-reduced SUM over that many ranks (the division rides in the unscale factor).
+    The three norm modes differ on ONE gradient: finite elements whose squared norm overflows fp32.  With norm_parts or grid_norm the step is skipped
+    like a non-finite one; without either (the launch reads the whole gradient) it is taken with a clip coefficient of max_norm / inf = 0, as
+    torch.nn.utils.clip_grad_norm_ would.  The agent fixes the mode when it plans a run (norm_parts on one GPU, grid_norm or re-formed shares
+    data-parallel, neither without the one-launch reduction), the same on every rank, so the two behaviours never meet within a run or across ranks;
+    tests/test_gpu_ppo_glue_envelope.py pins both."""
     n = params.numel()
     extra = None
     if packed is not None or next_rms is not None or norm_parts is not None or grad_div != 1.0 or grid_norm is not None:
