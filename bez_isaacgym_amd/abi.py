@@ -282,28 +282,25 @@ def config_from_task_cfg(cfg, seed=42, env_id_offset=0, strict_reference_quirks=
     return c
 
 
-def actuator_tensor_id(which):
-    """ACTUATOR_DOF_FORCE / ACTUATOR_DRIVE_TORQUE / ACTUATOR_STATUS from the int or from "dof_force" / "drive_torque" / "status"."""
-    names = {"dof_force": ACTUATOR_DOF_FORCE, "drive_torque": ACTUATOR_DRIVE_TORQUE, "status": ACTUATOR_STATUS}
+def _tensor_id(kind, names, which):
+    """The id of a `kind` tensor from the int or from its name (any case); `names`: the names in id order."""
     if isinstance(which, str):
         if which.strip().lower() not in names:
-            raise ValueError("actuator tensor must be one of %s, got %r" % (sorted(names), which))
-        return names[which.strip().lower()]
-    if isinstance(which, bool) or not isinstance(which, int) or not 0 <= which < ACTUATOR_TENSORS:
-        raise ValueError("actuator tensor id must be in [0, %d), got %r" % (ACTUATOR_TENSORS, which))
+            raise ValueError("%s tensor must be one of %s, got %r" % (kind, sorted(names), which))
+        return names.index(which.strip().lower())
+    if isinstance(which, bool) or not isinstance(which, int) or not 0 <= which < len(names):
+        raise ValueError("%s tensor id must be in [0, %d), got %r" % (kind, len(names), which))
     return int(which)
+
+
+def actuator_tensor_id(which):
+    """ACTUATOR_DOF_FORCE / ACTUATOR_DRIVE_TORQUE / ACTUATOR_STATUS from the int or from "dof_force" / "drive_torque" / "status"."""
+    return _tensor_id("actuator", ("dof_force", "drive_torque", "status"), which)
 
 
 def dynamics_tensor_id(which):
     """DYNAMICS_JACOBIAN / DYNAMICS_MASS_MATRIX from the int or from "jacobian" / "mass_matrix"."""
-    names = {"jacobian": DYNAMICS_JACOBIAN, "mass_matrix": DYNAMICS_MASS_MATRIX}
-    if isinstance(which, str):
-        if which.strip().lower() not in names:
-            raise ValueError("dynamics tensor must be one of %s, got %r" % (sorted(names), which))
-        return names[which.strip().lower()]
-    if isinstance(which, bool) or not isinstance(which, int) or not 0 <= which < DYNAMICS_COUNT:
-        raise ValueError("dynamics tensor id must be in [0, %d), got %r" % (DYNAMICS_COUNT, which))
-    return int(which)
+    return _tensor_id("dynamics", ("jacobian", "mass_matrix"), which)
 
 
 def body_force_space(space):

@@ -1,0 +1,490 @@
+// bez_dynamics.h -- the kernels that run forward kinematics outside the control step (rigid-body refresh, dynamics tensors, inverse and
+// centroidal dynamics, external wrenches) and what they share: DynArgs, tile I/O, the composite-rigid-body sweep.  Included by bez_sim.hip only.
+#pragma once
+#include "bez_kernels.h"
+
+namespace bez {
+
+BEZ_DEV void mat_to_quat(const M3& R, float q[4]) {
+  float tr = R.m00 + R.m11 + R.m22;
+  if (tr > 0.f) {
+    float s = sqrtf(tr + 1.f) * 2.f;
+    q[3] = 0.25f * s; q[0] = (R.m21 - R.m12) / s; q[1] = (R.m02 - R.m20) / s; q[2] = (R.m10 - R.m01) / s;
+  } else if (R.m00 > R.m11 && R.m00 > R.m22) {
+    float s = sqrtf(1.f + R.m00 - R.m11 - R.m22) * 2.f;
+    q[3] = (R.m21 - R.m12) / s; q[0] = 0.25f * s; q[1] = (R.m01 + R.m10) / s; q[2] = (R.m02 + R.m20) / s;
+  } else if (R.m11 > R.m22) {
+    float s = sqrtf(1.f + R.m11 - R.m00 - R.m22) * 2.f;
+    q[3] = (R.m02 - R.m20) / s; q[0] = (R.m01 + R.m10) / s; q[1] = 0.25f * s; q[2] = (R.m12 + R.m21) / s;
+  } else {
+    float s = sqrtf(1.f + R.m22 - R.m00 - R.m11) * 2.f;
+    q[3] = (R.m10 - R.m01) / s; q[0] = (R.m02 + R.m20) / s; q[1] = (R.m12 + R.m21) / s; q[2] = 0.25f * s;
+  }
+}
+
+// Forward kinematics of one env's link frames: orientation E[l] and origin r[l] (relative to the root's position) of every link, and
+// WITH_VEL the spatial velocities V[l] (without: V is scratch, the joints stand still)
+template <bool CL, bool WITH_VEL>
+BEZ_DEV void link_frames(const EnvState& S, uint32_t flags, M3 (&E)[BEZ_NL], V3 (&r)[BEZ_NL], SV (&V)[BEZ_NL]) {
+  E[0] = quat_to_mat(S.rq[0], S.rq[1], S.rq[2], S.rq[3]);
+  r[0] = mk(0, 0, 0);
+  V[0] = WITH_VEL ? mksv(S.root_ang, S.root_lin) : svzero();
+  static_for<BEZ_NL - 1>([&](auto I) {
+    constexpr int L = 1 + decltype(I)::value;
+    constexpr int p = BEZ_LINK_PARENT[L];
+    E[L] = E[p]; r[L] = r[p]; V[L] = V[p];
+    SV Sj, cb;
+    link_kinematics<L>(S.q[L - 1], WITH_VEL ? S.qd[L - 1] : 0.f, E[L], r[L], V[L], Sj, cb, quirk_rz<CL>(flags));
+  });
+}
+// Robot body b of the asset: the link it is fixed to, its origin's offset in that link's frame, its centre of mass in its own frame
+struct BodyFrame { int link; V3 off, com; };
+template <bool CL>
+BEZ_DEV BodyFrame body_frame(int b) {
+  const double* o = CL ? BEZ_BODY_OFFSET_CL[b] : BEZ_BODY_OFFSET[b];
+  const double* c = CL ? BEZ_BODY_COM_CL[b] : BEZ_BODY_COM[b];
+  return {CL ? BEZ_BODY_LINK_CL[b] : BEZ_BODY_LINK[b], mk((float)o[0], (float)o[1], (float)o[2]), mk((float)c[0], (float)c[1], (float)c[2])};
+}
+
+// gym.refresh_rigid_body_state_tensor: forward kinematics of all 21 robot bodies + the ball row
+template <bool CL>
+__global__ void refresh_rigid_body_kernel(const float* __restrict__ st, float* __restrict__ out, int n, int has_ball, uint32_t flags) {
+  int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  EnvState S;
+  load_state(st, n, e, S);
+  M3 E[BEZ_NL]; V3 r[BEZ_NL]; SV V[BEZ_NL];
+  link_frames<CL, true>(S, flags, E, r, V);
+  constexpr int NB = nb_of<CL>();
+  const int nbe = NB + (has_ball ? 1 : 0);
+  static_for<NB>([&](auto I) {
+    const BodyFrame f = body_frame<CL>(decltype(I)::value);
+    const int b = decltype(I)::value, l = f.link;
+    V3 x = r[l] + mul(E[l], f.off);
+    V3 vel = point_of(V[l], x);
+    float q[4];
+    mat_to_quat(E[l], q);
+    float* o = out + ((size_t)e * nbe + b) * 13;
+    o[0] = S.root_pos.x + x.x; o[1] = S.root_pos.y + x.y; o[2] = S.root_pos.z + x.z;
+    o[3] = q[0]; o[4] = q[1]; o[5] = q[2]; o[6] = q[3];
+    o[7] = vel.x; o[8] = vel.y; o[9] = vel.z; o[10] = V[l].a.x; o[11] = V[l].a.y; o[12] = V[l].a.z;
+  });
+  if (!has_ball) return;
+  float* o = out + ((size_t)e * nbe + NB) * 13;
+  o[0] = S.ball_pos.x; o[1] = S.ball_pos.y; o[2] = S.ball_pos.z;
+  o[3] = S.bq[0]; o[4] = S.bq[1]; o[5] = S.bq[2]; o[6] = S.bq[3];
+  o[7] = S.ball_lin.x; o[8] = S.ball_lin.y; o[9] = S.ball_lin.z; o[10] = S.ball_ang.x; o[11] = S.ball_ang.y; o[12] = S.ball_ang.z;
+}
+
+// ---- gym.refresh_jacobian_tensors / gym.refresh_mass_matrix_tensors (definitions: include/bez_sim.h "Dynamics tensors").
+// A workgroup takes DYN_TILE consecutive envs.  Phase 1, one lane per env: forward kinematics, then the world joint axes, the joint
+// origins and the body origins (both relative to the root origin) go to LDS, and -- still in that lane -- the composite-rigid-body
+// recursion in the frame link_inertia already uses (world axes about the root origin: composites add up without transforms) leaves
+// every DISTINCT entry of M in LDS.  Phase 2, all lanes: the tile's output range is contiguous (DYN_TILE x nb x 144 floats of J,
+// DYN_TILE x 576 of M), and each lane forms four consecutive elements from LDS and stores them as one float4, so every store
+// instruction of a wave covers 1 KB of consecutive addresses.  Structural zeros and ones are constants, never computed.
+constexpr int DYN_TILE = 16, DYN_THREADS = 256, DYN_NG = 6 + BEZ_ND;
+constexpr int link_depth(int l) { int d = 0; for (; l > 0; l = BEZ_LINK_PARENT[l]) ++d; return d; }
+constexpr int dyn_pair_base(int l) { int s = 0; for (int k = 1; k < l; ++k) s += link_depth(k); return s; }   // (l, its path to the root) starts here
+constexpr uint32_t link_ancestors(int l) { uint32_t m = 0; for (; l > 0; l = BEZ_LINK_PARENT[l]) m |= 1u << l; return m; }   // bit l' : DOF l' - 1 moves link l
+// LDS words of one env: [axis 18x3][joint origin 18x3][body origin nb x 3][the distinct entries of M]
+constexpr int DYN_AX = 0, DYN_RO = 3 * BEZ_ND, DYN_XB = 6 * BEZ_ND, DYN_MS = DYN_XB + 3 * BEZ_NB_CL;
+// entries of M: 0 the constant zero, total mass, h, -h, Ibar (xx yy zz xy xz yz), F_l = I^c_l S_l as [lin; ang] per joint, S_j . F_l per path pair
+constexpr int MS_ZERO = 0, MS_MASS = 1, MS_H = 2, MS_NH = 5, MS_IBAR = 8, MS_F = 14, MS_PAIR = MS_F + 6 * BEZ_ND, MS_COUNT = MS_PAIR + dyn_pair_base(BEZ_NL);
+constexpr int DYN_STRIDE = (DYN_MS + MS_COUNT) | 1;   // odd: the lanes of phase 1 (one env each) write distinct banks
+struct MassSlots { int16_t s[DYN_NG * DYN_NG]; };
+constexpr MassSlots mass_slots() {
+  MassSlots T = {};
+  for (int i = 0; i < DYN_NG * DYN_NG; ++i) T.s[i] = MS_ZERO;
+  const int ibar[3][3] = {{0, 3, 4}, {3, 1, 5}, {4, 5, 2}};
+  // skew(h) = [[0, -hz, hy], [hz, 0, -hx], [-hy, hx, 0]] as (component, negated)
+  const int sk[3][3] = {{-1, MS_NH + 2, MS_H + 1}, {MS_H + 2, -1, MS_NH + 0}, {MS_NH + 1, MS_H + 0, -1}};
+  for (int r = 0; r < 3; ++r) {
+    T.s[r * DYN_NG + r] = MS_MASS;
+    for (int c = 0; c < 3; ++c) {
+      T.s[(3 + r) * DYN_NG + 3 + c] = (int16_t)(MS_IBAR + ibar[r][c]);
+      if (sk[r][c] >= 0) T.s[(3 + r) * DYN_NG + c] = T.s[c * DYN_NG + 3 + r] = (int16_t)sk[r][c];   // ang row, lin column = skew(h); its transpose
+    }
+  }
+  for (int l = 1; l < BEZ_NL; ++l) {
+    for (int k = 0; k < 6; ++k) T.s[(5 + l) * DYN_NG + k] = T.s[k * DYN_NG + 5 + l] = (int16_t)(MS_F + 6 * (l - 1) + k);
+    int p = MS_PAIR + dyn_pair_base(l);
+    for (int j = l; j > 0; j = BEZ_LINK_PARENT[j], ++p) T.s[(5 + l) * DYN_NG + 5 + j] = T.s[(5 + j) * DYN_NG + 5 + l] = (int16_t)p;
+  }
+  return T;
+}
+__device__ const MassSlots MASS_SLOTS = mass_slots();
+struct BodyAncestors { uint32_t m[BEZ_NB_CL]; };
+template <bool CL> constexpr BodyAncestors body_ancestors() {
+  BodyAncestors T = {};
+  for (int b = 0; b < (CL ? BEZ_NB_CL : BEZ_NB); ++b) T.m[b] = link_ancestors(CL ? BEZ_BODY_LINK_CL[b] : BEZ_BODY_LINK[b]);
+  return T;
+}
+template <bool CL> __device__ const BodyAncestors BODY_ANCESTORS = body_ancestors<CL>();
+
+BEZ_DEV float pick(V3 v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
+BEZ_DEV V3 lds3(const float* p) { return mk(p[0], p[1], p[2]); }
+// J[row][col] of a body with origin x (relative to the root origin) whose link has the ancestor set `mask`; L: the env's LDS words
+BEZ_DEV float jacobian_entry(const float* L, uint32_t mask, V3 x, int row, int col) {
+  if (col < 3) return row == col ? 1.f : 0.f;
+  if (col < 6) {
+    if (row >= 3) return row == col ? 1.f : 0.f;
+    const int c = col - 3;                      // -skew(x) = [[0, z, -y], [-z, 0, x], [y, -x, 0]]
+    if (c == row) return 0.f;
+    const float v = pick(x, 3 - row - c);
+    return ((c - row + 3) % 3 == 1) ? v : -v;
+  }
+  const int d = col - 6;
+  if (!((mask >> (d + 1)) & 1u)) return 0.f;
+  const V3 a = lds3(L + DYN_AX + 3 * d);
+  if (row >= 3) return pick(a, row - 3);
+  return pick(cross(a, x - lds3(L + DYN_RO + 3 * d)), row);
+}
+
+// What the three dynamics kernels are told about the sim (the host's dyn_args): the SoA state, the BEZ_PARAM_MASS_SCALE and BEZ_PARAM_GRAVITY
+// rows they share with the step (null: the defaults) and the config's scalars
+struct DynArgs { const float *st, *mass_scale, *gravity_rows; int n; uint32_t flags; float armature, g[3]; };
+// link l's BEZ_PARAM_MASS_SCALE entry (1 without rows) and the env's BEZ_PARAM_GRAVITY row (the config's vector without rows)
+BEZ_DEV float mass_scale_of(const DynArgs& D, int e, int l) { return D.mass_scale ? D.mass_scale[(size_t)e * BEZ_NL + l] : 1.f; }
+BEZ_DEV V3 gravity_of(const DynArgs& D, int e) {
+  return D.gravity_rows ? mk(D.gravity_rows[(size_t)e * 3], D.gravity_rows[(size_t)e * 3 + 1], D.gravity_rows[(size_t)e * 3 + 2]) : mk(D.g[0], D.g[1], D.g[2]);
+}
+
+// Tile I/O: `nrows` rows of WIDTH floats between LDS (`rows`, STRIDE words apart) and the contiguous global range at `in` / `out`, by a
+// workgroup of THREADS lanes.  Rows are whole float4s, so a range that starts 16-byte aligned moves as float4; any other takes the scalar
+// path to the same bits.
+template <int WIDTH, int STRIDE>
+BEZ_DEV int tile_word(int i) {   // where element i of the global range lives in LDS
+  static_assert(WIDTH % 4 == 0, "whole float4s per row");
+  return (i / WIDTH) * STRIDE + i % WIDTH;
+}
+template <int WIDTH, int STRIDE, int THREADS>
+BEZ_DEV void tile_load(float* rows, const float* __restrict__ in, int nrows) {
+  auto slot = [&](int i) -> float& { return rows[tile_word<WIDTH, STRIDE>(i)]; };
+  if ((reinterpret_cast<uintptr_t>(in) & 15u) == 0) {
+    const float4* in4 = reinterpret_cast<const float4*>(in);
+    for (int i = threadIdx.x; i < nrows * (WIDTH / 4); i += THREADS) {
+      const float4 v = in4[i];
+      slot(4 * i) = v.x; slot(4 * i + 1) = v.y; slot(4 * i + 2) = v.z; slot(4 * i + 3) = v.w;
+    }
+  } else {
+    for (int i = threadIdx.x; i < nrows * WIDTH; i += THREADS) slot(i) = in[i];
+  }
+}
+template <int WIDTH, int STRIDE, int THREADS>
+BEZ_DEV void tile_store(const float* rows, float* __restrict__ out, int nrows) {
+  auto at = [&](int i) { return rows[tile_word<WIDTH, STRIDE>(i)]; };
+  if ((reinterpret_cast<uintptr_t>(out) & 15u) == 0) {
+    float4* o4 = reinterpret_cast<float4*>(out);
+    for (int i = threadIdx.x; i < nrows * (WIDTH / 4); i += THREADS) o4[i] = make_float4(at(4 * i), at(4 * i + 1), at(4 * i + 2), at(4 * i + 3));
+  } else {
+    for (int i = threadIdx.x; i < nrows * WIDTH; i += THREADS) out[i] = at(i);
+  }
+}
+
+// The composite-rigid-body front end of the mass matrix and of the momentum matrix, in the frame link_inertia uses (world axes about the
+// root origin: composites add up without transforms).  link_inertias: every link's own inertia for env e, joints at rest, no gravity;
+// each(l) follows link l's inertia (the centroidal kernel's kinetic energy: summed in a loop of its own it cost 14 VGPRs and 0.1 us).
+// composite_sweep, leaves first: link l is complete when its turn comes; each(l, F_l) sees F_l = I^c_l S_l, S_l = [a; r x a] with
+// a the joint's axis, then the link joins its parent.  Ic[0] ends as the whole robot's inertia.
+BEZ_DEV SV inertia_times(const LinkInertia& I, SV a) {   // I a = [Ibar a.a + h x a.l ; m a.l - h x a.a]
+  return mksv(mul(I.Ibar, a.a) + cross(I.h, a.l), a.l * I.m - cross(I.h, a.a));
+}
+template <bool CL, typename Each>
+BEZ_DEV void link_inertias(const DynArgs& D, int e, const M3 (&E)[BEZ_NL], const V3 (&r)[BEZ_NL], LinkInertia (&Ic)[BEZ_NL], Each&& each) {
+  static_for<BEZ_NL>([&](auto I) {
+    constexpr int l = decltype(I)::value;
+    SV pA;
+    link_inertia<l, CL>(mass_scale_of(D, e, l), mk(0, 0, 0), E[l], r[l], svzero(), Ic[l], pA);
+    each(I);
+  });
+}
+template <typename Each>
+BEZ_DEV void composite_sweep(LinkInertia (&Ic)[BEZ_NL], const M3 (&E)[BEZ_NL], const V3 (&r)[BEZ_NL], Each&& each) {
+  static_for<BEZ_NL - 1>([&](auto I) {
+    constexpr int l = BEZ_NL - 1 - decltype(I)::value, p = BEZ_LINK_PARENT[l];
+    const LinkInertia& C = Ic[l];
+    const V3 a = col(E[l], axis_index(l)) * axis_sign(l);   // the column of the link's frame that the joint rotation leaves alone
+    each(std::integral_constant<int, l>{}, inertia_times(C, mksv(a, cross(r[l], a))));
+    Ic[p].m += C.m; Ic[p].h = Ic[p].h + C.h; add_to(Ic[p].Ibar, C.Ibar);
+  });
+}
+
+template <bool CL>
+__global__ void __launch_bounds__(DYN_THREADS) refresh_dynamics_kernel(DynArgs D, float* __restrict__ J, float* __restrict__ M) {
+  __shared__ float lds[DYN_TILE * DYN_STRIDE];
+  constexpr int NB = nb_of<CL>();
+  const int n = D.n, e0 = blockIdx.x * DYN_TILE, ne = min(DYN_TILE, n - e0);
+  if ((int)threadIdx.x < ne) {
+    const int e = e0 + threadIdx.x;
+    float* L = lds + threadIdx.x * DYN_STRIDE;
+    EnvState S;
+    load_state(D.st, n, e, S);
+    M3 E[BEZ_NL]; V3 r[BEZ_NL]; SV V[BEZ_NL];
+    link_frames<CL, false>(S, D.flags, E, r, V);
+    auto put3 = [&](int at, V3 v) { L[at] = v.x; L[at + 1] = v.y; L[at + 2] = v.z; };
+    static_for<BEZ_ND>([&](auto I) {   // the joint's axis is the column of its link's frame that the joint rotation leaves alone
+      constexpr int l = 1 + decltype(I)::value;
+      put3(DYN_AX + 3 * (l - 1), col(E[l], axis_index(l)) * axis_sign(l));
+      put3(DYN_RO + 3 * (l - 1), r[l]);
+    });
+    static_for<NB>([&](auto I) {
+      const BodyFrame f = body_frame<CL>(decltype(I)::value);
+      put3(DYN_XB + 3 * decltype(I)::value, r[f.link] + mul(E[f.link], f.off));
+    });
+    if (M) {
+      LinkInertia Ic[BEZ_NL];
+      link_inertias<CL>(D, e, E, r, Ic, [](auto) {});
+      float* Ms = L + DYN_MS;
+      composite_sweep(Ic, E, r, [&](auto Lk, SV F) {
+        constexpr int l = decltype(Lk)::value;
+        put3(DYN_MS + MS_F + 6 * (l - 1), F.l);
+        put3(DYN_MS + MS_F + 6 * (l - 1) + 3, F.a);
+        int at = MS_PAIR + dyn_pair_base(l);
+        for (int j = l; j > 0; j = BEZ_LINK_PARENT[j], ++at) {
+          const V3 aj = lds3(L + DYN_AX + 3 * (j - 1)), sj = cross(lds3(L + DYN_RO + 3 * (j - 1)), aj);
+          const float v = dot(aj, F.a) + dot(sj, F.l);
+          Ms[at] = j == l ? v + D.armature : v;
+        }
+      });
+      const LinkInertia& C = Ic[0];
+      Ms[MS_ZERO] = 0.f; Ms[MS_MASS] = C.m;
+      put3(DYN_MS + MS_H, C.h); put3(DYN_MS + MS_NH, -C.h);
+      Ms[MS_IBAR] = C.Ibar.xx; Ms[MS_IBAR + 1] = C.Ibar.yy; Ms[MS_IBAR + 2] = C.Ibar.zz;
+      Ms[MS_IBAR + 3] = C.Ibar.xy; Ms[MS_IBAR + 4] = C.Ibar.xz; Ms[MS_IBAR + 5] = C.Ibar.yz;
+    }
+  }
+  __syncthreads();
+  if (J) {
+    float4* out = reinterpret_cast<float4*>(J + (size_t)e0 * NB * 6 * DYN_NG);
+    const int total = ne * NB * 6 * (DYN_NG / 4);
+    for (int i = threadIdx.x; i < total; i += DYN_THREADS) {
+      const int c4 = i % (DYN_NG / 4), t = i / (DYN_NG / 4), row = t % 6, b = (t / 6) % NB, el = t / (6 * NB);
+      const float* L = lds + el * DYN_STRIDE;
+      const uint32_t mask = BODY_ANCESTORS<CL>.m[b];
+      const V3 x = lds3(L + DYN_XB + 3 * b);
+      out[i] = make_float4(jacobian_entry(L, mask, x, row, 4 * c4), jacobian_entry(L, mask, x, row, 4 * c4 + 1),
+                           jacobian_entry(L, mask, x, row, 4 * c4 + 2), jacobian_entry(L, mask, x, row, 4 * c4 + 3));
+    }
+  }
+  if (M) {
+    float4* out = reinterpret_cast<float4*>(M + (size_t)e0 * DYN_NG * DYN_NG);
+    constexpr int PER_ENV = DYN_NG * DYN_NG / 4;
+    for (int i = threadIdx.x; i < ne * PER_ENV; i += DYN_THREADS) {
+      const float* Ms = lds + (i / PER_ENV) * DYN_STRIDE + DYN_MS;
+      const int16_t* sl = MASS_SLOTS.s + 4 * (i % PER_ENV);
+      out[i] = make_float4(Ms[sl[0]], Ms[sl[1]], Ms[sl[2]], Ms[sl[3]]);
+    }
+  }
+}
+
+// ---- bez_sim_inverse_dynamics (definition: include/bez_sim.h "Inverse dynamics"): recursive Newton-Euler in the frame every bias force
+// here uses (world axes about the root origin), where a subtree's wrench is the plain sum of its links' wrenches.
+// A workgroup is ONE wave and takes ID_TILE consecutive envs.  All lanes bring the tile's udot rows -- one contiguous range -- into LDS
+// (tile_load); then one lane per env walks the tree CHAIN BY CHAIN: out along a chain (two legs of 6 joints, two arms and the head
+// of 2) keeping per joint only S = [a; r x a] and handing the link's acceleration down, back along it adding up the wrenches and emitting
+// tau = S . F into the udot slot it has just consumed, and the chain's total joins the torso's wrench.  At most six links are live,
+// never the 19 frames of link_frames.  Last, all lanes write the tile's rows as one contiguous range of float4 stores.
+// A term is dropped by zeroing its input (udot, the velocities, g): one code path, and the dropped term's products are exact zeros.
+// The chains are taken last to first and each is summed from its leaf, the order in which refresh_dynamics_kernel adds up the masses.
+constexpr int ID_TILE = 16, ID_THREADS = 64, ID_STRIDE = DYN_NG + 1;   // odd row stride: the lanes' own rows start in distinct LDS banks
+template <int FIRST, int LEN> constexpr bool is_chain() {
+  if (BEZ_LINK_PARENT[FIRST] != 0) return false;
+  for (int i = 1; i < LEN; ++i) if (BEZ_LINK_PARENT[FIRST + i] != FIRST + i - 1) return false;
+  return FIRST + LEN == BEZ_NL || BEZ_LINK_PARENT[FIRST + LEN] == 0;
+}
+// One link of a chain and, by recursion, the links below it: on the way out the link's frame, velocity and accelerations from its
+// parent's (by value: each level keeps its own) and its own wrenches; on the way back tau = S . F goes to U[5 + L], the slot whose udot
+// the way out consumed, and the subtree's wrenches are returned.  (Plain locals per level, no arrays over the links: the compiler keeps
+// arrays of spatial vectors live as whole register blocks for all five chains at once.)
+// The three terms are carried APART -- the acceleration as aI (from udot) and aV (velocity products), the wrench as i = I aI,
+// v = I aV + v x* I v and g = -I [0; g] -- and meet only in the last two additions of every output element: the wrenches that cancel
+// along a chain to a small joint torque are then rounded within their own term, a term's value does not depend on which other terms
+// were asked for, and all terms together are the fp32 sum (inertia + velocity) + gravity of the three single-term results.
+struct IdCtx { const DynArgs& D; int e; bool vel; float quirk_z; V3 g; };
+struct IdWrench { SV i, v, g; };
+BEZ_DEV IdWrench operator+(const IdWrench& a, const IdWrench& b) { return {a.i + b.i, a.v + b.v, a.g + b.g}; }
+BEZ_DEV IdWrench id_wrench(const LinkInertia& I, SV aI, SV aV, SV pV, V3 g) {
+  return {inertia_times(I, aI), inertia_times(I, aV) + pV, mksv(-cross(I.h, g), -(g * I.m))};
+}
+BEZ_DEV float id_sum(float i, float v, float g) { return (i + v) + g; }
+template <int L, int END, bool CL>
+BEZ_DEV IdWrench id_links(const IdCtx& C, M3 E, V3 r, SV V, SV aI, SV aV, float* U) {
+  const float q = C.D.st[(size_t)(F_Q + L - 1) * C.D.n + C.e], qd = C.vel ? C.D.st[(size_t)(F_QD + L - 1) * C.D.n + C.e] : 0.f, qdd = U[5 + L];
+  SV S, cb;
+  link_kinematics<L>(q, qd, E, r, V, S, cb, C.quirk_z);
+  aI = aI + S * qdd; aV = aV + cb;
+  LinkInertia LI; SV pV;
+  link_inertia<L, CL>(mass_scale_of(C.D, C.e, L), mk(0, 0, 0), E, r, V, LI, pV);
+  IdWrench F = id_wrench(LI, aI, aV, pV, C.g);
+  if constexpr (L + 1 < END) F = F + id_links<L + 1, END, CL>(C, E, r, V, aI, aV, U);
+  U[5 + L] = id_sum(fmaf(C.D.armature, qdd, dot(S, F.i)), dot(S, F.v), dot(S, F.g));
+  return F;
+}
+template <bool CL>
+__global__ void __launch_bounds__(ID_THREADS) inverse_dynamics_kernel(DynArgs D, const float* __restrict__ udot, float* __restrict__ out, uint32_t terms) {
+  __shared__ float rows[ID_TILE * ID_STRIDE];
+  const float* st = D.st;
+  const int n = D.n, e0 = blockIdx.x * ID_TILE, ne = min(ID_TILE, n - e0);
+  if (udot && (terms & BEZ_ID_INERTIA)) {
+    tile_load<DYN_NG, ID_STRIDE, ID_THREADS>(rows, udot + (size_t)e0 * DYN_NG, ne);
+  } else {
+    for (int i = threadIdx.x; i < ne * DYN_NG; i += ID_THREADS) rows[tile_word<DYN_NG, ID_STRIDE>(i)] = 0.f;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < ne) {
+    const int e = e0 + threadIdx.x;
+    float* U = rows + threadIdx.x * ID_STRIDE;
+    auto ld = [&](int f) { return st[(size_t)f * n + e]; };
+    const bool vel = (terms & BEZ_ID_VELOCITY) != 0;
+    const M3 E0 = quat_to_mat(ld(F_ROOT_QUAT), ld(F_ROOT_QUAT + 1), ld(F_ROOT_QUAT + 2), ld(F_ROOT_QUAT + 3));
+    const SV V0 = vel ? mksv(mk(ld(F_ROOT_ANG), ld(F_ROOT_ANG + 1), ld(F_ROOT_ANG + 2)), mk(ld(F_ROOT_LIN), ld(F_ROOT_LIN + 1), ld(F_ROOT_LIN + 2))) : svzero();
+    V3 g = mk(0, 0, 0);
+    if (terms & BEZ_ID_GRAVITY) g = gravity_of(D, e);
+    // spatial acceleration of the torso about the (momentarily fixed) point its origin passes through: [wdot; vdot - w x v]
+    const SV aI0 = mksv(mk(U[3], U[4], U[5]), mk(U[0], U[1], U[2])), aV0 = mksv(mk(0, 0, 0), -cross(V0.a, V0.l));
+    LinkInertia I0; SV pV0;
+    link_inertia<0, CL>(mass_scale_of(D, e, 0), mk(0, 0, 0), E0, mk(0, 0, 0), V0, I0, pV0);
+    IdWrench F0 = id_wrench(I0, aI0, aV0, pV0, g);
+    // (the env index is made opaque per chain, together with the wrench so far: otherwise every chain's loads are issued up front and
+    // the five chains are interleaved, at the price of their registers)
+    IdCtx C = {D, e, vel, quirk_rz<CL>(D.flags), g};
+    auto chain = [&](auto first, auto len) {
+      constexpr int FIRST = decltype(first)::value, LEN = decltype(len)::value;
+      static_assert(is_chain<FIRST, LEN>(), "not a chain off the torso");
+      asm volatile("" : "+v"(C.e), "+v"(F0.i.l.x));
+      F0 = F0 + id_links<FIRST, FIRST + LEN, CL>(C, E0, mk(0, 0, 0), V0, aI0, aV0, U);
+    };
+    using std::integral_constant;
+    chain(integral_constant<int, 13>{}, integral_constant<int, 6>{});
+    chain(integral_constant<int, 11>{}, integral_constant<int, 2>{});
+    chain(integral_constant<int, 5>{}, integral_constant<int, 6>{});
+    chain(integral_constant<int, 3>{}, integral_constant<int, 2>{});
+    chain(integral_constant<int, 1>{}, integral_constant<int, 2>{});
+    U[0] = id_sum(F0.i.l.x, F0.v.l.x, F0.g.l.x); U[1] = id_sum(F0.i.l.y, F0.v.l.y, F0.g.l.y); U[2] = id_sum(F0.i.l.z, F0.v.l.z, F0.g.l.z);
+    U[3] = id_sum(F0.i.a.x, F0.v.a.x, F0.g.a.x); U[4] = id_sum(F0.i.a.y, F0.v.a.y, F0.g.a.y); U[5] = id_sum(F0.i.a.z, F0.v.a.z, F0.g.a.z);
+  }
+  __syncthreads();
+  tile_store<DYN_NG, ID_STRIDE, ID_THREADS>(rows, out + (size_t)e0 * DYN_NG, ne);
+}
+
+// ---- bez_sim_centroidal (definition: include/bez_sim.h "Centroidal dynamics"): the composite-rigid-body sums of refresh_dynamics_kernel
+// stopped at rows 0:6 of M -- no path-pair products -- with the moment shifted from the root origin to the centre of mass.
+// A workgroup is ONE wave and takes CM_TILE consecutive envs.  Phase 1, one lane per env, in world axes about the root origin (where the
+// LinkInertia composites add up without transforms): forward kinematics with velocities, the links' inertias, then links 18 -> 1: F_l =
+// I^c_l S_l as [lin; ang] -- column 6 + l - 1 of the momentum map about the root origin -- goes to the env's LDS row where A_G has it, and
+// the composite joins its parent's.  With I^c_0 = {m, h, Ibar} the centre of mass is c = h / m; a second pass over the columns takes
+// c x (linear rows) off the angular rows and adds up the momentum A_G u on the way.  The base block is written from its definition:
+// m I, -skew(h), the constant 0 and I_G = Ibar - m (|c|^2 I - c c^T), six values for nine slots.
+// The kinetic energy is the sum over links of 1/2 V_l . I_l V_l with the link's OWN inertia and spatial velocity (+ 1/2 armature |qd|^2):
+// 19 non-negative terms, equal to 1/2 u^T M u, without the subtree sums that the rows 6:24 of M u would need.
+// Phase 2, all lanes: the tile's rows are two contiguous ranges (CM_TILE x 16 floats of state, CM_TILE x 144 of matrix), stored as float4
+// (pointers that are not 16-byte aligned: a scalar path to the same bits).  Rows of CM_STRIDE words, odd: the lanes of phase 1 write
+// distinct banks.
+constexpr int CM_TILE = 16, CM_THREADS = 64, CM_MATRIX = 6 * DYN_NG, CM_STRIDE = (BEZ_CM_WORDS + CM_MATRIX) | 1;
+template <bool CL>
+__global__ void __launch_bounds__(CM_THREADS) centroidal_kernel(DynArgs D, float* __restrict__ state_out, float* __restrict__ matrix_out) {
+  __shared__ float lds[CM_TILE * CM_STRIDE];
+  const int n = D.n, e0 = blockIdx.x * CM_TILE, ne = min(CM_TILE, n - e0);
+  if ((int)threadIdx.x < ne) {
+    const int e = e0 + threadIdx.x;
+    float* W = lds + threadIdx.x * CM_STRIDE;   // the env's state words
+    float* A = W + BEZ_CM_WORDS;                // its A_G, 6 x 24 row-major
+    auto put_col = [&](int row0, int c, V3 v) { A[row0 * DYN_NG + c] = v.x; A[(row0 + 1) * DYN_NG + c] = v.y; A[(row0 + 2) * DYN_NG + c] = v.z; };
+    auto get_col = [&](int row0, int c) { return mk(A[row0 * DYN_NG + c], A[(row0 + 1) * DYN_NG + c], A[(row0 + 2) * DYN_NG + c]); };
+    EnvState S;
+    load_state(D.st, n, e, S);
+    M3 E[BEZ_NL]; V3 r[BEZ_NL]; SV V[BEZ_NL];
+    link_frames<CL, true>(S, D.flags, E, r, V);
+    LinkInertia Ic[BEZ_NL];
+    float ke2 = 0.f;   // twice the kinetic energy
+    link_inertias<CL>(D, e, E, r, Ic, [&](auto I) { constexpr int l = decltype(I)::value; ke2 += dot(V[l], inertia_times(Ic[l], V[l])); });
+    float qd2 = 0.f;
+    composite_sweep(Ic, E, r, [&](auto Lk, SV F) {
+      constexpr int l = decltype(Lk)::value;
+      put_col(0, 5 + l, F.l);
+      put_col(3, 5 + l, F.a);
+      qd2 = fmaf(S.qd[l - 1], S.qd[l - 1], qd2);
+    });
+    const LinkInertia& C = Ic[0];
+    const float m = C.m;
+    const V3 h = C.h, c = mk(h.x / m, h.y / m, h.z / m), w = S.root_ang;
+    Sym3 G;   // I_G = Ibar - m (|c|^2 I - c c^T): each of the six values is formed once and written to both triangles
+    G.xx = C.Ibar.xx - fmaf(h.y, c.y, h.z * c.z); G.yy = C.Ibar.yy - fmaf(h.x, c.x, h.z * c.z); G.zz = C.Ibar.zz - fmaf(h.x, c.x, h.y * c.y);
+    G.xy = fmaf(h.x, c.y, C.Ibar.xy); G.xz = fmaf(h.x, c.z, C.Ibar.xz); G.yz = fmaf(h.y, c.z, C.Ibar.yz);
+    put_col(0, 0, mk(m, 0.f, 0.f)); put_col(0, 1, mk(0.f, m, 0.f)); put_col(0, 2, mk(0.f, 0.f, m));
+    put_col(0, 3, mk(0.f, -h.z, h.y)); put_col(0, 4, mk(h.z, 0.f, -h.x)); put_col(0, 5, mk(-h.y, h.x, 0.f));   // -skew(h) = -m skew(c)
+    put_col(3, 0, mk(0, 0, 0)); put_col(3, 1, mk(0, 0, 0)); put_col(3, 2, mk(0, 0, 0));
+    put_col(3, 3, mk(G.xx, G.xy, G.xz)); put_col(3, 4, mk(G.xy, G.yy, G.yz)); put_col(3, 5, mk(G.xz, G.yz, G.zz));
+    // the momentum A_G u: the base columns (their structural zeros skipped), then the joints'
+    V3 P = S.root_lin * m - cross(h, w), L = mul(G, w);
+    static_for<BEZ_ND>([&](auto I) {
+      constexpr int d = decltype(I)::value;
+      const V3 Fl = get_col(0, 6 + d), Fg = get_col(3, 6 + d) - cross(c, Fl);
+      put_col(3, 6 + d, Fg);
+      P = fma3(Fl, S.qd[d], P);
+      L = fma3(Fg, S.qd[d], L);
+    });
+    const V3 g = gravity_of(D, e), com = S.root_pos + c;
+    W[BEZ_CM_COM] = com.x; W[BEZ_CM_COM + 1] = com.y; W[BEZ_CM_COM + 2] = com.z;
+    // (x + 0.0f is x except that it turns -0.0 into +0.0: a state at rest and a zero gravity row give zeros to the bit)
+    P = P + mk(0.f, 0.f, 0.f); L = L + mk(0.f, 0.f, 0.f);
+    W[BEZ_CM_COM_VEL] = P.x / m; W[BEZ_CM_COM_VEL + 1] = P.y / m; W[BEZ_CM_COM_VEL + 2] = P.z / m;
+    W[BEZ_CM_LIN_MOM] = P.x; W[BEZ_CM_LIN_MOM + 1] = P.y; W[BEZ_CM_LIN_MOM + 2] = P.z;
+    W[BEZ_CM_ANG_MOM] = L.x; W[BEZ_CM_ANG_MOM + 1] = L.y; W[BEZ_CM_ANG_MOM + 2] = L.z;
+    W[BEZ_CM_MASS] = m;
+    W[BEZ_CM_KINETIC] = 0.5f * fmaf(D.armature, qd2, ke2) + 0.f;
+    W[BEZ_CM_POTENTIAL] = 0.f - m * dot(g, com);
+    W[15] = 0.f;
+  }
+  __syncthreads();
+  if (state_out) tile_store<BEZ_CM_WORDS, CM_STRIDE, CM_THREADS>(lds, state_out + (size_t)e0 * BEZ_CM_WORDS, ne);
+  if (matrix_out) tile_store<CM_MATRIX, CM_STRIDE, CM_THREADS>(lds + BEZ_CM_WORDS, matrix_out + (size_t)e0 * CM_MATRIX, ne);
+}
+
+// ---- bez_sim_apply_body_forces: one thread per env turns the Isaac-layout inputs of its env into the pending per-link wrenches (bez_kernels.h
+// ext_wrench): forward kinematics of the current state for the link frames, LOCAL vectors and every point of application resolved now,
+// fixed bodies folded into their links, everything ADDED to what earlier calls left (read-modify-write by the env's one thread).
+template <bool CL>
+__global__ void ext_prepare_kernel(const float* __restrict__ st, float* __restrict__ ext, const float* __restrict__ F, const float* __restrict__ T,
+                                   const float* __restrict__ X, int local, int n, int has_ball, uint32_t flags) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  EnvState S;
+  load_state(st, n, e, S);
+  M3 E[BEZ_NL]; V3 r[BEZ_NL]; SV V[BEZ_NL];
+  link_frames<CL, false>(S, flags, E, r, V);
+  constexpr int NB = nb_of<CL>();
+  const int nbe = NB + (has_ball ? 1 : 0);
+  bool any = false;
+  // adds (force fw, torque tw, point p in the frame of link l) to link l's entries
+  auto add = [&](int l, V3 fw, V3 tw, V3 p) {
+    float* x = ext + (size_t)l * EXT_COMP * n + e;
+    const float v[EXT_COMP] = {fw.x, fw.y, fw.z, tw.x, tw.y, tw.z, p.x * fw.x, p.x * fw.y, p.x * fw.z, p.y * fw.x, p.y * fw.y, p.y * fw.z,
+                               p.z * fw.x, p.z * fw.y, p.z * fw.z};
+#pragma unroll
+    for (int k = 0; k < EXT_COMP; ++k) x[(size_t)k * n] += v[k];
+  };
+  auto in3 = [&](const float* a, int b) { const float* q = a + ((size_t)e * nbe + b) * 3; return mk(q[0], q[1], q[2]); };
+  for (int b = 0; b < nbe; ++b) {
+    const V3 f = F ? in3(F, b) : mk(0, 0, 0), t = T ? in3(T, b) : mk(0, 0, 0);
+    if (!(f.x != 0.f || f.y != 0.f || f.z != 0.f || t.x != 0.f || t.y != 0.f || t.z != 0.f)) continue;   // (a NaN is != 0: it goes in)
+    any = true;
+    if (b < NB) {   // a robot body: its link's frame, its origin's offset in that frame, its own centre of mass
+      const BodyFrame bf = body_frame<CL>(b);
+      const int l = bf.link;
+      V3 p;
+      if (!X) p = bf.off + bf.com;
+      else if (local) p = bf.off + in3(X, b);
+      else p = mulT(E[l], in3(X, b) - S.root_pos - r[l]);
+      add(l, local ? mul(E[l], f) : f, local ? mul(E[l], t) : t, p);
+    } else {        // the ball: its own frame about its centre
+      const M3 Rb = quat_to_mat(S.bq[0], S.bq[1], S.bq[2], S.bq[3]);
+      const V3 p = !X ? mk(0, 0, 0) : (local ? in3(X, b) : mulT(Rb, in3(X, b) - S.ball_pos));
+      add(BEZ_NL, local ? mul(Rb, f) : f, local ? mul(Rb, t) : t, p);
+    }
+  }
+  if (any) ext[(size_t)EXT_FLAG * n + e] = 1.f;
+}
+
+}  // namespace bez

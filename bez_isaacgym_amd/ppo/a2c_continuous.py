@@ -19,6 +19,7 @@ behaviour and anchored on the YAML keys and on the shipped checkpoint's tensor n
 Checkpoints keep rl_games' key layout (model / running_mean_std / reward_mean_std / optimizer / epoch / frame /
 last_mean_rewards) as evidenced by results/Bez_Kick/Normal/Bez_Kick_33.pth.
 """
+import gc
 import math
 import os
 import time
@@ -1350,8 +1351,16 @@ class A2CAgent:
         """body() recorded as one HIP graph, in the pool all graphs of this agent share"""
         self._pool = self._pool or torch.cuda.graph_pool_handle()
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, pool=self._pool):
-            body()
+        # no garbage collection while the stream captures: a pass that finds a dead agent or sim of this process (reference cycles keep
+        # them until one) runs their finalizers -- hipFree, graph and pool destruction -- in the middle of the capture, which aborts
+        gc_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(g, pool=self._pool):
+                body()
+        finally:
+            if gc_on:
+                gc.enable()
         return g
 
     def calc_gradients(self, mb, kl_out, loss_out, next_i=None):

@@ -145,6 +145,21 @@ class BezSim:
             raise BezSimError("expected %d elements, got %d" % (numel, t.numel()))
         return C.c_void_p(t.data_ptr())
 
+    def _checked(self, name, t, shapes):
+        """t, once it is known to be a torch tensor of one of `shapes`"""
+        if not isinstance(t, torch.Tensor):
+            raise BezSimError("%s: expected a torch tensor, got %s" % (name, type(t).__name__))
+        if tuple(t.shape) not in shapes:
+            raise BezSimError("%s: expected shape %s, got %s" % (name, " or ".join(str(s) for s in shapes), tuple(t.shape)))
+        return t
+
+    def _scratch(self, key, shape):
+        """the sim's own float32 result buffer `key`: allocated by the first call that needs it, overwritten by every later one"""
+        bufs = self.__dict__.setdefault("_buffers", {})
+        if key not in bufs:
+            bufs[key] = torch.zeros(shape, device=self.device, dtype=torch.float32)
+        return bufs[key]
+
     def _describe(self, getter, which):
         """(device pointer, shape, typestr) of a sim-owned buffer"""
         p, shape, nd, dt = C.c_void_p(), (C.c_int64 * 3)(), C.c_int(), C.c_int()
@@ -222,16 +237,10 @@ class BezSim:
         every later one.  One launch on the current stream."""
         shape = (self.num_envs, abi.NUM_GEN)
         for name, t in (("udot", udot), ("out", out)):
-            if t is None:
-                continue
-            if not isinstance(t, torch.Tensor):
-                raise BezSimError("%s: expected a torch tensor, got %s" % (name, type(t).__name__))
-            if tuple(t.shape) != shape:
-                raise BezSimError("%s: expected shape %s, got %s" % (name, shape, tuple(t.shape)))
+            if t is not None:
+                self._checked(name, t, (shape,))
         if out is None:
-            if getattr(self, "_id_out", None) is None:
-                self._id_out = torch.zeros(shape, device=self.device, dtype=torch.float32)
-            out = self._id_out
+            out = self._scratch("inverse_dynamics", shape)
         n = shape[0] * shape[1]
         self._check(self.lib.bez_sim_inverse_dynamics(self.h, None if udot is None else self._ptr(udot, torch.float32, n), int(terms),
                                                       self._ptr(out, torch.float32, n), self._stream()))
@@ -247,20 +256,12 @@ class BezSim:
         call that needs it and overwritten by every later one."""
         shapes = {"state": (self.num_envs, abi.CM_WORDS), "matrix": (self.num_envs, 6, abi.NUM_GEN)}
         for name, t in (("state", state), ("matrix", matrix)):
-            if t is None:
-                continue
-            if not isinstance(t, torch.Tensor):
-                raise BezSimError("%s: expected a torch tensor, got %s" % (name, type(t).__name__))
-            if tuple(t.shape) != shapes[name]:
-                raise BezSimError("%s: expected shape %s, got %s" % (name, shapes[name], tuple(t.shape)))
+            if t is not None:
+                self._checked(name, t, (shapes[name],))
         if state is None:
-            if getattr(self, "_cm_state", None) is None:
-                self._cm_state = torch.zeros(shapes["state"], device=self.device, dtype=torch.float32)
-            state = self._cm_state
+            state = self._scratch("centroidal_state", shapes["state"])
         if matrix is None and want_matrix:
-            if getattr(self, "_cm_matrix", None) is None:
-                self._cm_matrix = torch.zeros(shapes["matrix"], device=self.device, dtype=torch.float32)
-            matrix = self._cm_matrix
+            matrix = self._scratch("centroidal_matrix", shapes["matrix"])
         self._check(self.lib.bez_sim_centroidal(self.h, self._ptr(state, torch.float32, state.numel()),
                                                 None if matrix is None else self._ptr(matrix, torch.float32, matrix.numel()), self._stream()))
         return state, matrix
@@ -308,18 +309,9 @@ class BezSim:
         Each tensor: float32 on the sim's device, contiguous, (N*B, 3) or (N, B, 3) in RIGID_BODY_STATE order, or None.  `space`:
         abi.SPACE_ENV / abi.SPACE_LOCAL or "env" / "local".  Everything is checked before the library is called."""
         space = abi.body_force_space(space)
-        n = self.num_envs * self.num_bodies * 3
-        ptrs = []
-        for name, t in (("forces", forces), ("torques", torques), ("positions", positions)):
-            if t is None:
-                ptrs.append(None)
-                continue
-            if not isinstance(t, torch.Tensor):
-                raise BezSimError("%s: expected a torch tensor, got %s" % (name, type(t).__name__))
-            if tuple(t.shape) not in ((self.num_envs * self.num_bodies, 3), (self.num_envs, self.num_bodies, 3)):
-                raise BezSimError("%s: expected shape (%d, 3) or (%d, %d, 3), got %s" % (name, self.num_envs * self.num_bodies, self.num_envs,
-                                                                                         self.num_bodies, tuple(t.shape)))
-            ptrs.append(self._ptr(t, torch.float32, n))
+        n, nb = self.num_envs, self.num_bodies
+        ptrs = [None if t is None else self._ptr(self._checked(name, t, ((n * nb, 3), (n, nb, 3))), torch.float32, n * nb * 3)
+                for name, t in (("forces", forces), ("torques", torques), ("positions", positions))]
         self._check(self.lib.bez_sim_apply_body_forces(self.h, ptrs[0], ptrs[1], ptrs[2], space, self._stream()))
 
     # ---- the non-finite guard (abi.FLAG_NONFINITE_GUARD)

@@ -1,11 +1,20 @@
-"""Times bez_sim_refresh_dynamics_tensors (the Jacobian, the mass matrix, both) at num_envs = 4096 beside a plain device fill of the
-same bytes in the same run -- the kernel is store-bound by construction, so the fill is its yardstick.
+"""Times one of the dynamics queries at num_envs = 4096 beside its yardsticks in the same run.  Prints one JSON line.
+
+  python tools/dynamics_bench.py {tensors,inverse_dynamics,centroidal} [--num-envs 4096] [--launches 200] [--warmup 20] [--cleats]
+  python tools/dynamics_bench.py inverse_dynamics > profiles/inverse_dynamics_bench.json      (the committed records)
+  python tools/dynamics_bench.py centroidal > profiles/centroidal_bench.json
+
+tensors: bez_sim_refresh_dynamics_tensors (the Jacobian, the mass matrix, both) beside a plain device fill of the same bytes -- the kernel
+is store-bound by construction, so the fill (hipMemsetAsync over the very buffer the refresh writes) is its yardstick.
+inverse_dynamics: bez_sim_inverse_dynamics (all terms; gravity only) beside refresh_rigid_body_state -- the same per-lane forward
+kinematics -- and the route the call replaces: a mass-matrix refresh followed by torch.bmm(M, udot).
+centroidal: bez_sim_centroidal (both outputs; the state alone) beside bez_sim_inverse_dynamics with all terms -- the neighbour of the same
+shape -- and the route the call replaces: a mass-matrix refresh followed by the torch ops that rebuild the 16 + 144 numbers per env from M
+and u (rows 0:6 of M times u, the centre of mass un-skewed from M[0:3, 3:6], the moment shifted to it, 1/2 u^T M u).  The replaced route
+is handed u and the root positions ready-made: refreshing them is not counted against it.
 
 Each figure is the median over --launches (>= 200) single launches, each between its own pair of events on one stream, after --warmup
-launches; the fill is hipMemsetAsync over the very buffer the refresh writes, timed the same way.  Nothing flushes the caches between
-launches, for the refresh and the fill alike.  Prints one JSON line.
-
-  python tools/dynamics_bench.py [--num-envs 4096] [--launches 200] [--warmup 20] [--cleats]
+launches.  Nothing flushes the caches between launches, for a call and its yardsticks alike.
 """
 import argparse
 import ctypes as C
@@ -19,6 +28,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bez_isaacgym_amd import abi  # noqa: E402
 from bez_isaacgym_amd.sim import BezSim  # noqa: E402
+
+DEV = "cuda:0"
 
 
 def timed(fn, launches, warmup):
@@ -35,8 +46,105 @@ def timed(fn, launches, warmup):
     return {"median_us": round(statistics.median(us), 2), "min_us": round(us[0], 2), "p90_us": round(us[int(0.9 * len(us))], 2)}
 
 
+def tensors(sim, n, t):
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemsetAsync.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
+    hip.hipMemsetAsync.restype = C.c_int
+    sim.step(torch.zeros(n * 18, device=DEV))   # a state off the reset pose
+    J, M = sim.dynamics_tensor("jacobian"), sim.dynamics_tensor("mass_matrix")
+
+    def fill(*bufs):
+        def run():
+            for b in bufs:
+                assert hip.hipMemsetAsync(C.c_void_p(b.data_ptr()), 0, b.numel() * 4, C.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
+        return run
+
+    res = {"bytes": {"jacobian": J.numel() * 4, "mass_matrix": M.numel() * 4}}
+    for name, which, bufs in (("jacobian", ["jacobian"], (J,)), ("mass_matrix", ["mass_matrix"], (M,)), ("both", ["jacobian", "mass_matrix"], (J, M))):
+        r, f = t(lambda: sim.refresh_dynamics_tensors(which)), t(fill(*bufs))
+        nbytes = sum(b.numel() * 4 for b in bufs)
+        res[name] = {"refresh": r, "fill": f, "ratio": round(r["median_us"] / f["median_us"], 3),
+                     "refresh_GBps": round(nbytes / r["median_us"] / 1e3, 1), "fill_GBps": round(nbytes / f["median_us"] / 1e3, 1)}
+    sim.refresh_dynamics_tensors()
+    torch.cuda.synchronize()
+    assert torch.isfinite(J).all() and torch.isfinite(M).all()
+    return res
+
+
+def inverse_dynamics(sim, n, t):
+    sim.step(torch.zeros(n * 18, device=DEV))   # a state off the reset pose
+    udot = torch.rand(n, abi.NUM_GEN, device=DEV) * 20 - 10
+    out = torch.zeros(n, abi.NUM_GEN, device=DEV)
+    M = sim.dynamics_tensor("mass_matrix")
+    mu = torch.zeros(n, abi.NUM_GEN, 1, device=DEV)
+
+    def replaced():
+        sim.refresh_dynamics_tensors("mass_matrix")
+        torch.bmm(M, udot.unsqueeze(2), out=mu)
+
+    res = {"inverse_dynamics_all_terms": t(lambda: sim.inverse_dynamics(udot, abi.ID_ALL, out)),
+           "inverse_dynamics_gravity_only": t(lambda: sim.inverse_dynamics(None, abi.ID_GRAVITY, out)),
+           "refresh_rigid_body_state": t(lambda: sim.refresh(abi.TENSOR_RIGID_BODY_STATE)),
+           "mass_matrix_refresh_plus_bmm": t(replaced)}
+    res["ratio_to_rigid_body_refresh"] = round(res["inverse_dynamics_all_terms"]["median_us"] / res["refresh_rigid_body_state"]["median_us"], 3)
+    res["ratio_to_replaced_route"] = round(res["inverse_dynamics_all_terms"]["median_us"] / res["mass_matrix_refresh_plus_bmm"]["median_us"], 3)
+    # the two routes agree on the inertia term
+    sim.inverse_dynamics(udot, abi.ID_INERTIA, out)
+    replaced()
+    torch.cuda.synchronize()
+    res["max_abs_difference_of_the_inertia_term"] = float((out - mu[:, :, 0]).abs().max())
+    assert torch.isfinite(out).all()
+    return res
+
+
+def centroidal(sim, n, t):
+    sim.step(torch.rand(n * 18, device=DEV) * 2 - 1)   # a state off the reset pose, in motion
+    state = torch.zeros(n, abi.CM_WORDS, device=DEV)
+    matrix = torch.zeros(n, 6, abi.NUM_GEN, device=DEV)
+    udot = torch.rand(n, abi.NUM_GEN, device=DEV) * 20 - 10
+    out = torch.zeros(n, abi.NUM_GEN, device=DEV)
+    M = sim.dynamics_tensor("mass_matrix")
+    root = sim.refresh(abi.TENSOR_ROOT_STATE).view(n, sim.num_actors, 13)[:, 0].clone()
+    qd = sim.refresh(abi.TENSOR_DOF_STATE).view(n, abi.NUM_DOFS, 2)[:, :, 1]
+    u = torch.cat([root[:, 7:13], qd], dim=1).contiguous()
+    g = torch.tensor(list(sim.cfg.gravity), device=DEV)
+    route = {}
+
+    def replaced():
+        sim.refresh_dynamics_tensors("mass_matrix")
+        B = M[:, 0:6, :]                                                    # the momentum map about the root origin
+        mom = torch.bmm(B, u.unsqueeze(2))[:, :, 0]
+        m = M[:, 0, 0]
+        c = torch.stack([M[:, 1, 5], M[:, 2, 3], M[:, 0, 4]], dim=1) / m[:, None]   # M[0:3, 3:6] = -m skew(c)
+        A = B.clone()
+        A[:, 3:6, :] -= torch.cross(c[:, :, None].expand(-1, -1, abi.NUM_GEN), B[:, 0:3, :], dim=1)
+        p = mom[:, 0:3]
+        ang = mom[:, 3:6] - torch.cross(c, p, dim=1)
+        ke = 0.5 * (u * torch.bmm(M, u.unsqueeze(2))[:, :, 0]).sum(dim=1)
+        com = root[:, 0:3] + c
+        pe = -m * (com * g).sum(dim=1)
+        route["state"] = torch.cat([com, p / m[:, None], p, ang, m[:, None], ke[:, None], pe[:, None], torch.zeros_like(pe)[:, None]], dim=1)
+        route["matrix"] = A
+
+    res = {"centroidal_state_and_matrix": t(lambda: sim.centroidal(state, matrix)),
+           "centroidal_state_only": t(lambda: sim.centroidal(state)),
+           "inverse_dynamics_all_terms": t(lambda: sim.inverse_dynamics(udot, abi.ID_ALL, out)),
+           "mass_matrix_refresh_plus_torch_ops": t(replaced)}
+    res["ratio_to_inverse_dynamics"] = round(res["centroidal_state_and_matrix"]["median_us"] / res["inverse_dynamics_all_terms"]["median_us"], 3)
+    res["ratio_to_replaced_route"] = round(res["centroidal_state_and_matrix"]["median_us"] / res["mass_matrix_refresh_plus_torch_ops"]["median_us"], 3)
+    # the two routes agree
+    sim.centroidal(state, matrix)
+    replaced()
+    torch.cuda.synchronize()
+    res["max_abs_difference_state"] = float((state - route["state"]).abs().max())
+    res["max_abs_difference_matrix"] = float((matrix - route["matrix"]).abs().max())
+    assert torch.isfinite(state).all() and torch.isfinite(matrix).all()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("call", choices=["tensors", "inverse_dynamics", "centroidal"])
     ap.add_argument("--num-envs", type=int, default=4096)
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
@@ -46,33 +154,10 @@ def main():
     if args.cleats:
         cfg.flags |= abi.FLAG_CLEATS
     sim = BezSim(cfg, 0)
-    hip = C.CDLL("libamdhip64.so")
-    hip.hipMemsetAsync.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
-    hip.hipMemsetAsync.restype = C.c_int
-    act = torch.zeros(args.num_envs * 18, device="cuda:0")
-    sim.step(act)   # a state off the reset pose
-    J, M = sim.dynamics_tensor("jacobian"), sim.dynamics_tensor("mass_matrix")
-    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-    def fill(*tensors):
-        def run():
-            for t in tensors:
-                assert hip.hipMemsetAsync(C.c_void_p(t.data_ptr()), 0, t.numel() * 4, stream()) == 0
-        return run
-
-    out = {"num_envs": args.num_envs, "launches": args.launches, "warmup": args.warmup, "device": torch.cuda.get_device_name(0),
-           "bytes": {"jacobian": J.numel() * 4, "mass_matrix": M.numel() * 4}}
-    for name, which, tensors in (("jacobian", ["jacobian"], (J,)), ("mass_matrix", ["mass_matrix"], (M,)), ("both", ["jacobian", "mass_matrix"], (J, M))):
-        r = timed(lambda: sim.refresh_dynamics_tensors(which), args.launches, args.warmup)
-        f = timed(fill(*tensors), args.launches, args.warmup)
-        nbytes = sum(t.numel() * 4 for t in tensors)
-        out[name] = {"refresh": r, "fill": f, "ratio": round(r["median_us"] / f["median_us"], 3),
-                     "refresh_GBps": round(nbytes / r["median_us"] / 1e3, 1), "fill_GBps": round(nbytes / f["median_us"] / 1e3, 1)}
-    sim.refresh_dynamics_tensors()
-    torch.cuda.synchronize()
-    assert torch.isfinite(J).all() and torch.isfinite(M).all()
+    res = {"num_envs": args.num_envs, "launches": args.launches, "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
+    res.update(globals()[args.call](sim, args.num_envs, lambda fn: timed(fn, args.launches, args.warmup)))
     sim.close()
-    print(json.dumps(out))
+    print(json.dumps(res))
 
 
 if __name__ == "__main__":

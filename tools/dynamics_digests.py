@@ -1,0 +1,62 @@
+#!/usr/bin/env python3
+"""SHA-256 digests of what the dynamics queries write, on the seeded states, udot and parameter rows of the GPU tests
+(tests.test_gpu_inverse_dynamics._prepared: generate_states through _write_states).  Two builds that print the same lines compute the same bits:
+
+  BEZ_SIM_LIB=build_ab/parent.so python tools/dynamics_digests.py        (one process per library; profiles/dynamics_refactor_digests.txt)
+
+One line per asset x task x parameters (the defaults; random BEZ_PARAM_MASS_SCALE and BEZ_PARAM_GRAVITY rows) x num_envs: RIGID_BODY_STATE;
+the Jacobian and the mass matrix each refreshed alone, then both in one launch; inverse_dynamics for ID_ALL, ID_INERTIA, ID_VELOCITY and
+ID_GRAVITY and centroidal (state, matrix), each into 16-byte aligned buffers and into views 4 bytes off (the kernels' scalar path)."""
+import hashlib
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import bez_isaacgym_amd   # noqa: E402,F401  (before anything initialises HIP: DESIGN.md 6.2)
+import torch   # noqa: E402
+
+from bez_isaacgym_amd import abi   # noqa: E402
+from tests.test_gpu_inverse_dynamics import ASSETS, _prepared, make_cfg   # noqa: E402
+
+SIZES = (1, 15, 16, 17, 65, 300)
+NG = abi.NUM_GEN
+
+
+def digest(*tensors):
+    torch.cuda.synchronize()
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(t.detach().cpu().contiguous().numpy().tobytes())
+    return h.hexdigest()[:16]
+
+
+def off4(shape):
+    """a contiguous float32 view of `shape` that starts 4 bytes past a 16-byte aligned address"""
+    return torch.zeros(torch.Size(shape).numel() + 1, device="cuda:0")[1:].view(shape)
+
+
+def main():
+    for asset in ASSETS:
+        for task in ("bez_kick", "bez_walk"):
+            for params in ("default", "random"):
+                for n in SIZES:
+                    sim, udot = _prepared(make_cfg(n, task=task, seed=5, **ASSETS[asset]), n, params == "random")
+                    d = {"rigid_body": digest(sim.refresh(abi.TENSOR_RIGID_BODY_STATE))}
+                    J, M = sim.dynamics_tensor("jacobian"), sim.dynamics_tensor("mass_matrix")
+                    for name, which, bufs in (("jacobian", "jacobian", (J,)), ("mass_matrix", "mass_matrix", (M,)), ("both", None, (J, M))):
+                        for b in bufs:
+                            b.fill_(-1.0)
+                        sim.refresh_dynamics_tensors(which)
+                        d[name] = digest(*bufs)
+                    for where, make in (("aligned", lambda shape: torch.zeros(shape, device="cuda:0")), ("offset", off4)):
+                        u, out = make((n, NG)), make((n, NG))
+                        u.copy_(udot)
+                        d["id_" + where] = digest(*[sim.inverse_dynamics(u, terms, out).clone()
+                                                    for terms in (abi.ID_ALL, abi.ID_INERTIA, abi.ID_VELOCITY, abi.ID_GRAVITY)])
+                        d["cm_" + where] = digest(*sim.centroidal(make((n, abi.CM_WORDS)), make((n, 6, NG))))
+                    sim.close()
+                    print("%-7s %-8s %-7s n=%-3d %s" % (asset, task, params, n, " ".join("%s=%s" % kv for kv in d.items())), flush=True)
+
+
+if __name__ == "__main__":
+    main()
