@@ -47,6 +47,9 @@ ID_ALL = 7
 # matrix is (N, 6, NUM_GEN) with rows [linear momentum 3; angular momentum about the centre of mass 3]
 CM_WORDS = 16
 CM_COM, CM_COM_VEL, CM_LIN_MOM, CM_ANG_MOM, CM_MASS, CM_KINETIC, CM_POTENTIAL = 0, 3, 6, 9, 12, 13, 14
+# bez_sim_body_accelerations (include/bez_sim.h "Body accelerations", BezSim.body_accelerations): the terms of J udot + Jdot u - g to add up
+ACC_UDOT, ACC_VELOCITY, ACC_GRAVITY = 1, 2, 4
+ACC_MOTION, ACC_ALL = 3, 7
 DOF_FORCE_KEY = "env.enableDofForceSensors"   # this build's task key for FLAG_DOF_FORCE (default False)
 SPACE_ENV = 0                   # bez_sim_apply_body_forces: world axes / world points (gymapi.ENV_SPACE)
 SPACE_LOCAL = 1                 # the body's own frame (gymapi.LOCAL_SPACE)

@@ -1,5 +1,5 @@
 // bez_dynamics.h -- the kernels that run forward kinematics outside the control step (rigid-body refresh, dynamics tensors, inverse and
-// centroidal dynamics, external wrenches) and what they share: DynArgs, tile I/O, the composite-rigid-body sweep.  Included by bez_sim.hip only.
+// centroidal dynamics, body accelerations, external wrenches) and what they share: DynArgs, tile I/O, the composite-rigid-body sweep.  Included by bez_sim.hip only.
 #pragma once
 #include "bez_kernels.h"
 
@@ -440,6 +440,119 @@ __global__ void __launch_bounds__(CM_THREADS) centroidal_kernel(DynArgs D, float
   __syncthreads();
   if (state_out) tile_store<BEZ_CM_WORDS, CM_STRIDE, CM_THREADS>(lds, state_out + (size_t)e0 * BEZ_CM_WORDS, ne);
   if (matrix_out) tile_store<CM_MATRIX, CM_STRIDE, CM_THREADS>(lds + BEZ_CM_WORDS, matrix_out + (size_t)e0 * CM_MATRIX, ne);
+}
+
+// ---- bez_sim_body_accelerations (definition: include/bez_sim.h "Body accelerations"): the outward half of inverse_dynamics_kernel -- no
+// inertias, no return sweep -- with a read-out per body like refresh_rigid_body_kernel's.
+// A workgroup is ONE wave and takes ACC_TILE consecutive envs.  All lanes bring the tile's udot rows into LDS (tile_load); then one lane
+// per env walks the tree chain by chain, in world axes about the root origin, carrying per link only its frame E, r, its spatial
+// velocity V and its spatial acceleration in two parts: aI (from udot: aI += S qdd) and aV (velocity products: aV += cb of
+// link_kinematics).  Every body on the link is read out where the walk stands: with x the body's origin relative to the root origin,
+//     UDOT      [aI.l + aI.a x x ; aI.a]
+//     VELOCITY  [aV.l + aV.a x x + w x (v + w x x) ; aV.a]        (classical acceleration of the origin: d/dt of RIGID_BODY_STATE[7:10])
+//     GRAVITY   [0 - g ; 0]
+// and the element is (UDOT + VELOCITY) + GRAVITY, the parts canonicalised (x + 0.0f: -0.0 becomes +0.0) so that a dropped or vanishing
+// term is +0.0f to the bit.  BEZ_SPACE_LOCAL turns both triples by the link frame's transpose after that sum.
+// The velocity part is evaluated with root_lin = 0: J's columns 0:3 are constant, so Jdot u does not depend on root_lin (a uniform
+// translation changes no acceleration), and with it go the pair -w x v + w x v that would cancel in every row and the torso's aV, which
+// is then zero by construction.  Bodies of the torso link take their rows from the definition: [vdot + wdot x x ; wdot] and
+// [w x (w x x) ; 0], so the torso itself (x = 0) returns udot[0:6] and zeros.
+// Last, all lanes write the tile's rows -- one contiguous range of ne x 6 NB floats, not whole float4s -- with tile_store_ragged.
+constexpr int ACC_TILE = 16, ACC_THREADS = 64, ACC_USTRIDE = DYN_NG + 1;   // odd row strides: the lanes' own rows start in distinct LDS banks
+// tile_store for rows that are not whole float4s: `count` floats of the contiguous range at `out`; a 16-byte aligned range moves as
+// float4 with a scalar tail of count % 4 elements, any other takes the scalar path to the same bits.
+template <int WIDTH, int STRIDE, int THREADS>
+BEZ_DEV void tile_store_ragged(const float* rows, float* __restrict__ out, int count) {
+  auto at = [&](int i) { return rows[(i / WIDTH) * STRIDE + i % WIDTH]; };
+  if ((reinterpret_cast<uintptr_t>(out) & 15u) == 0) {
+    float4* o4 = reinterpret_cast<float4*>(out);
+    const int n4 = count / 4;
+    for (int i = threadIdx.x; i < n4; i += THREADS) o4[i] = make_float4(at(4 * i), at(4 * i + 1), at(4 * i + 2), at(4 * i + 3));
+    for (int i = 4 * n4 + threadIdx.x; i < count; i += THREADS) out[i] = at(i);
+  } else {
+    for (int i = threadIdx.x; i < count; i += THREADS) out[i] = at(i);
+  }
+}
+struct AccCtx { float* O; V3 g; bool local; };   // the env's output row in LDS, 0 - g, BEZ_SPACE_LOCAL
+BEZ_DEV V3 acc_sum(V3 i, V3 v, V3 g) {
+  const V3 z = mk(0.f, 0.f, 0.f);
+  return ((i + z) + (v + z)) + g;
+}
+// the rows of every body fixed to link L; E, r, V, aI, aV: the link's
+template <bool CL, int L>
+BEZ_DEV void acc_bodies(const AccCtx& C, const M3& E, V3 r, SV V, SV aI, SV aV) {
+  static_for<nb_of<CL>()>([&](auto I) {
+    constexpr int b = decltype(I)::value;
+    if constexpr ((CL ? BEZ_BODY_LINK_CL[b] : BEZ_BODY_LINK[b]) == L) {
+      const double* o = CL ? BEZ_BODY_OFFSET_CL[b] : BEZ_BODY_OFFSET[b];
+      const bool at_link_origin = o[0] == 0.0 && o[1] == 0.0 && o[2] == 0.0;
+      const V3 x = at_link_origin ? r : r + mul(E, mk((float)o[0], (float)o[1], (float)o[2]));
+      V3 li, lv;
+      if constexpr (L == 0) {
+        li = at_link_origin ? aI.l : aI.l + cross(aI.a, x);
+        lv = at_link_origin ? mk(0.f, 0.f, 0.f) : cross(V.a, cross(V.a, x));
+      } else {
+        li = point_of(aI, x);
+        lv = point_of(aV, x) + cross(V.a, point_of(V, x));
+      }
+      V3 lin = acc_sum(li, lv, C.g), ang = acc_sum(aI.a, aV.a, mk(0.f, 0.f, 0.f));
+      if (C.local) { lin = mulT(E, lin) + mk(0.f, 0.f, 0.f); ang = mulT(E, ang) + mk(0.f, 0.f, 0.f); }   // (products of +0.0 may be -0.0)
+      float* O = C.O + 6 * b;
+      O[0] = lin.x; O[1] = lin.y; O[2] = lin.z; O[3] = ang.x; O[4] = ang.y; O[5] = ang.z;
+    }
+  });
+}
+template <bool CL>
+__global__ void __launch_bounds__(ACC_THREADS) body_accelerations_kernel(DynArgs D, const float* __restrict__ udot, float* __restrict__ out,
+                                                                         uint32_t terms, int local) {
+  constexpr int WIDTH = 6 * nb_of<CL>(), STRIDE = WIDTH | 1;
+  __shared__ float urows[ACC_TILE * ACC_USTRIDE];
+  __shared__ float orows[ACC_TILE * STRIDE];
+  const float* st = D.st;
+  const int n = D.n, e0 = blockIdx.x * ACC_TILE, ne = min(ACC_TILE, n - e0);
+  if (udot && (terms & BEZ_ACC_UDOT)) {
+    tile_load<DYN_NG, ACC_USTRIDE, ACC_THREADS>(urows, udot + (size_t)e0 * DYN_NG, ne);
+  } else {
+    for (int i = threadIdx.x; i < ne * DYN_NG; i += ACC_THREADS) urows[tile_word<DYN_NG, ACC_USTRIDE>(i)] = 0.f;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < ne) {
+    int e = e0 + threadIdx.x;
+    const float* U = urows + threadIdx.x * ACC_USTRIDE;
+    auto ld = [&](int f) { return st[(size_t)f * n + e]; };
+    const bool vel = (terms & BEZ_ACC_VELOCITY) != 0;
+    const M3 E0 = quat_to_mat(ld(F_ROOT_QUAT), ld(F_ROOT_QUAT + 1), ld(F_ROOT_QUAT + 2), ld(F_ROOT_QUAT + 3));
+    const SV V0 = mksv(vel ? mk(ld(F_ROOT_ANG), ld(F_ROOT_ANG + 1), ld(F_ROOT_ANG + 2)) : mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 0.f));
+    // spatial acceleration of the torso about the (momentarily fixed) point its origin passes through: [wdot; vdot - w x v], whose
+    // second part is a velocity product that vanishes with root_lin = 0
+    const SV aI0 = mksv(mk(U[3], U[4], U[5]), mk(U[0], U[1], U[2]));
+    V3 g = mk(0.f, 0.f, 0.f);
+    if (terms & BEZ_ACC_GRAVITY) g = gravity_of(D, e);
+    AccCtx C = {orows + threadIdx.x * STRIDE, mk(0.f - g.x, 0.f - g.y, 0.f - g.z), local != 0};
+    const float quirk_z = quirk_rz<CL>(D.flags);
+    acc_bodies<CL, 0>(C, E0, mk(0.f, 0.f, 0.f), V0, aI0, svzero());
+    auto chain = [&](auto first, auto len) {
+      constexpr int FIRST = decltype(first)::value, LEN = decltype(len)::value;
+      static_assert(is_chain<FIRST, LEN>(), "not a chain off the torso");
+      asm volatile("" : "+v"(e));   // (opaque per chain: otherwise every chain's loads are issued up front, at the price of their registers)
+      M3 E = E0; V3 r = mk(0.f, 0.f, 0.f); SV V = V0, aI = aI0, aV = svzero();
+      static_for<LEN>([&](auto I) {
+        constexpr int L = FIRST + decltype(I)::value;
+        SV S, cb;
+        link_kinematics<L>(ld(F_Q + L - 1), vel ? ld(F_QD + L - 1) : 0.f, E, r, V, S, cb, quirk_z);
+        aI = aI + S * U[5 + L]; aV = aV + cb;
+        acc_bodies<CL, L>(C, E, r, V, aI, aV);
+      });
+    };
+    using std::integral_constant;
+    chain(integral_constant<int, 1>{}, integral_constant<int, 2>{});
+    chain(integral_constant<int, 3>{}, integral_constant<int, 2>{});
+    chain(integral_constant<int, 5>{}, integral_constant<int, 6>{});
+    chain(integral_constant<int, 11>{}, integral_constant<int, 2>{});
+    chain(integral_constant<int, 13>{}, integral_constant<int, 6>{});
+  }
+  __syncthreads();
+  tile_store_ragged<WIDTH, STRIDE, ACC_THREADS>(orows, out + (size_t)e0 * WIDTH, ne * WIDTH);
 }
 
 // ---- bez_sim_apply_body_forces: one thread per env turns the Isaac-layout inputs of its env into the pending per-link wrenches (bez_kernels.h

@@ -781,6 +781,13 @@ int bez_sim_centroidal(BezSim* s, float* state_dev, float* matrix_dev, void* str
   if (!state_dev && !matrix_dev) return fail(s, -1, "bez_sim_centroidal: state_dev and matrix_dev are both null (nothing to write)");
   return LAUNCH_ASSET(s, centroidal_kernel, CM_TILE, CM_THREADS, (hipStream_t)stream, dyn_args(s), state_dev, matrix_dev);
 }
+int bez_sim_body_accelerations(BezSim* s, const float* udot_dev, uint32_t terms, int32_t space, float* out_dev, void* stream) {
+  if (!s) return fail(s, -1, "bez_sim_body_accelerations: sim is null");
+  if (terms == 0u || (terms & ~(uint32_t)BEZ_ACC_ALL)) return fail(s, -1, "bez_sim_body_accelerations: terms must be a non-empty set of BEZ_ACC_UDOT | BEZ_ACC_VELOCITY | BEZ_ACC_GRAVITY");
+  if (space != BEZ_SPACE_ENV && space != BEZ_SPACE_LOCAL) return fail(s, -1, "bez_sim_body_accelerations: space must be BEZ_SPACE_ENV or BEZ_SPACE_LOCAL");
+  if (!out_dev) return fail(s, -1, "bez_sim_body_accelerations: out_dev is null");
+  return LAUNCH_ASSET(s, body_accelerations_kernel, ACC_TILE, ACC_THREADS, (hipStream_t)stream, dyn_args(s), udot_dev, out_dev, terms, (int)space);
+}
 int bez_sim_set_obs_calls(BezSim* s, int64_t calls) { if (!s) return -1; s->obs_calls = calls; return 0; }
 
 int bez_sim_pre_physics(BezSim* s, const float* actions_dev, void* stream) {

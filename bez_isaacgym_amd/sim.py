@@ -61,6 +61,7 @@ SIGS = {
     "bez_sim_refresh_dynamics_tensors": (C.c_int, [vp, u32, vp]),
     "bez_sim_inverse_dynamics": (C.c_int, [vp, fp, u32, fp, vp]),
     "bez_sim_centroidal": (C.c_int, [vp, fp, fp, vp]),
+    "bez_sim_body_accelerations": (C.c_int, [vp, fp, u32, i32, fp, vp]),
 }
 EXPORTS = list(SIGS)
 
@@ -265,6 +266,27 @@ class BezSim:
         self._check(self.lib.bez_sim_centroidal(self.h, self._ptr(state, torch.float32, state.numel()),
                                                 None if matrix is None else self._ptr(matrix, torch.float32, matrix.numel()), self._stream()))
         return state, matrix
+
+    # ---- body accelerations: J udot + Jdot u of every rigid body of the robot, and what an accelerometer on it reads
+    def body_accelerations(self, udot=None, terms=abi.ACC_MOTION, space=abi.SPACE_ENV, out=None):
+        """(N, NB, 6) float32: the sum of the terms selected by `terms` (abi.ACC_UDOT | ACC_VELOCITY | ACC_GRAVITY) for the robot's NB
+        bodies in RIGID_BODY_STATE order, no ball row (include/bez_sim.h "Body accelerations").  Rows 0:3: the acceleration of the body's
+        origin, rows 3:6: its angular acceleration -- the time derivatives of RIGID_BODY_STATE[:, 7:10] and [:, 10:13] for ACC_MOTION;
+        ACC_UDOT alone is J @ udot, ACC_VELOCITY alone Jdot @ u, ACC_GRAVITY adds -g to rows 0:3.  `udot`: (N, 24) float32 on the sim's
+        device, contiguous, or None for zero.  `space`: abi.SPACE_ENV / abi.SPACE_LOCAL or "env" / "local" (world axes / the body's own
+        frame).  `out`: a tensor of the result's kind to write into; None: one buffer per sim, allocated by the first such call and
+        overwritten by every later one.  One launch on the current stream."""
+        space = abi.body_force_space(space)
+        n, nb = self.num_envs, self.num_bodies - (1 if self.has_ball else 0)
+        if udot is not None:
+            self._checked("udot", udot, ((n, abi.NUM_GEN),))
+        if out is None:
+            out = self._scratch("body_accelerations", (n, nb, 6))
+        else:
+            self._checked("out", out, ((n, nb, 6),))
+        self._check(self.lib.bez_sim_body_accelerations(self.h, None if udot is None else self._ptr(udot, torch.float32, n * abi.NUM_GEN), int(terms),
+                                                        space, self._ptr(out, torch.float32, n * nb * 6), self._stream()))
+        return out
 
     def refresh(self, which):
         self._check(self.lib.bez_sim_refresh_tensor(self.h, which, self._stream()))

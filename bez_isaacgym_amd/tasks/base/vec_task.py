@@ -242,6 +242,37 @@ class VecTask(Env):
         s = self.centroidal_state()
         return s[:, abi.CM_KINETIC], s[:, abi.CM_POTENTIAL]
 
+    # ---- body accelerations of the current state (include/bez_sim.h "Body accelerations"); each method is one launch, and what it
+    # returns is (a view of) the sim's one result buffer of that kind: the next call overwrites it
+    def body_accelerations(self, udot=None, terms=3, space="env"):
+        """(N, NB, 6): the terms (abi.ACC_UDOT | ACC_VELOCITY | ACC_GRAVITY; default ACC_MOTION = d/dt of the bodies' velocity rows) of
+        J_b udot + Jdot_b u - g for the robot's NB bodies in RIGID_BODY_STATE order; udot (N, 24) or None for zero; space "env" / "local"."""
+        return self.sim.body_accelerations(udot, terms, space)
+
+    def jacobian_dot_u(self):
+        """(N, NB, 6): Jdot_b u, the bias acceleration of every body in the current state, world axes"""
+        from ... import abi
+        return self.sim.body_accelerations(None, abi.ACC_VELOCITY, abi.SPACE_ENV)
+
+    def body_index(self, name):
+        """the RIGID_BODY_STATE row of the robot body `name` (the model's body_names for the asset in use)"""
+        from ... import abi
+        names = self.__dict__.get("_body_names")
+        if names is None:
+            import json
+            import os
+            model = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "model", "bez_model.json")))
+            names = self._body_names = list((model["cleats"] if int(self.sim.cfg.flags) & abi.FLAG_CLEATS else model)["body_names"])
+        if name not in names:
+            raise ValueError("no rigid body %r: the asset's bodies are %s" % (name, ", ".join(names)))
+        return names.index(name)
+
+    def accelerometer(self, udot, body="/imu_link"):
+        """(N, 3): the specific force at the origin of `body` in the body's own frame for the acceleration udot (N, 24) of the current
+        state -- J udot + Jdot u - g, what an accelerometer mounted there reads"""
+        from ... import abi
+        return self.sim.body_accelerations(udot, abi.ACC_ALL, abi.SPACE_LOCAL)[:, self.body_index(body), 0:3]
+
     def actuator_snapshot(self):
         """(drive torque, status, joint velocity), each (N, 18), of the last physics launch: one refresh of the actuator tensors and one of
         DOF_STATE (the PPO loop's per-epoch actuator statistics)."""

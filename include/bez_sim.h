@@ -396,6 +396,42 @@ int bez_sim_inverse_dynamics(BezSim* sim, const float* udot_dev, uint32_t terms,
 int bez_sim_centroidal(BezSim* sim, float* state_dev /* (N,16) or NULL */,
                        float* matrix_dev /* (N,6,24) or NULL */, void* stream);
 
+/* Body accelerations: J_b udot + Jdot_b u of every rigid body of the robot, without forming J or differencing it -- the term of
+ *       xddot_b = J_b udot + Jdot_b u,     tau = J^T Lambda (xddot_des - Jdot u) + h
+ * that the Jacobian, the mass matrix and inverse dynamics leave open, and, with gravity taken off in the body's frame, what an
+ * accelerometer on a body reads.
+ *   Coordinates: u = [root_lin(3), root_ang(3), qd(18)] of the dynamics tensors above; udot_dev is f32 (N, 24), env-major, the time
+ *     derivative of u as in inverse dynamics; udot_dev == NULL means udot = 0.
+ *   out_dev  f32 (N, NB, 6), env-major; NB = 21 robot bodies (29 with cleats) in RIGID_BODY_STATE order, no ball row (as the Jacobian).
+ *     With BEZ_SPACE_ENV rows 0:3 are the time derivative of RIGID_BODY_STATE[e,b,7:10] -- the classical acceleration of the body's
+ *     ORIGIN in world axes, not the linear part of a spatial acceleration -- and rows 3:6 the derivative of [e,b,10:13].  With the link's
+ *     velocity [w; v_O] and spatial acceleration [alpha; a_O] about the root origin (the torso's: [wdot; vdot - w x v]) and x the body's
+ *     origin relative to the root origin, rows 0:3 are a_O + alpha x x + w x (v_O + w x x) and rows 3:6 are alpha.  Fixed bodies
+ *     (imu_link, camera, the cleats) use their link's motion with their own origin; the asset (cleats, box, the joint origin box + cleats
+ *     moves) is the step's.  Masses play no part, and neither do root_pos and root_lin: a uniform translation changes no acceleration.
+ *   out = the sum of the terms selected in `terms`, evaluated on the state as it stands on `stream`:
+ *     BEZ_ACC_UDOT      J[e,b] @ udot[e];
+ *     BEZ_ACC_VELOCITY  Jdot[e,b] @ u[e], the bias acceleration of the state's u; with UDOT (BEZ_ACC_MOTION) it is d/dt (J[e,b] @ u[e]);
+ *     BEZ_ACC_GRAVITY   -g on rows 0:3, zero on rows 3:6: all three (BEZ_ACC_ALL) are the specific force at the body's origin.
+ *     A term is dropped by zeroing its input, and the terms are evaluated apart and meet only in the last additions of each element:
+ *     in BEZ_SPACE_ENV, MOTION is the fp32 sum of the two single-term results and ALL is (udot + velocity) + gravity, bit for bit.
+ *     +0.0f to the bit: the UDOT term of udot_dev == NULL, the VELOCITY term of a state with u = 0, rows 3:6 of the GRAVITY term, the
+ *     GRAVITY term under a zero gravity row; its rows 0:3 are 0 - g exactly.  Body 0 (the torso, whose origin is the root's) in
+ *     BEZ_SPACE_ENV: the UDOT term is udot[0:6] to the bit, the VELOCITY term zeros.
+ *   Gravity is what the step would use: the env's BEZ_PARAM_GRAVITY row if set, else cfg.gravity.
+ *   space: BEZ_SPACE_ENV -- world axes; BEZ_SPACE_LOCAL -- both row triples in the body's own frame: the transpose of the orientation
+ *     RIGID_BODY_STATE reports for the body is applied after the terms are summed.
+ *   BEZ_FLAG_FIX_BASE changes nothing: the stored state is evaluated as it is.  A non-finite input is written through.
+ *   One kernel launch.  The call allocates nothing, never synchronises, reads nothing on the host and writes only out_dev: it captures
+ *   into a HIP graph.  terms == 0, an unknown bit, an unknown space, a null out_dev or a null sim: rc -1 with a message. */
+#define BEZ_ACC_UDOT     1u  /* J_b udot */
+#define BEZ_ACC_VELOCITY 2u  /* Jdot_b u: the bias acceleration of the state's u */
+#define BEZ_ACC_GRAVITY  4u  /* -g on rows 0:3: with the other two, the specific force an accelerometer at the body's origin reads */
+#define BEZ_ACC_MOTION   3u
+#define BEZ_ACC_ALL      7u
+int bez_sim_body_accelerations(BezSim* sim, const float* udot_dev /* (N,24) or NULL */, uint32_t terms,
+                               int32_t space /* BEZ_SPACE_ENV | BEZ_SPACE_LOCAL */, float* out_dev /* (N, NB, 6) */, void* stream);
+
 /* gym.refresh_{actor_root_state,dof_state,rigid_body_state,net_contact_force}_tensor
  * (kick_env.py:750-753): materialise the Isaac-layout tensor from the SoA state.  ROOT_STATE, DOF_STATE, RIGID_BODY_STATE,
  * NET_CONTACT_FORCE, DOF_TARGET, PREV_LIN_VEL, FEET and GOAL need it; every other BezTensor is always live (the kernels

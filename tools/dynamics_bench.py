@@ -1,8 +1,9 @@
 """Times one of the dynamics queries at num_envs = 4096 beside its yardsticks in the same run.  Prints one JSON line.
 
-  python tools/dynamics_bench.py {tensors,inverse_dynamics,centroidal} [--num-envs 4096] [--launches 200] [--warmup 20] [--cleats]
+  python tools/dynamics_bench.py {tensors,inverse_dynamics,centroidal,body_accelerations} [--num-envs 4096] [--launches 200] [--warmup 20] [--cleats]
   python tools/dynamics_bench.py inverse_dynamics > profiles/inverse_dynamics_bench.json      (the committed records)
   python tools/dynamics_bench.py centroidal > profiles/centroidal_bench.json
+  python tools/dynamics_bench.py body_accelerations > profiles/body_accelerations_bench.json
 
 tensors: bez_sim_refresh_dynamics_tensors (the Jacobian, the mass matrix, both) beside a plain device fill of the same bytes -- the kernel
 is store-bound by construction, so the fill (hipMemsetAsync over the very buffer the refresh writes) is its yardstick.
@@ -12,6 +13,10 @@ centroidal: bez_sim_centroidal (both outputs; the state alone) beside bez_sim_in
 shape -- and the route the call replaces: a mass-matrix refresh followed by the torch ops that rebuild the 16 + 144 numbers per env from M
 and u (rows 0:6 of M times u, the centre of mass un-skewed from M[0:3, 3:6], the moment shifted to it, 1/2 u^T M u).  The replaced route
 is handed u and the root positions ready-made: refreshing them is not counted against it.
+body_accelerations: bez_sim_body_accelerations (motion terms in world axes; all terms in the bodies' frames; the bias acceleration alone)
+beside refresh_rigid_body_state -- the same per-lane forward kinematics and a read-out of the same kind -- beside bez_sim_inverse_dynamics
+with all terms -- whose outward half it is -- and beside the route the call replaces for the UDOT term: a Jacobian refresh followed by
+torch.matmul(J, udot).
 
 Each figure is the median over --launches (>= 200) single launches, each between its own pair of events on one stream, after --warmup
 launches.  Nothing flushes the caches between launches, for a call and its yardsticks alike.
@@ -142,9 +147,42 @@ def centroidal(sim, n, t):
     return res
 
 
+def body_accelerations(sim, n, t):
+    sim.step(torch.rand(n * 18, device=DEV) * 2 - 1)   # a state off the reset pose, in motion
+    nb = sim.num_bodies - (1 if sim.has_ball else 0)
+    udot = torch.rand(n, abi.NUM_GEN, device=DEV) * 20 - 10
+    out = torch.zeros(n, nb, 6, device=DEV)
+    tau = torch.zeros(n, abi.NUM_GEN, device=DEV)
+    J = sim.dynamics_tensor("jacobian").view(n, nb * 6, abi.NUM_GEN)
+    ju = torch.zeros(n, nb * 6, 1, device=DEV)
+
+    def replaced():
+        sim.refresh_dynamics_tensors("jacobian")
+        torch.matmul(J, udot.unsqueeze(2), out=ju)
+
+    res = {"bytes_out": out.numel() * 4,
+           "body_accelerations_motion_env": t(lambda: sim.body_accelerations(udot, abi.ACC_MOTION, abi.SPACE_ENV, out)),
+           "body_accelerations_all_local": t(lambda: sim.body_accelerations(udot, abi.ACC_ALL, abi.SPACE_LOCAL, out)),
+           "body_accelerations_velocity_only": t(lambda: sim.body_accelerations(None, abi.ACC_VELOCITY, abi.SPACE_ENV, out)),
+           "refresh_rigid_body_state": t(lambda: sim.refresh(abi.TENSOR_RIGID_BODY_STATE)),
+           "inverse_dynamics_all_terms": t(lambda: sim.inverse_dynamics(udot, abi.ID_ALL, tau)),
+           "jacobian_refresh_plus_matmul": t(replaced)}
+    mine = res["body_accelerations_motion_env"]["median_us"]
+    res["ratio_to_rigid_body_refresh"] = round(mine / res["refresh_rigid_body_state"]["median_us"], 3)
+    res["ratio_to_inverse_dynamics"] = round(mine / res["inverse_dynamics_all_terms"]["median_us"], 3)
+    res["ratio_to_replaced_route"] = round(mine / res["jacobian_refresh_plus_matmul"]["median_us"], 3)
+    # the two routes agree on the UDOT term
+    sim.body_accelerations(udot, abi.ACC_UDOT, abi.SPACE_ENV, out)
+    replaced()
+    torch.cuda.synchronize()
+    res["max_abs_difference_of_the_udot_term"] = float((out.view(n, nb * 6) - ju[:, :, 0]).abs().max())
+    assert torch.isfinite(out).all()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("call", choices=["tensors", "inverse_dynamics", "centroidal"])
+    ap.add_argument("call", choices=["tensors", "inverse_dynamics", "centroidal", "body_accelerations"])
     ap.add_argument("--num-envs", type=int, default=4096)
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)

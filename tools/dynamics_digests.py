@@ -6,7 +6,9 @@
 
 One line per asset x task x parameters (the defaults; random BEZ_PARAM_MASS_SCALE and BEZ_PARAM_GRAVITY rows) x num_envs: RIGID_BODY_STATE;
 the Jacobian and the mass matrix each refreshed alone, then both in one launch; inverse_dynamics for ID_ALL, ID_INERTIA, ID_VELOCITY and
-ID_GRAVITY and centroidal (state, matrix), each into 16-byte aligned buffers and into views 4 bytes off (the kernels' scalar path)."""
+ID_GRAVITY, centroidal (state, matrix) and body_accelerations for ACC_UDOT, ACC_VELOCITY, ACC_GRAVITY, ACC_MOTION (world axes) and ACC_ALL
+(the bodies' frames), each into 16-byte aligned buffers and into views 4 bytes off (the kernels' scalar path).  A library without
+bez_sim_body_accelerations (BEZ_SIM_LIB naming an older build) prints no acc_* entries."""
 import hashlib
 import os
 import sys
@@ -54,6 +56,15 @@ def main():
                         d["id_" + where] = digest(*[sim.inverse_dynamics(u, terms, out).clone()
                                                     for terms in (abi.ID_ALL, abi.ID_INERTIA, abi.ID_VELOCITY, abi.ID_GRAVITY)])
                         d["cm_" + where] = digest(*sim.centroidal(make((n, abi.CM_WORDS)), make((n, 6, NG))))
+                    nb = sim.num_bodies - (1 if sim.has_ball else 0)
+                    for where, make in (("aligned", lambda shape: torch.zeros(shape, device="cuda:0")), ("offset", off4)):
+                        if not hasattr(sim.lib, "bez_sim_body_accelerations"):
+                            break
+                        u, out = make((n, NG)), make((n, nb, 6))
+                        u.copy_(udot)
+                        d["acc_" + where] = digest(*[sim.body_accelerations(u, terms, space, out).clone() for terms, space in
+                                                     ((abi.ACC_UDOT, "env"), (abi.ACC_VELOCITY, "env"), (abi.ACC_GRAVITY, "env"), (abi.ACC_MOTION, "env"),
+                                                      (abi.ACC_ALL, "local"))])
                     sim.close()
                     print("%-7s %-8s %-7s n=%-3d %s" % (asset, task, params, n, " ".join("%s=%s" % kv for kv in d.items())), flush=True)
 
