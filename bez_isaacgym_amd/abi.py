@@ -53,6 +53,7 @@ ACC_MOTION, ACC_ALL = 3, 7
 DOF_FORCE_KEY = "env.enableDofForceSensors"   # this build's task key for FLAG_DOF_FORCE (default False)
 SPACE_ENV = 0                   # bez_sim_apply_body_forces: world axes / world points (gymapi.ENV_SPACE)
 SPACE_LOCAL = 1                 # the body's own frame (gymapi.LOCAL_SPACE)
+GF_AT_ORIGIN = 2                # bez_sim_generalized_forces only, OR-ed into the space: without positions, wrenches act at the bodies' origins
 HEALTH_NONFINITE = 1            # health word bits (TENSOR_HEALTH, BezSim.health)
 HEALTH_SPIN_TIMEOUT = 2
 TASK_KICK, TASK_WALK, TASK_ORIENT = 0, 1, 2
@@ -318,3 +319,11 @@ def body_force_space(space):
     if isinstance(space, bool) or not isinstance(space, int) or space not in (SPACE_ENV, SPACE_LOCAL):
         raise ValueError("space must be SPACE_ENV (0) or SPACE_LOCAL (1), got %r" % (space,))
     return int(space)
+
+
+def generalized_force_space(space, at="com"):
+    """the `space` word of bez_sim_generalized_forces: body_force_space(space), with GF_AT_ORIGIN OR-ed in for at="origin" (at="com",
+    the default point of application of apply_body_forces, adds nothing); any other `at` raises ValueError."""
+    if not isinstance(at, str) or at.strip().lower() not in ("com", "origin"):
+        raise ValueError("at must be 'com' or 'origin', got %r" % (at,))
+    return body_force_space(space) | (GF_AT_ORIGIN if at.strip().lower() == "origin" else 0)

@@ -555,6 +555,150 @@ __global__ void __launch_bounds__(ACC_THREADS) body_accelerations_kernel(DynArgs
   tile_store_ragged<WIDTH, STRIDE, ACC_THREADS>(orows, out + (size_t)e0 * WIDTH, ne * WIDTH);
 }
 
+// ---- bez_sim_generalized_forces (definition: include/bez_sim.h "Generalised forces"): sum_b J_b^T w_b without J -- the return sweep of
+// inverse_dynamics_kernel with the links' inertial wrenches replaced by the wrenches the caller hands in.
+// A workgroup is ONE wave and takes GF_TILE consecutive envs.  All lanes bring the tile's force, torque and position rows -- per tensor
+// one contiguous range of ne x 3 B floats, B with the ball's row where the task has one, not whole float4s -- into LDS with
+// tile_load_ragged; then one lane per env walks the tree chain by chain in link-local coordinates: out along a chain for each link's
+// frame E, r in the root's axes (link_kinematics with qd = 0; ENV inputs are turned by it, LOCAL inputs need no turn), collecting the
+// wrenches of the bodies fixed to the link as [t + d x f ; f] in the link's axes, d the point of application relative to the link's
+// origin; back along it adding up the subtree's wrench, writing tau = +-M[axis] to the env's output row in LDS and taking the wrench to
+// the parent's axes and origin; the chain's total, by then in the root's axes about the root origin, joins the torso's wrench, which is
+// turned to world axes for rows 0:6 (ENV wrenches on the torso's own bodies stay in world axes throughout).  A body whose
+// force and torque rows are all zero is skipped before its position row is looked at (ext_prepare_kernel's rule: a NaN is != 0 and goes
+// in); the ball's row is never read.  Every output is canonicalised (x + 0.0f), so a subtree without a loaded body gives +0.0f to the bit.
+// Last, all lanes write the tile's (ne, 24) rows with tile_store.
+constexpr int GF_TILE = 16, GF_THREADS = 64, GF_OSTRIDE = DYN_NG + 1;   // odd row strides: the lanes' own rows start in distinct LDS banks
+// tile_load for rows that are not whole float4s, the counterpart of tile_store_ragged: `count` floats of the contiguous range at `in`
+template <int WIDTH, int STRIDE, int THREADS>
+BEZ_DEV void tile_load_ragged(float* rows, const float* __restrict__ in, int count) {
+  auto slot = [&](int i) -> float& { return rows[(i / WIDTH) * STRIDE + i % WIDTH]; };
+  if ((reinterpret_cast<uintptr_t>(in) & 15u) == 0) {
+    const float4* in4 = reinterpret_cast<const float4*>(in);
+    const int n4 = count / 4;
+    for (int i = threadIdx.x; i < n4; i += THREADS) {
+      const float4 v = in4[i];
+      slot(4 * i) = v.x; slot(4 * i + 1) = v.y; slot(4 * i + 2) = v.z; slot(4 * i + 3) = v.w;
+    }
+    for (int i = 4 * n4 + threadIdx.x; i < count; i += THREADS) slot(i) = in[i];
+  } else {
+    for (int i = threadIdx.x; i < count; i += THREADS) slot(i) = in[i];
+  }
+}
+// the env's rows in LDS (null: the tensor was not given), its root position, the call's space, and the rotation whose transpose takes
+// an ENV vector into the root's axes
+struct GfCtx { const float *F, *T, *X; V3 root_pos; bool local, at_origin; M3 Rin; };
+// the wrench [moment about the LINK's origin; force], in the LINK's own axes, of every loaded body fixed to link L; E, r: the link's
+// frame in the root's axes, which only ENV inputs need -- a LOCAL row is used as it is given
+template <bool CL, int L>
+BEZ_DEV SV gf_bodies(const GfCtx& C, const M3& E, V3 r) {
+  SV W = svzero();
+  static_for<nb_of<CL>()>([&](auto I) {
+    constexpr int b = decltype(I)::value;
+    if constexpr ((CL ? BEZ_BODY_LINK_CL[b] : BEZ_BODY_LINK[b]) == L) {
+      const V3 f = C.F ? lds3(C.F + 3 * b) : mk(0.f, 0.f, 0.f), t = C.T ? lds3(C.T + 3 * b) : mk(0.f, 0.f, 0.f);
+      if (f.x != 0.f || f.y != 0.f || f.z != 0.f || t.x != 0.f || t.y != 0.f || t.z != 0.f) {   // (a NaN is != 0: it goes in)
+        const BodyFrame bf = body_frame<CL>(b);
+        const bool at_link_origin = bf.off.x == 0.f && bf.off.y == 0.f && bf.off.z == 0.f;
+        const V3 fl = C.local ? f : mulT(E, mulT(C.Rin, f)), tl = C.local ? t : mulT(E, mulT(C.Rin, t));
+        V3 d;   // the point of application relative to the link's origin
+        if (!C.X) d = C.at_origin ? bf.off : bf.off + bf.com;
+        else if (C.local) d = bf.off + lds3(C.X + 3 * b);
+        else d = mulT(E, mulT(C.Rin, lds3(C.X + 3 * b) - C.root_pos) - r);
+        W = W + mksv((!C.X && C.at_origin && at_link_origin) ? tl : tl + cross(d, fl), fl);
+      }
+    }
+  });
+  return W;
+}
+// v in link L's axes -> in its parent's: the joint's rotation about the frame axis it leaves alone (rotate_about's matrix)
+template <int L>
+BEZ_DEV V3 gf_to_parent(V3 v, float s, float c) {
+  constexpr int ax = axis_index(L);
+  if constexpr (ax == 0) return mk(v.x, fmaf(c, v.y, -(s * v.z)), fmaf(s, v.y, c * v.z));
+  else if constexpr (ax == 1) return mk(fmaf(s, v.z, c * v.x), v.y, fmaf(c, v.z, -(s * v.x)));
+  else return mk(fmaf(c, v.x, -(s * v.y)), fmaf(s, v.x, c * v.y), v.z);
+}
+// One link of a chain and, by recursion, the links below it (id_links without inertias), in LINK-LOCAL coordinates: the subtree's
+// wrench is kept in the link's own axes about its own origin, where the joint torque is one component of the moment, tau = +-M[axis],
+// and goes up to the parent by the joint's rotation and the constant joint origin.  The definition works per link: a LOCAL wrench gives
+// joint torques that do not depend on the root pose, and no product of six rotations stands between a LOCAL row and its own joint.
+// Measured on MI355X against the bar of a yardstick that works per link (tests/test_gpu_generalized_forces.py), the joint rows of
+// three world-axes forms of this walk reach: about the root origin (id_links' frame; a foot's joint torque is then the difference of
+// two moments of 0.3 m x 10 N that cancel to 0.05 m x 10 N) 1.09; about the links' origins in world axes (E0^T E0 - I of an fp32
+// quaternion, unit to 1e-7, enters every LOCAL row) 1.23; about the links' origins in the root's axes (the rounding of the accumulated
+// link rotation is left) 1.10.  Returns the subtree's wrench in the PARENT's axes about the parent's origin; Q: the env's output row.
+template <int L, int END, bool CL>
+BEZ_DEV SV gf_links(const GfCtx& C, const float* st, int n, int e, float quirk_z, M3 E, V3 r, float* Q) {
+  const float q = st[(size_t)(F_Q + L - 1) * n + e];
+  SV S, cb, V = svzero();
+  link_kinematics<L>(q, 0.f, E, r, V, S, cb, quirk_z);
+  SV F = gf_bodies<CL, L>(C, E, r);
+  if constexpr (L + 1 < END) F = F + gf_links<L + 1, END, CL>(C, st, n, e, quirk_z, E, r, Q);
+  Q[5 + L] = axis_sign(L) * pick(F.a, axis_index(L)) + 0.f;
+  float sn, cs;
+  fsincos(axis_sign(L) * q, &sn, &cs);
+  const V3 xyz = mk((float)BEZ_LINK_XYZ[L][0], (float)BEZ_LINK_XYZ[L][1], L == BEZ_BOXCL_LINK ? quirk_z : (float)BEZ_LINK_XYZ[L][2]);
+  const V3 fp = gf_to_parent<L>(F.l, sn, cs);
+  return mksv(gf_to_parent<L>(F.a, sn, cs) + cross(xyz, fp), fp);
+}
+template <bool CL>
+__global__ void __launch_bounds__(GF_THREADS) generalized_forces_kernel(DynArgs D, const float* __restrict__ forces, const float* __restrict__ torques,
+                                                                        const float* __restrict__ positions, int space, int has_ball,
+                                                                        float* __restrict__ out) {
+  constexpr int NB = nb_of<CL>(), STRIDE = (3 * (NB + 1)) | 1;
+  __shared__ float in_rows[3][GF_TILE * STRIDE];
+  __shared__ float orows[GF_TILE * GF_OSTRIDE];
+  const float* st = D.st;
+  const int n = D.n, e0 = blockIdx.x * GF_TILE, ne = min(GF_TILE, n - e0);
+  const float* in[3] = {forces, torques, positions};
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if (!in[k]) continue;
+    if (has_ball) tile_load_ragged<3 * (NB + 1), STRIDE, GF_THREADS>(in_rows[k], in[k] + (size_t)e0 * (3 * (NB + 1)), ne * 3 * (NB + 1));
+    else tile_load_ragged<3 * NB, STRIDE, GF_THREADS>(in_rows[k], in[k] + (size_t)e0 * (3 * NB), ne * 3 * NB);
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < ne) {
+    int e = e0 + threadIdx.x;
+    float* Q = orows + threadIdx.x * GF_OSTRIDE;
+    auto ld = [&](int f) { return st[(size_t)f * n + e]; };
+    auto row = [&](int k) -> const float* { return in[k] ? in_rows[k] + threadIdx.x * STRIDE : nullptr; };
+    const M3 E0 = quat_to_mat(ld(F_ROOT_QUAT), ld(F_ROOT_QUAT + 1), ld(F_ROOT_QUAT + 2), ld(F_ROOT_QUAT + 3));
+    const M3 I3 = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    const V3 O = mk(0.f, 0.f, 0.f);
+    const GfCtx C = {row(0), row(1), row(2), mk(ld(F_ROOT_POS), ld(F_ROOT_POS + 1), ld(F_ROOT_POS + 2)), (space & BEZ_SPACE_LOCAL) != 0,
+                     (space & BEZ_GF_AT_ORIGIN) != 0, E0};
+    const float quirk_z = quirk_rz<CL>(D.flags);
+    // the torso's bodies: in the root's axes like the chains' totals, except ENV wrenches at ENV points, which stay in world axes,
+    // untouched by E0 (a wrench on body 0 at the root position comes out as it went in)
+    SV Fw = svzero(), F0 = svzero();
+    if (C.local || !C.X) F0 = gf_bodies<CL, 0>(C, I3, O);
+    else {
+      GfCtx Cw = C;
+      Cw.Rin = I3;
+      Fw = gf_bodies<CL, 0>(Cw, I3, O);
+    }
+    auto chain = [&](auto first, auto len) {
+      constexpr int FIRST = decltype(first)::value, LEN = decltype(len)::value;
+      static_assert(is_chain<FIRST, LEN>(), "not a chain off the torso");
+      asm volatile("" : "+v"(e), "+v"(F0.l.x));   // (opaque per chain, as in inverse_dynamics_kernel)
+      F0 = F0 + gf_links<FIRST, FIRST + LEN, CL>(C, st, n, e, quirk_z, I3, O, Q);
+    };
+    using std::integral_constant;
+    chain(integral_constant<int, 13>{}, integral_constant<int, 6>{});
+    chain(integral_constant<int, 11>{}, integral_constant<int, 2>{});
+    chain(integral_constant<int, 5>{}, integral_constant<int, 6>{});
+    chain(integral_constant<int, 3>{}, integral_constant<int, 2>{});
+    chain(integral_constant<int, 1>{}, integral_constant<int, 2>{});
+    const V3 fo = Fw.l + mul(E0, F0.l), mo = Fw.a + mul(E0, F0.a);   // the root-frame total, turned to world axes
+    Q[0] = fo.x + 0.f; Q[1] = fo.y + 0.f; Q[2] = fo.z + 0.f;
+    Q[3] = mo.x + 0.f; Q[4] = mo.y + 0.f; Q[5] = mo.z + 0.f;
+  }
+  __syncthreads();
+  tile_store<DYN_NG, GF_OSTRIDE, GF_THREADS>(orows, out + (size_t)e0 * DYN_NG, ne);
+}
+
 // ---- bez_sim_apply_body_forces: one thread per env turns the Isaac-layout inputs of its env into the pending per-link wrenches (bez_kernels.h
 // ext_wrench): forward kinematics of the current state for the link frames, LOCAL vectors and every point of application resolved now,
 // fixed bodies folded into their links, everything ADDED to what earlier calls left (read-modify-write by the env's one thread).

@@ -788,6 +788,16 @@ int bez_sim_body_accelerations(BezSim* s, const float* udot_dev, uint32_t terms,
   if (!out_dev) return fail(s, -1, "bez_sim_body_accelerations: out_dev is null");
   return LAUNCH_ASSET(s, body_accelerations_kernel, ACC_TILE, ACC_THREADS, (hipStream_t)stream, dyn_args(s), udot_dev, out_dev, terms, (int)space);
 }
+int bez_sim_generalized_forces(BezSim* s, const float* forces_dev, const float* torques_dev, const float* positions_dev, int32_t space,
+                               float* out_dev, void* stream) {
+  if (!s) return fail(s, -1, "bez_sim_generalized_forces: sim is null");
+  if (space & ~(int32_t)(BEZ_SPACE_LOCAL | BEZ_GF_AT_ORIGIN)) return fail(s, -1, "bez_sim_generalized_forces: space must be BEZ_SPACE_ENV or BEZ_SPACE_LOCAL, optionally | BEZ_GF_AT_ORIGIN");
+  if ((space & BEZ_GF_AT_ORIGIN) && positions_dev) return fail(s, -1, "bez_sim_generalized_forces: BEZ_GF_AT_ORIGIN needs positions_dev == NULL");
+  if (!forces_dev && !torques_dev) return fail(s, -1, "bez_sim_generalized_forces: forces_dev and torques_dev are both null (nothing to map)");
+  if (!out_dev) return fail(s, -1, "bez_sim_generalized_forces: out_dev is null");
+  return LAUNCH_ASSET(s, generalized_forces_kernel, GF_TILE, GF_THREADS, (hipStream_t)stream, dyn_args(s), forces_dev, torques_dev, positions_dev,
+                      (int)space, (int)s->has_ball, out_dev);
+}
 int bez_sim_set_obs_calls(BezSim* s, int64_t calls) { if (!s) return -1; s->obs_calls = calls; return 0; }
 
 int bez_sim_pre_physics(BezSim* s, const float* actions_dev, void* stream) {

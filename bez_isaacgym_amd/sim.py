@@ -62,6 +62,7 @@ SIGS = {
     "bez_sim_inverse_dynamics": (C.c_int, [vp, fp, u32, fp, vp]),
     "bez_sim_centroidal": (C.c_int, [vp, fp, fp, vp]),
     "bez_sim_body_accelerations": (C.c_int, [vp, fp, u32, i32, fp, vp]),
+    "bez_sim_generalized_forces": (C.c_int, [vp, fp, fp, fp, i32, fp, vp]),
 }
 EXPORTS = list(SIGS)
 
@@ -286,6 +287,32 @@ class BezSim:
             self._checked("out", out, ((n, nb, 6),))
         self._check(self.lib.bez_sim_body_accelerations(self.h, None if udot is None else self._ptr(udot, torch.float32, n * abi.NUM_GEN), int(terms),
                                                         space, self._ptr(out, torch.float32, n * nb * 6), self._stream()))
+        return out
+
+    # ---- generalised forces: sum over bodies of J_b^T [f; t], the map from wrenches on rigid bodies to forces on u
+    def generalized_forces(self, forces=None, torques=None, positions=None, space=abi.SPACE_ENV, at="com", out=None):
+        """(N, 24) float32: the generalised force of wrenches on the rigid bodies, in u = [root_lin, root_ang, qd] -- rows 0:3 the total
+        force, 3:6 the total moment about the root origin (world axes), 6:24 the joint torques, the rows of inverse_dynamics (include/bez_sim.h
+        "Generalised forces").  `forces`, `torques`, `positions`, `space`: what apply_body_forces takes -- float32 on the sim's device,
+        contiguous, (N*B, 3) or (N, B, 3) in RIGID_BODY_STATE order (the ball's row included where the task has one, never read), or None;
+        forces and torques must not both be None.  `at`: where a wrench acts when `positions` is None: "com", the body's centre of mass
+        (as apply_body_forces), or "origin", the body's origin -- the result is then J^T [f; t] with the Jacobian tensor's J.  `out`: a
+        tensor of the result's kind to write into; None: one buffer per sim, allocated by the first such call and overwritten by every
+        later one.  One launch on the current stream; everything is checked before the library is called."""
+        space = abi.generalized_force_space(space, at)
+        n, nb = self.num_envs, self.num_bodies
+        if forces is None and torques is None:
+            raise BezSimError("generalized_forces: forces and torques are both None (nothing to map)")
+        if positions is not None and space & abi.GF_AT_ORIGIN:
+            raise BezSimError("generalized_forces: at='origin' is the point of application when positions is None")
+        ptrs = [None if t is None else self._ptr(self._checked(name, t, ((n * nb, 3), (n, nb, 3))), torch.float32, n * nb * 3)
+                for name, t in (("forces", forces), ("torques", torques), ("positions", positions))]
+        if out is None:
+            out = self._scratch("generalized_forces", (n, abi.NUM_GEN))
+        else:
+            self._checked("out", out, ((n, abi.NUM_GEN),))
+        self._check(self.lib.bez_sim_generalized_forces(self.h, ptrs[0], ptrs[1], ptrs[2], space, self._ptr(out, torch.float32, n * abi.NUM_GEN),
+                                                        self._stream()))
         return out
 
     def refresh(self, which):

@@ -273,6 +273,31 @@ class VecTask(Env):
         from ... import abi
         return self.sim.body_accelerations(udot, abi.ACC_ALL, abi.SPACE_LOCAL)[:, self.body_index(body), 0:3]
 
+    # ---- generalised forces of wrenches on the rigid bodies (include/bez_sim.h "Generalised forces"); one launch, and what is returned is
+    # the sim's one result buffer of that kind: the next call overwrites it
+    def generalized_forces(self, forces=None, torques=None, positions=None, space="env", at="com"):
+        """(N, 24): sum over bodies of J_b^T [f; t] in u = [root_lin, root_ang, qd], rows [force; moment about the root origin; joint
+        torques]; forces / torques / positions / space as for apply_rigid_body_force_tensors, (N*B, 3) or (N, B, 3); at "com" / "origin":
+        where a wrench acts when positions is None"""
+        return self.sim.generalized_forces(forces, torques, positions, space, at)
+
+    def body_wrench_forces(self, body, force=None, torque=None, space="env", at="origin"):
+        """(N, 24): J_body^T [f; t] for (N, 3) vectors on the one rigid body `body` (a name of body_index), the generalised force of
+        operational-space control on a foot or hand; at "origin" J is the Jacobian tensor's row block of that body"""
+        if force is None and torque is None:
+            raise ValueError("body_wrench_forces: force and torque are both None")
+        b = self.body_index(body)
+        bufs = self.__dict__.get("_wrench_rows")
+        if bufs is None:   # two zero (N, B, 3) tensors per env object; each call rewrites row b of them and zeroes it again
+            bufs = self._wrench_rows = [torch.zeros(self.num_envs, self.sim.num_bodies, 3, device=self.sim.device) for _ in range(2)]
+        for buf, v in zip(bufs, (force, torque)):
+            if v is not None:
+                buf[:, b].copy_(v)
+        out = self.sim.generalized_forces(bufs[0], bufs[1], None, space, at)
+        for buf in bufs:
+            buf[:, b].zero_()
+        return out
+
     def actuator_snapshot(self):
         """(drive torque, status, joint velocity), each (N, 18), of the last physics launch: one refresh of the actuator tensors and one of
         DOF_STATE (the PPO loop's per-epoch actuator statistics)."""

@@ -432,6 +432,36 @@ int bez_sim_centroidal(BezSim* sim, float* state_dev /* (N,16) or NULL */,
 int bez_sim_body_accelerations(BezSim* sim, const float* udot_dev /* (N,24) or NULL */, uint32_t terms,
                                int32_t space /* BEZ_SPACE_ENV | BEZ_SPACE_LOCAL */, float* out_dev /* (N, NB, 6) */, void* stream);
 
+/* Generalised forces: sum over bodies of J_b^T w_b -- the last term of the equation of motion above, the map from wrenches on rigid
+ * bodies to generalised forces -- without forming J: operational-space control (tau = J^T F + h), virtual-model control on a foot or
+ * hand, contact-wrench estimation, and the generalised force a bez_sim_apply_body_forces call exerts.
+ *   forces_dev, torques_dev, positions_dev: exactly the tensors bez_sim_apply_body_forces takes -- f32 (N*B, 3) in RIGID_BODY_STATE order,
+ *     B with the ball's row where the task has a ball (22 / 21, with cleats 30 / 29) -- so the same buffers can be handed to both calls.
+ *     Any of the three may be NULL (zero forces / zero torques / the default point of application).  The ball is not part of u: its row
+ *     is never read, and a NaN there changes nothing.
+ *   space: BEZ_SPACE_ENV / BEZ_SPACE_LOCAL as for bez_sim_apply_body_forces -- a LOCAL vector is in the body's own frame (its link's), a
+ *     LOCAL point in the body's frame, an ENV point in env coordinates.  With positions_dev == NULL the point of application is the
+ *     body's own centre of mass (BEZ_BODY_COM), as in the apply call; with BEZ_GF_AT_ORIGIN OR-ed into `space` (this call only) it is
+ *     the body's ORIGIN, and the call is out = sum_b J_b^T [f_b; t_b] with J of BEZ_DYNAMICS_JACOBIAN, rows and columns as defined there.
+ *     BEZ_GF_AT_ORIGIN with a non-NULL positions_dev: rc -1.
+ *   out_dev  f32 (N, 24), env-major, in u = [root_lin, root_ang, qd]: rows 0:3 the total force in world axes, rows 3:6 the total moment
+ *     about the root origin in world axes, rows 6:24 the joint torques in DOF_STATE order -- the row convention of
+ *     bez_sim_inverse_dynamics, dual to u: u . out is the power of the wrenches.  Fixed bodies (imu_link, camera, the cleats) act on
+ *     their link at their own origin or centre of mass; the asset (cleats, box, the joint origin box + cleats moves) is the step's.
+ *   Masses, gravity rows, velocities and BEZ_FLAG_FIX_BASE play no part: the stored q and root pose are evaluated as they stand on `stream`.
+ *   A body whose force row and torque row are all zero contributes exactly nothing, whatever its position row holds; a NaN is not zero
+ *     and goes in (the rule of the apply call).  A non-finite input is written through and stays in its own env.
+ *   To the bit: all-zero inputs give 24 times +0.0f; a joint row is +0.0f when no loaded body lies on the joint's link or below it; a
+ *     wrench on body 0 alone in BEZ_SPACE_ENV whose position row equals the root position gives out[0:6] = [f; t] and +0.0f on rows
+ *     6:24.  (Every output is canonicalised with x + 0.0f: -0.0 becomes +0.0.)
+ *   One kernel launch.  The call allocates nothing, never synchronises, reads nothing on the host, writes only out_dev and leaves the
+ *   sim's state and any pending external wrenches untouched: it captures into a HIP graph.  Results do not depend on N or on an env's
+ *   place in its tile.  forces_dev and torques_dev both NULL (nothing to map), a null out_dev, a null sim or an unknown `space`: rc -1
+ *   with a message. */
+#define BEZ_GF_AT_ORIGIN 2   /* OR-ed into `space`, for this call only */
+int bez_sim_generalized_forces(BezSim* sim, const float* forces_dev, const float* torques_dev, const float* positions_dev,
+                               int32_t space, float* out_dev /* (N, 24) */, void* stream);
+
 /* gym.refresh_{actor_root_state,dof_state,rigid_body_state,net_contact_force}_tensor
  * (kick_env.py:750-753): materialise the Isaac-layout tensor from the SoA state.  ROOT_STATE, DOF_STATE, RIGID_BODY_STATE,
  * NET_CONTACT_FORCE, DOF_TARGET, PREV_LIN_VEL, FEET and GOAL need it; every other BezTensor is always live (the kernels

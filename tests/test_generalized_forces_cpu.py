@@ -1,0 +1,218 @@
+"""CPU: the C ABI declares, lists and exports bez_sim_generalized_forces; its kernel compiles for gfx950 without spills or scratch; and the
+reference that pins it on the GPU (tests/generalized_forces_numpy.gf_ref) is what it says it is -- held to identities it was not built
+from, on the states of tests/test_state_tensors_cpu.generate_states in fp64 -- and notices the mistakes it is there to catch."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+from bez_isaacgym_amd import abi
+from tests import dynamics_numpy as D
+from tests import generalized_forces_numpy as GF
+from tests import inverse_dynamics_numpy as ID
+from tests.test_state_tensors_cpu import generate_states
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = open(os.path.join(ROOT, "include", "bez_sim.h")).read()
+N = 24
+SPACES = (GF.SPACE_ENV, GF.SPACE_LOCAL)
+KINDS = ("all", "round_robin", "feet")
+
+
+def test_abi_declares_lists_and_exports_the_generalized_force_call():
+    """the header declares the function with the issue's signature and BEZ_GF_AT_ORIGIN = 2 in the section after "Body accelerations";
+    abi.py, sim.SIGS and sim.EXPORTS list it; the built library exports it; BezSim and VecTask bind it; BEZ_SIM_ABI_VERSION,
+    BEZ_TENSOR_COUNT and the BezDynamicsTensor enum are untouched"""
+    m = re.search(r"\bint bez_sim_generalized_forces\(BezSim\* sim, const float\* forces_dev, const float\* torques_dev, const float\* positions_dev,\s*"
+                  r"int32_t space, float\* out_dev /\* \(N, 24\) \*/, void\* stream\);", HEADER)
+    assert m and HEADER.index("int bez_sim_body_accelerations(") < m.start()
+    assert re.search(r"#define BEZ_GF_AT_ORIGIN 2\b", HEADER) and abi.GF_AT_ORIGIN == 2
+    assert abi.generalized_force_space("env") == 0 and abi.generalized_force_space("local", "com") == 1
+    assert abi.generalized_force_space(abi.SPACE_ENV, "origin") == 2 and abi.generalized_force_space("LOCAL", "origin") == 3
+    for bad in (dict(space="env", at="foot"), dict(space=2), dict(space="env", at=None)):
+        with pytest.raises(ValueError):
+            abi.generalized_force_space(**bad)
+    with pytest.raises(ValueError):
+        abi.body_force_space(abi.GF_AT_ORIGIN)      # the apply call's resolver keeps refusing anything but 0 and 1
+    from bez_isaacgym_amd.build import lib_path
+    from bez_isaacgym_amd.sim import EXPORTS, SIGS, BezSim
+    from bez_isaacgym_amd.tasks.base.vec_task import VecTask
+    assert "bez_sim_generalized_forces" in EXPORTS
+    assert SIGS["bez_sim_generalized_forces"] == (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p])
+    assert getattr(C.CDLL(lib_path()), "bez_sim_generalized_forces") is not None
+    assert callable(BezSim.generalized_forces) and callable(VecTask.generalized_forces) and callable(VecTask.body_wrench_forces)
+    assert int(re.search(r"#define BEZ_SIM_ABI_VERSION (\d+)", HEADER).group(1)) == 5
+    body = re.search(r"enum BezDynamicsTensor \{(.*?)\};", HEADER, re.S).group(1)
+    assert dict((m.group(1), int(m.group(2))) for m in re.finditer(r"BEZ_DYNAMICS_(\w+) = (\d+)", body)) == {"JACOBIAN": 0, "MASS_MATRIX": 1, "COUNT": 2}
+    assert abi.TENSOR_COUNT == 17
+
+
+def test_the_kernel_of_both_assets_has_no_spills_and_no_scratch(tmp_path):
+    """and sits well below inverse dynamics' 256 VGPRs (there are no inertias or velocities to carry): at most 168, the budget of three
+    waves per SIMD where 256 leaves room for one"""
+    from tests.test_body_forces_cpu import kernel_resources
+    res = kernel_resources(os.path.join(ROOT, "bez_isaacgym_amd", "csrc", "bez_sim.hip"), str(tmp_path))
+    mine = {k: v for k, v in res.items() if "generalized_forces_kernel" in k}
+    assert len(mine) == 2, sorted(res)
+    for name, (vgpr, vspill, sgpr, sspill, scratch, lds) in mine.items():
+        print("GEN_FORCES_RESOURCES %s: %d VGPRs, %d SGPRs, spills %d / %d, scratch %d B, LDS %d B" % (name, vgpr, sgpr, vspill, sspill, scratch, lds))
+        assert vspill == 0 and sspill == 0 and scratch == 0, (name, vspill, sspill, scratch)
+        assert vgpr <= 168 and 0 < lds <= 64 * 1024
+
+
+# ---------------------------------------------------------------- the reference
+
+@pytest.fixture(scope="module")
+def cases():
+    """N states (seams, joint limits, random roots) with exactly unit quaternions, for the default and the cleats model"""
+    root, dof, _ = generate_states(300)
+    pick = np.concatenate([np.arange(0, 10), np.arange(40, 300, 17)])[:N]
+    root, dof = root[pick].astype(np.float64), dof[pick].astype(np.float64)
+    root[:, 3:7] /= np.linalg.norm(root[:, 3:7], axis=1, keepdims=True)
+    return [dict(model=GF.model_of(asset), asset=asset, root=root, dof=dof) for asset in ("default", "cleats")]
+
+
+def _loads(c, kind, space, ball):
+    nbe = len(c["model"]["body_link"]) + ball
+    return [a.astype(np.float64) for a in GF.loading(kind, c["model"], c["root"], c["dof"], nbe, space)]
+
+
+def _points(c, space, X, at=None):
+    """(n, nb, 3): the points of application relative to the root origin, world axes, from forward kinematics alone"""
+    model = c["model"]
+    nb = len(model["body_link"])
+    _, rot, pos = GF.body_velocities(model, c["root"], c["dof"])
+    if X is None:
+        p = np.zeros((nb, 3)) if at == "origin" else np.asarray(model["body_com"], np.float64)
+        return pos + np.einsum("ebij,bj->ebi", rot, p)
+    if space == GF.SPACE_LOCAL:
+        return pos + np.einsum("ebij,ebj->ebi", rot, X[:, :nb])
+    return X[:, :nb] - c["root"][:, None, 0:3]
+
+
+def _world(c, space, V):
+    nb = len(c["model"]["body_link"])
+    if space == GF.SPACE_ENV:
+        return V[:, :nb]
+    return np.einsum("ebij,ebj->ebi", GF.body_velocities(c["model"], c["root"], c["dof"])[1], V[:, :nb])
+
+
+def test_virtual_power(cases):
+    """u . Q == sum_b f_b . v_point + t_b . w_b with the bodies' velocities from an independent forward-kinematics pass (velocities added
+    link by link); every loading, both spaces, positions given / NULL / NULL at the origins, with and without a ball row"""
+    worst = 0.0
+    for c in cases:
+        u = np.concatenate([c["root"][:, 7:13], c["dof"][:, :, 1]], axis=1)
+        vel, _, pos = GF.body_velocities(c["model"], c["root"], c["dof"])
+        for kind in KINDS:
+            for space in SPACES:
+                for ball in (0, 1):
+                    F, T, X = _loads(c, kind, space, ball)
+                    for Xin, at in ((X, "com"), (None, "com"), (None, "origin")):
+                        Q = GF.gf_ref(c["model"], c["root"], c["dof"], F, T, Xin, space, at)
+                        fw, tw, x = _world(c, space, F), _world(c, space, T), _points(c, space, Xin, at)
+                        vp = vel[:, :, 0:3] + np.cross(vel[:, :, 3:6], x - pos)
+                        want = (fw * vp).sum(axis=(1, 2)) + (tw * vel[:, :, 3:6]).sum(axis=(1, 2))
+                        size = (np.abs(fw) * np.abs(vp)).sum(axis=(1, 2)) + (np.abs(tw) * np.abs(vel[:, :, 3:6])).sum(axis=(1, 2))
+                        worst = max(worst, float((np.abs((u * Q).sum(axis=1) - want) / size).max()))
+    print("GEN_FORCES_POWER worst |u . Q - power| / sum |f||v| + |t||w|:", worst)
+    assert worst <= 1e-12
+
+
+def test_duality_with_the_finite_difference_jacobian(cases):
+    """Q == sum_b J_b^T [f; t + d x f], d from the body's origin to the point of application, with J from dynamics_numpy.J_ref_fd (the URDF
+    fixture's forward kinematics differenced: default asset).  The bar is J_ref_fd's OWN error: per env, its largest entry-wise distance from the analytic
+    Jacobian of tests/body_accel_numpy.J_ref (forward kinematics alone; up to 1.7e-7 on these fp32 states, whose quaternion J_ref_fd
+    normalises), times sum |w|, + 1e-12 sum |J| |w|.  The reference is handed the same normalised quaternion."""
+    from tests import body_accel_numpy as BA
+    from tests.test_state_tensors_cpu import quat_mat
+    c = cases[0]
+    J = D.J_ref_fd(c["root"].astype(np.float32), c["dof"].astype(np.float32))
+    c = dict(c, root=c["root"].astype(np.float32).astype(np.float64), dof=c["dof"].astype(np.float32).astype(np.float64))
+    c["root"][:, 3:7] /= np.linalg.norm(c["root"][:, 3:7], axis=1, keepdims=True)
+    _, _, pos = GF.body_velocities(c["model"], c["root"], c["dof"])
+    per_entry = np.array([np.abs(J[e] - BA.J_ref(c["model"], quat_mat(c["root"][e, 3:7]), c["dof"][e, :, 0])).max() for e in range(N)])
+    assert 0 < per_entry.max() < 1e-6
+    worst = 0.0
+    for kind in KINDS:
+        for space in SPACES:
+            F, T, X = _loads(c, kind, space, 1)
+            for Xin, at in ((X, "com"), (None, "com"), (None, "origin")):
+                Q = GF.gf_ref(c["model"], c["root"], c["dof"], F, T, Xin, space, at)
+                fw, tw, x = _world(c, space, F), _world(c, space, T), _points(c, space, Xin, at)
+                w = np.concatenate([fw, tw + np.cross(x - pos, fw)], axis=2)
+                want = np.einsum("ebrc,ebr->ec", J, w)
+                tol = (per_entry * np.abs(w).sum(axis=(1, 2)))[:, None] + 1e-12 * np.einsum("ebrc,ebr->ec", np.abs(J), np.abs(w))
+                worst = max(worst, float((np.abs(Q - want) / tol).max()))
+    print("GEN_FORCES_DUALITY worst |Q - J^T w| / bar:", worst)
+    assert worst <= 1.0
+
+
+def test_linear_in_the_wrenches(cases):
+    for c in cases:
+        for space in SPACES:
+            F1, T1, X = _loads(c, "all", space, 0)
+            F2, T2, _ = [a.astype(np.float64) for a in GF.loading("all", c["model"], c["root"], c["dof"], F1.shape[1], space, seed=43)]
+            q = lambda F, T: GF.gf_ref(c["model"], c["root"], c["dof"], F, T, X, space)
+            a, b = q(F1, T1), q(F2, T2)
+            both = q(2.5 * F1 - 0.75 * F2, 2.5 * T1 - 0.75 * T2)
+            assert np.abs(both - (2.5 * a - 0.75 * b)).max() <= 1e-12 * (np.abs(a).max() + np.abs(b).max())
+            assert np.abs(q(F1, None) + q(None, T1) - a).max() <= 1e-12 * np.abs(a).max()
+        assert not GF.gf_ref(c["model"], c["root"], c["dof"], np.zeros_like(F1), np.zeros_like(T1), X, GF.SPACE_ENV).any()
+
+
+def test_weights_give_minus_the_gravity_term_of_inverse_dynamics(cases):
+    """the weights m_b g at the bodies' centres of mass (NULL positions) map to minus the gravity term of inverse_dynamics_numpy.id_ref, with
+    the bodies' masses from tests/golden/urdf_bodies.json (not the model's link table) and a mass-scale row.  Both sides are fp64 sums
+    of a few hundred products of the same numbers: the bar is 1e-12 of the robot's weight (in N on the force rows, N m on the others)."""
+    from tests import urdf_independent as U
+    c = cases[0]
+    model = c["model"]
+    g = np.array([0.3, -0.2, -9.81])
+    scale = np.random.default_rng(3).uniform(0.5, 1.5, 19)
+    worst = np.zeros(3)
+    for ms in (None, scale):
+        bodies = U.load_fixture() if ms is None else D.scaled_bodies(U.load_fixture(), ms, model["body_link"])
+        mass = np.array([B["mass"] for B in bodies])
+        assert mass.shape == (len(model["body_link"]),)
+        F = np.broadcast_to(mass[None, :, None] * g[None, None, :], (N, mass.shape[0], 3))
+        Q = GF.gf_ref(model, c["root"], c["dof"], F, None, None, GF.SPACE_ENV, "com")
+        for e in range(N):
+            want = ID.id_ref(model, c["root"][e, 3:7], np.zeros(6), c["dof"][e, :, 0], np.zeros(18), None, g, ms, 0.0, ID.ID_GRAVITY)
+            err = np.abs(Q[e] + want)
+            worst = np.maximum(worst, [err[sl].max() for _, sl in GF.BLOCKS])
+            assert err.max() <= 1e-12 * mass.sum() * np.linalg.norm(g), (e, err)
+    print("GEN_FORCES_WEIGHTS worst |Q(weights) + gravity term| per block:", worst)
+
+
+def test_the_reference_is_sensitive(cases):
+    """a body offset ignored, two bodies swapped, two DOFs swapped, LOCAL treated as ENV: each moves the reference by more than 100x the
+    fp32 yardstick's error on the states of generate_states.  The ignored offset is planted under NULL positions (centres of mass and
+    the camera's offset), the others under given points."""
+    root, dof, _ = generate_states(64)
+    perm = np.arange(18); perm[[7, 8]] = perm[[8, 7]]       # two DOFs of the left leg
+    for c in cases:
+        model = c["model"]
+        nb, names = len(model["body_link"]), model["body_names"]
+        for space in SPACES:
+            F, T, X = GF.loading("all", model, root, dof, nb + 1, space)
+            base = GF.gf_ref(model, root, dof, F, T, X, space)
+            err32 = GF.yardstick_error(base, model, root, dof, F, T, X, space).max()
+            assert 0 < err32 < 1e-5 * np.abs(base).max()
+            moved = {}
+            bp = np.arange(nb + 1); a, b = names.index("/left_forearm"), names.index("/left_thigh"); bp[[a, b]] = bp[[b, a]]
+            moved["bodies_swapped"] = GF.gf_ref(model, root, dof, F[:, bp], T[:, bp], X[:, bp], space)
+            sw = GF.gf_ref(model, root, dof[:, perm], F, T, X, space)
+            sw[:, 6:] = sw[:, 6:][:, perm]
+            moved["dofs_swapped"] = sw
+            if space == GF.SPACE_LOCAL:
+                moved["local_as_env"] = GF.gf_ref(model, root, dof, F, T, X, space, mutate="local_as_env")
+            for what, m in moved.items():
+                assert np.abs(m - base).max() > 100 * err32, (c["asset"], space, what, np.abs(m - base).max(), err32)
+            for at in ("com", "origin"):
+                b0 = GF.gf_ref(model, root, dof, F, T, None, space, at)
+                e0 = GF.yardstick_error(b0, model, root, dof, F, T, None, space, at).max()
+                m0 = GF.gf_ref(model, root, dof, F, T, None, space, at, mutate="offset_ignored")
+                assert np.abs(m0 - b0).max() > 100 * e0, (c["asset"], space, at, np.abs(m0 - b0).max(), e0)

@@ -1,9 +1,10 @@
 """Times one of the dynamics queries at num_envs = 4096 beside its yardsticks in the same run.  Prints one JSON line.
 
-  python tools/dynamics_bench.py {tensors,inverse_dynamics,centroidal,body_accelerations} [--num-envs 4096] [--launches 200] [--warmup 20] [--cleats]
+  python tools/dynamics_bench.py {tensors,inverse_dynamics,centroidal,body_accelerations,generalized_forces} [--num-envs 4096] [--launches 200] [--warmup 20] [--cleats]
   python tools/dynamics_bench.py inverse_dynamics > profiles/inverse_dynamics_bench.json      (the committed records)
   python tools/dynamics_bench.py centroidal > profiles/centroidal_bench.json
   python tools/dynamics_bench.py body_accelerations > profiles/body_accelerations_bench.json
+  python tools/dynamics_bench.py generalized_forces > profiles/generalized_forces_bench.json
 
 tensors: bez_sim_refresh_dynamics_tensors (the Jacobian, the mass matrix, both) beside a plain device fill of the same bytes -- the kernel
 is store-bound by construction, so the fill (hipMemsetAsync over the very buffer the refresh writes) is its yardstick.
@@ -17,6 +18,9 @@ body_accelerations: bez_sim_body_accelerations (motion terms in world axes; all 
 beside refresh_rigid_body_state -- the same per-lane forward kinematics and a read-out of the same kind -- beside bez_sim_inverse_dynamics
 with all terms -- whose outward half it is -- and beside the route the call replaces for the UDOT term: a Jacobian refresh followed by
 torch.matmul(J, udot).
+generalized_forces: bez_sim_generalized_forces (every body loaded, ENV space with points; one body loaded -- the skipped bodies' rows are
+still brought into LDS) beside refresh_rigid_body_state, beside bez_sim_inverse_dynamics with all terms -- whose return sweep it is -- and
+beside the route the call replaces: a Jacobian refresh followed by torch.einsum of J with the wrenches at the bodies' origins.
 
 Each figure is the median over --launches (>= 200) single launches, each between its own pair of events on one stream, after --warmup
 launches.  Nothing flushes the caches between launches, for a call and its yardsticks alike.
@@ -180,9 +184,50 @@ def body_accelerations(sim, n, t):
     return res
 
 
+def generalized_forces(sim, n, t):
+    sim.step(torch.rand(n * 18, device=DEV) * 2 - 1)   # a state off the reset pose
+    nbe = sim.num_bodies
+    nb = nbe - (1 if sim.has_ball else 0)
+    F, T = torch.rand(n, nbe, 3, device=DEV) * 20 - 10, torch.rand(n, nbe, 3, device=DEV) * 2 - 1
+    X = sim.refresh(abi.TENSOR_RIGID_BODY_STATE).view(n, nbe, 13)[:, :, 0:3] + (torch.rand(n, nbe, 3, device=DEV) * 0.2 - 0.1)
+    X = X.contiguous()
+    F1, T1 = torch.zeros_like(F), torch.zeros_like(T)
+    F1[:, nb - 1], T1[:, nb - 1] = F[:, nb - 1], T[:, nb - 1]   # a foot (with cleats: its last cleat)
+    out = torch.zeros(n, abi.NUM_GEN, device=DEV)
+    tau = torch.zeros(n, abi.NUM_GEN, device=DEV)
+    udot = torch.rand(n, abi.NUM_GEN, device=DEV) * 20 - 10
+    J = sim.dynamics_tensor("jacobian").view(n, nb, 6, abi.NUM_GEN)
+    W = torch.cat([F[:, :nb], T[:, :nb]], dim=2).contiguous()
+    jw = torch.zeros(n, abi.NUM_GEN, device=DEV)
+
+    def replaced():
+        sim.refresh_dynamics_tensors("jacobian")
+        jw.copy_(torch.einsum("ebrc,ebr->ec", J, W))
+
+    res = {"bytes_in": 3 * F.numel() * 4, "bytes_out": out.numel() * 4,
+           "generalized_forces_all_bodies": t(lambda: sim.generalized_forces(F, T, X, abi.SPACE_ENV, out=out)),
+           "generalized_forces_all_bodies_local": t(lambda: sim.generalized_forces(F, T, X, abi.SPACE_LOCAL, out=out)),
+           "generalized_forces_all_bodies_at_origin": t(lambda: sim.generalized_forces(F, T, None, abi.SPACE_ENV, "origin", out=out)),
+           "generalized_forces_one_body": t(lambda: sim.generalized_forces(F1, T1, X, abi.SPACE_ENV, out=out)),
+           "refresh_rigid_body_state": t(lambda: sim.refresh(abi.TENSOR_RIGID_BODY_STATE)),
+           "inverse_dynamics_all_terms": t(lambda: sim.inverse_dynamics(udot, abi.ID_ALL, tau)),
+           "jacobian_refresh_plus_einsum": t(replaced)}
+    mine = res["generalized_forces_all_bodies"]["median_us"]
+    res["ratio_to_rigid_body_refresh"] = round(mine / res["refresh_rigid_body_state"]["median_us"], 3)
+    res["ratio_to_inverse_dynamics"] = round(mine / res["inverse_dynamics_all_terms"]["median_us"], 3)
+    res["ratio_to_replaced_route"] = round(res["generalized_forces_all_bodies_at_origin"]["median_us"] / res["jacobian_refresh_plus_einsum"]["median_us"], 3)
+    # the two routes agree
+    sim.generalized_forces(F, T, None, abi.SPACE_ENV, "origin", out=out)
+    replaced()
+    torch.cuda.synchronize()
+    res["max_abs_difference_of_the_two_routes"] = float((out - jw).abs().max())
+    assert torch.isfinite(out).all()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("call", choices=["tensors", "inverse_dynamics", "centroidal", "body_accelerations"])
+    ap.add_argument("call", choices=["tensors", "inverse_dynamics", "centroidal", "body_accelerations", "generalized_forces"])
     ap.add_argument("--num-envs", type=int, default=4096)
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)

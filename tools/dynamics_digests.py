@@ -8,7 +8,8 @@ One line per asset x task x parameters (the defaults; random BEZ_PARAM_MASS_SCAL
 the Jacobian and the mass matrix each refreshed alone, then both in one launch; inverse_dynamics for ID_ALL, ID_INERTIA, ID_VELOCITY and
 ID_GRAVITY, centroidal (state, matrix) and body_accelerations for ACC_UDOT, ACC_VELOCITY, ACC_GRAVITY, ACC_MOTION (world axes) and ACC_ALL
 (the bodies' frames), each into 16-byte aligned buffers and into views 4 bytes off (the kernels' scalar path).  A library without
-bez_sim_body_accelerations (BEZ_SIM_LIB naming an older build) prints no acc_* entries."""
+bez_sim_body_accelerations (BEZ_SIM_LIB naming an older build) prints no acc_* entries, one without bez_sim_generalized_forces no gf_*
+entries (wrenches on every body; ENV with points, LOCAL with points, NULL positions at the centres of mass and at the origins)."""
 import hashlib
 import os
 import sys
@@ -65,6 +66,18 @@ def main():
                         d["acc_" + where] = digest(*[sim.body_accelerations(u, terms, space, out).clone() for terms, space in
                                                      ((abi.ACC_UDOT, "env"), (abi.ACC_VELOCITY, "env"), (abi.ACC_GRAVITY, "env"), (abi.ACC_MOTION, "env"),
                                                       (abi.ACC_ALL, "local"))])
+                    for where, make in (("aligned", lambda shape: torch.zeros(shape, device="cuda:0")), ("offset", off4)):
+                        if not hasattr(sim.lib, "bez_sim_generalized_forces"):
+                            break
+                        gen = torch.Generator().manual_seed(11)
+                        rows = []
+                        for lo, hi in ((-10.0, 10.0), (-1.0, 1.0), (-0.1, 0.1)):
+                            t = make((n, sim.num_bodies, 3))
+                            t.copy_(torch.rand(n, sim.num_bodies, 3, generator=gen) * (hi - lo) + lo)
+                            rows.append(t)
+                        out = make((n, NG))
+                        d["gf_" + where] = digest(*[sim.generalized_forces(rows[0], rows[1], x, space, at, out).clone() for x, space, at in
+                                                    ((rows[2], "env", "com"), (rows[2], "local", "com"), (None, "env", "com"), (None, "local", "origin"))])
                     sim.close()
                     print("%-7s %-8s %-7s n=%-3d %s" % (asset, task, params, n, " ".join("%s=%s" % kv for kv in d.items())), flush=True)
 
