@@ -54,6 +54,14 @@ DOF_FORCE_KEY = "env.enableDofForceSensors"   # this build's task key for FLAG_D
 SPACE_ENV = 0                   # bez_sim_apply_body_forces: world axes / world points (gymapi.ENV_SPACE)
 SPACE_LOCAL = 1                 # the body's own frame (gymapi.LOCAL_SPACE)
 GF_AT_ORIGIN = 2                # bez_sim_generalized_forces only, OR-ed into the space: without positions, wrenches act at the bodies' origins
+# bez_sim_limb_ik (include/bez_sim.h "Limb inverse kinematics", BezSim.limb_ik): the five chains off the torso in the order of their first
+# DOF, their DOF ranges and end bodies; targets are (N, IK_CHAINS, 7) [position, quaternion xyzw], errors (N, IK_CHAINS, 6)
+IK_CHAINS = 5
+IK_SPACE_ENV, IK_SPACE_ROOT = 0, 1
+IK_MAX_ITERS = 64
+IK_CHAIN_NAMES = ("head", "left_arm", "left_leg", "right_arm", "right_leg")
+IK_CHAIN_DOFS = ((0, 2), (2, 4), (4, 10), (10, 12), (12, 18))
+IK_END_BODIES = ("/head", "/left_forearm", "/left_foot", "/right_forearm", "/right_foot")
 HEALTH_NONFINITE = 1            # health word bits (TENSOR_HEALTH, BezSim.health)
 HEALTH_SPIN_TIMEOUT = 2
 TASK_KICK, TASK_WALK, TASK_ORIENT = 0, 1, 2
@@ -327,3 +335,68 @@ def generalized_force_space(space, at="com"):
     if not isinstance(at, str) or at.strip().lower() not in ("com", "origin"):
         raise ValueError("at must be 'com' or 'origin', got %r" % (at,))
     return body_force_space(space) | (GF_AT_ORIGIN if at.strip().lower() == "origin" else 0)
+
+
+class BezIkParams(C.Structure):
+    """include/bez_sim.h BezIkParams, passed to bez_sim_limb_ik by pointer and to its kernel by value"""
+    _fields_ = [
+        ("weight", (C.c_float * 2) * IK_CHAINS),
+        ("offset", (C.c_float * 3) * IK_CHAINS),
+        ("damping", C.c_float),
+        ("max_step", C.c_float),
+        ("iters", C.c_int32),
+        ("space", C.c_int32),
+    ]
+
+
+def ik_space(space):
+    """IK_SPACE_ENV / IK_SPACE_ROOT from the int or from "env" / "root" (any case); anything else raises ValueError."""
+    if isinstance(space, str):
+        key = space.strip().lower()
+        if key in ("env", "root"):
+            return IK_SPACE_ENV if key == "env" else IK_SPACE_ROOT
+        raise ValueError("space must be 'env' or 'root', got %r" % space)
+    if isinstance(space, bool) or not isinstance(space, int) or space not in (IK_SPACE_ENV, IK_SPACE_ROOT):
+        raise ValueError("space must be IK_SPACE_ENV (0) or IK_SPACE_ROOT (1), got %r" % (space,))
+    return int(space)
+
+
+def ik_params(weights, offsets=None, damping=0.05, max_step=0.0, iters=1, space=IK_SPACE_ENV):
+    """The BezIkParams of a bez_sim_limb_ik call, every argument checked here (ValueError) before the library sees it.  weights:
+    (IK_CHAINS, 2) [w_pos, w_rot] >= 0, finite; a chain with both 0 is not asked for.  offsets: (IK_CHAINS, 3), finite, or None for zero.
+    damping: a positive finite number.  max_step: > 0 the largest |dq_i| of one iteration, <= 0 no limit; not NaN.  iters: an int in
+    0 .. IK_MAX_ITERS.  space: ik_space()."""
+    import operator
+    p = BezIkParams()
+    rows = [list(r) for r in weights] if weights is not None else None
+    if rows is None or len(rows) != IK_CHAINS or any(len(r) != 2 for r in rows):
+        raise ValueError("weights must be (%d, 2): [w_pos, w_rot] per chain (%s)" % (IK_CHAINS, ", ".join(IK_CHAIN_NAMES)))
+    for c, r in enumerate(rows):
+        for k, w in enumerate(r):
+            w = float(w)
+            if not math.isfinite(w) or w < 0.0:
+                raise ValueError("weights[%d][%d] must be finite and >= 0, got %r" % (c, k, w))
+            p.weight[c][k] = w
+    if offsets is not None:
+        rows = [list(r) for r in offsets]
+        if len(rows) != IK_CHAINS or any(len(r) != 3 for r in rows):
+            raise ValueError("offsets must be (%d, 3) or None" % IK_CHAINS)
+        for c, r in enumerate(rows):
+            for k, o in enumerate(r):
+                o = float(o)
+                if not math.isfinite(o):
+                    raise ValueError("offsets[%d][%d] must be finite, got %r" % (c, k, o))
+                p.offset[c][k] = o
+    damping, max_step = float(damping), float(max_step)
+    if not math.isfinite(damping) or damping <= 0.0:
+        raise ValueError("damping must be a positive finite number, got %r" % damping)
+    if math.isnan(max_step):
+        raise ValueError("max_step is NaN (<= 0 means no step limit)")
+    try:   # any integer type (numpy and torch scalars included), never a bool or a float
+        iters = None if isinstance(iters, bool) else operator.index(iters)
+    except TypeError:
+        iters = None
+    if iters is None or not 0 <= iters <= IK_MAX_ITERS:
+        raise ValueError("iters must be an integer in 0 .. %d" % IK_MAX_ITERS)
+    p.damping, p.max_step, p.iters, p.space = damping, max_step, iters, ik_space(space)
+    return p

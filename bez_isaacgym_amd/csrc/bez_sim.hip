@@ -798,6 +798,25 @@ int bez_sim_generalized_forces(BezSim* s, const float* forces_dev, const float* 
   return LAUNCH_ASSET(s, generalized_forces_kernel, GF_TILE, GF_THREADS, (hipStream_t)stream, dyn_args(s), forces_dev, torques_dev, positions_dev,
                       (int)space, (int)s->has_ball, out_dev);
 }
+int bez_sim_limb_ik(BezSim* s, const float* targets_dev, const BezIkParams* params, float* q_out_dev, float* err_out_dev, void* stream) {
+  if (!s) return fail(s, -1, "bez_sim_limb_ik: sim is null");
+  if (!targets_dev) return fail(s, -1, "bez_sim_limb_ik: targets_dev is null");
+  if (!params) return fail(s, -1, "bez_sim_limb_ik: params is null");
+  if (!q_out_dev && !err_out_dev) return fail(s, -1, "bez_sim_limb_ik: q_out_dev and err_out_dev are both null (nothing to write)");
+  const BezIkParams& p = *params;
+  if (p.iters < 0 || p.iters > BEZ_IK_MAX_ITERS) return fail(s, -1, "bez_sim_limb_ik: iters must be in 0 .. BEZ_IK_MAX_ITERS");
+  if (!(std::isfinite(p.damping) && p.damping > 0.f)) return fail(s, -1, "bez_sim_limb_ik: damping must be a positive finite number");
+  if (std::isnan(p.max_step)) return fail(s, -1, "bez_sim_limb_ik: max_step is NaN (<= 0 means no step limit)");
+  for (int c = 0; c < BEZ_IK_CHAINS; ++c) {
+    for (int k = 0; k < 2; ++k)
+      if (!(std::isfinite(p.weight[c][k]) && p.weight[c][k] >= 0.f)) return fail(s, -1, "bez_sim_limb_ik: a weight is negative or not finite");
+    for (int k = 0; k < 3; ++k)
+      if (!std::isfinite(p.offset[c][k])) return fail(s, -1, "bez_sim_limb_ik: an offset is not finite");
+  }
+  if (p.space != BEZ_IK_SPACE_ENV && p.space != BEZ_IK_SPACE_ROOT) return fail(s, -1, "bez_sim_limb_ik: space must be BEZ_IK_SPACE_ENV or BEZ_IK_SPACE_ROOT");
+  return LAUNCH_ASSET(s, limb_ik_kernel, IK_TILE, IK_THREADS, (hipStream_t)stream, dyn_args(s), s->dr[BEZ_PARAM_DOF_LOWER], s->dr[BEZ_PARAM_DOF_UPPER],
+                      targets_dev, p, q_out_dev, err_out_dev);
+}
 int bez_sim_set_obs_calls(BezSim* s, int64_t calls) { if (!s) return -1; s->obs_calls = calls; return 0; }
 
 int bez_sim_pre_physics(BezSim* s, const float* actions_dev, void* stream) {

@@ -63,6 +63,7 @@ SIGS = {
     "bez_sim_centroidal": (C.c_int, [vp, fp, fp, vp]),
     "bez_sim_body_accelerations": (C.c_int, [vp, fp, u32, i32, fp, vp]),
     "bez_sim_generalized_forces": (C.c_int, [vp, fp, fp, fp, i32, fp, vp]),
+    "bez_sim_limb_ik": (C.c_int, [vp, fp, C.POINTER(abi.BezIkParams), fp, fp, vp]),
 }
 EXPORTS = list(SIGS)
 
@@ -314,6 +315,37 @@ class BezSim:
         self._check(self.lib.bez_sim_generalized_forces(self.h, ptrs[0], ptrs[1], ptrs[2], space, self._ptr(out, torch.float32, n * abi.NUM_GEN),
                                                         self._stream()))
         return out
+
+    # ---- limb inverse kinematics: damped least squares on each of the five chains off the torso
+    def limb_ik(self, targets, weights, offsets=None, damping=0.05, max_step=0.0, iters=1, space="env", out=None, err_out=None):
+        """(q, err): q (N, 18) float32 joint angles in DOF_STATE order after `iters` damped-least-squares iterations per chain from the
+        current state's q, err (N, 5, 6) the pose error [position; 2 sin(theta/2) axis] at that q, in the root's axes (include/bez_sim.h
+        "Limb inverse kinematics").  `targets`: (N, 5, 7) float32 on the sim's device, contiguous: per chain (abi.IK_CHAIN_NAMES) the wanted
+        position and quaternion xyzw of the controlled frame -- space "env": as RIGID_BODY_STATE rows carry them; "root": relative to the
+        root origin in the root's axes.  `weights` (5, 2) [w_pos, w_rot] >= 0 per chain, both 0: the chain is left alone; `offsets` (5, 3)
+        or None: the controlled frame is the chain's end body (abi.IK_END_BODIES) displaced by this in its own frame; `damping` lambda > 0;
+        `max_step` > 0: the largest |dq_i| of one iteration, <= 0: none; `iters` 0 .. abi.IK_MAX_ITERS (0: the pose error of the current
+        state).  `out`, `err_out`: tensors of the results' kinds to write into; None: one buffer of each kind per sim, allocated by the
+        first such call and overwritten by every later one.  The state is untouched.  One launch on the current stream; everything is
+        checked before the library is called."""
+        try:
+            params = abi.ik_params(weights, offsets, damping, max_step, iters, space)
+        except ValueError as e:
+            raise BezSimError("limb_ik: %s" % e)
+        n = self.num_envs
+        self._checked("targets", targets, ((n, abi.IK_CHAINS, 7), (n * abi.IK_CHAINS, 7)))
+        if out is None:
+            out = self._scratch("limb_ik_q", (n, abi.NUM_DOFS))
+        else:
+            self._checked("out", out, ((n, abi.NUM_DOFS),))
+        if err_out is None:
+            err_out = self._scratch("limb_ik_err", (n, abi.IK_CHAINS, 6))
+        else:
+            self._checked("err_out", err_out, ((n, abi.IK_CHAINS, 6),))
+        self._check(self.lib.bez_sim_limb_ik(self.h, self._ptr(targets, torch.float32, n * abi.IK_CHAINS * 7), C.byref(params),
+                                             self._ptr(out, torch.float32, n * abi.NUM_DOFS),
+                                             self._ptr(err_out, torch.float32, n * abi.IK_CHAINS * 6), self._stream()))
+        return out, err_out
 
     def refresh(self, which):
         self._check(self.lib.bez_sim_refresh_tensor(self.h, which, self._stream()))

@@ -298,6 +298,47 @@ class VecTask(Env):
             buf[:, b].zero_()
         return out
 
+    # ---- limb inverse kinematics (include/bez_sim.h "Limb inverse kinematics"); one launch, and what is returned are the sim's two result
+    # buffers of that kind: the next call overwrites them.  Chains: abi.IK_CHAIN_NAMES, end bodies abi.IK_END_BODIES
+    def limb_ik(self, targets, weights, offsets=None, damping=0.05, max_step=0.0, iters=1, space="env", out=None, err_out=None):
+        """((N, 18) joint angles, (N, 5, 6) pose errors at them) after `iters` damped-least-squares iterations per chain towards `targets`
+        (N, 5, 7) [position, quaternion xyzw]; weights (5, 2) [w_pos, w_rot], both 0 leaves a chain alone; offsets (5, 3) or None; space
+        "env" (as RIGID_BODY_STATE rows) or "root" (relative to the root, in its axes).  The state is not written: hand the angles to
+        set_dof_position_target_tensor or a setter."""
+        return self.sim.limb_ik(targets, weights, offsets, damping, max_step, iters, space, out, err_out)
+
+    def limb_pose_error(self, targets, weights=None, offsets=None, space="env"):
+        """(N, 5, 6): [p_des - p ; 2 sin(theta/2) axis] of the current state's controlled frames against `targets`, in the root's axes;
+        weights only select the chains (default: all five)"""
+        from ... import abi
+        if weights is None:
+            weights = [[1.0, 1.0]] * abi.IK_CHAINS
+        return self.sim.limb_ik(targets, weights, offsets, iters=0, space=space)[1]
+
+    def limb_targets(self):
+        """(N, 5, 7): the current poses of the five end bodies as RIGID_BODY_STATE reports them (one refresh) -- the "env" targets that
+        hold every limb where it is"""
+        from ... import abi
+        rb = self.sim.refresh(abi.TENSOR_RIGID_BODY_STATE).view(self.num_envs, -1, 13)
+        return rb[:, [self.body_index(b) for b in abi.IK_END_BODIES], 0:7].contiguous()
+
+    def ik_offset(self, body):
+        """(chain index, (3,) offset) with which limb_ik controls the frame of `body`, a rigid body fixed to a chain's end link (/camera,
+        a cleat, the end body itself): its origin relative to the end body's, in that body's frame -- offsets[chain] = the offset"""
+        from ... import abi
+        b = self.body_index(body)
+        model = self.__dict__.get("_ik_model")
+        if model is None:
+            import json
+            import os
+            model = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "model", "bez_model.json")))
+            model = self._ik_model = model["cleats"] if int(self.sim.cfg.flags) & abi.FLAG_CLEATS else model
+        for c, end in enumerate(abi.IK_END_BODIES):
+            e = self.body_index(end)
+            if model["body_link"][b] == model["body_link"][e]:
+                return c, tuple(float(x) - float(y) for x, y in zip(model["body_offset"][b], model["body_offset"][e]))
+        raise ValueError("rigid body %r is not fixed to the end link of a chain (%s)" % (body, ", ".join(abi.IK_END_BODIES)))
+
     def actuator_snapshot(self):
         """(drive torque, status, joint velocity), each (N, 18), of the last physics launch: one refresh of the actuator tensors and one of
         DOF_STATE (the PPO loop's per-epoch actuator statistics)."""

@@ -462,6 +462,56 @@ int bez_sim_body_accelerations(BezSim* sim, const float* udot_dev /* (N,24) or N
 int bez_sim_generalized_forces(BezSim* sim, const float* forces_dev, const float* torques_dev, const float* positions_dev,
                                int32_t space, float* out_dev /* (N, 24) */, void* stream);
 
+/* Limb inverse kinematics: damped least squares per chain -- which joint angles put a foot, a hand or the camera at a pose.  The tree is
+ * five serial chains off the torso with disjoint joints, in the order of their first DOF:
+ *     0 head (DOF 0:2, end body /head), 1 left arm (2:4, /left_forearm), 2 left leg (4:10, /left_foot), 3 right arm (10:12,
+ *     /right_forearm), 4 right leg (12:18, /right_foot);   the end body of a chain is the body of its last link,
+ * so a torso-relative problem for all five end bodies is five independent problems of size 2, 2, 6, 2, 6, each solved in registers; no
+ * Jacobian tensor is formed.
+ *   targets_dev  f32 (N, 5, 7), env-major: per chain the wanted position (3) and orientation (quaternion xyzw, normalised by the call) of
+ *     the controlled frame.  BEZ_IK_SPACE_ENV: as RIGID_BODY_STATE rows carry them (env position, world quaternion) -- they are taken into
+ *     the root's frame once, by the state's root pose (its quaternion used as it stands, as every other query uses it).
+ *     BEZ_IK_SPACE_ROOT: relative to the root origin in the root's axes (what a gait generator emits); the root pose is then not read.
+ *   params (by value into the launch): weight[c] = {w_pos, w_rot} >= 0 on the squared position / rotation error; both 0: chain c is not
+ *     asked for.  offset[c]: the controlled frame is the chain's end body displaced by this vector, in that body's frame (same axes).
+ *     damping lambda > 0; max_step > 0: the largest |dq_i| of one iteration (the chain's step is scaled as a whole), <= 0: no limit;
+ *     iters 0 .. BEZ_IK_MAX_ITERS; space.
+ *   The iteration of chain c with k joints, on a private copy of its k angles that starts from the state's q, `iters` times:
+ *     1. forward kinematics of the chain in the root's axes relative to the root origin (the asset's, the joint origin box + cleats moves
+ *        included): the controlled frame's origin p and rotation R, the joints' axes a_j and origins r_j;
+ *     2. e = [p_des - p ; 2 sign(w) (x, y, z)] with (x, y, z, w) the quaternion of R_des R^T, sign(0) = +1 (the rotation part is
+ *        2 sin(theta / 2) axis);
+ *     3. J_j = [a_j x (p - r_j) ; a_j];
+ *     4. (J^T W J + lambda^2 I) dq = J^T W e with W = diag(w_pos x3, w_rot x3), by a k x k Cholesky factorisation;
+ *     5. dq is scaled so that max |dq_i| <= max_step;
+ *     6. q <- clamp(q + dq, lower, upper), the limits the env's BEZ_PARAM_DOF_LOWER / BEZ_PARAM_DOF_UPPER rows where set, else the model's.
+ *   q_out_dev    f32 (N, 18) in DOF_STATE order, or NULL: the angles after the last iteration.
+ *   err_out_dev  f32 (N, 5, 6), or NULL: e of step 2 at the final q (one more pass of steps 1 and 2), unweighted: iters = 0 is a pure
+ *     pose-error query of the current state.
+ *   To the bit: a chain with both weights 0 returns the state's q for its joints (unclamped) and +0.0f error rows, and nothing of its
+ *     target row enters any output (a NaN there is harmless); a chain's outputs do not depend on any other chain's target, weights or
+ *     offset; iters = 0 returns the state's q; results do not depend on N, on an env's place in its tile or on the buffers' alignment.
+ *     A non-finite target on an active chain makes that chain's q_out (iters >= 1) and every error row it enters non-finite, and no
+ *     other chain's.  lambda^2 must stay above the fp32 rounding of J^T W J (about 1e-6 of its largest entry).
+ *   One kernel launch with params in its arguments.  The call allocates nothing, copies nothing, never synchronises and writes only the
+ *   two outputs: the sim's state and every tensor are untouched, and it captures into a HIP graph.  rc -1 with a message: a null sim,
+ *   targets_dev or params, both outputs NULL, iters out of range, damping not a positive finite number, a negative or non-finite weight,
+ *   a non-finite offset, a NaN max_step, an unknown space. */
+#define BEZ_IK_CHAINS 5
+#define BEZ_IK_SPACE_ENV  0
+#define BEZ_IK_SPACE_ROOT 1
+#define BEZ_IK_MAX_ITERS 64
+typedef struct BezIkParams {
+  float weight[BEZ_IK_CHAINS][2];
+  float offset[BEZ_IK_CHAINS][3];
+  float damping;
+  float max_step;
+  int32_t iters;
+  int32_t space;
+} BezIkParams;
+int bez_sim_limb_ik(BezSim* sim, const float* targets_dev /* (N,5,7) */, const BezIkParams* params,
+                    float* q_out_dev /* (N,18) or NULL */, float* err_out_dev /* (N,5,6) or NULL */, void* stream);
+
 /* gym.refresh_{actor_root_state,dof_state,rigid_body_state,net_contact_force}_tensor
  * (kick_env.py:750-753): materialise the Isaac-layout tensor from the SoA state.  ROOT_STATE, DOF_STATE, RIGID_BODY_STATE,
  * NET_CONTACT_FORCE, DOF_TARGET, PREV_LIN_VEL, FEET and GOAL need it; every other BezTensor is always live (the kernels

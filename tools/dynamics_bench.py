@@ -1,10 +1,11 @@
 """Times one of the dynamics queries at num_envs = 4096 beside its yardsticks in the same run.  Prints one JSON line.
 
-  python tools/dynamics_bench.py {tensors,inverse_dynamics,centroidal,body_accelerations,generalized_forces} [--num-envs 4096] [--launches 200] [--warmup 20] [--cleats]
+  python tools/dynamics_bench.py {tensors,inverse_dynamics,centroidal,body_accelerations,generalized_forces,limb_ik} [--num-envs 4096] [--launches 200] [--warmup 20] [--cleats]
   python tools/dynamics_bench.py inverse_dynamics > profiles/inverse_dynamics_bench.json      (the committed records)
   python tools/dynamics_bench.py centroidal > profiles/centroidal_bench.json
   python tools/dynamics_bench.py body_accelerations > profiles/body_accelerations_bench.json
   python tools/dynamics_bench.py generalized_forces > profiles/generalized_forces_bench.json
+  python tools/dynamics_bench.py limb_ik > profiles/limb_ik_bench.json
 
 tensors: bez_sim_refresh_dynamics_tensors (the Jacobian, the mass matrix, both) beside a plain device fill of the same bytes -- the kernel
 is store-bound by construction, so the fill (hipMemsetAsync over the very buffer the refresh writes) is its yardstick.
@@ -21,6 +22,9 @@ torch.matmul(J, udot).
 generalized_forces: bez_sim_generalized_forces (every body loaded, ENV space with points; one body loaded -- the skipped bodies' rows are
 still brought into LDS) beside refresh_rigid_body_state, beside bez_sim_inverse_dynamics with all terms -- whose return sweep it is -- and
 beside the route the call replaces: a Jacobian refresh followed by torch.einsum of J with the wrenches at the bodies' origins.
+limb_ik: bez_sim_limb_ik (all five chains for 1 and 8 iterations; the pose-error query; the two legs alone with a step limit) beside
+refresh_rigid_body_state and beside the route the call replaces for ONE iteration: a rigid-body and a Jacobian refresh, the limbs'
+columns sliced in torch and torch.linalg.solve per chain (more iterations of that route need the state written back in between).
 
 Each figure is the median over --launches (>= 200) single launches, each between its own pair of events on one stream, after --warmup
 launches.  Nothing flushes the caches between launches, for a call and its yardsticks alike.
@@ -225,9 +229,67 @@ def generalized_forces(sim, n, t):
     return res
 
 
+def limb_ik(sim, n, t):
+    sim.step(torch.rand(n * 18, device=DEV) * 2 - 1)   # a state off the reset pose
+    nbe = sim.num_bodies
+    nb = nbe - (1 if sim.has_ball else 0)
+    names = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "bez_isaacgym_amd", "model", "bez_model.json")))
+    names = (names["cleats"] if int(sim.cfg.flags) & abi.FLAG_CLEATS else names)["body_names"]
+    ends = [names.index(b) for b in abi.IK_END_BODIES]
+    rb = sim.refresh(abi.TENSOR_RIGID_BODY_STATE).view(n, nbe, 13)
+    T = rb[:, ends, 0:7].clone()
+    T[:, :, 0:3] += torch.rand(n, 5, 3, device=DEV) * 0.06 - 0.03        # 3 cm and about 0.1 rad off the current poses
+    T[:, :, 3:7] += torch.rand(n, 5, 4, device=DEV) * 0.1 - 0.05
+    T = T.contiguous()
+    w, lam = [[1.0, 0.25]] * abi.IK_CHAINS, 0.05
+    q, err = torch.zeros(n, abi.NUM_DOFS, device=DEV), torch.zeros(n, abi.IK_CHAINS, 6, device=DEV)
+    J = sim.dynamics_tensor("jacobian").view(n, nb, 6, abi.NUM_GEN)
+    q0 = sim.refresh(abi.TENSOR_DOF_STATE).view(n, abi.NUM_DOFS, 2)[:, :, 0].clone()
+    W6 = torch.tensor([1.0, 1.0, 1.0, 0.25, 0.25, 0.25], device=DEV)
+    route = {}
+
+    def replaced():   # Isaac's pattern: refresh the body states and the Jacobian tensor, slice a limb's columns, solve in torch (world axes)
+        sim.refresh_dynamics_tensors("jacobian")
+        cur = sim.refresh(abi.TENSOR_RIGID_BODY_STATE).view(n, nbe, 13)[:, ends, 0:7]
+        td = T[:, :, 3:7] / T[:, :, 3:7].norm(dim=2, keepdim=True)
+        dv, dw, cv, cw = td[:, :, 0:3], td[:, :, 3:4], -cur[:, :, 3:6], cur[:, :, 6:7]          # q_des * conj(q)
+        ev = dw * cv + cw * dv + torch.cross(dv, cv, dim=2)
+        ew = dw * cw - (dv * cv).sum(dim=2, keepdim=True)
+        e = torch.cat([T[:, :, 0:3] - cur[:, :, 0:3], 2.0 * torch.where(ew < 0, -ev, ev)], dim=2)
+        dq = torch.zeros(n, abi.NUM_DOFS, device=DEV)
+        for c, (d0, d1) in enumerate(abi.IK_CHAIN_DOFS):
+            Jc = J[:, ends[c], :, 6 + d0:6 + d1]
+            JW = Jc.transpose(1, 2) * W6
+            N = JW @ Jc + lam * lam * torch.eye(d1 - d0, device=DEV)
+            dq[:, d0:d1] = torch.linalg.solve(N, (JW @ e[:, c, :, None]))[:, :, 0]
+        route["q"] = q0 + dq
+
+    big = torch.full((n, abi.NUM_DOFS), 100.0, device=DEV)
+    res = {"bytes_in": T.numel() * 4, "bytes_out": (q.numel() + err.numel()) * 4,
+           "limb_ik_iters_1": t(lambda: sim.limb_ik(T, w, None, lam, 0.0, 1, "env", q, err)),
+           "limb_ik_iters_8": t(lambda: sim.limb_ik(T, w, None, lam, 0.0, 8, "env", q, err)),
+           "limb_ik_iters_0_pose_error": t(lambda: sim.limb_ik(T, w, None, lam, 0.0, 0, "env", q, err)),
+           "limb_ik_iters_8_legs_only": t(lambda: sim.limb_ik(T, [[0.0, 0.0], [0.0, 0.0], [1.0, 0.25], [0.0, 0.0], [1.0, 0.25]], None, lam, 0.2, 8, "env", q, err)),
+           "refresh_rigid_body_state": t(lambda: sim.refresh(abi.TENSOR_RIGID_BODY_STATE)),
+           "jacobian_refresh_plus_torch_solve_one_iteration": t(replaced)}
+    rbs = res["refresh_rigid_body_state"]["median_us"]
+    res["ratio_to_rigid_body_refresh"] = {"iters_1": round(res["limb_ik_iters_1"]["median_us"] / rbs, 3), "iters_8": round(res["limb_ik_iters_8"]["median_us"] / rbs, 3)}
+    one = res["jacobian_refresh_plus_torch_solve_one_iteration"]["median_us"]
+    res["ratio_to_replaced_route"] = {"iters_1": round(res["limb_ik_iters_1"]["median_us"] / one, 4), "iters_8_to_one_iteration_of_it": round(res["limb_ik_iters_8"]["median_us"] / one, 4)}
+    # the two routes agree on one unclamped step
+    sim.set_env_params(abi.PARAM_DOF_LOWER, (-big).reshape(-1))
+    sim.set_env_params(abi.PARAM_DOF_UPPER, big.reshape(-1))
+    sim.limb_ik(T, w, None, lam, 0.0, 1, "env", q, err)
+    replaced()
+    torch.cuda.synchronize()
+    res["max_abs_difference_of_the_two_routes_rad"] = float((q - route["q"]).abs().max())
+    assert torch.isfinite(q).all() and torch.isfinite(err).all()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("call", choices=["tensors", "inverse_dynamics", "centroidal", "body_accelerations", "generalized_forces"])
+    ap.add_argument("call", choices=["tensors", "inverse_dynamics", "centroidal", "body_accelerations", "generalized_forces", "limb_ik"])
     ap.add_argument("--num-envs", type=int, default=4096)
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)

@@ -9,7 +9,9 @@ the Jacobian and the mass matrix each refreshed alone, then both in one launch; 
 ID_GRAVITY, centroidal (state, matrix) and body_accelerations for ACC_UDOT, ACC_VELOCITY, ACC_GRAVITY, ACC_MOTION (world axes) and ACC_ALL
 (the bodies' frames), each into 16-byte aligned buffers and into views 4 bytes off (the kernels' scalar path).  A library without
 bez_sim_body_accelerations (BEZ_SIM_LIB naming an older build) prints no acc_* entries, one without bez_sim_generalized_forces no gf_*
-entries (wrenches on every body; ENV with points, LOCAL with points, NULL positions at the centres of mass and at the origins)."""
+entries (wrenches on every body; ENV with points, LOCAL with points, NULL positions at the centres of mass and at the origins), one
+without bez_sim_limb_ik no ik_* entries (q and errors for 0, 1 and 8 iterations, ENV and ROOT targets, offsets, with and without a step
+limit)."""
 import hashlib
 import os
 import sys
@@ -78,6 +80,15 @@ def main():
                         out = make((n, NG))
                         d["gf_" + where] = digest(*[sim.generalized_forces(rows[0], rows[1], x, space, at, out).clone() for x, space, at in
                                                     ((rows[2], "env", "com"), (rows[2], "local", "com"), (None, "env", "com"), (None, "local", "origin"))])
+                    for where, make in (("aligned", lambda shape: torch.zeros(shape, device="cuda:0")), ("offset", off4)):
+                        if not hasattr(sim.lib, "bez_sim_limb_ik"):
+                            break
+                        gen = torch.Generator().manual_seed(13)
+                        t, q, e = make((n, abi.IK_CHAINS, 7)), make((n, abi.NUM_DOFS)), make((n, abi.IK_CHAINS, 6))
+                        t.copy_(torch.rand(n, abi.IK_CHAINS, 7, generator=gen) * 0.6 - 0.3)
+                        w, off = [[1.0, 0.25]] * abi.IK_CHAINS, [[0.01, -0.02, 0.03]] * abi.IK_CHAINS
+                        d["ik_" + where] = digest(*[x.clone() for iters, space, step in ((0, "env", 0.0), (1, "root", 0.0), (8, "env", 0.1), (8, "root", 0.1))
+                                                    for x in sim.limb_ik(t, w, off, 0.05, step, iters, space, q, e)])
                     sim.close()
                     print("%-7s %-8s %-7s n=%-3d %s" % (asset, task, params, n, " ".join("%s=%s" % kv for kv in d.items())), flush=True)
 
