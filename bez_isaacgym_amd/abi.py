@@ -62,6 +62,18 @@ IK_MAX_ITERS = 64
 IK_CHAIN_NAMES = ("head", "left_arm", "left_leg", "right_arm", "right_leg")
 IK_CHAIN_DOFS = ((0, 2), (2, 4), (4, 10), (10, 12), (12, 18))
 IK_END_BODIES = ("/head", "/left_forearm", "/left_foot", "/right_forearm", "/right_foot")
+# bez_sim_proximity (include/bez_sim.h "Proximity", BezSim.proximity): ground (N, PROX_GROUND_ROWS, 3), ball (N, PROX_BOXES, PROX_WORDS),
+# pairs (N, PROX_PAIRS, PROX_WORDS); a row of PROX_WORDS is [gap, normal 3, point 3, 0].  The names follow bez_model.json: a ground point
+# is "<kind><link>_<its index among the link's points>" (the cleats asset's foot points are its cleats, in the same rows)
+PROX_GROUND_ROWS, PROX_BALL_ROW, PROX_BOXES, PROX_PAIRS, PROX_WORDS = 23, 22, 11, 28, 8
+PROX_GAP, PROX_NORMAL, PROX_POINT = 0, 1, 4
+PROX_GROUND_NAMES = (tuple("foot/%s_foot_%d" % (s, i) for s in ("left", "right") for i in range(4)) + tuple("guard/torso_%d" % i for i in range(8))
+                     + tuple("guard/head_%d" % i for i in range(4)) + ("guard/left_forearm_0", "guard/right_forearm_0"))
+_PROX_LEG = ("hip_front", "thigh", "calve", "ankle", "foot")
+PROX_BOX_BODIES = tuple("/%s_%s" % (s, p) for s in ("left", "right") for p in _PROX_LEG) + ("/torso",)
+_PROX_CAPSULES = tuple("/%s_%s" % (s, p) for s in ("left", "right") for p in _PROX_LEG + ("foot",))   # two capsules per foot
+PROX_PAIRS_CAPSULES = ((0, 6), (0, 7)) + tuple((1, b) for b in range(6, 12)) + tuple((a, b) for a in range(2, 6) for b in range(7, 12))
+PROX_PAIR_BODIES = tuple((_PROX_CAPSULES[a], _PROX_CAPSULES[b]) for a, b in PROX_PAIRS_CAPSULES)
 HEALTH_NONFINITE = 1            # health word bits (TENSOR_HEALTH, BezSim.health)
 HEALTH_SPIN_TIMEOUT = 2
 TASK_KICK, TASK_WALK, TASK_ORIENT = 0, 1, 2

@@ -1,5 +1,5 @@
 // bez_dynamics.h -- the kernels that run forward kinematics outside the control step (rigid-body refresh, dynamics tensors, inverse and
-// centroidal dynamics, body accelerations, external wrenches, limb inverse kinematics) and what they share: DynArgs, tile I/O, the composite-rigid-body sweep.  Included by bez_sim.hip only.
+// centroidal dynamics, body accelerations, external wrenches, limb inverse kinematics, proximity) and what they share: DynArgs, tile I/O, the composite-rigid-body sweep.  Included by bez_sim.hip only.
 #pragma once
 #include "bez_kernels.h"
 
@@ -863,6 +863,180 @@ __global__ void __launch_bounds__(IK_THREADS) limb_ik_kernel(DynArgs D, const fl
   __syncthreads();
   if (q_out) tile_store_ragged<BEZ_ND, IK_QSTRIDE, IK_THREADS>(qrows, q_out + (size_t)e0 * BEZ_ND, ne * BEZ_ND);
   if (err_out) tile_store_ragged<IK_EW, IK_ESTRIDE, IK_THREADS>(erows, err_out + (size_t)e0 * IK_EW, ne * IK_EW);
+}
+
+// ---- bez_sim_proximity (definition: include/bez_sim.h "Proximity"): the step's three narrow phases -- link_ground_points, test_box_at /
+// test_torso_box, segment_closest / self_pair (bez_kernels.h) -- as signed distances that are defined on both sides of contact.
+// A workgroup takes PX_TILE consecutive envs.  Phase 1, one lane per env: the chains are walked with link_kinematics at qd = 0 in world
+// axes about the root origin (the legs for boxes, capsules and feet; the head and the arms for their guard points alone); the ground rows
+// go to the env's output row in LDS, root_pos joining in the last addition, and what the tests need -- the eleven box frames, the twelve
+// capsule axes' end points, the ball centre relative to the root origin, root_pos -- to the env's PX_F* words.  Phase 2, all lanes: the
+// tile's 16 x (28 + 11) tests, the env fastest, so that every wave runs one kind of test (16 x 28 is a whole number of waves); the
+// constants of a test are looked up in PROX_TABLES.  Phase 3, all lanes: the tile's three contiguous ranges are stored with tile_store /
+// tile_store_ragged.  Rows of odd strides: the lanes of phase 1 write distinct banks.
+// The family's form -- one wave, one lane per env that also runs its env's 39 tests, frames and capsules in registers -- computes the
+// same bits and was measured on MI355X beside this one (profiles/proximity_tiles.txt).
+constexpr int PX_TILE = 16, PX_THREADS = 256;
+constexpr int PX_GW = 3 * BEZ_PROX_GROUND_ROWS, PX_BW = BEZ_PROX_WORDS * BEZ_PROX_BOXES, PX_PW = BEZ_PROX_WORDS * BEZ_PROX_PAIRS;
+constexpr int PX_GSTRIDE = PX_GW | 1, PX_BSTRIDE = PX_BW | 1, PX_PSTRIDE = PX_PW | 1;
+// the PX_F* words of one env: [box frame: E row-major 9, r 3] x 11, [capsule p0 3, p1 3] x 12, ball centre rel. root origin 3, root_pos 3
+constexpr int PX_FBOX = 0, PX_FCAP = 12 * BEZ_NBOX, PX_FBALL = PX_FCAP + 6 * BEZ_NCAP, PX_FROOT = PX_FBALL + 3, PX_FSTRIDE = (PX_FROOT + 3) | 1;
+static_assert(BEZ_NPT + 1 == BEZ_PROX_GROUND_ROWS && BEZ_NBOX == BEZ_PROX_BOXES && BEZ_NCPAIR == BEZ_PROX_PAIRS, "include/bez_sim.h Proximity");
+static_assert(BEZ_TORSO_BOX == BEZ_NBOX - 1, "the torso box is the last entry of the box table");
+// box b's centre and half extents (entry BEZ_NBOX: the box asset's torso box), the capsules' radii, the pairs
+struct ProxTables { float center[BEZ_NBOX + 1][3], half[BEZ_NBOX + 1][3], cap_r[BEZ_NCAP]; int8_t pair[BEZ_NCPAIR][2]; };
+constexpr ProxTables prox_tables() {
+  ProxTables T = {};
+  for (int k = 0; k < 3; ++k) {
+    for (int b = 0; b < BEZ_NBOX; ++b) { T.center[b][k] = (float)BEZ_BOX_CENTER[b][k]; T.half[b][k] = (float)BEZ_BOX_HALF[b][k]; }
+    T.center[BEZ_NBOX][k] = (float)BEZ_TORSO_BOX_CENTER_BOX[k]; T.half[BEZ_NBOX][k] = (float)BEZ_TORSO_BOX_HALF_BOX[k];
+  }
+  for (int c = 0; c < BEZ_NCAP; ++c) T.cap_r[c] = (float)BEZ_CAP_R[c];
+  for (int p = 0; p < BEZ_NCPAIR; ++p) { T.pair[p][0] = (int8_t)BEZ_CPAIR[p][0]; T.pair[p][1] = (int8_t)BEZ_CPAIR[p][1]; }
+  return T;
+}
+__device__ const ProxTables PROX_TABLES = prox_tables();
+// a row [gap, normal, point, +0.0f]; p is relative to the root origin
+BEZ_DEV void prox_put(float* o, float gap, V3 n, V3 p, V3 root_pos) {
+  o[BEZ_PROX_GAP] = gap;
+  o[BEZ_PROX_NORMAL] = n.x; o[BEZ_PROX_NORMAL + 1] = n.y; o[BEZ_PROX_NORMAL + 2] = n.z;
+  o[BEZ_PROX_POINT] = root_pos.x + p.x; o[BEZ_PROX_POINT + 1] = root_pos.y + p.y; o[BEZ_PROX_POINT + 2] = root_pos.z + p.z;
+  o[7] = 0.f;
+}
+// test_box_at as a signed distance: sphere (centre bc rel. O) against the box (centre cl, half extents he) of a link with frame (E, r).
+// gap = -depth of test_box_at, kept when positive; n: world normal box -> ball; p: closest point of the box surface rel. O.
+// (sqrtf and the division are the correctly rounded ones: nothing here feeds a force that an approximation's ulp would be lost in)
+BEZ_DEV void prox_box(V3 cl, V3 he, const M3& E, V3 r, V3 bc, float& gap, V3& n, V3& p) {
+  const float R = (float)BEZ_BALL_RADIUS;
+  const V3 ql = mulT(E, bc - r) - cl;
+  V3 cp = mk(fminf(fmaxf(ql.x, -he.x), he.x), fminf(fmaxf(ql.y, -he.y), he.y), fminf(fmaxf(ql.z, -he.z), he.z));
+  const bool inside = (cp.x == ql.x) && (cp.y == ql.y) && (cp.z == ql.z);
+  V3 nl;
+  if (!inside) {   // (a NaN centre comes here and is written through)
+    const V3 dlt = ql - cp;
+    const float dist = sqrtf(dot(dlt, dlt)), inv = 1.f / dist;
+    gap = dist - R;
+    nl = dlt * inv;
+  } else {
+    const float dx = he.x - fabsf(ql.x), dy = he.y - fabsf(ql.y), dz = he.z - fabsf(ql.z);
+    int ax = 0; float md = dx;
+    if (dy < md) { md = dy; ax = 1; }
+    if (dz < md) { md = dz; ax = 2; }
+    nl = mk(0.f, 0.f, 0.f);
+    if (ax == 0) { nl.x = ql.x >= 0.f ? 1.f : -1.f; cp.x = nl.x * he.x; }
+    else if (ax == 1) { nl.y = ql.y >= 0.f ? 1.f : -1.f; cp.y = nl.y * he.y; }
+    else { nl.z = ql.z >= 0.f ? 1.f : -1.f; cp.z = nl.z * he.z; }
+    gap = -(R + md);
+  }
+  n = mul(E, nl);
+  p = r + mul(E, cp + cl);
+}
+// self_pair's geometry as a signed distance: capsule axes a0-a1, b0-b1 (rel. O), radii ra, rb.  segment_closest is the step's; gap =
+// -depth of self_pair, kept when positive; n from b's closest point to a's; p = cb + n (rb - depth / 2), the step's contact point.
+BEZ_DEV void prox_pair(float ra, float rb, V3 a0, V3 a1, V3 b0, V3 b1, float& gap, V3& n, V3& p) {
+  V3 ca, cb;
+  segment_closest(a0, a1, b0, b1, ca, cb);
+  const V3 dl = ca - cb;
+  const float d2 = dot(dl, dl), rs = ra + rb;
+  if (d2 <= 1e-12f) {   // the axes meet: no direction (a NaN is not <=: it goes on and is written through)
+    gap = -rs; n = mk(0.f, 0.f, 0.f); p = cb;
+    return;
+  }
+  const float dist = sqrtf(d2), inv = 1.f / dist;
+  gap = dist - rs;
+  n = dl * inv;
+  p = fma3(n, fmaf(0.5f, gap, rb), cb);
+}
+template <bool CL>
+__global__ void __launch_bounds__(PX_THREADS) proximity_kernel(DynArgs D, float* __restrict__ ground, float* __restrict__ ball, float* __restrict__ pairs) {
+  __shared__ float frames[PX_TILE * PX_FSTRIDE];
+  __shared__ float grows[PX_TILE * PX_GSTRIDE];
+  __shared__ float brows[PX_TILE * PX_BSTRIDE];
+  __shared__ float prows[PX_TILE * PX_PSTRIDE];
+  const float* st = D.st;
+  const int n = D.n, e0 = blockIdx.x * PX_TILE, ne = min(PX_TILE, n - e0);
+  if ((int)threadIdx.x < ne) {
+    int e = e0 + threadIdx.x;
+    float* F = frames + threadIdx.x * PX_FSTRIDE;
+    float* G = grows + threadIdx.x * PX_GSTRIDE;
+    auto ld = [&](int f) { return st[(size_t)f * n + e]; };
+    auto put3 = [&](float* at, V3 v) { at[0] = v.x; at[1] = v.y; at[2] = v.z; };
+    const V3 root_pos = mk(ld(F_ROOT_POS), ld(F_ROOT_POS + 1), ld(F_ROOT_POS + 2)), ball_pos = mk(ld(F_BALL_POS), ld(F_BALL_POS + 1), ld(F_BALL_POS + 2));
+    const M3 E0 = quat_to_mat(ld(F_ROOT_QUAT), ld(F_ROOT_QUAT + 1), ld(F_ROOT_QUAT + 2), ld(F_ROOT_QUAT + 3));
+    const float quirk_z = quirk_rz<CL>(D.flags);
+    Params P;   // (pt_pos_of looks at the flags alone)
+    P.flags = D.flags;
+    put3(F + PX_FROOT, root_pos);
+    put3(F + PX_FBALL, ball_pos - root_pos);
+    put3(G + 3 * BEZ_PROX_BALL_ROW, mk(ball_pos.x, ball_pos.y, ball_pos.z - (float)BEZ_BALL_RADIUS));
+    // what link L carries: its ground points (the z word as the step forms it: root_pos.z + x.z), its box's frame, its capsules' axes
+    auto link = [&](auto Lk, const M3& E, V3 r) {
+      constexpr int L = decltype(Lk)::value;
+      static_for<BEZ_NPT>([&](auto I) {
+        constexpr int i = decltype(I)::value;
+        if constexpr (BEZ_PT_LINK[i] == L) {
+          const V3 x = r + mul(E, mk(pt_pos_of<CL>(P, i, 0), pt_pos_of<CL>(P, i, 1), pt_pos_of<CL>(P, i, 2)));
+          put3(G + 3 * i, mk(root_pos.x + x.x, root_pos.y + x.y, root_pos.z + x.z));
+        }
+      });
+      if constexpr (link_has_box(L)) {
+        float* B = F + PX_FBOX + 12 * link_box(L);
+        B[0] = E.m00; B[1] = E.m01; B[2] = E.m02; B[3] = E.m10; B[4] = E.m11; B[5] = E.m12; B[6] = E.m20; B[7] = E.m21; B[8] = E.m22;
+        put3(B + 9, r);
+      }
+      static_for<BEZ_NCAP>([&](auto I) {
+        constexpr int c = decltype(I)::value;
+        if constexpr (BEZ_CAP_LINK[c] == L) {
+          put3(F + PX_FCAP + 6 * c, r + mul(E, mk((float)BEZ_CAP_P0[c][0], (float)BEZ_CAP_P0[c][1], (float)BEZ_CAP_P0[c][2])));
+          put3(F + PX_FCAP + 6 * c + 3, r + mul(E, mk((float)BEZ_CAP_P1[c][0], (float)BEZ_CAP_P1[c][1], (float)BEZ_CAP_P1[c][2])));
+        }
+      });
+    };
+    link(std::integral_constant<int, 0>{}, E0, mk(0.f, 0.f, 0.f));
+    auto chain = [&](auto first, auto len) {
+      constexpr int FIRST = decltype(first)::value, LEN = decltype(len)::value;
+      static_assert(is_chain<FIRST, LEN>(), "not a chain off the torso");
+      asm volatile("" : "+v"(e));   // (opaque per chain, as in inverse_dynamics_kernel)
+      M3 E = E0; V3 r = mk(0.f, 0.f, 0.f);
+      static_for<LEN>([&](auto I) {
+        constexpr int L = FIRST + decltype(I)::value;
+        SV S, cb, V = svzero();
+        link_kinematics<L>(ld(F_Q + L - 1), 0.f, E, r, V, S, cb, quirk_z);
+        link(std::integral_constant<int, L>{}, E, r);
+      });
+    };
+    using std::integral_constant;
+    chain(integral_constant<int, 1>{}, integral_constant<int, 2>{});
+    chain(integral_constant<int, 3>{}, integral_constant<int, 2>{});
+    chain(integral_constant<int, 5>{}, integral_constant<int, 6>{});
+    chain(integral_constant<int, 11>{}, integral_constant<int, 2>{});
+    chain(integral_constant<int, 13>{}, integral_constant<int, 6>{});
+  }
+  __syncthreads();
+  const bool box_asset = (D.flags & BEZ_FLAG_BOX_ASSET) != 0;
+  const int first = pairs ? 0 : PX_TILE * BEZ_NCPAIR, last = ball ? PX_TILE * (BEZ_NCPAIR + BEZ_NBOX) : PX_TILE * BEZ_NCPAIR;
+  for (int i = first + threadIdx.x; i < last; i += PX_THREADS) {
+    const int el = i % PX_TILE, t = i / PX_TILE;
+    if (el >= ne) continue;
+    const float* F = frames + el * PX_FSTRIDE;
+    float gap; V3 nn, p;
+    if (t < BEZ_NCPAIR) {
+      const int ia = PROX_TABLES.pair[t][0], ib = PROX_TABLES.pair[t][1];
+      const float *A = F + PX_FCAP + 6 * ia, *B = F + PX_FCAP + 6 * ib;
+      prox_pair(PROX_TABLES.cap_r[ia], PROX_TABLES.cap_r[ib], lds3(A), lds3(A + 3), lds3(B), lds3(B + 3), gap, nn, p);
+      prox_put(prows + el * PX_PSTRIDE + BEZ_PROX_WORDS * t, gap, nn, p, lds3(F + PX_FROOT));
+    } else {
+      const int b = t - BEZ_NCPAIR, k = (b == BEZ_TORSO_BOX && box_asset) ? BEZ_NBOX : b;
+      const float* B = F + PX_FBOX + 12 * b;
+      const M3 E = {B[0], B[1], B[2], B[3], B[4], B[5], B[6], B[7], B[8]};
+      prox_box(lds3(PROX_TABLES.center[k]), lds3(PROX_TABLES.half[k]), E, lds3(B + 9), lds3(F + PX_FBALL), gap, nn, p);
+      prox_put(brows + el * PX_BSTRIDE + BEZ_PROX_WORDS * b, gap, nn, p, lds3(F + PX_FROOT));
+    }
+  }
+  __syncthreads();
+  if (ground) tile_store_ragged<PX_GW, PX_GSTRIDE, PX_THREADS>(grows, ground + (size_t)e0 * PX_GW, ne * PX_GW);
+  if (ball) tile_store<PX_BW, PX_BSTRIDE, PX_THREADS>(brows, ball + (size_t)e0 * PX_BW, ne);
+  if (pairs) tile_store<PX_PW, PX_PSTRIDE, PX_THREADS>(prows, pairs + (size_t)e0 * PX_PW, ne);
 }
 
 // ---- bez_sim_apply_body_forces: one thread per env turns the Isaac-layout inputs of its env into the pending per-link wrenches (bez_kernels.h

@@ -817,6 +817,11 @@ int bez_sim_limb_ik(BezSim* s, const float* targets_dev, const BezIkParams* para
   return LAUNCH_ASSET(s, limb_ik_kernel, IK_TILE, IK_THREADS, (hipStream_t)stream, dyn_args(s), s->dr[BEZ_PARAM_DOF_LOWER], s->dr[BEZ_PARAM_DOF_UPPER],
                       targets_dev, p, q_out_dev, err_out_dev);
 }
+int bez_sim_proximity(BezSim* s, float* ground_dev, float* ball_dev, float* pairs_dev, void* stream) {
+  if (!s) return fail(s, -1, "bez_sim_proximity: sim is null");
+  if (!ground_dev && !ball_dev && !pairs_dev) return fail(s, -1, "bez_sim_proximity: ground_dev, ball_dev and pairs_dev are all null (nothing to write)");
+  return LAUNCH_ASSET(s, proximity_kernel, PX_TILE, PX_THREADS, (hipStream_t)stream, dyn_args(s), ground_dev, ball_dev, pairs_dev);
+}
 int bez_sim_set_obs_calls(BezSim* s, int64_t calls) { if (!s) return -1; s->obs_calls = calls; return 0; }
 
 int bez_sim_pre_physics(BezSim* s, const float* actions_dev, void* stream) {

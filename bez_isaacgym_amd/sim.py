@@ -64,6 +64,7 @@ SIGS = {
     "bez_sim_body_accelerations": (C.c_int, [vp, fp, u32, i32, fp, vp]),
     "bez_sim_generalized_forces": (C.c_int, [vp, fp, fp, fp, i32, fp, vp]),
     "bez_sim_limb_ik": (C.c_int, [vp, fp, C.POINTER(abi.BezIkParams), fp, fp, vp]),
+    "bez_sim_proximity": (C.c_int, [vp, fp, fp, fp, vp]),
 }
 EXPORTS = list(SIGS)
 
@@ -346,6 +347,36 @@ class BezSim:
                                              self._ptr(out, torch.float32, n * abi.NUM_DOFS),
                                              self._ptr(err_out, torch.float32, n * abi.IK_CHAINS * 6), self._stream()))
         return out, err_out
+
+    # ---- proximity: the contact geometry of the step -- ground points, ball against boxes, leg against leg -- as distances
+    def proximity(self, ground=None, ball=None, pairs=None, want=("ground", "ball", "pairs")):
+        """(ground, ball, pairs) of the current state in one launch on the current stream (include/bez_sim.h "Proximity").
+        ground (N, 23, 3) float32: the asset's 22 ground points in env coordinates (abi.PROX_GROUND_NAMES; z < 0 is the step's contact
+        decision) and, row abi.PROX_BALL_ROW, the ball's lowest point.  ball (N, 11, 8): per box (abi.PROX_BOX_BODIES) [gap, normal 3,
+        point 3, 0] -- the signed distance of the ball's surface to the box, the world normal from the box to the ball, the closest point
+        of the box in env coordinates.  pairs (N, 28, 8): per capsule pair (abi.PROX_PAIR_BODIES, a on the left leg) the same words -- the
+        signed distance of the two capsules, the normal from b to a, the step's contact point.  `want`: which of the three to compute; an
+        output that is not wanted is None in the result and is not written.  `ground`, `ball`, `pairs`: contiguous float32 tensors on
+        the sim's device to write into (a given tensor is wanted); None: one buffer of each kind per sim, allocated by the first call
+        that needs it and overwritten by every later one."""
+        n = self.num_envs
+        shapes = {"ground": (n, abi.PROX_GROUND_ROWS, 3), "ball": (n, abi.PROX_BOXES, abi.PROX_WORDS), "pairs": (n, abi.PROX_PAIRS, abi.PROX_WORDS)}
+        if isinstance(want, str):
+            want = (want,)
+        for w in want:
+            if w not in shapes:
+                raise BezSimError("proximity: want holds %r, expected a subset of %s" % (w, tuple(shapes)))
+        out = {}
+        for name, t in (("ground", ground), ("ball", ball), ("pairs", pairs)):
+            if t is not None:
+                out[name] = self._checked(name, t, (shapes[name],))
+            else:
+                out[name] = self._scratch("proximity_" + name, shapes[name]) if name in want else None
+        if all(t is None for t in out.values()):
+            raise BezSimError("proximity: nothing is wanted (want is empty and no output tensor is given)")
+        ptrs = [None if out[k] is None else self._ptr(out[k], torch.float32, torch.Size(shapes[k]).numel()) for k in ("ground", "ball", "pairs")]
+        self._check(self.lib.bez_sim_proximity(self.h, ptrs[0], ptrs[1], ptrs[2], self._stream()))
+        return out["ground"], out["ball"], out["pairs"]
 
     def refresh(self, which):
         self._check(self.lib.bez_sim_refresh_tensor(self.h, which, self._stream()))

@@ -339,6 +339,34 @@ class VecTask(Env):
                 return c, tuple(float(x) - float(y) for x, y in zip(model["body_offset"][b], model["body_offset"][e]))
         raise ValueError("rigid body %r is not fixed to the end link of a chain (%s)" % (body, ", ".join(abi.IK_END_BODIES)))
 
+    # ---- proximity (include/bez_sim.h "Proximity"): the contact geometry the step decides on; one launch, and what is returned are the
+    # sim's result buffers of that kind: the next call overwrites them
+    def proximity(self, ground=None, ball=None, pairs=None, want=("ground", "ball", "pairs")):
+        """(ground (N, 23, 3), ball (N, 11, 8), pairs (N, 28, 8)) of the current state: the ground points' positions (abi.PROX_GROUND_NAMES,
+        then the ball's lowest point), and [gap, normal, point, 0] of the ball against every box (abi.PROX_BOX_BODIES) and of every
+        left-leg x right-leg capsule pair (abi.PROX_PAIR_BODIES); an output not named in `want` is None"""
+        return self.sim.proximity(ground, ball, pairs, want)
+
+    def foot_clearance(self):
+        """(N, 2): the height above the ground of the lowest of each foot's four ground points (left, right); negative: in contact"""
+        g = self.sim.proximity(want=("ground",))[0]
+        return g[:, 0:8, 2].reshape(self.num_envs, 2, 4).min(dim=2).values
+
+    def self_collision_gap(self):
+        """(N,): the smallest gap of the 28 leg-to-leg capsule pairs; negative: the legs overlap by that much"""
+        from ... import abi
+        return self.sim.proximity(want=("pairs",))[2][:, :, abi.PROX_GAP].min(dim=1).values
+
+    def ball_gap(self):
+        """((N,) gap, (N,) box index): the smallest gap of the ball to the eleven boxes and the box (abi.PROX_BOX_BODIES) it belongs to;
+        on ties the first box in the step's order: the legs first, the torso last (an env with a non-finite gap: NaN and abi.PROX_BOXES)"""
+        import torch
+        from ... import abi
+        gap = self.sim.proximity(want=("ball",))[1][:, :, abi.PROX_GAP]
+        least = gap.min(dim=1).values
+        order = torch.arange(abi.PROX_BOXES, device=gap.device).expand_as(gap)
+        return least, torch.where(gap == least[:, None], order, abi.PROX_BOXES).min(dim=1).values
+
     def actuator_snapshot(self):
         """(drive torque, status, joint velocity), each (N, 18), of the last physics launch: one refresh of the actuator tensors and one of
         DOF_STATE (the PPO loop's per-epoch actuator statistics)."""

@@ -512,6 +512,46 @@ typedef struct BezIkParams {
 int bez_sim_limb_ik(BezSim* sim, const float* targets_dev /* (N,5,7) */, const BezIkParams* params,
                     float* q_out_dev /* (N,18) or NULL */, float* err_out_dev /* (N,5,6) or NULL */, void* stream);
 
+/* Proximity: the contact geometry the step kernels decide on every substep -- 22 ground points against the plane z = 0, the ball against
+ * eleven boxes, 28 left-leg x right-leg capsule pairs -- as distances, normals and points of the state as it stands on `stream`: foot
+ * clearance, a self-collision penalty, the distance of the ball to the kicking foot, and a known answer for tests of the narrow phase.
+ * All outputs are f32, env-major; any of them may be NULL.  Geometry is evaluated relative to the root origin, as the step does, and
+ * root_pos enters only the last addition of an env-coordinate output: a root far from the env origin costs nothing in the gaps.
+ *   ground_dev  (N, 23, 3): rows 0:22 the positions, in env coordinates, of the asset's ground points in table order (bez_model.json
+ *     "ground_points": four per foot, the torso's guard points, the head's, one per forearm) -- the cleats table with BEZ_FLAG_CLEATS, the
+ *     upper-body guard points BEZ_FLAG_BOX_ASSET moves, the joint origin box + cleats moves.  The z word is root_pos.z + x.z with x the
+ *     point relative to the root origin -- the step's d = -z > 0 decision -- and does not depend on root_pos.x / root_pos.y, to the bit.
+ *     Row 22 (BEZ_PROX_BALL_ROW) is ball_pos - (0, 0, R), the ball's lowest point.
+ *   ball_dev    (N, 11, 8): one row per box in the model's box order (left leg hip -> foot 0:5, right leg 5:10, torso 10; with
+ *     BEZ_FLAG_BOX_ASSET the box asset's own torso box).  gap: the signed distance from the ball's surface to the box, minus the step's
+ *     depth and defined when positive too -- centre outside the box: |centre - clamped point| - R; centre inside: -(R + smallest face
+ *     distance).  normal: from the box to the ball, world axes.  point: the closest point of the box surface, env coordinates; with the
+ *     centre inside, its projection onto the nearest face (first of x, y, z on ties), as the step's.
+ *   pairs_dev   (N, 28, 8): one row per capsule pair in the model's "capsule_pairs" order (a on the left leg, b on the right).  gap: the
+ *     distance between the two axis segments minus (ra + rb).  normal: from capsule b's closest point to capsule a's -- the step's n: the
+ *     contact force on link a is along +n.  point: the step's contact point cb + n (rb - depth / 2), depth = -gap, env coordinates, by
+ *     the same formula for positive gaps.  Where the axes meet (squared distance <= 1e-12, where the step applies no force): gap =
+ *     -(ra + rb), normal three +0.0f, point = cb.
+ *   A row of 8 words is [gap, normal(3), point(3), +0.0f].
+ *   Velocities, masses, gravity, BEZ_FLAG_FIX_BASE and BEZ_FLAG_NO_SELF_COLLISION play no part: the call reports geometry whether or not
+ *   the step would act on it.  A task without a ball has it parked, and the ball rows are computed from the stored ball state like any
+ *   other.  A non-finite state is written through and stays in its own env; the pad words stay +0.0f.  Results do not depend on N, on an
+ *   env's place in its tile or on the buffers' alignment.
+ *   Not reported: the calf <-> foot-plate pair of BEZ_FLAG_ANKLE_STOP and the 118 extra points of BEZ_FLAG_ALL_GROUND_SHAPES, which live
+ *   on the one-env-per-lane step kernel only.
+ *   One kernel launch.  The call allocates nothing, never synchronises, reads nothing on the host and writes only the outputs: it
+ *   captures into a HIP graph.  All outputs NULL or a null sim: rc -1 with a message. */
+#define BEZ_PROX_GROUND_ROWS 23   /* 22 ground points + the ball's lowest point */
+#define BEZ_PROX_BALL_ROW    22
+#define BEZ_PROX_BOXES       11
+#define BEZ_PROX_PAIRS       28
+#define BEZ_PROX_WORDS        8   /* gap, normal(3), point(3), 0.0f */
+#define BEZ_PROX_GAP 0
+#define BEZ_PROX_NORMAL 1
+#define BEZ_PROX_POINT 4
+int bez_sim_proximity(BezSim* sim, float* ground_dev /* (N,23,3) or NULL */,
+                      float* ball_dev /* (N,11,8) or NULL */, float* pairs_dev /* (N,28,8) or NULL */, void* stream);
+
 /* gym.refresh_{actor_root_state,dof_state,rigid_body_state,net_contact_force}_tensor
  * (kick_env.py:750-753): materialise the Isaac-layout tensor from the SoA state.  ROOT_STATE, DOF_STATE, RIGID_BODY_STATE,
  * NET_CONTACT_FORCE, DOF_TARGET, PREV_LIN_VEL, FEET and GOAL need it; every other BezTensor is always live (the kernels

@@ -1,11 +1,12 @@
 """Times one of the dynamics queries at num_envs = 4096 beside its yardsticks in the same run.  Prints one JSON line.
 
-  python tools/dynamics_bench.py {tensors,inverse_dynamics,centroidal,body_accelerations,generalized_forces,limb_ik} [--num-envs 4096] [--launches 200] [--warmup 20] [--cleats]
+  python tools/dynamics_bench.py {tensors,inverse_dynamics,centroidal,body_accelerations,generalized_forces,limb_ik,proximity} [--num-envs 4096] [--launches 200] [--warmup 20] [--cleats]
   python tools/dynamics_bench.py inverse_dynamics > profiles/inverse_dynamics_bench.json      (the committed records)
   python tools/dynamics_bench.py centroidal > profiles/centroidal_bench.json
   python tools/dynamics_bench.py body_accelerations > profiles/body_accelerations_bench.json
   python tools/dynamics_bench.py generalized_forces > profiles/generalized_forces_bench.json
   python tools/dynamics_bench.py limb_ik > profiles/limb_ik_bench.json
+  python tools/dynamics_bench.py proximity > profiles/proximity_bench.json
 
 tensors: bez_sim_refresh_dynamics_tensors (the Jacobian, the mass matrix, both) beside a plain device fill of the same bytes -- the kernel
 is store-bound by construction, so the fill (hipMemsetAsync over the very buffer the refresh writes) is its yardstick.
@@ -25,6 +26,9 @@ beside the route the call replaces: a Jacobian refresh followed by torch.einsum 
 limb_ik: bez_sim_limb_ik (all five chains for 1 and 8 iterations; the pose-error query; the two legs alone with a step limit) beside
 refresh_rigid_body_state and beside the route the call replaces for ONE iteration: a rigid-body and a Jacobian refresh, the limbs'
 columns sliced in torch and torch.linalg.solve per chain (more iterations of that route need the state written back in between).
+proximity: bez_sim_proximity (all three outputs; the ground rows alone; the pairs alone) beside refresh_rigid_body_state -- the same
+per-lane forward kinematics -- and the route the call replaces: a rigid-body refresh followed by batched torch ops that rebuild the
+collision shapes from bez_model.json on the body rows and compute the same 23 + 11 + 28 rows.
 
 Each figure is the median over --launches (>= 200) single launches, each between its own pair of events on one stream, after --warmup
 launches.  Nothing flushes the caches between launches, for a call and its yardsticks alike.
@@ -287,9 +291,95 @@ def limb_ik(sim, n, t):
     return res
 
 
+def proximity(sim, n, t):
+    sim.step(torch.rand(n * 18, device=DEV) * 2 - 1)   # a state off the reset pose
+    nbe = sim.num_bodies
+    assert sim.has_ball, "the replaced route reads the ball's body row"
+    m = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "bez_isaacgym_amd", "model", "bez_model.json")))
+    cl = bool(int(sim.cfg.flags) & abi.FLAG_CLEATS)
+    link_body = [L["body"] for L in (m["cleats"] if cl else m)["links"]]
+    dev = lambda rows, key: torch.tensor([r[key] for r in rows], device=DEV, dtype=torch.float32)
+    body_of = lambda rows: torch.tensor([link_body[r["link"]] for r in rows], device=DEV)
+    pts = (m["cleats"] if cl else m)["ground_points"]
+    pt_body, pt_p = body_of(pts), dev(pts, "p")
+    box_body, box_c, box_h = body_of(m["boxes"]), dev(m["boxes"], "center"), dev(m["boxes"], "half")
+    cap_body, cap_p0, cap_p1, cap_r = body_of(m["capsules"]), dev(m["capsules"], "p0"), dev(m["capsules"], "p1"), dev(m["capsules"], "r")
+    ia, ib = (torch.tensor([p[k] for p in m["capsule_pairs"]], device=DEV) for k in (0, 1))
+    R = float(m["ball"]["radius"])
+    ground, ball, pairs = (torch.zeros(n, r, w, device=DEV) for r, w in ((abi.PROX_GROUND_ROWS, 3), (abi.PROX_BOXES, 8), (abi.PROX_PAIRS, 8)))
+    route = {}
+
+    def rot(q):   # (..., 4) xyzw -> (..., 3, 3)
+        x, y, z, w = q.unbind(-1)
+        return torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w), 2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                            2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], dim=-1).view(q.shape[:-1] + (3, 3))
+
+    def replaced():
+        rb = sim.refresh(abi.TENSOR_RIGID_BODY_STATE).view(n, nbe, 13)
+        pos, E = rb[:, :, 0:3], rot(rb[:, :, 3:7])
+        centre = pos[:, nbe - 1]
+        low = centre.clone()
+        low[:, 2] -= R
+        g = torch.cat([pos[:, pt_body] + (E[:, pt_body] @ pt_p[None, :, :, None])[..., 0], low[:, None]], dim=1)
+        Eb = E[:, box_body]
+        ql = (Eb.transpose(2, 3) @ (centre[:, None] - pos[:, box_body])[..., None])[..., 0] - box_c
+        cp = torch.minimum(torch.maximum(ql, -box_h), box_h)
+        inside = (cp == ql).all(dim=2)
+        dlt = ql - cp
+        dist = dlt.norm(dim=2)
+        face = box_h - ql.abs()
+        md, ax = face.min(dim=2)
+        sgn = torch.where(ql.gather(2, ax[..., None])[..., 0] >= 0, 1.0, -1.0)
+        n_in = torch.zeros_like(ql).scatter(2, ax[..., None], sgn[..., None])
+        cp_in = cp.scatter(2, ax[..., None], (sgn * box_h.expand_as(ql).gather(2, ax[..., None])[..., 0])[..., None])
+        gap = torch.where(inside, -(R + md), dist - R)
+        nl = torch.where(inside[..., None], n_in, dlt / dist[..., None])
+        cpl = torch.where(inside[..., None], cp_in, cp) + box_c
+        b = torch.cat([gap[..., None], (Eb @ nl[..., None])[..., 0], pos[:, box_body] + (Eb @ cpl[..., None])[..., 0], torch.zeros_like(gap)[..., None]], dim=2)
+        Ec, pc = E[:, cap_body], pos[:, cap_body]
+        c0, c1 = pc + (Ec @ cap_p0[None, :, :, None])[..., 0], pc + (Ec @ cap_p1[None, :, :, None])[..., 0]
+        p1, p2 = c0[:, ia], c0[:, ib]
+        d1, d2 = c1[:, ia] - p1, c1[:, ib] - p2
+        r = p1 - p2
+        a, e, f, c, bb = (d1 * d1).sum(2), (d2 * d2).sum(2), (d2 * r).sum(2), (d1 * r).sum(2), (d1 * d2).sum(2)
+        den = a * e - bb * bb
+        s = torch.where(den > 1e-12, ((bb * f - c * e) / den).clamp(0, 1), torch.zeros_like(den))
+        tt = (bb * s + f) / e
+        tc = tt.clamp(0, 1)
+        s = torch.where(tt != tc, ((bb * tc - c) / a).clamp(0, 1), s)
+        ca, cb = p1 + d1 * s[..., None], p2 + d2 * tc[..., None]
+        dl = ca - cb
+        dd = dl.norm(dim=2)
+        rs, rbr = cap_r[ia] + cap_r[ib], cap_r[ib]
+        pg = dd - rs
+        pn = dl / dd[..., None]
+        p = torch.cat([pg[..., None], pn, cb + pn * (rbr + 0.5 * pg)[..., None], torch.zeros_like(pg)[..., None]], dim=2)
+        route["ground"], route["ball"], route["pairs"] = g, b, p
+
+    res = {"bytes_out": (ground.numel() + ball.numel() + pairs.numel()) * 4,
+           "proximity_all": t(lambda: sim.proximity(ground, ball, pairs)),
+           "proximity_ground_only": t(lambda: sim.proximity(ground=ground, want=())),
+           "proximity_ball_only": t(lambda: sim.proximity(ball=ball, want=())),
+           "proximity_pairs_only": t(lambda: sim.proximity(pairs=pairs, want=())),
+           "refresh_rigid_body_state": t(lambda: sim.refresh(abi.TENSOR_RIGID_BODY_STATE)),
+           "rigid_body_refresh_plus_torch_ops": t(replaced)}
+    mine = res["proximity_all"]["median_us"]
+    res["ratio_to_rigid_body_refresh"] = round(mine / res["refresh_rigid_body_state"]["median_us"], 3)
+    res["ratio_to_replaced_route"] = round(mine / res["rigid_body_refresh_plus_torch_ops"]["median_us"], 4)
+    # the two routes agree (the replaced route works on body rows that carry the root position: its points are rounded at that size)
+    sim.proximity(ground, ball, pairs)
+    replaced()
+    torch.cuda.synchronize()
+    res["max_abs_difference_ground_m"] = float((ground - route["ground"]).abs().max())
+    res["max_abs_difference_ball_gap_m"] = float((ball[:, :, 0] - route["ball"][:, :, 0]).abs().max())
+    res["max_abs_difference_pair_gap_m"] = float((pairs[:, :, 0] - route["pairs"][:, :, 0]).abs().max())
+    assert torch.isfinite(ground).all() and torch.isfinite(ball).all() and torch.isfinite(pairs).all()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("call", choices=["tensors", "inverse_dynamics", "centroidal", "body_accelerations", "generalized_forces", "limb_ik"])
+    ap.add_argument("call", choices=["tensors", "inverse_dynamics", "centroidal", "body_accelerations", "generalized_forces", "limb_ik", "proximity"])
     ap.add_argument("--num-envs", type=int, default=4096)
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)

@@ -11,7 +11,7 @@ ID_GRAVITY, centroidal (state, matrix) and body_accelerations for ACC_UDOT, ACC_
 bez_sim_body_accelerations (BEZ_SIM_LIB naming an older build) prints no acc_* entries, one without bez_sim_generalized_forces no gf_*
 entries (wrenches on every body; ENV with points, LOCAL with points, NULL positions at the centres of mass and at the origins), one
 without bez_sim_limb_ik no ik_* entries (q and errors for 0, 1 and 8 iterations, ENV and ROOT targets, offsets, with and without a step
-limit)."""
+limit), one without bez_sim_proximity no prox_* entries (the ground, ball and pair rows)."""
 import hashlib
 import os
 import sys
@@ -89,6 +89,11 @@ def main():
                         w, off = [[1.0, 0.25]] * abi.IK_CHAINS, [[0.01, -0.02, 0.03]] * abi.IK_CHAINS
                         d["ik_" + where] = digest(*[x.clone() for iters, space, step in ((0, "env", 0.0), (1, "root", 0.0), (8, "env", 0.1), (8, "root", 0.1))
                                                     for x in sim.limb_ik(t, w, off, 0.05, step, iters, space, q, e)])
+                    for where, make in (("aligned", lambda shape: torch.zeros(shape, device="cuda:0")), ("offset", off4)):
+                        if not hasattr(sim.lib, "bez_sim_proximity"):
+                            break
+                        d["prox_" + where] = digest(*sim.proximity(make((n, abi.PROX_GROUND_ROWS, 3)), make((n, abi.PROX_BOXES, abi.PROX_WORDS)),
+                                                                   make((n, abi.PROX_PAIRS, abi.PROX_WORDS))))
                     sim.close()
                     print("%-7s %-8s %-7s n=%-3d %s" % (asset, task, params, n, " ".join("%s=%s" % kv for kv in d.items())), flush=True)
 
