@@ -43,6 +43,9 @@ NUM_GEN = 24
 # bez_sim_inverse_dynamics (include/bez_sim.h "Inverse dynamics", BezSim.inverse_dynamics): the terms of M(q) udot + h(q, u) to add up
 ID_INERTIA, ID_VELOCITY, ID_GRAVITY = 1, 2, 4
 ID_ALL = 7
+# bez_sim_forward_dynamics (include/bez_sim.h "Forward dynamics", BezSim.forward_dynamics): udot = M^-1 (f - h); `bias` is a subset of
+# ID_VELOCITY | ID_GRAVITY, the mode bit holds the root and solves the joint block alone
+FD_FIXED_BASE = 1
 # bez_sim_centroidal (include/bez_sim.h "Centroidal dynamics", BezSim.centroidal): the words of a (N, CM_WORDS) state row; the momentum
 # matrix is (N, 6, NUM_GEN) with rows [linear momentum 3; angular momentum about the centre of mass 3]
 CM_WORDS = 16

@@ -1,4 +1,4 @@
-// bez_dynamics.h -- the kernels that run forward kinematics outside the control step (rigid-body refresh, dynamics tensors, inverse and
+// bez_dynamics.h -- the kernels that run forward kinematics outside the control step (rigid-body refresh, dynamics tensors, inverse, forward and
 // centroidal dynamics, body accelerations, external wrenches, limb inverse kinematics, proximity) and what they share: DynArgs, tile I/O, the composite-rigid-body sweep.  Included by bez_sim.hip only.
 #pragma once
 #include "bez_kernels.h"
@@ -210,6 +210,42 @@ BEZ_DEV void composite_sweep(LinkInertia (&Ic)[BEZ_NL], const M3 (&E)[BEZ_NL], c
   });
 }
 
+// Phase 1 for one env, shared with forward_dynamics_kernel.  L: the env's LDS words; E, r: its link frames (link_frames).
+// dyn_joint_words: the world joint axes and the joint origins; dyn_mass_words, which reads them back: the distinct entries of M
+// (without PAIRS: the base block and the F_l alone).
+BEZ_DEV void dyn_put3(float* L, int at, V3 v) { L[at] = v.x; L[at + 1] = v.y; L[at + 2] = v.z; }
+BEZ_DEV void dyn_joint_words(float* L, const M3 (&E)[BEZ_NL], const V3 (&r)[BEZ_NL]) {
+  static_for<BEZ_ND>([&](auto I) {   // the joint's axis is the column of its link's frame that the joint rotation leaves alone
+    constexpr int l = 1 + decltype(I)::value;
+    dyn_put3(L, DYN_AX + 3 * (l - 1), col(E[l], axis_index(l)) * axis_sign(l));
+    dyn_put3(L, DYN_RO + 3 * (l - 1), r[l]);
+  });
+}
+template <bool CL, bool PAIRS = true>
+BEZ_DEV void dyn_mass_words(const DynArgs& D, int e, float* L, const M3 (&E)[BEZ_NL], const V3 (&r)[BEZ_NL]) {
+  LinkInertia Ic[BEZ_NL];
+  link_inertias<CL>(D, e, E, r, Ic, [](auto) {});
+  float* Ms = L + DYN_MS;
+  composite_sweep(Ic, E, r, [&](auto Lk, SV F) {
+    constexpr int l = decltype(Lk)::value;
+    dyn_put3(L, DYN_MS + MS_F + 6 * (l - 1), F.l);
+    dyn_put3(L, DYN_MS + MS_F + 6 * (l - 1) + 3, F.a);
+    if constexpr (PAIRS) {
+      int at = MS_PAIR + dyn_pair_base(l);
+      for (int j = l; j > 0; j = BEZ_LINK_PARENT[j], ++at) {
+        const V3 aj = lds3(L + DYN_AX + 3 * (j - 1)), sj = cross(lds3(L + DYN_RO + 3 * (j - 1)), aj);
+        const float v = dot(aj, F.a) + dot(sj, F.l);
+        Ms[at] = j == l ? v + D.armature : v;
+      }
+    }
+  });
+  const LinkInertia& C = Ic[0];
+  Ms[MS_ZERO] = 0.f; Ms[MS_MASS] = C.m;
+  dyn_put3(L, DYN_MS + MS_H, C.h); dyn_put3(L, DYN_MS + MS_NH, -C.h);
+  Ms[MS_IBAR] = C.Ibar.xx; Ms[MS_IBAR + 1] = C.Ibar.yy; Ms[MS_IBAR + 2] = C.Ibar.zz;
+  Ms[MS_IBAR + 3] = C.Ibar.xy; Ms[MS_IBAR + 4] = C.Ibar.xz; Ms[MS_IBAR + 5] = C.Ibar.yz;
+}
+
 template <bool CL>
 __global__ void __launch_bounds__(DYN_THREADS) refresh_dynamics_kernel(DynArgs D, float* __restrict__ J, float* __restrict__ M) {
   __shared__ float lds[DYN_TILE * DYN_STRIDE];
@@ -222,37 +258,12 @@ __global__ void __launch_bounds__(DYN_THREADS) refresh_dynamics_kernel(DynArgs D
     load_state(D.st, n, e, S);
     M3 E[BEZ_NL]; V3 r[BEZ_NL]; SV V[BEZ_NL];
     link_frames<CL, false>(S, D.flags, E, r, V);
-    auto put3 = [&](int at, V3 v) { L[at] = v.x; L[at + 1] = v.y; L[at + 2] = v.z; };
-    static_for<BEZ_ND>([&](auto I) {   // the joint's axis is the column of its link's frame that the joint rotation leaves alone
-      constexpr int l = 1 + decltype(I)::value;
-      put3(DYN_AX + 3 * (l - 1), col(E[l], axis_index(l)) * axis_sign(l));
-      put3(DYN_RO + 3 * (l - 1), r[l]);
-    });
+    dyn_joint_words(L, E, r);
     static_for<NB>([&](auto I) {
       const BodyFrame f = body_frame<CL>(decltype(I)::value);
-      put3(DYN_XB + 3 * decltype(I)::value, r[f.link] + mul(E[f.link], f.off));
+      dyn_put3(L, DYN_XB + 3 * decltype(I)::value, r[f.link] + mul(E[f.link], f.off));
     });
-    if (M) {
-      LinkInertia Ic[BEZ_NL];
-      link_inertias<CL>(D, e, E, r, Ic, [](auto) {});
-      float* Ms = L + DYN_MS;
-      composite_sweep(Ic, E, r, [&](auto Lk, SV F) {
-        constexpr int l = decltype(Lk)::value;
-        put3(DYN_MS + MS_F + 6 * (l - 1), F.l);
-        put3(DYN_MS + MS_F + 6 * (l - 1) + 3, F.a);
-        int at = MS_PAIR + dyn_pair_base(l);
-        for (int j = l; j > 0; j = BEZ_LINK_PARENT[j], ++at) {
-          const V3 aj = lds3(L + DYN_AX + 3 * (j - 1)), sj = cross(lds3(L + DYN_RO + 3 * (j - 1)), aj);
-          const float v = dot(aj, F.a) + dot(sj, F.l);
-          Ms[at] = j == l ? v + D.armature : v;
-        }
-      });
-      const LinkInertia& C = Ic[0];
-      Ms[MS_ZERO] = 0.f; Ms[MS_MASS] = C.m;
-      put3(DYN_MS + MS_H, C.h); put3(DYN_MS + MS_NH, -C.h);
-      Ms[MS_IBAR] = C.Ibar.xx; Ms[MS_IBAR + 1] = C.Ibar.yy; Ms[MS_IBAR + 2] = C.Ibar.zz;
-      Ms[MS_IBAR + 3] = C.Ibar.xy; Ms[MS_IBAR + 4] = C.Ibar.xz; Ms[MS_IBAR + 5] = C.Ibar.yz;
-    }
+    if (M) dyn_mass_words<CL>(D, e, L, E, r);
   }
   __syncthreads();
   if (J) {
@@ -719,6 +730,42 @@ static_assert(IK_TILE <= 64, "one lane of a wave per env of the tile");
 constexpr int ik_chain_first(int c) { for (int l = 1; l < BEZ_NL; ++l) if (BEZ_LINK_PARENT[l] == 0 && c-- == 0) return l; return -1; }
 constexpr int ik_chain_len(int c) { const int f = ik_chain_first(c); int k = 1; while (f + k < BEZ_NL && BEZ_LINK_PARENT[f + k] != 0) ++k; return k; }
 static_assert(ik_chain_first(BEZ_IK_CHAINS - 1) > 0 && ik_chain_first(BEZ_IK_CHAINS) < 0, "BEZ_IK_CHAINS chains off the torso");
+// The Cholesky factorisation of a symmetric positive definite K x K matrix given by its lower triangle, in place as L L^T with the
+// reciprocals of L's diagonal beside it, and the two substitutions that solve L L^T x = b in place.  Every index is compile-time, so
+// the factor lives in registers.  Shared with forward_dynamics_kernel.
+template <int K>
+BEZ_DEV void chol_factor(float (&A)[K][K], float (&inv)[K]) {
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    float d = A[j][j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) d = fmaf(-A[j][k], A[j][k], d);
+    d = sqrtf(d);
+    inv[j] = 1.f / d;
+#pragma unroll
+    for (int i = j + 1; i < K; ++i) {
+      float s = A[i][j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) s = fmaf(-A[i][k], A[j][k], s);
+      A[i][j] = s * inv[j];
+    }
+  }
+}
+template <int K>
+BEZ_DEV void chol_solve(const float (&A)[K][K], const float (&inv)[K], float (&x)[K]) {
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+#pragma unroll
+    for (int k = 0; k < i; ++k) x[i] = fmaf(-A[i][k], x[k], x[i]);
+    x[i] *= inv[i];
+  }
+#pragma unroll
+  for (int i = K - 1; i >= 0; --i) {
+#pragma unroll
+    for (int k = i + 1; k < K; ++k) x[i] = fmaf(-A[k][i], x[k], x[i]);
+    x[i] *= inv[i];
+  }
+}
 // what a chain needs of the call: the env, the joint limit rows, the root pose that takes ENV targets into the root's frame
 struct IkCtx { const float *st, *lower, *upper; int n, e; float quirk_z; bool env; M3 E0; V3 root_pos; float lam2, max_step; int iters; };
 // x held to [lo, hi]; a NaN stays a NaN (fminf / fmaxf would return the limit)
@@ -790,33 +837,8 @@ BEZ_DEV void ik_chain(const IkCtx& K, const BezIkParams& P, const float* T, floa
       A[i][i] += K.lam2;
       x[i] = fmaf(wp, dot(Jl[i], ep), wr * dot(a[i], er));
     }
-#pragma unroll
-    for (int j = 0; j < LEN; ++j) {
-      float d = A[j][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) d = fmaf(-A[j][k], A[j][k], d);
-      d = sqrtf(d);
-      inv[j] = 1.f / d;
-#pragma unroll
-      for (int i = j + 1; i < LEN; ++i) {
-        float s = A[i][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) s = fmaf(-A[i][k], A[j][k], s);
-        A[i][j] = s * inv[j];
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < LEN; ++i) {
-#pragma unroll
-      for (int k = 0; k < i; ++k) x[i] = fmaf(-A[i][k], x[k], x[i]);
-      x[i] *= inv[i];
-    }
-#pragma unroll
-    for (int i = LEN - 1; i >= 0; --i) {
-#pragma unroll
-      for (int k = i + 1; k < LEN; ++k) x[i] = fmaf(-A[k][i], x[k], x[i]);
-      x[i] *= inv[i];
-    }
+    chol_factor<LEN>(A, inv);
+    chol_solve<LEN>(A, inv, x);
     float big = 0.f;
 #pragma unroll
     for (int i = 0; i < LEN; ++i) big = fmaxf(big, fabsf(x[i]));
@@ -863,6 +885,268 @@ __global__ void __launch_bounds__(IK_THREADS) limb_ik_kernel(DynArgs D, const fl
   __syncthreads();
   if (q_out) tile_store_ragged<BEZ_ND, IK_QSTRIDE, IK_THREADS>(qrows, q_out + (size_t)e0 * BEZ_ND, ne * BEZ_ND);
   if (err_out) tile_store_ragged<IK_EW, IK_ESTRIDE, IK_THREADS>(erows, err_out + (size_t)e0 * IK_EW, ne * IK_EW);
+}
+
+// ---- bez_sim_forward_dynamics (definition: include/bez_sim.h "Forward dynamics"): udot = M^-1 (f - h), solved on the tree's structure.
+// The tree is a torso and five chains whose joints are disjoint, so the blocks of M between different chains are exact zeros and M is
+// a block arrow: [M00 B^T; B diag(M_cc)] with M00 the 6 x 6 base block, M_cc the k x k joint block of chain c (k = 2 or 6) and B_c its
+// k x 6 coupling to the base, the rows F_l = I^c_l S_l of its links.  Eliminating the chains leaves the Schur complement on the base:
+//     y_c = M_cc^-1 r_c,  Z_c = M_cc^-1 B_c,  S = M00 - sum_c B_c^T Z_c,  g = r_0 - sum_c B_c^T y_c,  x_0 = S^-1 g,  x_c = y_c - Z_c x_0
+// with r = f - h.  Nothing larger than 6 x 6 is factored, and no 24 x 24 matrix is held anywhere.
+// A workgroup is four waves and takes FD_TILE consecutive envs; a unit is FD_TILE consecutive lanes, one per env of the tile.  All
+// lanes bring the tile's force rows into LDS (tile_load; zeros for a null pointer).  Then two waves work at once: unit 0 (wave 0) walks
+// the tree for h (fd_bias) with the bias terms asked for and leaves it in the env's second row; unit 4 (wave 1) runs phase 1 of
+// refresh_dynamics_kernel (dyn_joint_words, dyn_mass_words) and leaves the base block and the F_l in the env's MS_* words.  Then every
+// chain has a unit of its own, as in limb_ik_kernel -- the legs and the right arm a wave each, the head and the left arm (2 x 2
+// problems) the first two units of wave 0, which runs them one after the other: the unit walks its chain for M_cc (fd_chain_block), reads B_c through
+// the slot table of the mass matrix, factors M_cc (chol_factor) and keeps y_c and the six columns of Z_c in registers; the 21 distinct values of
+// B_c^T Z_c and the 6 of B_c^T y_c go to the chain's words of the env.  Unit 0 then forms S and g, the chains' parts taken off in the
+// fixed order c = 0 .. 4, factors S, and writes x_0 over the force row's first six words; the chains' units finish with x_c = y_c -
+// Z_c x_0 over their own words of that row, and all lanes store the tile's rows (tile_store).
+// (Four waves, not one per chain: a fifth wave shares a SIMD with another, which caps every wave at 256 registers, and the 19 link
+// frames that phase 1 keeps live need 10 more -- the compiler then spills 14 registers to 60 bytes of scratch per lane.)
+// BEZ_FD_FIXED_BASE: x_0 = +0.0f, x_c = y_c -- no Z_c, no Schur complement; a chain's result then depends on its own rows alone.
+// An env's values pass through that env's lanes and LDS words only: its bits depend neither on N nor on its place in the tile, and a
+// non-finite input stays in its env.  Every result is canonicalised (x + 0.0f).
+constexpr int FD_TILE = 16, FD_THREADS = 256, FD_RSTRIDE = DYN_NG + 1;   // odd row strides: the lanes' own rows start in distinct LDS banks
+constexpr int FD_CW = 21 + 6, FD_CSTRIDE = (FD_CW * BEZ_IK_CHAINS) | 1;                 // a chain's words: tri(B^T Z), B^T y
+constexpr int fd_unit(int c) { return c < 2 ? c : 4 * (c - 1); }                        // the unit that takes chain c
+static_assert(FD_TILE == DYN_TILE && 64 % FD_TILE == 0 && (fd_unit(BEZ_IK_CHAINS - 1) + 1) * FD_TILE <= FD_THREADS, "units of one lane per env; the tile of refresh_dynamics_kernel");
+constexpr MassSlots MASS_SLOT_TABLE = mass_slots();
+constexpr int fd_tri(int a, int b) { return a * (a + 1) / 2 + b; }   // (a, b), a >= b, of a lower triangle stored row by row
+// M[I][J] of the env whose MS_* words start at Ms
+template <int I, int J>
+BEZ_DEV float mass_at(const float* Ms) {
+  constexpr int slot = MASS_SLOT_TABLE.s[I * DYN_NG + J];
+  return Ms[slot];
+}
+// Link L's mass, its centre of mass c (E, r: the link's frame) and its inertia about c in the axes of E's columns: link_inertia's
+// inputs, not moved to the origin of r
+template <int L, bool CL>
+BEZ_DEV void link_com_inertia(float ms, const M3& E, V3 r, float& m, V3& c, Sym3& Iw) {
+  m = (float)link_mass<CL>(L) * ms;
+  c = r + mul(E, mk((float)link_com<CL>(L, 0), (float)link_com<CL>(L, 1), (float)link_com<CL>(L, 2)));
+  Sym3 Il;
+  Il.xx = (float)link_inertia_c<CL>(L, 0) * ms; Il.yy = (float)link_inertia_c<CL>(L, 1) * ms; Il.zz = (float)link_inertia_c<CL>(L, 2) * ms;
+  Il.xy = (float)link_inertia_c<CL>(L, 3) * ms; Il.xz = (float)link_inertia_c<CL>(L, 4) * ms; Il.yz = (float)link_inertia_c<CL>(L, 5) * ms;
+  constexpr bool DIAG = link_inertia_c<CL>(L, 3) == 0. && link_inertia_c<CL>(L, 4) == 0. && link_inertia_c<CL>(L, 5) == 0.;
+  Iw = DIAG ? rotate_inertia_diag(E, Il.xx, Il.yy, Il.zz) : rotate_inertia(E, Il);
+}
+// The lower triangle of M_cc, chain C's joint block of M, with every lever arm taken from the joint's own origin:
+//     M_ij = sum over the links l at or below joint i of  m_l (a_i x (c_l - r_i)) . (a_j x (c_l - r_j)) + a_j . I_l a_i  (+ armature, i = j)
+// in the root's axes (the block does not depend on the root's pose).  The MS_PAIR words of refresh_dynamics_kernel hold the same
+// numbers as a_j . (F.a - r_j x F.l) with F = I^c_i S_i about the ROOT origin: a moment of the size m |r|^2 taken back to the joint, which
+// leaves 2.3e-6 of sqrt(M_ii M_jj) in them.  The solve multiplies that by M_cc^-1: measured on MI355X, the joint rows
+// of udot = M^-1 f then miss the fp64 reference by 1.1e-3 rad/s^2 of 500, of which the fp32 elimination itself accounts for 2e-4.
+template <bool CL, int C>
+BEZ_DEV void fd_chain_block(const DynArgs& D, int e, float (&A)[ik_chain_len(C)][ik_chain_len(C)]) {
+  constexpr int FIRST = ik_chain_first(C), LEN = ik_chain_len(C);
+  static_assert(is_chain<FIRST, LEN>(), "not a chain off the torso");
+  const float quirk_z = quirk_rz<CL>(D.flags);
+  M3 E = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+  V3 r = mk(0.f, 0.f, 0.f), a[LEN], ro[LEN];
+  static_for<LEN>([&](auto Lk) {
+    constexpr int l = decltype(Lk)::value;
+    SV S, cb, V = svzero();
+    link_kinematics<FIRST + l>(D.st[(size_t)(F_Q + FIRST + l - 1) * D.n + e], 0.f, E, r, V, S, cb, quirk_z);
+    a[l] = S.a; ro[l] = r;
+    float m; V3 c; Sym3 Iw;
+    link_com_inertia<FIRST + l, CL>(mass_scale_of(D, e, FIRST + l), E, r, m, c, Iw);
+    V3 u[l + 1], w[l + 1];
+#pragma unroll
+    for (int i = 0; i <= l; ++i) { u[i] = cross(a[i], c - ro[i]); w[i] = mul(Iw, a[i]); }
+#pragma unroll
+    for (int i = 0; i <= l; ++i) {
+#pragma unroll
+      for (int j = 0; j <= i; ++j) {
+        const float v = fmaf(m, dot(u[i], u[j]), dot(a[j], w[i]));
+        A[i][j] = (i == l) ? (i == j ? v + D.armature : v) : A[i][j] + v;   // (row l starts with link l)
+      }
+    }
+  });
+}
+// Chain C of one env.  Ms: the env's MS_* words; F, H: its force and bias rows; W: the chain's FD_CW words; y, Z: what the chain keeps
+// for fd_chain_finish (the first LEN rows are used)
+template <bool CL, int C>
+BEZ_DEV void fd_chain_reduce(const DynArgs& D, int e, const float* Ms, const float* F, const float* H, bool floating, float* W, float (&y)[6],
+                             float (&Z)[6][6]) {
+  constexpr int LEN = ik_chain_len(C), R0 = 5 + ik_chain_first(C);   // the chain's first row of M
+  static_assert(LEN <= 6, "a chain's factor is at most 6 x 6");
+  float A[LEN][LEN], inv[LEN], x[LEN];
+  fd_chain_block<CL, C>(D, e, A);
+#pragma unroll
+  for (int i = 0; i < LEN; ++i) x[i] = F[R0 + i] - H[R0 + i];
+  chol_factor<LEN>(A, inv);
+  chol_solve<LEN>(A, inv, x);
+#pragma unroll
+  for (int i = 0; i < LEN; ++i) y[i] = x[i];
+  if (!floating) return;
+  float B[LEN][6];
+  static_for<LEN>([&](auto I) {
+    constexpr int i = decltype(I)::value;
+    static_for<6>([&](auto K) { B[i][decltype(K)::value] = mass_at<R0 + i, decltype(K)::value>(Ms); });
+  });
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+#pragma unroll
+    for (int i = 0; i < LEN; ++i) x[i] = B[i][k];
+    chol_solve<LEN>(A, inv, x);
+#pragma unroll
+    for (int i = 0; i < LEN; ++i) Z[i][k] = x[i];
+  }
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+#pragma unroll
+    for (int b = 0; b <= a; ++b) {
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < LEN; ++i) s = fmaf(B[i][a], Z[i][b], s);
+      W[fd_tri(a, b)] = s;
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < LEN; ++i) s = fmaf(B[i][a], y[i], s);
+    W[21 + a] = s;
+  }
+}
+// x_c = y_c - Z_c x_0 (fixed base: y_c) into the chain's words of the env's row X, whose first six words hold x_0
+template <int C>
+BEZ_DEV void fd_chain_finish(bool floating, float* X, const float (&y)[6], const float (&Z)[6][6]) {
+  constexpr int LEN = ik_chain_len(C), R0 = 5 + ik_chain_first(C);
+  float x0[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) x0[k] = floating ? X[k] : 0.f;
+#pragma unroll
+  for (int i = 0; i < LEN; ++i) {
+    float x = y[i];
+    if (floating) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) x = fmaf(-Z[i][k], x0[k], x);
+    }
+    X[R0 + i] = x + 0.f;
+  }
+}
+// The base of one env: S = M00 - sum_c B_c^T Z_c and g = r_0 - sum_c B_c^T y_c from the chains' words W, x_0 = S^-1 g over X[0:6]
+BEZ_DEV void fd_base_solve(const float* Ms, const float* H, const float* W, float* X) {
+  float S[6][6], inv[6], g[6];
+  static_for<6>([&](auto I) {
+    constexpr int i = decltype(I)::value;
+    static_for<i + 1>([&](auto J) {
+      constexpr int j = decltype(J)::value;
+      float s = mass_at<i, j>(Ms);
+#pragma unroll
+      for (int c = 0; c < BEZ_IK_CHAINS; ++c) s -= W[FD_CW * c + fd_tri(i, j)];
+      S[i][j] = s;
+    });
+    float s = X[i] - H[i];
+#pragma unroll
+    for (int c = 0; c < BEZ_IK_CHAINS; ++c) s -= W[FD_CW * c + 21 + i];
+    g[i] = s;
+  });
+  chol_factor<6>(S, inv);
+  chol_solve<6>(S, inv, g);
+#pragma unroll
+  for (int i = 0; i < 6; ++i) X[i] = g[i] + 0.f;
+}
+// h(q, u) of one env, the terms in `bias`, into its row H: the walk of inverse_dynamics_kernel with udot = 0 and every link's wrench taken
+// about the LINK's own origin (world axes), where the joint torque is a . n.  id_links takes all moments about the root origin: a
+// distal joint's torque is then what is left of moments of 0.3 m x 75 N (the test states turn joints at 20 rad/s), and that rounding,
+// harmless in a force, is multiplied by M_cc^-1 here -- measured on MI355X with h from id_links, the joint rows of udot missed their
+// bar by 1.15 on states with a mass-scale row.  On the way back a link hands its subtree's wrench to its parent's origin, a lever arm
+// of one link.  The velocity product and gravity are link_inertia's own bias force pA = v x* I v - I [0; g].
+template <int L, int END, bool CL>
+BEZ_DEV SV fd_bias_links(const IdCtx& C, M3 E, V3 r, SV V, SV aV, float* H) {
+  const V3 r_parent = r;
+  const float q = C.D.st[(size_t)(F_Q + L - 1) * C.D.n + C.e], qd = C.vel ? C.D.st[(size_t)(F_QD + L - 1) * C.D.n + C.e] : 0.f;
+  SV S, cb;
+  link_kinematics<L>(q, qd, E, r, V, S, cb, C.quirk_z);
+  aV = aV + cb;
+  // the link's velocity and acceleration about its own origin (V, aV: about the root origin)
+  const SV Vl = mksv(V.a, point_of(V, r)), al = mksv(aV.a, point_of(aV, r));
+  LinkInertia LI; SV F;
+  link_inertia<L, CL>(mass_scale_of(C.D, C.e, L), C.g, E, mk(0.f, 0.f, 0.f), Vl, LI, F);
+  F = F + inertia_times(LI, al);
+  if constexpr (L + 1 < END) F = F + fd_bias_links<L + 1, END, CL>(C, E, r, V, aV, H);
+  H[5 + L] = dot(S.a, F.a);
+  return mksv(F.a + cross(r - r_parent, F.l), F.l);
+}
+template <bool CL>
+BEZ_DEV void fd_bias(const DynArgs& D, int e, uint32_t bias, float* H) {
+  auto ld = [&](int f) { return D.st[(size_t)f * D.n + e]; };
+  const bool vel = (bias & BEZ_ID_VELOCITY) != 0;
+  const M3 E0 = quat_to_mat(ld(F_ROOT_QUAT), ld(F_ROOT_QUAT + 1), ld(F_ROOT_QUAT + 2), ld(F_ROOT_QUAT + 3));
+  const SV V0 = vel ? mksv(mk(ld(F_ROOT_ANG), ld(F_ROOT_ANG + 1), ld(F_ROOT_ANG + 2)), mk(ld(F_ROOT_LIN), ld(F_ROOT_LIN + 1), ld(F_ROOT_LIN + 2))) : svzero();
+  V3 g = mk(0.f, 0.f, 0.f);
+  if (bias & BEZ_ID_GRAVITY) g = gravity_of(D, e);
+  const SV aV0 = mksv(mk(0.f, 0.f, 0.f), -cross(V0.a, V0.l));   // (inverse_dynamics_kernel: the torso's acceleration about a fixed point)
+  LinkInertia I0; SV F0;
+  link_inertia<0, CL>(mass_scale_of(D, e, 0), g, E0, mk(0.f, 0.f, 0.f), V0, I0, F0);
+  F0 = F0 + inertia_times(I0, aV0);
+  IdCtx C = {D, e, vel, quirk_rz<CL>(D.flags), g};
+  auto chain = [&](auto first, auto len) {
+    constexpr int FIRST = decltype(first)::value, LEN = decltype(len)::value;
+    static_assert(is_chain<FIRST, LEN>(), "not a chain off the torso");
+    asm volatile("" : "+v"(C.e), "+v"(F0.l.x));   // (opaque per chain, as in inverse_dynamics_kernel)
+    F0 = F0 + fd_bias_links<FIRST, FIRST + LEN, CL>(C, E0, mk(0.f, 0.f, 0.f), V0, aV0, H);
+  };
+  using std::integral_constant;
+  chain(integral_constant<int, 13>{}, integral_constant<int, 6>{});
+  chain(integral_constant<int, 11>{}, integral_constant<int, 2>{});
+  chain(integral_constant<int, 5>{}, integral_constant<int, 6>{});
+  chain(integral_constant<int, 3>{}, integral_constant<int, 2>{});
+  chain(integral_constant<int, 1>{}, integral_constant<int, 2>{});
+  H[0] = F0.l.x; H[1] = F0.l.y; H[2] = F0.l.z; H[3] = F0.a.x; H[4] = F0.a.y; H[5] = F0.a.z;
+}
+template <bool CL>
+__global__ void __launch_bounds__(FD_THREADS) forward_dynamics_kernel(DynArgs D, const float* force, float* out, uint32_t bias, int fixed) {
+  __shared__ float lds[FD_TILE * DYN_STRIDE];
+  __shared__ float frows[FD_TILE * FD_RSTRIDE];   // f, then udot
+  __shared__ float hrows[FD_TILE * FD_RSTRIDE];   // h
+  __shared__ float crows[FD_TILE * FD_CSTRIDE];
+  const int n = D.n, e0 = blockIdx.x * FD_TILE, ne = min(FD_TILE, n - e0);
+  if (force) tile_load<DYN_NG, FD_RSTRIDE, FD_THREADS>(frows, force + (size_t)e0 * DYN_NG, ne);
+  for (int i = threadIdx.x; i < ne * DYN_NG; i += FD_THREADS) {
+    if (!force) frows[tile_word<DYN_NG, FD_RSTRIDE>(i)] = 0.f;
+    hrows[tile_word<DYN_NG, FD_RSTRIDE>(i)] = 0.f;
+  }
+  __syncthreads();
+  const int el = threadIdx.x % FD_TILE, unit = threadIdx.x / FD_TILE;
+  const bool mine = el < ne, floating = !fixed;
+  const int e = e0 + el;
+  float* L = lds + el * DYN_STRIDE;
+  float* X = frows + el * FD_RSTRIDE;
+  const float* H = hrows + el * FD_RSTRIDE;
+  float* W = crows + el * FD_CSTRIDE;
+  if (mine && unit == 0 && bias) fd_bias<CL>(D, e, bias, hrows + el * FD_RSTRIDE);
+  if (mine && unit == 4) {
+    EnvState S;
+    load_state(D.st, n, e, S);
+    M3 E[BEZ_NL]; V3 r[BEZ_NL]; SV V[BEZ_NL];
+    link_frames<CL, false>(S, D.flags, E, r, V);
+    dyn_joint_words(L, E, r);
+    dyn_mass_words<CL, false>(D, e, L, E, r);
+  }
+  __syncthreads();
+  float y[6], Z[6][6];
+  static_for<BEZ_IK_CHAINS>([&](auto Ci) {
+    constexpr int c = decltype(Ci)::value;
+    if (mine && unit == fd_unit(c)) fd_chain_reduce<CL, c>(D, e, L + DYN_MS, X, H, floating, W + FD_CW * c, y, Z);
+  });
+  __syncthreads();
+  if (mine && unit == 0) {
+    if (floating) fd_base_solve(L + DYN_MS, H, W, X);
+    else {
+#pragma unroll
+      for (int i = 0; i < 6; ++i) X[i] = 0.f;
+    }
+  }
+  __syncthreads();
+  static_for<BEZ_IK_CHAINS>([&](auto Ci) {
+    constexpr int c = decltype(Ci)::value;
+    if (mine && unit == fd_unit(c)) fd_chain_finish<c>(floating, X, y, Z);
+  });
+  __syncthreads();
+  tile_store<DYN_NG, FD_RSTRIDE, FD_THREADS>(frows, out + (size_t)e0 * DYN_NG, ne);
 }
 
 // ---- bez_sim_proximity (definition: include/bez_sim.h "Proximity"): the step's three narrow phases -- link_ground_points, test_box_at /

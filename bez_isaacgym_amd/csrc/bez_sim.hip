@@ -776,6 +776,15 @@ int bez_sim_inverse_dynamics(BezSim* s, const float* udot_dev, uint32_t terms, f
   if (!out_dev) return fail(s, -1, "bez_sim_inverse_dynamics: out_dev is null");
   return LAUNCH_ASSET(s, inverse_dynamics_kernel, ID_TILE, ID_THREADS, (hipStream_t)stream, dyn_args(s), udot_dev, out_dev, terms);
 }
+int bez_sim_forward_dynamics(BezSim* s, const float* force_dev, uint32_t bias, uint32_t mode, float* out_dev, void* stream) {
+  if (!s) return fail(s, -1, "bez_sim_forward_dynamics: sim is null");
+  if (bias & ~(uint32_t)(BEZ_ID_VELOCITY | BEZ_ID_GRAVITY)) return fail(s, -1, "bez_sim_forward_dynamics: bias must be a subset of BEZ_ID_VELOCITY | BEZ_ID_GRAVITY");
+  if (bias == 0u && !force_dev) return fail(s, -1, "bez_sim_forward_dynamics: bias is 0 and force_dev is null (nothing to solve for)");
+  if (mode & ~(uint32_t)BEZ_FD_FIXED_BASE) return fail(s, -1, "bez_sim_forward_dynamics: mode must be 0 or BEZ_FD_FIXED_BASE");
+  if (!out_dev) return fail(s, -1, "bez_sim_forward_dynamics: out_dev is null");
+  return LAUNCH_ASSET(s, forward_dynamics_kernel, FD_TILE, FD_THREADS, (hipStream_t)stream, dyn_args(s), force_dev, out_dev, bias,
+                      (int)(mode & BEZ_FD_FIXED_BASE));
+}
 int bez_sim_centroidal(BezSim* s, float* state_dev, float* matrix_dev, void* stream) {
   if (!s) return fail(s, -1, "bez_sim_centroidal: sim is null");
   if (!state_dev && !matrix_dev) return fail(s, -1, "bez_sim_centroidal: state_dev and matrix_dev are both null (nothing to write)");

@@ -60,6 +60,7 @@ SIGS = {
     "bez_sim_get_dynamics_tensor": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bez_sim_refresh_dynamics_tensors": (C.c_int, [vp, u32, vp]),
     "bez_sim_inverse_dynamics": (C.c_int, [vp, fp, u32, fp, vp]),
+    "bez_sim_forward_dynamics": (C.c_int, [vp, fp, u32, u32, fp, vp]),
     "bez_sim_centroidal": (C.c_int, [vp, fp, fp, vp]),
     "bez_sim_body_accelerations": (C.c_int, [vp, fp, u32, i32, fp, vp]),
     "bez_sim_generalized_forces": (C.c_int, [vp, fp, fp, fp, i32, fp, vp]),
@@ -248,6 +249,31 @@ class BezSim:
         n = shape[0] * shape[1]
         self._check(self.lib.bez_sim_inverse_dynamics(self.h, None if udot is None else self._ptr(udot, torch.float32, n), int(terms),
                                                       self._ptr(out, torch.float32, n), self._stream()))
+        return out
+
+    # ---- forward dynamics: udot = M(q)^-1 (f - h(q, u)) of the current state without forming M
+    def forward_dynamics(self, force=None, bias=abi.ID_VELOCITY | abi.ID_GRAVITY, fixed_base=False, out=None):
+        """(N, 24) float32: udot = M^-1 (f - h), the accelerations that the generalised force `force` produces on the current state, in
+        the coordinates and rows of inverse_dynamics (include/bez_sim.h "Forward dynamics").  `force`: (N, 24) float32 on the sim's
+        device, contiguous, or None for zero.  `bias`: the terms of h taken off the force, a subset of abi.ID_VELOCITY | ID_GRAVITY; 0
+        with a force is the plain mass solve M^-1 f.  `fixed_base`: hold the root -- rows 0:6 are zero and rows 6:24 solve the joint
+        block alone.  `out`: the same kind of tensor to write into (it may be `force`); None: one buffer per sim, allocated by the first
+        such call and overwritten by every later one.  One launch on the current stream; everything is checked before the library is
+        called."""
+        shape = (self.num_envs, abi.NUM_GEN)
+        for name, t in (("force", force), ("out", out)):
+            if t is not None:
+                self._checked(name, t, (shape,))
+        bias = int(bias)
+        if bias & ~(abi.ID_VELOCITY | abi.ID_GRAVITY):
+            raise BezSimError("forward_dynamics: bias must be a subset of abi.ID_VELOCITY | abi.ID_GRAVITY, got %d" % bias)
+        if bias == 0 and force is None:
+            raise BezSimError("forward_dynamics: bias is 0 and force is None (nothing to solve for)")
+        if out is None:
+            out = self._scratch("forward_dynamics", shape)
+        n = shape[0] * shape[1]
+        self._check(self.lib.bez_sim_forward_dynamics(self.h, None if force is None else self._ptr(force, torch.float32, n), bias,
+                                                      abi.FD_FIXED_BASE if fixed_base else 0, self._ptr(out, torch.float32, n), self._stream()))
         return out
 
     # ---- centroidal dynamics: centre of mass, momentum about it, the momentum matrix A_G, mechanical energy

@@ -215,6 +215,25 @@ class VecTask(Env):
         from ... import abi
         return self.sim.inverse_dynamics(None, abi.ID_GRAVITY)
 
+    # ---- forward dynamics of the current state (include/bez_sim.h "Forward dynamics"); each method is one launch, and what it returns
+    # is the sim's one result buffer of that kind: the next call overwrites it
+    def forward_dynamics(self, force=None, bias=6, fixed_base=None):
+        """(N, 24): udot = M(q)^-1 (force - h(q, u)) in u = [root_lin, root_ang, qd]; force (N, 24) or None for zero; bias: the terms of
+        h taken off it (abi.ID_VELOCITY | ID_GRAVITY; default both); fixed_base: hold the root (rows 0:6 zero), None: as the task's
+        urdfAsset.fixBaseLink says"""
+        from ... import abi
+        if fixed_base is None:
+            fixed_base = bool(int(self.sim.cfg.flags) & abi.FLAG_FIX_BASE)
+        return self.sim.forward_dynamics(force, bias, fixed_base)
+
+    def free_acceleration(self):
+        """(N, 24): the acceleration of the current state with nothing acting on it but gravity and its own motion"""
+        return self.forward_dynamics(None)
+
+    def mass_solve(self, b):
+        """(N, 24): M(q)^-1 b for a generalised force b (N, 24)"""
+        return self.forward_dynamics(b, 0)
+
     # ---- centroidal dynamics of the current state (include/bez_sim.h "Centroidal dynamics"); each method is one launch, and what it
     # returns is (a view of) the sim's one result buffer of that kind: the next call overwrites it
     def centroidal_state(self):

@@ -364,6 +364,35 @@ int bez_sim_refresh_dynamics_tensors(BezSim* sim, uint32_t which_mask, void* str
 #define BEZ_ID_ALL      7u
 int bez_sim_inverse_dynamics(BezSim* sim, const float* udot_dev, uint32_t terms, float* out_dev, void* stream);
 
+/* Forward dynamics: the accelerations that a generalised force produces,
+ *       udot = M(q)^-1 (f - h(q, u)),
+ * the inverse of the call above -- the free acceleration of a state, the response to a candidate joint torque, a push or a contact
+ * wrench, M^-1 J^T for operational-space control, a model-based predictor.  (The Isaac Gym route: the mass-matrix tensor and
+ * torch.linalg.solve.)  M is never formed: the tree is a torso and five chains, so M is a block arrow, and the solve is five Cholesky
+ * factorisations of at most 6 x 6 and one of the 6 x 6 Schur complement on the base.
+ *   Coordinates, rows and state are those of bez_sim_inverse_dynamics: u = [root_lin(3), root_ang(3), qd(18)]; force_dev is a generalised
+ *     force, f32 (N, 24), env-major, rows [force, world axes; moment about the root origin, world axes; joint torques] -- what
+ *     bez_sim_generalized_forces returns; out_dev is udot, f32 (N, 24).  The state is read as it stands on `stream`.
+ *     force_dev == NULL means f = 0.
+ *   bias: a subset of BEZ_ID_VELOCITY | BEZ_ID_GRAVITY, the terms of h that are taken off f.  bias == 0 with a force tensor is the plain
+ *     mass solve M^-1 f.
+ *   M is the matrix of BEZ_DYNAMICS_MASS_MATRIX: the armature on the 18 joint diagonals, the env's BEZ_PARAM_MASS_SCALE row, the asset's
+ *     model (cleats, box, the joint origin box + cleats moves).  Gravity is the env's BEZ_PARAM_GRAVITY row if set, else cfg.gravity.
+ *     The ball takes no part.
+ *   bez_sim_inverse_dynamics(out, BEZ_ID_INERTIA | bias) gives f back.
+ *   mode == 0: the floating base, all 24 rows are solved.  BEZ_FLAG_FIX_BASE changes nothing, as in every sibling call.
+ *   mode == BEZ_FD_FIXED_BASE: the root is held.  Rows 0:6 of out are +0.0f to the bit, rows 6:24 solve M[6:,6:] qdd = (f - h)[6:], and
+ *     rows 0:6 of force_dev take no part.  The five chains are then independent problems: with bias == 0 a chain whose 2 or 6 force rows
+ *     are all zero returns +0.0f to the bit, and a chain's result does not depend on the other chains' rows.
+ *   A non-finite input is written through for its own env and changes no bit of any other env.  An env's bits depend neither on N nor
+ *     on where the env stands.
+ *   One kernel launch.  The call allocates nothing, never synchronises, reads nothing on the host and writes only out_dev, which may
+ *   alias force_dev: it captures into a HIP graph.  A pointer that is only 4-byte aligned gives the same bits.
+ *   BEZ_ID_INERTIA or an unknown bit in bias, bias == 0 together with force_dev == NULL (nothing to solve for), an unknown mode bit or a
+ *   null out_dev: rc -1 with a message, and nothing is written. */
+#define BEZ_FD_FIXED_BASE 1u   /* hold the root: udot[0:6] = 0, solve the joint block alone */
+int bez_sim_forward_dynamics(BezSim* sim, const float* force_dev, uint32_t bias, uint32_t mode, float* out_dev, void* stream);
+
 /* Centroidal dynamics: the robot's centre of mass, its momentum about it, the map from u to that momentum, and the mechanical energy --
  * what balance controllers, capture-point and angular-momentum rewards and energy diagnostics read.
  *   Coordinates: u = [root_lin(3), root_ang(3), qd(18)] of the dynamics tensors above; world (env) axes throughout.

@@ -1,6 +1,6 @@
 """Times one of the dynamics queries at num_envs = 4096 beside its yardsticks in the same run.  Prints one JSON line.
 
-  python tools/dynamics_bench.py {tensors,inverse_dynamics,centroidal,body_accelerations,generalized_forces,limb_ik,proximity} [--num-envs 4096] [--launches 200] [--warmup 20] [--cleats]
+  python tools/dynamics_bench.py {tensors,inverse_dynamics,centroidal,body_accelerations,generalized_forces,limb_ik,proximity,forward_dynamics} [--num-envs 4096] [--launches 200] [--warmup 20] [--cleats]
   python tools/dynamics_bench.py inverse_dynamics > profiles/inverse_dynamics_bench.json      (the committed records)
   python tools/dynamics_bench.py centroidal > profiles/centroidal_bench.json
   python tools/dynamics_bench.py body_accelerations > profiles/body_accelerations_bench.json
@@ -29,6 +29,9 @@ columns sliced in torch and torch.linalg.solve per chain (more iterations of tha
 proximity: bez_sim_proximity (all three outputs; the ground rows alone; the pairs alone) beside refresh_rigid_body_state -- the same
 per-lane forward kinematics -- and the route the call replaces: a rigid-body refresh followed by batched torch ops that rebuild the
 collision shapes from bez_model.json on the body rows and compute the same 23 + 11 + 28 rows.
+forward_dynamics: bez_sim_forward_dynamics (floating base with all bias; fixed base; the plain mass solve) beside bez_sim_inverse_dynamics
+with all terms -- whose walk is one of its two front ends -- beside the mass-matrix refresh -- the other -- and the route the call
+replaces: a mass-matrix refresh, bez_sim_inverse_dynamics for h and torch.linalg.solve.
 
 Each figure is the median over --launches (>= 200) single launches, each between its own pair of events on one stream, after --warmup
 launches.  Nothing flushes the caches between launches, for a call and its yardsticks alike.
@@ -377,9 +380,43 @@ def proximity(sim, n, t):
     return res
 
 
+def forward_dynamics(sim, n, t):
+    sim.step(torch.rand(n * 18, device=DEV) * 2 - 1)   # a state off the reset pose, in motion
+    bias = abi.ID_VELOCITY | abi.ID_GRAVITY
+    force = torch.rand(n, abi.NUM_GEN, device=DEV) - 0.5
+    out = torch.zeros(n, abi.NUM_GEN, device=DEV)
+    h = torch.zeros(n, abi.NUM_GEN, device=DEV)
+    udot = torch.zeros(n, abi.NUM_GEN, device=DEV)
+    M = sim.dynamics_tensor("mass_matrix")
+    route = {}
+
+    def replaced():
+        sim.refresh_dynamics_tensors("mass_matrix")
+        sim.inverse_dynamics(None, bias, h)
+        route["udot"] = torch.linalg.solve(M, (force - h).unsqueeze(2))[:, :, 0]
+
+    res = {"forward_dynamics_floating": t(lambda: sim.forward_dynamics(force, bias, False, out)),
+           "forward_dynamics_fixed_base": t(lambda: sim.forward_dynamics(force, bias, True, out)),
+           "forward_dynamics_mass_solve": t(lambda: sim.forward_dynamics(force, 0, False, out)),
+           "inverse_dynamics_all_terms": t(lambda: sim.inverse_dynamics(udot, abi.ID_ALL, h)),
+           "mass_matrix_refresh": t(lambda: sim.refresh_dynamics_tensors("mass_matrix")),
+           "mass_matrix_refresh_plus_bias_plus_linalg_solve": t(replaced)}
+    mine = res["forward_dynamics_floating"]["median_us"]
+    res["ratio_to_inverse_dynamics"] = round(mine / res["inverse_dynamics_all_terms"]["median_us"], 3)
+    res["ratio_to_replaced_route"] = round(mine / res["mass_matrix_refresh_plus_bias_plus_linalg_solve"]["median_us"], 4)
+    # the two routes agree
+    sim.forward_dynamics(force, bias, False, out)
+    replaced()
+    torch.cuda.synchronize()
+    res["max_abs_difference_of_udot"] = float((out - route["udot"]).abs().max())
+    res["max_abs_udot"] = float(out.abs().max())
+    assert torch.isfinite(out).all()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("call", choices=["tensors", "inverse_dynamics", "centroidal", "body_accelerations", "generalized_forces", "limb_ik", "proximity"])
+    ap.add_argument("call", choices=["tensors", "inverse_dynamics", "centroidal", "body_accelerations", "generalized_forces", "limb_ik", "proximity", "forward_dynamics"])
     ap.add_argument("--num-envs", type=int, default=4096)
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
