@@ -1,5 +1,15 @@
 // bez_dynamics.h -- the kernels that run forward kinematics outside the control step (rigid-body refresh, dynamics tensors, inverse, forward and
-// centroidal dynamics, body accelerations, external wrenches, limb inverse kinematics, proximity) and what they share: DynArgs, tile I/O, the composite-rigid-body sweep.  Included by bez_sim.hip only.
+// centroidal dynamics, body accelerations, external wrenches, limb inverse kinematics, proximity).  Included by bez_sim.hip only.
+// What they share, each defined once and named, not restated, in the kernels' own comments:
+//   body_frame, for_each_body_of_link      a body's link, offset and centre of mass; the bodies fixed to one link
+//   chain_first / chain_len, for_each_chain the tree's five chains off the torso, derived from BEZ_LINK_PARENT, in either order
+//   still_chain_walk                        a chain's link frames and joint axes with the joints standing still
+//   DynArgs, mass_scale_of, gravity_of      what the host tells every kernel about the sim; the parameter rows
+//   state_at, state3_at, root_rotation      single fields of an env's state (load_state / link_frames: all of it)
+//   tile_load, tile_store, tile_load_or_zero  a tile's rows between LDS and one contiguous global range, any row width
+//   link_inertias, composite_sweep          the composite-rigid-body front end of the mass and momentum matrices
+//   mass_slots (MASS_SLOT_TABLE, MASS_SLOTS) where every entry of M lives among an env's distinct words
+//   chol_factor, chol_solve                 a register-resident Cholesky solve of up to 6 x 6
 #pragma once
 #include "bez_kernels.h"
 
@@ -41,9 +51,63 @@ BEZ_DEV void link_frames(const EnvState& S, uint32_t flags, M3 (&E)[BEZ_NL], V3 
 struct BodyFrame { int link; V3 off, com; };
 template <bool CL>
 BEZ_DEV BodyFrame body_frame(int b) {
+  // (the offsets are handed out as floats, and "the body sits at its link's origin" is asked of those: none may vanish only in float)
+  static_assert([] {
+    for (int i = 0; i < nb_of<CL>(); ++i)
+      for (int k = 0; k < 3; ++k) {
+        const double v = CL ? BEZ_BODY_OFFSET_CL[i][k] : BEZ_BODY_OFFSET[i][k];
+        if (v != 0.0 && (float)v == 0.f) return false;
+      }
+    return true;
+  }(), "a body offset component is non-zero in double and zero in float");
   const double* o = CL ? BEZ_BODY_OFFSET_CL[b] : BEZ_BODY_OFFSET[b];
   const double* c = CL ? BEZ_BODY_COM_CL[b] : BEZ_BODY_COM[b];
   return {CL ? BEZ_BODY_LINK_CL[b] : BEZ_BODY_LINK[b], mk((float)o[0], (float)o[1], (float)o[2]), mk((float)c[0], (float)c[1], (float)c[2])};
+}
+// The bodies fixed to link L, in the order of their indices: each(b as an integral constant, its BodyFrame, whether its origin is the link's)
+template <bool CL, int L, typename Each>
+BEZ_DEV void for_each_body_of_link(Each&& each) {
+  static_for<nb_of<CL>()>([&](auto I) {
+    constexpr int b = decltype(I)::value;
+    if constexpr ((CL ? BEZ_BODY_LINK_CL[b] : BEZ_BODY_LINK[b]) == L) {
+      const BodyFrame bf = body_frame<CL>(b);
+      each(I, bf, bf.off.x == 0.f && bf.off.y == 0.f && bf.off.z == 0.f);
+    }
+  });
+}
+
+// The tree is a torso (link 0) and BEZ_IK_CHAINS chains off it.  Chain c: the c-th link whose parent is the torso, and the links after
+// it up to the next such link.  for_each_chain hands every chain's (FIRST, LEN) to f as integral constants, first to last or
+// LAST_FIRST; the kernels that walk the tree lane by lane take the chains one after the other through it.
+template <int FIRST, int LEN> constexpr bool is_chain() {
+  if (BEZ_LINK_PARENT[FIRST] != 0) return false;
+  for (int i = 1; i < LEN; ++i) if (BEZ_LINK_PARENT[FIRST + i] != FIRST + i - 1) return false;
+  return FIRST + LEN == BEZ_NL || BEZ_LINK_PARENT[FIRST + LEN] == 0;
+}
+constexpr int chain_first(int c) { for (int l = 1; l < BEZ_NL; ++l) if (BEZ_LINK_PARENT[l] == 0 && c-- == 0) return l; return -1; }
+constexpr int chain_len(int c) { const int f = chain_first(c); int k = 1; while (f + k < BEZ_NL && BEZ_LINK_PARENT[f + k] != 0) ++k; return k; }
+static_assert(chain_first(BEZ_IK_CHAINS - 1) > 0 && chain_first(BEZ_IK_CHAINS) < 0, "BEZ_IK_CHAINS chains off the torso");
+static_assert(chain_first(0) == 1 && chain_len(0) == 2 && chain_first(1) == 3 && chain_len(1) == 2 && chain_first(2) == 5 && chain_len(2) == 6 &&
+              chain_first(3) == 11 && chain_len(3) == 2 && chain_first(4) == 13 && chain_len(4) == 6, "head, two arms, two legs: (1,2) (3,2) (5,6) (11,2) (13,6)");
+template <bool LAST_FIRST, typename F>
+BEZ_DEV void for_each_chain(F&& f) {
+  static_for<BEZ_IK_CHAINS>([&](auto I) {
+    constexpr int c = LAST_FIRST ? BEZ_IK_CHAINS - 1 - decltype(I)::value : decltype(I)::value;
+    // (this one assertion covers the kernels that take chain c by its index, too: some kernel of this header always comes through here)
+    static_assert(is_chain<chain_first(c), chain_len(c)>(), "not a chain off the torso");
+    f(std::integral_constant<int, chain_first(c)>{}, std::integral_constant<int, chain_len(c)>{});
+  });
+}
+// A chain walked with its joints standing still (link_kinematics at qd = 0), from the frame (E, r), which is left as the last link's:
+// q(L) is link L's joint angle, each(L, S) sees the link's frame in E, r and its joint's motion axis S = [a; r x a]
+template <int FIRST, int LEN, typename Angle, typename Each>
+BEZ_DEV void still_chain_walk(M3& E, V3& r, float quirk_z, Angle&& q, Each&& each) {
+  static_for<LEN>([&](auto I) {
+    constexpr int L = FIRST + decltype(I)::value;
+    SV S, cb, V = svzero();
+    link_kinematics<L>(q(std::integral_constant<int, L>{}), 0.f, E, r, V, S, cb, quirk_z);
+    each(std::integral_constant<int, L>{}, S);
+  });
 }
 
 // gym.refresh_rigid_body_state_tensor: forward kinematics of all 21 robot bodies + the ball row
@@ -113,7 +177,8 @@ constexpr MassSlots mass_slots() {
   }
   return T;
 }
-__device__ const MassSlots MASS_SLOTS = mass_slots();
+constexpr MassSlots MASS_SLOT_TABLE = mass_slots();        // for compile-time indices (mass_at)
+__device__ const MassSlots MASS_SLOTS = MASS_SLOT_TABLE;   // for run-time ones (phase 2 of refresh_dynamics_kernel)
 struct BodyAncestors { uint32_t m[BEZ_NB_CL]; };
 template <bool CL> constexpr BodyAncestors body_ancestors() {
   BodyAncestors T = {};
@@ -150,35 +215,58 @@ BEZ_DEV V3 gravity_of(const DynArgs& D, int e) {
   return D.gravity_rows ? mk(D.gravity_rows[(size_t)e * 3], D.gravity_rows[(size_t)e * 3 + 1], D.gravity_rows[(size_t)e * 3 + 2]) : mk(D.g[0], D.g[1], D.g[2]);
 }
 
-// Tile I/O: `nrows` rows of WIDTH floats between LDS (`rows`, STRIDE words apart) and the contiguous global range at `in` / `out`, by a
-// workgroup of THREADS lanes.  Rows are whole float4s, so a range that starts 16-byte aligned moves as float4; any other takes the scalar
-// path to the same bits.
-template <int WIDTH, int STRIDE>
-BEZ_DEV int tile_word(int i) {   // where element i of the global range lives in LDS
-  static_assert(WIDTH % 4 == 0, "whole float4s per row");
-  return (i / WIDTH) * STRIDE + i % WIDTH;
+// The state of env e: field f of the SoA state, three consecutive fields as a vector, the root's orientation.  For the kernels that read
+// a few fields where they need them; load_state / link_frames bring in all of it.
+BEZ_DEV float state_at(const DynArgs& D, int f, int e) { return D.st[(size_t)f * D.n + e]; }
+BEZ_DEV V3 state3_at(const DynArgs& D, int f, int e) { return mk(state_at(D, f, e), state_at(D, f + 1, e), state_at(D, f + 2, e)); }
+BEZ_DEV M3 root_rotation(const DynArgs& D, int e) {
+  return quat_to_mat(state_at(D, F_ROOT_QUAT, e), state_at(D, F_ROOT_QUAT + 1, e), state_at(D, F_ROOT_QUAT + 2, e), state_at(D, F_ROOT_QUAT + 3, e));
 }
+
+// Tile I/O: `nrows` rows of WIDTH floats between LDS (`rows`, STRIDE words apart) and the contiguous global range at `in` / `out`, by a
+// workgroup of THREADS lanes.  A range that starts 16-byte aligned moves as float4, with a scalar tail of (nrows * WIDTH) % 4 elements
+// where rows are not whole float4s; any other takes the scalar path to the same bits.  tile_load_or_zero: zeros where there is no input.
+template <int WIDTH, int STRIDE>
+BEZ_DEV int tile_word(int i) { return (i / WIDTH) * STRIDE + i % WIDTH; }   // where element i of the global range lives in LDS
 template <int WIDTH, int STRIDE, int THREADS>
 BEZ_DEV void tile_load(float* rows, const float* __restrict__ in, int nrows) {
   auto slot = [&](int i) -> float& { return rows[tile_word<WIDTH, STRIDE>(i)]; };
+  const int count = nrows * WIDTH;
   if ((reinterpret_cast<uintptr_t>(in) & 15u) == 0) {
     const float4* in4 = reinterpret_cast<const float4*>(in);
-    for (int i = threadIdx.x; i < nrows * (WIDTH / 4); i += THREADS) {
+    const int n4 = count / 4;
+    for (int i = threadIdx.x; i < n4; i += THREADS) {
       const float4 v = in4[i];
       slot(4 * i) = v.x; slot(4 * i + 1) = v.y; slot(4 * i + 2) = v.z; slot(4 * i + 3) = v.w;
     }
+    if constexpr (WIDTH % 4 != 0) {
+      for (int i = 4 * n4 + threadIdx.x; i < count; i += THREADS) slot(i) = in[i];
+    }
   } else {
-    for (int i = threadIdx.x; i < nrows * WIDTH; i += THREADS) slot(i) = in[i];
+    for (int i = threadIdx.x; i < count; i += THREADS) slot(i) = in[i];
   }
 }
 template <int WIDTH, int STRIDE, int THREADS>
 BEZ_DEV void tile_store(const float* rows, float* __restrict__ out, int nrows) {
   auto at = [&](int i) { return rows[tile_word<WIDTH, STRIDE>(i)]; };
+  const int count = nrows * WIDTH;
   if ((reinterpret_cast<uintptr_t>(out) & 15u) == 0) {
     float4* o4 = reinterpret_cast<float4*>(out);
-    for (int i = threadIdx.x; i < nrows * (WIDTH / 4); i += THREADS) o4[i] = make_float4(at(4 * i), at(4 * i + 1), at(4 * i + 2), at(4 * i + 3));
+    const int n4 = count / 4;
+    for (int i = threadIdx.x; i < n4; i += THREADS) o4[i] = make_float4(at(4 * i), at(4 * i + 1), at(4 * i + 2), at(4 * i + 3));
+    if constexpr (WIDTH % 4 != 0) {
+      for (int i = 4 * n4 + threadIdx.x; i < count; i += THREADS) out[i] = at(i);
+    }
   } else {
-    for (int i = threadIdx.x; i < nrows * WIDTH; i += THREADS) out[i] = at(i);
+    for (int i = threadIdx.x; i < count; i += THREADS) out[i] = at(i);
+  }
+}
+template <int WIDTH, int STRIDE, int THREADS>
+BEZ_DEV void tile_load_or_zero(float* rows, const float* in, int nrows) {
+  if (in) {
+    tile_load<WIDTH, STRIDE, THREADS>(rows, in, nrows);
+  } else {
+    for (int i = threadIdx.x; i < nrows * WIDTH; i += THREADS) rows[tile_word<WIDTH, STRIDE>(i)] = 0.f;
   }
 }
 
@@ -292,18 +380,13 @@ __global__ void __launch_bounds__(DYN_THREADS) refresh_dynamics_kernel(DynArgs D
 // ---- bez_sim_inverse_dynamics (definition: include/bez_sim.h "Inverse dynamics"): recursive Newton-Euler in the frame every bias force
 // here uses (world axes about the root origin), where a subtree's wrench is the plain sum of its links' wrenches.
 // A workgroup is ONE wave and takes ID_TILE consecutive envs.  All lanes bring the tile's udot rows -- one contiguous range -- into LDS
-// (tile_load); then one lane per env walks the tree CHAIN BY CHAIN: out along a chain (two legs of 6 joints, two arms and the head
-// of 2) keeping per joint only S = [a; r x a] and handing the link's acceleration down, back along it adding up the wrenches and emitting
+// (tile_load_or_zero); then one lane per env walks the tree CHAIN BY CHAIN (for_each_chain): out along a chain (two legs of 6 joints,
+// two arms and the head of 2) keeping per joint only S = [a; r x a] and handing the link's acceleration down, back along it adding up the wrenches and emitting
 // tau = S . F into the udot slot it has just consumed, and the chain's total joins the torso's wrench.  At most six links are live,
 // never the 19 frames of link_frames.  Last, all lanes write the tile's rows as one contiguous range of float4 stores.
 // A term is dropped by zeroing its input (udot, the velocities, g): one code path, and the dropped term's products are exact zeros.
 // The chains are taken last to first and each is summed from its leaf, the order in which refresh_dynamics_kernel adds up the masses.
 constexpr int ID_TILE = 16, ID_THREADS = 64, ID_STRIDE = DYN_NG + 1;   // odd row stride: the lanes' own rows start in distinct LDS banks
-template <int FIRST, int LEN> constexpr bool is_chain() {
-  if (BEZ_LINK_PARENT[FIRST] != 0) return false;
-  for (int i = 1; i < LEN; ++i) if (BEZ_LINK_PARENT[FIRST + i] != FIRST + i - 1) return false;
-  return FIRST + LEN == BEZ_NL || BEZ_LINK_PARENT[FIRST + LEN] == 0;
-}
 // One link of a chain and, by recursion, the links below it: on the way out the link's frame, velocity and accelerations from its
 // parent's (by value: each level keeps its own) and its own wrenches; on the way back tau = S . F goes to U[5 + L], the slot whose udot
 // the way out consumed, and the subtree's wrenches are returned.  (Plain locals per level, no arrays over the links: the compiler keeps
@@ -321,7 +404,7 @@ BEZ_DEV IdWrench id_wrench(const LinkInertia& I, SV aI, SV aV, SV pV, V3 g) {
 BEZ_DEV float id_sum(float i, float v, float g) { return (i + v) + g; }
 template <int L, int END, bool CL>
 BEZ_DEV IdWrench id_links(const IdCtx& C, M3 E, V3 r, SV V, SV aI, SV aV, float* U) {
-  const float q = C.D.st[(size_t)(F_Q + L - 1) * C.D.n + C.e], qd = C.vel ? C.D.st[(size_t)(F_QD + L - 1) * C.D.n + C.e] : 0.f, qdd = U[5 + L];
+  const float q = state_at(C.D, F_Q + L - 1, C.e), qd = C.vel ? state_at(C.D, F_QD + L - 1, C.e) : 0.f, qdd = U[5 + L];
   SV S, cb;
   link_kinematics<L>(q, qd, E, r, V, S, cb, C.quirk_z);
   aI = aI + S * qdd; aV = aV + cb;
@@ -335,21 +418,15 @@ BEZ_DEV IdWrench id_links(const IdCtx& C, M3 E, V3 r, SV V, SV aI, SV aV, float*
 template <bool CL>
 __global__ void __launch_bounds__(ID_THREADS) inverse_dynamics_kernel(DynArgs D, const float* __restrict__ udot, float* __restrict__ out, uint32_t terms) {
   __shared__ float rows[ID_TILE * ID_STRIDE];
-  const float* st = D.st;
   const int n = D.n, e0 = blockIdx.x * ID_TILE, ne = min(ID_TILE, n - e0);
-  if (udot && (terms & BEZ_ID_INERTIA)) {
-    tile_load<DYN_NG, ID_STRIDE, ID_THREADS>(rows, udot + (size_t)e0 * DYN_NG, ne);
-  } else {
-    for (int i = threadIdx.x; i < ne * DYN_NG; i += ID_THREADS) rows[tile_word<DYN_NG, ID_STRIDE>(i)] = 0.f;
-  }
+  tile_load_or_zero<DYN_NG, ID_STRIDE, ID_THREADS>(rows, (udot && (terms & BEZ_ID_INERTIA)) ? udot + (size_t)e0 * DYN_NG : nullptr, ne);
   __syncthreads();
   if ((int)threadIdx.x < ne) {
     const int e = e0 + threadIdx.x;
     float* U = rows + threadIdx.x * ID_STRIDE;
-    auto ld = [&](int f) { return st[(size_t)f * n + e]; };
     const bool vel = (terms & BEZ_ID_VELOCITY) != 0;
-    const M3 E0 = quat_to_mat(ld(F_ROOT_QUAT), ld(F_ROOT_QUAT + 1), ld(F_ROOT_QUAT + 2), ld(F_ROOT_QUAT + 3));
-    const SV V0 = vel ? mksv(mk(ld(F_ROOT_ANG), ld(F_ROOT_ANG + 1), ld(F_ROOT_ANG + 2)), mk(ld(F_ROOT_LIN), ld(F_ROOT_LIN + 1), ld(F_ROOT_LIN + 2))) : svzero();
+    const M3 E0 = root_rotation(D, e);
+    const SV V0 = vel ? mksv(state3_at(D, F_ROOT_ANG, e), state3_at(D, F_ROOT_LIN, e)) : svzero();
     V3 g = mk(0, 0, 0);
     if (terms & BEZ_ID_GRAVITY) g = gravity_of(D, e);
     // spatial acceleration of the torso about the (momentarily fixed) point its origin passes through: [wdot; vdot - w x v]
@@ -360,18 +437,11 @@ __global__ void __launch_bounds__(ID_THREADS) inverse_dynamics_kernel(DynArgs D,
     // (the env index is made opaque per chain, together with the wrench so far: otherwise every chain's loads are issued up front and
     // the five chains are interleaved, at the price of their registers)
     IdCtx C = {D, e, vel, quirk_rz<CL>(D.flags), g};
-    auto chain = [&](auto first, auto len) {
+    for_each_chain<true>([&](auto first, auto len) {
       constexpr int FIRST = decltype(first)::value, LEN = decltype(len)::value;
-      static_assert(is_chain<FIRST, LEN>(), "not a chain off the torso");
       asm volatile("" : "+v"(C.e), "+v"(F0.i.l.x));
       F0 = F0 + id_links<FIRST, FIRST + LEN, CL>(C, E0, mk(0, 0, 0), V0, aI0, aV0, U);
-    };
-    using std::integral_constant;
-    chain(integral_constant<int, 13>{}, integral_constant<int, 6>{});
-    chain(integral_constant<int, 11>{}, integral_constant<int, 2>{});
-    chain(integral_constant<int, 5>{}, integral_constant<int, 6>{});
-    chain(integral_constant<int, 3>{}, integral_constant<int, 2>{});
-    chain(integral_constant<int, 1>{}, integral_constant<int, 2>{});
+    });
     U[0] = id_sum(F0.i.l.x, F0.v.l.x, F0.g.l.x); U[1] = id_sum(F0.i.l.y, F0.v.l.y, F0.g.l.y); U[2] = id_sum(F0.i.l.z, F0.v.l.z, F0.g.l.z);
     U[3] = id_sum(F0.i.a.x, F0.v.a.x, F0.g.a.x); U[4] = id_sum(F0.i.a.y, F0.v.a.y, F0.g.a.y); U[5] = id_sum(F0.i.a.z, F0.v.a.z, F0.g.a.z);
   }
@@ -455,8 +525,8 @@ __global__ void __launch_bounds__(CM_THREADS) centroidal_kernel(DynArgs D, float
 
 // ---- bez_sim_body_accelerations (definition: include/bez_sim.h "Body accelerations"): the outward half of inverse_dynamics_kernel -- no
 // inertias, no return sweep -- with a read-out per body like refresh_rigid_body_kernel's.
-// A workgroup is ONE wave and takes ACC_TILE consecutive envs.  All lanes bring the tile's udot rows into LDS (tile_load); then one lane
-// per env walks the tree chain by chain, in world axes about the root origin, carrying per link only its frame E, r, its spatial
+// A workgroup is ONE wave and takes ACC_TILE consecutive envs.  All lanes bring the tile's udot rows into LDS (tile_load_or_zero); then one
+// lane per env walks the tree chain by chain, in world axes about the root origin, carrying per link only its frame E, r, its spatial
 // velocity V and its spatial acceleration in two parts: aI (from udot: aI += S qdd) and aV (velocity products: aV += cb of
 // link_kinematics).  Every body on the link is read out where the walk stands: with x the body's origin relative to the root origin,
 //     UDOT      [aI.l + aI.a x x ; aI.a]
@@ -468,22 +538,8 @@ __global__ void __launch_bounds__(CM_THREADS) centroidal_kernel(DynArgs D, float
 // translation changes no acceleration), and with it go the pair -w x v + w x v that would cancel in every row and the torso's aV, which
 // is then zero by construction.  Bodies of the torso link take their rows from the definition: [vdot + wdot x x ; wdot] and
 // [w x (w x x) ; 0], so the torso itself (x = 0) returns udot[0:6] and zeros.
-// Last, all lanes write the tile's rows -- one contiguous range of ne x 6 NB floats, not whole float4s -- with tile_store_ragged.
+// Last, all lanes write the tile's rows -- one contiguous range of ne x 6 NB floats, not whole float4s -- with tile_store.
 constexpr int ACC_TILE = 16, ACC_THREADS = 64, ACC_USTRIDE = DYN_NG + 1;   // odd row strides: the lanes' own rows start in distinct LDS banks
-// tile_store for rows that are not whole float4s: `count` floats of the contiguous range at `out`; a 16-byte aligned range moves as
-// float4 with a scalar tail of count % 4 elements, any other takes the scalar path to the same bits.
-template <int WIDTH, int STRIDE, int THREADS>
-BEZ_DEV void tile_store_ragged(const float* rows, float* __restrict__ out, int count) {
-  auto at = [&](int i) { return rows[(i / WIDTH) * STRIDE + i % WIDTH]; };
-  if ((reinterpret_cast<uintptr_t>(out) & 15u) == 0) {
-    float4* o4 = reinterpret_cast<float4*>(out);
-    const int n4 = count / 4;
-    for (int i = threadIdx.x; i < n4; i += THREADS) o4[i] = make_float4(at(4 * i), at(4 * i + 1), at(4 * i + 2), at(4 * i + 3));
-    for (int i = 4 * n4 + threadIdx.x; i < count; i += THREADS) out[i] = at(i);
-  } else {
-    for (int i = threadIdx.x; i < count; i += THREADS) out[i] = at(i);
-  }
-}
 struct AccCtx { float* O; V3 g; bool local; };   // the env's output row in LDS, 0 - g, BEZ_SPACE_LOCAL
 BEZ_DEV V3 acc_sum(V3 i, V3 v, V3 g) {
   const V3 z = mk(0.f, 0.f, 0.f);
@@ -492,25 +548,20 @@ BEZ_DEV V3 acc_sum(V3 i, V3 v, V3 g) {
 // the rows of every body fixed to link L; E, r, V, aI, aV: the link's
 template <bool CL, int L>
 BEZ_DEV void acc_bodies(const AccCtx& C, const M3& E, V3 r, SV V, SV aI, SV aV) {
-  static_for<nb_of<CL>()>([&](auto I) {
-    constexpr int b = decltype(I)::value;
-    if constexpr ((CL ? BEZ_BODY_LINK_CL[b] : BEZ_BODY_LINK[b]) == L) {
-      const double* o = CL ? BEZ_BODY_OFFSET_CL[b] : BEZ_BODY_OFFSET[b];
-      const bool at_link_origin = o[0] == 0.0 && o[1] == 0.0 && o[2] == 0.0;
-      const V3 x = at_link_origin ? r : r + mul(E, mk((float)o[0], (float)o[1], (float)o[2]));
-      V3 li, lv;
-      if constexpr (L == 0) {
-        li = at_link_origin ? aI.l : aI.l + cross(aI.a, x);
-        lv = at_link_origin ? mk(0.f, 0.f, 0.f) : cross(V.a, cross(V.a, x));
-      } else {
-        li = point_of(aI, x);
-        lv = point_of(aV, x) + cross(V.a, point_of(V, x));
-      }
-      V3 lin = acc_sum(li, lv, C.g), ang = acc_sum(aI.a, aV.a, mk(0.f, 0.f, 0.f));
-      if (C.local) { lin = mulT(E, lin) + mk(0.f, 0.f, 0.f); ang = mulT(E, ang) + mk(0.f, 0.f, 0.f); }   // (products of +0.0 may be -0.0)
-      float* O = C.O + 6 * b;
-      O[0] = lin.x; O[1] = lin.y; O[2] = lin.z; O[3] = ang.x; O[4] = ang.y; O[5] = ang.z;
+  for_each_body_of_link<CL, L>([&](auto B, const BodyFrame& bf, bool at_link_origin) {
+    const V3 x = at_link_origin ? r : r + mul(E, bf.off);
+    V3 li, lv;
+    if constexpr (L == 0) {
+      li = at_link_origin ? aI.l : aI.l + cross(aI.a, x);
+      lv = at_link_origin ? mk(0.f, 0.f, 0.f) : cross(V.a, cross(V.a, x));
+    } else {
+      li = point_of(aI, x);
+      lv = point_of(aV, x) + cross(V.a, point_of(V, x));
     }
+    V3 lin = acc_sum(li, lv, C.g), ang = acc_sum(aI.a, aV.a, mk(0.f, 0.f, 0.f));
+    if (C.local) { lin = mulT(E, lin) + mk(0.f, 0.f, 0.f); ang = mulT(E, ang) + mk(0.f, 0.f, 0.f); }   // (products of +0.0 may be -0.0)
+    float* O = C.O + 6 * decltype(B)::value;
+    O[0] = lin.x; O[1] = lin.y; O[2] = lin.z; O[3] = ang.x; O[4] = ang.y; O[5] = ang.z;
   });
 }
 template <bool CL>
@@ -519,21 +570,15 @@ __global__ void __launch_bounds__(ACC_THREADS) body_accelerations_kernel(DynArgs
   constexpr int WIDTH = 6 * nb_of<CL>(), STRIDE = WIDTH | 1;
   __shared__ float urows[ACC_TILE * ACC_USTRIDE];
   __shared__ float orows[ACC_TILE * STRIDE];
-  const float* st = D.st;
   const int n = D.n, e0 = blockIdx.x * ACC_TILE, ne = min(ACC_TILE, n - e0);
-  if (udot && (terms & BEZ_ACC_UDOT)) {
-    tile_load<DYN_NG, ACC_USTRIDE, ACC_THREADS>(urows, udot + (size_t)e0 * DYN_NG, ne);
-  } else {
-    for (int i = threadIdx.x; i < ne * DYN_NG; i += ACC_THREADS) urows[tile_word<DYN_NG, ACC_USTRIDE>(i)] = 0.f;
-  }
+  tile_load_or_zero<DYN_NG, ACC_USTRIDE, ACC_THREADS>(urows, (udot && (terms & BEZ_ACC_UDOT)) ? udot + (size_t)e0 * DYN_NG : nullptr, ne);
   __syncthreads();
   if ((int)threadIdx.x < ne) {
     int e = e0 + threadIdx.x;
     const float* U = urows + threadIdx.x * ACC_USTRIDE;
-    auto ld = [&](int f) { return st[(size_t)f * n + e]; };
     const bool vel = (terms & BEZ_ACC_VELOCITY) != 0;
-    const M3 E0 = quat_to_mat(ld(F_ROOT_QUAT), ld(F_ROOT_QUAT + 1), ld(F_ROOT_QUAT + 2), ld(F_ROOT_QUAT + 3));
-    const SV V0 = mksv(vel ? mk(ld(F_ROOT_ANG), ld(F_ROOT_ANG + 1), ld(F_ROOT_ANG + 2)) : mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 0.f));
+    const M3 E0 = root_rotation(D, e);
+    const SV V0 = mksv(vel ? state3_at(D, F_ROOT_ANG, e) : mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 0.f));
     // spatial acceleration of the torso about the (momentarily fixed) point its origin passes through: [wdot; vdot - w x v], whose
     // second part is a velocity product that vanishes with root_lin = 0
     const SV aI0 = mksv(mk(U[3], U[4], U[5]), mk(U[0], U[1], U[2]));
@@ -542,35 +587,28 @@ __global__ void __launch_bounds__(ACC_THREADS) body_accelerations_kernel(DynArgs
     AccCtx C = {orows + threadIdx.x * STRIDE, mk(0.f - g.x, 0.f - g.y, 0.f - g.z), local != 0};
     const float quirk_z = quirk_rz<CL>(D.flags);
     acc_bodies<CL, 0>(C, E0, mk(0.f, 0.f, 0.f), V0, aI0, svzero());
-    auto chain = [&](auto first, auto len) {
+    for_each_chain<false>([&](auto first, auto len) {
       constexpr int FIRST = decltype(first)::value, LEN = decltype(len)::value;
-      static_assert(is_chain<FIRST, LEN>(), "not a chain off the torso");
       asm volatile("" : "+v"(e));   // (opaque per chain: otherwise every chain's loads are issued up front, at the price of their registers)
       M3 E = E0; V3 r = mk(0.f, 0.f, 0.f); SV V = V0, aI = aI0, aV = svzero();
       static_for<LEN>([&](auto I) {
         constexpr int L = FIRST + decltype(I)::value;
         SV S, cb;
-        link_kinematics<L>(ld(F_Q + L - 1), vel ? ld(F_QD + L - 1) : 0.f, E, r, V, S, cb, quirk_z);
+        link_kinematics<L>(state_at(D, F_Q + L - 1, e), vel ? state_at(D, F_QD + L - 1, e) : 0.f, E, r, V, S, cb, quirk_z);
         aI = aI + S * U[5 + L]; aV = aV + cb;
         acc_bodies<CL, L>(C, E, r, V, aI, aV);
       });
-    };
-    using std::integral_constant;
-    chain(integral_constant<int, 1>{}, integral_constant<int, 2>{});
-    chain(integral_constant<int, 3>{}, integral_constant<int, 2>{});
-    chain(integral_constant<int, 5>{}, integral_constant<int, 6>{});
-    chain(integral_constant<int, 11>{}, integral_constant<int, 2>{});
-    chain(integral_constant<int, 13>{}, integral_constant<int, 6>{});
+    });
   }
   __syncthreads();
-  tile_store_ragged<WIDTH, STRIDE, ACC_THREADS>(orows, out + (size_t)e0 * WIDTH, ne * WIDTH);
+  tile_store<WIDTH, STRIDE, ACC_THREADS>(orows, out + (size_t)e0 * WIDTH, ne);
 }
 
 // ---- bez_sim_generalized_forces (definition: include/bez_sim.h "Generalised forces"): sum_b J_b^T w_b without J -- the return sweep of
 // inverse_dynamics_kernel with the links' inertial wrenches replaced by the wrenches the caller hands in.
 // A workgroup is ONE wave and takes GF_TILE consecutive envs.  All lanes bring the tile's force, torque and position rows -- per tensor
 // one contiguous range of ne x 3 B floats, B with the ball's row where the task has one, not whole float4s -- into LDS with
-// tile_load_ragged; then one lane per env walks the tree chain by chain in link-local coordinates: out along a chain for each link's
+// tile_load; then one lane per env walks the tree chain by chain in link-local coordinates: out along a chain for each link's
 // frame E, r in the root's axes (link_kinematics with qd = 0; ENV inputs are turned by it, LOCAL inputs need no turn), collecting the
 // wrenches of the bodies fixed to the link as [t + d x f ; f] in the link's axes, d the point of application relative to the link's
 // origin; back along it adding up the subtree's wrench, writing tau = +-M[axis] to the env's output row in LDS and taking the wrench to
@@ -580,22 +618,6 @@ __global__ void __launch_bounds__(ACC_THREADS) body_accelerations_kernel(DynArgs
 // in); the ball's row is never read.  Every output is canonicalised (x + 0.0f), so a subtree without a loaded body gives +0.0f to the bit.
 // Last, all lanes write the tile's (ne, 24) rows with tile_store.
 constexpr int GF_TILE = 16, GF_THREADS = 64, GF_OSTRIDE = DYN_NG + 1;   // odd row strides: the lanes' own rows start in distinct LDS banks
-// tile_load for rows that are not whole float4s, the counterpart of tile_store_ragged: `count` floats of the contiguous range at `in`
-template <int WIDTH, int STRIDE, int THREADS>
-BEZ_DEV void tile_load_ragged(float* rows, const float* __restrict__ in, int count) {
-  auto slot = [&](int i) -> float& { return rows[(i / WIDTH) * STRIDE + i % WIDTH]; };
-  if ((reinterpret_cast<uintptr_t>(in) & 15u) == 0) {
-    const float4* in4 = reinterpret_cast<const float4*>(in);
-    const int n4 = count / 4;
-    for (int i = threadIdx.x; i < n4; i += THREADS) {
-      const float4 v = in4[i];
-      slot(4 * i) = v.x; slot(4 * i + 1) = v.y; slot(4 * i + 2) = v.z; slot(4 * i + 3) = v.w;
-    }
-    for (int i = 4 * n4 + threadIdx.x; i < count; i += THREADS) slot(i) = in[i];
-  } else {
-    for (int i = threadIdx.x; i < count; i += THREADS) slot(i) = in[i];
-  }
-}
 // the env's rows in LDS (null: the tensor was not given), its root position, the call's space, and the rotation whose transpose takes
 // an ENV vector into the root's axes
 struct GfCtx { const float *F, *T, *X; V3 root_pos; bool local, at_origin; M3 Rin; };
@@ -604,20 +626,16 @@ struct GfCtx { const float *F, *T, *X; V3 root_pos; bool local, at_origin; M3 Ri
 template <bool CL, int L>
 BEZ_DEV SV gf_bodies(const GfCtx& C, const M3& E, V3 r) {
   SV W = svzero();
-  static_for<nb_of<CL>()>([&](auto I) {
-    constexpr int b = decltype(I)::value;
-    if constexpr ((CL ? BEZ_BODY_LINK_CL[b] : BEZ_BODY_LINK[b]) == L) {
-      const V3 f = C.F ? lds3(C.F + 3 * b) : mk(0.f, 0.f, 0.f), t = C.T ? lds3(C.T + 3 * b) : mk(0.f, 0.f, 0.f);
-      if (f.x != 0.f || f.y != 0.f || f.z != 0.f || t.x != 0.f || t.y != 0.f || t.z != 0.f) {   // (a NaN is != 0: it goes in)
-        const BodyFrame bf = body_frame<CL>(b);
-        const bool at_link_origin = bf.off.x == 0.f && bf.off.y == 0.f && bf.off.z == 0.f;
-        const V3 fl = C.local ? f : mulT(E, mulT(C.Rin, f)), tl = C.local ? t : mulT(E, mulT(C.Rin, t));
-        V3 d;   // the point of application relative to the link's origin
-        if (!C.X) d = C.at_origin ? bf.off : bf.off + bf.com;
-        else if (C.local) d = bf.off + lds3(C.X + 3 * b);
-        else d = mulT(E, mulT(C.Rin, lds3(C.X + 3 * b) - C.root_pos) - r);
-        W = W + mksv((!C.X && C.at_origin && at_link_origin) ? tl : tl + cross(d, fl), fl);
-      }
+  for_each_body_of_link<CL, L>([&](auto B, const BodyFrame& bf, bool at_link_origin) {
+    constexpr int b = decltype(B)::value;
+    const V3 f = C.F ? lds3(C.F + 3 * b) : mk(0.f, 0.f, 0.f), t = C.T ? lds3(C.T + 3 * b) : mk(0.f, 0.f, 0.f);
+    if (f.x != 0.f || f.y != 0.f || f.z != 0.f || t.x != 0.f || t.y != 0.f || t.z != 0.f) {   // (a NaN is != 0: it goes in)
+      const V3 fl = C.local ? f : mulT(E, mulT(C.Rin, f)), tl = C.local ? t : mulT(E, mulT(C.Rin, t));
+      V3 d;   // the point of application relative to the link's origin
+      if (!C.X) d = C.at_origin ? bf.off : bf.off + bf.com;
+      else if (C.local) d = bf.off + lds3(C.X + 3 * b);
+      else d = mulT(E, mulT(C.Rin, lds3(C.X + 3 * b) - C.root_pos) - r);
+      W = W + mksv((!C.X && C.at_origin && at_link_origin) ? tl : tl + cross(d, fl), fl);
     }
   });
   return W;
@@ -640,12 +658,12 @@ BEZ_DEV V3 gf_to_parent(V3 v, float s, float c) {
 // quaternion, unit to 1e-7, enters every LOCAL row) 1.23; about the links' origins in the root's axes (the rounding of the accumulated
 // link rotation is left) 1.10.  Returns the subtree's wrench in the PARENT's axes about the parent's origin; Q: the env's output row.
 template <int L, int END, bool CL>
-BEZ_DEV SV gf_links(const GfCtx& C, const float* st, int n, int e, float quirk_z, M3 E, V3 r, float* Q) {
-  const float q = st[(size_t)(F_Q + L - 1) * n + e];
+BEZ_DEV SV gf_links(const GfCtx& C, const DynArgs& D, int e, float quirk_z, M3 E, V3 r, float* Q) {
+  const float q = state_at(D, F_Q + L - 1, e);
   SV S, cb, V = svzero();
   link_kinematics<L>(q, 0.f, E, r, V, S, cb, quirk_z);
   SV F = gf_bodies<CL, L>(C, E, r);
-  if constexpr (L + 1 < END) F = F + gf_links<L + 1, END, CL>(C, st, n, e, quirk_z, E, r, Q);
+  if constexpr (L + 1 < END) F = F + gf_links<L + 1, END, CL>(C, D, e, quirk_z, E, r, Q);
   Q[5 + L] = axis_sign(L) * pick(F.a, axis_index(L)) + 0.f;
   float sn, cs;
   fsincos(axis_sign(L) * q, &sn, &cs);
@@ -660,26 +678,23 @@ __global__ void __launch_bounds__(GF_THREADS) generalized_forces_kernel(DynArgs 
   constexpr int NB = nb_of<CL>(), STRIDE = (3 * (NB + 1)) | 1;
   __shared__ float in_rows[3][GF_TILE * STRIDE];
   __shared__ float orows[GF_TILE * GF_OSTRIDE];
-  const float* st = D.st;
   const int n = D.n, e0 = blockIdx.x * GF_TILE, ne = min(GF_TILE, n - e0);
   const float* in[3] = {forces, torques, positions};
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     if (!in[k]) continue;
-    if (has_ball) tile_load_ragged<3 * (NB + 1), STRIDE, GF_THREADS>(in_rows[k], in[k] + (size_t)e0 * (3 * (NB + 1)), ne * 3 * (NB + 1));
-    else tile_load_ragged<3 * NB, STRIDE, GF_THREADS>(in_rows[k], in[k] + (size_t)e0 * (3 * NB), ne * 3 * NB);
+    if (has_ball) tile_load<3 * (NB + 1), STRIDE, GF_THREADS>(in_rows[k], in[k] + (size_t)e0 * (3 * (NB + 1)), ne);
+    else tile_load<3 * NB, STRIDE, GF_THREADS>(in_rows[k], in[k] + (size_t)e0 * (3 * NB), ne);
   }
   __syncthreads();
   if ((int)threadIdx.x < ne) {
     int e = e0 + threadIdx.x;
     float* Q = orows + threadIdx.x * GF_OSTRIDE;
-    auto ld = [&](int f) { return st[(size_t)f * n + e]; };
     auto row = [&](int k) -> const float* { return in[k] ? in_rows[k] + threadIdx.x * STRIDE : nullptr; };
-    const M3 E0 = quat_to_mat(ld(F_ROOT_QUAT), ld(F_ROOT_QUAT + 1), ld(F_ROOT_QUAT + 2), ld(F_ROOT_QUAT + 3));
+    const M3 E0 = root_rotation(D, e);
     const M3 I3 = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
     const V3 O = mk(0.f, 0.f, 0.f);
-    const GfCtx C = {row(0), row(1), row(2), mk(ld(F_ROOT_POS), ld(F_ROOT_POS + 1), ld(F_ROOT_POS + 2)), (space & BEZ_SPACE_LOCAL) != 0,
-                     (space & BEZ_GF_AT_ORIGIN) != 0, E0};
+    const GfCtx C = {row(0), row(1), row(2), state3_at(D, F_ROOT_POS, e), (space & BEZ_SPACE_LOCAL) != 0, (space & BEZ_GF_AT_ORIGIN) != 0, E0};
     const float quirk_z = quirk_rz<CL>(D.flags);
     // the torso's bodies: in the root's axes like the chains' totals, except ENV wrenches at ENV points, which stay in world axes,
     // untouched by E0 (a wrench on body 0 at the root position comes out as it went in)
@@ -690,18 +705,11 @@ __global__ void __launch_bounds__(GF_THREADS) generalized_forces_kernel(DynArgs 
       Cw.Rin = I3;
       Fw = gf_bodies<CL, 0>(Cw, I3, O);
     }
-    auto chain = [&](auto first, auto len) {
+    for_each_chain<true>([&](auto first, auto len) {
       constexpr int FIRST = decltype(first)::value, LEN = decltype(len)::value;
-      static_assert(is_chain<FIRST, LEN>(), "not a chain off the torso");
       asm volatile("" : "+v"(e), "+v"(F0.l.x));   // (opaque per chain, as in inverse_dynamics_kernel)
-      F0 = F0 + gf_links<FIRST, FIRST + LEN, CL>(C, st, n, e, quirk_z, I3, O, Q);
-    };
-    using std::integral_constant;
-    chain(integral_constant<int, 13>{}, integral_constant<int, 6>{});
-    chain(integral_constant<int, 11>{}, integral_constant<int, 2>{});
-    chain(integral_constant<int, 5>{}, integral_constant<int, 6>{});
-    chain(integral_constant<int, 3>{}, integral_constant<int, 2>{});
-    chain(integral_constant<int, 1>{}, integral_constant<int, 2>{});
+      F0 = F0 + gf_links<FIRST, FIRST + LEN, CL>(C, D, e, quirk_z, I3, O, Q);
+    });
     const V3 fo = Fw.l + mul(E0, F0.l), mo = Fw.a + mul(E0, F0.a);   // the root-frame total, turned to world axes
     Q[0] = fo.x + 0.f; Q[1] = fo.y + 0.f; Q[2] = fo.z + 0.f;
     Q[3] = mo.x + 0.f; Q[4] = mo.y + 0.f; Q[5] = mo.z + 0.f;
@@ -713,23 +721,19 @@ __global__ void __launch_bounds__(GF_THREADS) generalized_forces_kernel(DynArgs 
 // ---- bez_sim_limb_ik (definition: include/bez_sim.h "Limb inverse kinematics"): damped least squares on each of the five chains off
 // the torso, whose joints are disjoint: five independent problems of 2, 2, 6, 2, 6 unknowns per env.
 // A workgroup takes IK_TILE consecutive envs.  All lanes bring the tile's (ne, 35) target rows -- one contiguous range -- into LDS
-// (tile_load_ragged).  The workgroup is five waves, and wave c takes chain c of every env of the tile: one lane per (env, chain), with
+// (tile_load).  The workgroup is five waves, and wave c takes chain c of every env of the tile: one lane per (env, chain), with
 // every wave running one chain's code (the links are compile-time: lanes of one wave on different chains would run the five bodies
 // one after the other).  The family's form -- one wave, one lane per env walking the five chains in turn -- computes the same bits and
 // was measured on MI355X at 4096 envs, 8 iterations: 56.6 us against this form's 19.3 us (profiles/limb_ik_tiles.txt).
-// Per chain and iteration, in the root's axes about the root origin: link_kinematics down the chain keeping each joint's axis and
+// Per chain and iteration, in the root's axes about the root origin: still_chain_walk down the chain keeping each joint's axis and
 // origin, the tip's pose error, the k columns [a x (p - r); a], the lower triangle of J^T W J + lambda^2 I, its Cholesky factor and the
 // two substitutions -- all over compile-time indices, so every array lives in registers; only the iteration count is a run-time loop.
 // The angles and the errors go to the env's rows in LDS, and all lanes write the tile's (ne, 18) and (ne, 30) rows with
-// tile_store_ragged.  The limit rows come as two pointers beside DynArgs, not inside it: DynArgs heads every neighbour's arguments, and
+// tile_store.  The limit rows come as two pointers beside DynArgs, not inside it: DynArgs heads every neighbour's arguments, and
 // growing it would move theirs.
 constexpr int IK_TILE = 32, IK_THREADS = 64 * BEZ_IK_CHAINS, IK_TW = 7 * BEZ_IK_CHAINS, IK_EW = 6 * BEZ_IK_CHAINS;
 constexpr int IK_TSTRIDE = IK_TW | 1, IK_QSTRIDE = BEZ_ND | 1, IK_ESTRIDE = IK_EW | 1;   // odd row strides: the lanes' own rows start in distinct LDS banks
 static_assert(IK_TILE <= 64, "one lane of a wave per env of the tile");
-// chain c of the tree: the c-th link whose parent is the torso, and the links after it up to the next such link
-constexpr int ik_chain_first(int c) { for (int l = 1; l < BEZ_NL; ++l) if (BEZ_LINK_PARENT[l] == 0 && c-- == 0) return l; return -1; }
-constexpr int ik_chain_len(int c) { const int f = ik_chain_first(c); int k = 1; while (f + k < BEZ_NL && BEZ_LINK_PARENT[f + k] != 0) ++k; return k; }
-static_assert(ik_chain_first(BEZ_IK_CHAINS - 1) > 0 && ik_chain_first(BEZ_IK_CHAINS) < 0, "BEZ_IK_CHAINS chains off the torso");
 // The Cholesky factorisation of a symmetric positive definite K x K matrix given by its lower triangle, in place as L L^T with the
 // reciprocals of L's diagonal beside it, and the two substitutions that solve L L^T x = b in place.  Every index is compile-time, so
 // the factor lives in registers.  Shared with forward_dynamics_kernel.
@@ -767,17 +771,16 @@ BEZ_DEV void chol_solve(const float (&A)[K][K], const float (&inv)[K], float (&x
   }
 }
 // what a chain needs of the call: the env, the joint limit rows, the root pose that takes ENV targets into the root's frame
-struct IkCtx { const float *st, *lower, *upper; int n, e; float quirk_z; bool env; M3 E0; V3 root_pos; float lam2, max_step; int iters; };
+struct IkCtx { const DynArgs& D; const float *lower, *upper; int e; float quirk_z; bool env; M3 E0; V3 root_pos; float lam2, max_step; int iters; };
 // x held to [lo, hi]; a NaN stays a NaN (fminf / fmaxf would return the limit)
 BEZ_DEV float ik_clamp(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
 // T: the chain's target row (7 words), Q: the env's angle row (18), R: the chain's error row (6), all in LDS
 template <bool CL, int C>
 BEZ_DEV void ik_chain(const IkCtx& K, const BezIkParams& P, const float* T, float* Q, float* R) {
-  constexpr int FIRST = ik_chain_first(C), LEN = ik_chain_len(C), D0 = FIRST - 1;
-  static_assert(is_chain<FIRST, LEN>(), "not a chain off the torso");
+  constexpr int FIRST = chain_first(C), LEN = chain_len(C), D0 = FIRST - 1;
   float q[LEN];
 #pragma unroll
-  for (int i = 0; i < LEN; ++i) q[i] = K.st[(size_t)(F_Q + D0 + i) * K.n + K.e];
+  for (int i = 0; i < LEN; ++i) q[i] = state_at(K.D, F_Q + D0 + i, K.e);
   const float wp = P.weight[C][0], wr = P.weight[C][1];
   if (wp == 0.f && wr == 0.f) {   // not asked for: the state's angles, and the target row is not looked at
 #pragma unroll
@@ -808,11 +811,8 @@ BEZ_DEV void ik_chain(const IkCtx& K, const BezIkParams& P, const float* T, floa
   for (int it = 0;; ++it) {
     M3 E = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
     V3 r = mk(0.f, 0.f, 0.f), a[LEN], ro[LEN];
-    static_for<LEN>([&](auto I) {
-      constexpr int i = decltype(I)::value;
-      SV S, cb, V = svzero();
-      link_kinematics<FIRST + i>(q[i], 0.f, E, r, V, S, cb, K.quirk_z);
-      a[i] = S.a; ro[i] = r;
+    still_chain_walk<FIRST, LEN>(E, r, K.quirk_z, [&](auto L) { return q[decltype(L)::value - FIRST]; }, [&](auto L, const SV& S) {
+      a[decltype(L)::value - FIRST] = S.a; ro[decltype(L)::value - FIRST] = r;
     });
     const V3 p = r + mul(E, tip);
     ep = pd - p;
@@ -860,19 +860,17 @@ __global__ void __launch_bounds__(IK_THREADS) limb_ik_kernel(DynArgs D, const fl
   __shared__ float trows[IK_TILE * IK_TSTRIDE];
   __shared__ float qrows[IK_TILE * IK_QSTRIDE];
   __shared__ float erows[IK_TILE * IK_ESTRIDE];
-  const float* st = D.st;
   const int n = D.n, e0 = blockIdx.x * IK_TILE, ne = min(IK_TILE, n - e0);
-  tile_load_ragged<IK_TW, IK_TSTRIDE, IK_THREADS>(trows, targets + (size_t)e0 * IK_TW, ne * IK_TW);
+  tile_load<IK_TW, IK_TSTRIDE, IK_THREADS>(trows, targets + (size_t)e0 * IK_TW, ne);
   __syncthreads();
   const int lane = threadIdx.x % 64, wave = threadIdx.x / 64;
   if (lane < ne) {
     const int e = e0 + lane;
-    auto ld = [&](int f) { return st[(size_t)f * n + e]; };
-    IkCtx K = {st, lower, upper, n, e, quirk_rz<CL>(D.flags), P.space == BEZ_IK_SPACE_ENV, {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f},
+    IkCtx K = {D, lower, upper, e, quirk_rz<CL>(D.flags), P.space == BEZ_IK_SPACE_ENV, {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f},
                mk(0.f, 0.f, 0.f), P.damping * P.damping, P.max_step, P.iters};
     if (K.env) {   // (ROOT targets: the root pose is not read)
-      K.E0 = quat_to_mat(ld(F_ROOT_QUAT), ld(F_ROOT_QUAT + 1), ld(F_ROOT_QUAT + 2), ld(F_ROOT_QUAT + 3));
-      K.root_pos = mk(ld(F_ROOT_POS), ld(F_ROOT_POS + 1), ld(F_ROOT_POS + 2));
+      K.E0 = root_rotation(D, e);
+      K.root_pos = state3_at(D, F_ROOT_POS, e);
     }
     static_for<BEZ_IK_CHAINS>([&](auto Ci) {
       constexpr int c = decltype(Ci)::value;
@@ -883,8 +881,8 @@ __global__ void __launch_bounds__(IK_THREADS) limb_ik_kernel(DynArgs D, const fl
     });
   }
   __syncthreads();
-  if (q_out) tile_store_ragged<BEZ_ND, IK_QSTRIDE, IK_THREADS>(qrows, q_out + (size_t)e0 * BEZ_ND, ne * BEZ_ND);
-  if (err_out) tile_store_ragged<IK_EW, IK_ESTRIDE, IK_THREADS>(erows, err_out + (size_t)e0 * IK_EW, ne * IK_EW);
+  if (q_out) tile_store<BEZ_ND, IK_QSTRIDE, IK_THREADS>(qrows, q_out + (size_t)e0 * BEZ_ND, ne);
+  if (err_out) tile_store<IK_EW, IK_ESTRIDE, IK_THREADS>(erows, err_out + (size_t)e0 * IK_EW, ne);
 }
 
 // ---- bez_sim_forward_dynamics (definition: include/bez_sim.h "Forward dynamics"): udot = M^-1 (f - h), solved on the tree's structure.
@@ -894,7 +892,8 @@ __global__ void __launch_bounds__(IK_THREADS) limb_ik_kernel(DynArgs D, const fl
 //     y_c = M_cc^-1 r_c,  Z_c = M_cc^-1 B_c,  S = M00 - sum_c B_c^T Z_c,  g = r_0 - sum_c B_c^T y_c,  x_0 = S^-1 g,  x_c = y_c - Z_c x_0
 // with r = f - h.  Nothing larger than 6 x 6 is factored, and no 24 x 24 matrix is held anywhere.
 // A workgroup is four waves and takes FD_TILE consecutive envs; a unit is FD_TILE consecutive lanes, one per env of the tile.  All
-// lanes bring the tile's force rows into LDS (tile_load; zeros for a null pointer).  Then two waves work at once: unit 0 (wave 0) walks
+// lanes bring the tile's force rows into LDS (tile_load; zeros for a null pointer, in the one loop that also zeroes the bias rows --
+// tile_load_or_zero would pass over the tile a second time for them).  Then two waves work at once: unit 0 (wave 0) walks
 // the tree for h (fd_bias) with the bias terms asked for and leaves it in the env's second row; unit 4 (wave 1) runs phase 1 of
 // refresh_dynamics_kernel (dyn_joint_words, dyn_mass_words) and leaves the base block and the F_l in the env's MS_* words.  Then every
 // chain has a unit of its own, as in limb_ik_kernel -- the legs and the right arm a wave each, the head and the left arm (2 x 2
@@ -912,7 +911,6 @@ constexpr int FD_TILE = 16, FD_THREADS = 256, FD_RSTRIDE = DYN_NG + 1;   // odd 
 constexpr int FD_CW = 21 + 6, FD_CSTRIDE = (FD_CW * BEZ_IK_CHAINS) | 1;                 // a chain's words: tri(B^T Z), B^T y
 constexpr int fd_unit(int c) { return c < 2 ? c : 4 * (c - 1); }                        // the unit that takes chain c
 static_assert(FD_TILE == DYN_TILE && 64 % FD_TILE == 0 && (fd_unit(BEZ_IK_CHAINS - 1) + 1) * FD_TILE <= FD_THREADS, "units of one lane per env; the tile of refresh_dynamics_kernel");
-constexpr MassSlots MASS_SLOT_TABLE = mass_slots();
 constexpr int fd_tri(int a, int b) { return a * (a + 1) / 2 + b; }   // (a, b), a >= b, of a lower triangle stored row by row
 // M[I][J] of the env whose MS_* words start at Ms
 template <int I, int J>
@@ -939,16 +937,12 @@ BEZ_DEV void link_com_inertia(float ms, const M3& E, V3 r, float& m, V3& c, Sym3
 // leaves 2.3e-6 of sqrt(M_ii M_jj) in them.  The solve multiplies that by M_cc^-1: measured on MI355X, the joint rows
 // of udot = M^-1 f then miss the fp64 reference by 1.1e-3 rad/s^2 of 500, of which the fp32 elimination itself accounts for 2e-4.
 template <bool CL, int C>
-BEZ_DEV void fd_chain_block(const DynArgs& D, int e, float (&A)[ik_chain_len(C)][ik_chain_len(C)]) {
-  constexpr int FIRST = ik_chain_first(C), LEN = ik_chain_len(C);
-  static_assert(is_chain<FIRST, LEN>(), "not a chain off the torso");
-  const float quirk_z = quirk_rz<CL>(D.flags);
+BEZ_DEV void fd_chain_block(const DynArgs& D, int e, float (&A)[chain_len(C)][chain_len(C)]) {
+  constexpr int FIRST = chain_first(C), LEN = chain_len(C);
   M3 E = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
   V3 r = mk(0.f, 0.f, 0.f), a[LEN], ro[LEN];
-  static_for<LEN>([&](auto Lk) {
-    constexpr int l = decltype(Lk)::value;
-    SV S, cb, V = svzero();
-    link_kinematics<FIRST + l>(D.st[(size_t)(F_Q + FIRST + l - 1) * D.n + e], 0.f, E, r, V, S, cb, quirk_z);
+  still_chain_walk<FIRST, LEN>(E, r, quirk_rz<CL>(D.flags), [&](auto Lk) { return state_at(D, F_Q + decltype(Lk)::value - 1, e); }, [&](auto Lk, const SV& S) {
+    constexpr int l = decltype(Lk)::value - FIRST;
     a[l] = S.a; ro[l] = r;
     float m; V3 c; Sym3 Iw;
     link_com_inertia<FIRST + l, CL>(mass_scale_of(D, e, FIRST + l), E, r, m, c, Iw);
@@ -970,7 +964,7 @@ BEZ_DEV void fd_chain_block(const DynArgs& D, int e, float (&A)[ik_chain_len(C)]
 template <bool CL, int C>
 BEZ_DEV void fd_chain_reduce(const DynArgs& D, int e, const float* Ms, const float* F, const float* H, bool floating, float* W, float (&y)[6],
                              float (&Z)[6][6]) {
-  constexpr int LEN = ik_chain_len(C), R0 = 5 + ik_chain_first(C);   // the chain's first row of M
+  constexpr int LEN = chain_len(C), R0 = 5 + chain_first(C);   // the chain's first row of M
   static_assert(LEN <= 6, "a chain's factor is at most 6 x 6");
   float A[LEN][LEN], inv[LEN], x[LEN];
   fd_chain_block<CL, C>(D, e, A);
@@ -1012,7 +1006,7 @@ BEZ_DEV void fd_chain_reduce(const DynArgs& D, int e, const float* Ms, const flo
 // x_c = y_c - Z_c x_0 (fixed base: y_c) into the chain's words of the env's row X, whose first six words hold x_0
 template <int C>
 BEZ_DEV void fd_chain_finish(bool floating, float* X, const float (&y)[6], const float (&Z)[6][6]) {
-  constexpr int LEN = ik_chain_len(C), R0 = 5 + ik_chain_first(C);
+  constexpr int LEN = chain_len(C), R0 = 5 + chain_first(C);
   float x0[6];
 #pragma unroll
   for (int k = 0; k < 6; ++k) x0[k] = floating ? X[k] : 0.f;
@@ -1057,7 +1051,7 @@ BEZ_DEV void fd_base_solve(const float* Ms, const float* H, const float* W, floa
 template <int L, int END, bool CL>
 BEZ_DEV SV fd_bias_links(const IdCtx& C, M3 E, V3 r, SV V, SV aV, float* H) {
   const V3 r_parent = r;
-  const float q = C.D.st[(size_t)(F_Q + L - 1) * C.D.n + C.e], qd = C.vel ? C.D.st[(size_t)(F_QD + L - 1) * C.D.n + C.e] : 0.f;
+  const float q = state_at(C.D, F_Q + L - 1, C.e), qd = C.vel ? state_at(C.D, F_QD + L - 1, C.e) : 0.f;
   SV S, cb;
   link_kinematics<L>(q, qd, E, r, V, S, cb, C.quirk_z);
   aV = aV + cb;
@@ -1072,10 +1066,9 @@ BEZ_DEV SV fd_bias_links(const IdCtx& C, M3 E, V3 r, SV V, SV aV, float* H) {
 }
 template <bool CL>
 BEZ_DEV void fd_bias(const DynArgs& D, int e, uint32_t bias, float* H) {
-  auto ld = [&](int f) { return D.st[(size_t)f * D.n + e]; };
   const bool vel = (bias & BEZ_ID_VELOCITY) != 0;
-  const M3 E0 = quat_to_mat(ld(F_ROOT_QUAT), ld(F_ROOT_QUAT + 1), ld(F_ROOT_QUAT + 2), ld(F_ROOT_QUAT + 3));
-  const SV V0 = vel ? mksv(mk(ld(F_ROOT_ANG), ld(F_ROOT_ANG + 1), ld(F_ROOT_ANG + 2)), mk(ld(F_ROOT_LIN), ld(F_ROOT_LIN + 1), ld(F_ROOT_LIN + 2))) : svzero();
+  const M3 E0 = root_rotation(D, e);
+  const SV V0 = vel ? mksv(state3_at(D, F_ROOT_ANG, e), state3_at(D, F_ROOT_LIN, e)) : svzero();
   V3 g = mk(0.f, 0.f, 0.f);
   if (bias & BEZ_ID_GRAVITY) g = gravity_of(D, e);
   const SV aV0 = mksv(mk(0.f, 0.f, 0.f), -cross(V0.a, V0.l));   // (inverse_dynamics_kernel: the torso's acceleration about a fixed point)
@@ -1083,18 +1076,11 @@ BEZ_DEV void fd_bias(const DynArgs& D, int e, uint32_t bias, float* H) {
   link_inertia<0, CL>(mass_scale_of(D, e, 0), g, E0, mk(0.f, 0.f, 0.f), V0, I0, F0);
   F0 = F0 + inertia_times(I0, aV0);
   IdCtx C = {D, e, vel, quirk_rz<CL>(D.flags), g};
-  auto chain = [&](auto first, auto len) {
+  for_each_chain<true>([&](auto first, auto len) {
     constexpr int FIRST = decltype(first)::value, LEN = decltype(len)::value;
-    static_assert(is_chain<FIRST, LEN>(), "not a chain off the torso");
     asm volatile("" : "+v"(C.e), "+v"(F0.l.x));   // (opaque per chain, as in inverse_dynamics_kernel)
     F0 = F0 + fd_bias_links<FIRST, FIRST + LEN, CL>(C, E0, mk(0.f, 0.f, 0.f), V0, aV0, H);
-  };
-  using std::integral_constant;
-  chain(integral_constant<int, 13>{}, integral_constant<int, 6>{});
-  chain(integral_constant<int, 11>{}, integral_constant<int, 2>{});
-  chain(integral_constant<int, 5>{}, integral_constant<int, 6>{});
-  chain(integral_constant<int, 3>{}, integral_constant<int, 2>{});
-  chain(integral_constant<int, 1>{}, integral_constant<int, 2>{});
+  });
   H[0] = F0.l.x; H[1] = F0.l.y; H[2] = F0.l.z; H[3] = F0.a.x; H[4] = F0.a.y; H[5] = F0.a.z;
 }
 template <bool CL>
@@ -1151,13 +1137,13 @@ __global__ void __launch_bounds__(FD_THREADS) forward_dynamics_kernel(DynArgs D,
 
 // ---- bez_sim_proximity (definition: include/bez_sim.h "Proximity"): the step's three narrow phases -- link_ground_points, test_box_at /
 // test_torso_box, segment_closest / self_pair (bez_kernels.h) -- as signed distances that are defined on both sides of contact.
-// A workgroup takes PX_TILE consecutive envs.  Phase 1, one lane per env: the chains are walked with link_kinematics at qd = 0 in world
+// A workgroup takes PX_TILE consecutive envs.  Phase 1, one lane per env: the chains are walked with still_chain_walk in world
 // axes about the root origin (the legs for boxes, capsules and feet; the head and the arms for their guard points alone); the ground rows
 // go to the env's output row in LDS, root_pos joining in the last addition, and what the tests need -- the eleven box frames, the twelve
 // capsule axes' end points, the ball centre relative to the root origin, root_pos -- to the env's PX_F* words.  Phase 2, all lanes: the
 // tile's 16 x (28 + 11) tests, the env fastest, so that every wave runs one kind of test (16 x 28 is a whole number of waves); the
-// constants of a test are looked up in PROX_TABLES.  Phase 3, all lanes: the tile's three contiguous ranges are stored with tile_store /
-// tile_store_ragged.  Rows of odd strides: the lanes of phase 1 write distinct banks.
+// constants of a test are looked up in PROX_TABLES.  Phase 3, all lanes: the tile's three contiguous ranges are stored with tile_store.
+// Rows of odd strides: the lanes of phase 1 write distinct banks.
 // The family's form -- one wave, one lane per env that also runs its env's 39 tests, frames and capsules in registers -- computes the
 // same bits and was measured on MI355X beside this one (profiles/proximity_tiles.txt).
 constexpr int PX_TILE = 16, PX_THREADS = 256;
@@ -1237,16 +1223,14 @@ __global__ void __launch_bounds__(PX_THREADS) proximity_kernel(DynArgs D, float*
   __shared__ float grows[PX_TILE * PX_GSTRIDE];
   __shared__ float brows[PX_TILE * PX_BSTRIDE];
   __shared__ float prows[PX_TILE * PX_PSTRIDE];
-  const float* st = D.st;
   const int n = D.n, e0 = blockIdx.x * PX_TILE, ne = min(PX_TILE, n - e0);
   if ((int)threadIdx.x < ne) {
     int e = e0 + threadIdx.x;
     float* F = frames + threadIdx.x * PX_FSTRIDE;
     float* G = grows + threadIdx.x * PX_GSTRIDE;
-    auto ld = [&](int f) { return st[(size_t)f * n + e]; };
     auto put3 = [&](float* at, V3 v) { at[0] = v.x; at[1] = v.y; at[2] = v.z; };
-    const V3 root_pos = mk(ld(F_ROOT_POS), ld(F_ROOT_POS + 1), ld(F_ROOT_POS + 2)), ball_pos = mk(ld(F_BALL_POS), ld(F_BALL_POS + 1), ld(F_BALL_POS + 2));
-    const M3 E0 = quat_to_mat(ld(F_ROOT_QUAT), ld(F_ROOT_QUAT + 1), ld(F_ROOT_QUAT + 2), ld(F_ROOT_QUAT + 3));
+    const V3 root_pos = state3_at(D, F_ROOT_POS, e), ball_pos = state3_at(D, F_BALL_POS, e);
+    const M3 E0 = root_rotation(D, e);
     const float quirk_z = quirk_rz<CL>(D.flags);
     Params P;   // (pt_pos_of looks at the flags alone)
     P.flags = D.flags;
@@ -1277,24 +1261,12 @@ __global__ void __launch_bounds__(PX_THREADS) proximity_kernel(DynArgs D, float*
       });
     };
     link(std::integral_constant<int, 0>{}, E0, mk(0.f, 0.f, 0.f));
-    auto chain = [&](auto first, auto len) {
-      constexpr int FIRST = decltype(first)::value, LEN = decltype(len)::value;
-      static_assert(is_chain<FIRST, LEN>(), "not a chain off the torso");
+    for_each_chain<false>([&](auto first, auto len) {
       asm volatile("" : "+v"(e));   // (opaque per chain, as in inverse_dynamics_kernel)
       M3 E = E0; V3 r = mk(0.f, 0.f, 0.f);
-      static_for<LEN>([&](auto I) {
-        constexpr int L = FIRST + decltype(I)::value;
-        SV S, cb, V = svzero();
-        link_kinematics<L>(ld(F_Q + L - 1), 0.f, E, r, V, S, cb, quirk_z);
-        link(std::integral_constant<int, L>{}, E, r);
-      });
-    };
-    using std::integral_constant;
-    chain(integral_constant<int, 1>{}, integral_constant<int, 2>{});
-    chain(integral_constant<int, 3>{}, integral_constant<int, 2>{});
-    chain(integral_constant<int, 5>{}, integral_constant<int, 6>{});
-    chain(integral_constant<int, 11>{}, integral_constant<int, 2>{});
-    chain(integral_constant<int, 13>{}, integral_constant<int, 6>{});
+      still_chain_walk<decltype(first)::value, decltype(len)::value>(E, r, quirk_z, [&](auto Lk) { return state_at(D, F_Q + decltype(Lk)::value - 1, e); },
+                                                                     [&](auto Lk, const SV&) { link(Lk, E, r); });
+    });
   }
   __syncthreads();
   const bool box_asset = (D.flags & BEZ_FLAG_BOX_ASSET) != 0;
@@ -1318,7 +1290,7 @@ __global__ void __launch_bounds__(PX_THREADS) proximity_kernel(DynArgs D, float*
     }
   }
   __syncthreads();
-  if (ground) tile_store_ragged<PX_GW, PX_GSTRIDE, PX_THREADS>(grows, ground + (size_t)e0 * PX_GW, ne * PX_GW);
+  if (ground) tile_store<PX_GW, PX_GSTRIDE, PX_THREADS>(grows, ground + (size_t)e0 * PX_GW, ne);
   if (ball) tile_store<PX_BW, PX_BSTRIDE, PX_THREADS>(brows, ball + (size_t)e0 * PX_BW, ne);
   if (pairs) tile_store<PX_PW, PX_PSTRIDE, PX_THREADS>(prows, pairs + (size_t)e0 * PX_PW, ne);
 }
