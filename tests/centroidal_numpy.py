@@ -16,6 +16,8 @@ import copy
 import numpy as np
 
 from tests import dynamics_numpy as D
+from tests.inverse_dynamics_numpy import _mv
+from tests.state_sets import generate_states
 
 NG = 24
 CM_WORDS = 16
@@ -23,10 +25,6 @@ CM_COM, CM_COM_VEL, CM_LIN_MOM, CM_ANG_MOM, CM_MASS, CM_KINETIC, CM_POTENTIAL = 
 STATE_BLOCKS = (("com", slice(0, 3)), ("com_vel", slice(3, 6)), ("lin_mom", slice(6, 9)), ("ang_mom", slice(9, 12)), ("mass", slice(12, 13)),
                 ("kinetic", slice(13, 14)), ("potential", slice(14, 15)))
 MATRIX_BLOCKS = (("matrix_lin", slice(0, 3)), ("matrix_ang", slice(3, 6)))
-
-
-def _mv(A, x):
-    return (A @ x[..., None])[..., 0]
 
 
 def _quat_to_mat(q, f):
@@ -138,5 +136,12 @@ def cm_ref(model, state, mass_scale, gravity, dtype=np.float64, armature=0.0, mu
     return dict(state=out, matrix=A, L_root=LO)
 
 
-def model_of(asset):
-    return D.model_of(asset)
+def centroidal_states(n, seed=31):
+    """the states of tests/state_sets.generate_states (seams, joint limits, random roots; |w| up to 10 rad/s, |qd| up to
+    20 rad/s) with the root a few metres from the origin, so that COM carries a real offset without drowning it: fp32 (n, 13), (n, 18, 2)"""
+    root, dof, _ = generate_states(n)
+    rng = np.random.default_rng(seed)
+    root = root.copy()
+    root[:, 0:2] = rng.uniform(-3, 3, (n, 2))
+    root[:, 2] = rng.uniform(0.2, 2, n)
+    return root.astype(np.float32), dof.astype(np.float32)

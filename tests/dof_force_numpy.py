@@ -39,7 +39,7 @@ def rnea_torques(R, model, cfg, rs0, rs1, ds0, ds1, gravity=(0.0, 0.0, 0.0)):
 
 
 def inject_pressed(sim, n, model, seed, pressed_state, hips_default=True):
-    """n states of tests/test_oracle_round6._pressed_state through the Isaac-layout setters, the hip rolls and their targets left at the
+    """n states of tests/scenarios._pressed_state through the Isaac-layout setters, the hip rolls and their targets left at the
     default pose (legs apart) when `hips_default`; returns the action rows that produce the targets"""
     rng = np.random.default_rng(seed)
     dflt = np.asarray(model["dof_default"], float)

@@ -3,7 +3,7 @@ matrix, both in the generalised velocity u = [root_lin(3), root_ang(3), qd(18)],
 
   J_ref_oracle / J_ref_fd   column k of J is what the body rows carry as origin velocity (rows 0:3) and angular velocity (rows 3:6) in
                             the state whose generalised velocity is the unit vector e_k: from the CPU oracle's rigid-body rows (every
-                            asset, fp64 or fp32 build) and from the finite-difference FK of tests/test_state_tensors_cpu.fd_reference
+                            asset, fp64 or fp32 build) and from the finite-difference FK of tests/state_sets.fd_reference
                             (default asset; the URDF fixture, not the model tables).
   M_ref_rnea                column k of M is the generalised force of tests/rbd_numpy.rnea_floating at zero velocity and zero gravity
                             for the unit acceleration e_k; the base wrench is rotated to world axes and reordered to [force; moment
@@ -55,13 +55,13 @@ def _columns(rows, n, nb):
 
 def J_ref_oracle(make_cfg, precision, root, dof, nb):
     """make_cfg(num_envs) -> the oracle's config for the asset and task; nb robot bodies (the ball's row, if any, is dropped)"""
-    from tests.test_state_tensors_cpu import oracle_rows
+    from tests.state_sets import oracle_rows
     r, d = unit_velocity_states(root, dof)
     return _columns(oracle_rows(make_cfg(r.shape[0]), precision, r, d), root.shape[0], nb)
 
 
 def J_ref_fd(root, dof):
-    from tests.test_state_tensors_cpu import NB, fd_reference
+    from tests.state_sets import NB, fd_reference
     r, d = unit_velocity_states(root, dof)
     return _columns(fd_reference(r, d), root.shape[0], NB)
 

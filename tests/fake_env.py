@@ -2,6 +2,8 @@
 import numpy as np
 import torch
 
+from bez_isaacgym_amd.utils.config import load_config
+
 
 class _Box:
     def __init__(self, n):
@@ -38,3 +40,11 @@ class FakeVecEnv:
             self.state[idx] = torch.randn(len(idx), self.obs_dim, generator=self.gen)
             self.t[idx] = 0
         return {"obs": self.state.clone()}, rew, done.long(), {"time_outs": timeout.long()}
+
+
+def _params(num_actors, minibatch, horizon=8, epochs=3):
+    cfg = load_config(["task=bez_kick"], resolve=True)
+    p = cfg["train"]["params"]
+    p["config"].update(num_actors=num_actors, minibatch_size=minibatch, horizon_length=horizon, max_epochs=epochs,
+                       mixed_precision=False, save_frequency=0, save_best_after=10 ** 9)
+    return p

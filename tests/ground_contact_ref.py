@@ -370,9 +370,10 @@ def case_states(scenario, asset, n):
 def robot_com(sim, n, asset):
     """(n, 3) the robot's centre of mass in the env frame, from the root and DOF state and the URDF masses (tests/centroidal_numpy.py)"""
     from tests import centroidal_numpy as CM
+    from tests import dynamics_numpy as D
     root = sim.root_states.reshape(n, 2, 13)[:, 0].astype(np.float64)
     dof = sim.dof_state.reshape(n, 18, 2).astype(np.float64)
-    links = CM.model_of(asset)["links"]
+    links = D.model_of(asset)["links"]
     _, _, _, m, c, _ = CM._configuration(links, root[:, 3:7], dof[:, :, 0], np.ones((n, len(links))), np.float64)
     return root[:, 0:3] + sum(m[i][:, None] * c[i] for i in range(len(links))) / sum(m)[:, None]
 

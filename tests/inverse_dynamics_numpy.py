@@ -149,7 +149,3 @@ def id_ref(model, quat, v0, q, qd, udot, gravity, mass_scale=None, armature=0.0,
     dof = np.stack([np.asarray(q, dtype), np.asarray(qd, dtype)], axis=-1)[None]
     return id_ref_batch(model, root, dof, None if udot is None else np.asarray(udot, dtype)[None], gravity,
                         None if mass_scale is None else np.asarray(mass_scale, dtype)[None], armature, terms, dtype)[0]
-
-
-def model_of(asset):
-    return D.model_of(asset)

@@ -255,11 +255,12 @@ def robot_momentum(sim, n, asset):
     """(linear momentum (n, 3) of the robot from the rigid-body rows and the URDF masses (ball_contact_ref.robot_ball_momentum), angular
     momentum (n, 3) about its centre of mass from the root and DOF state and the URDF masses and inertias (tests/centroidal_numpy.cm_ref))"""
     from tests import centroidal_numpy as CM
+    from tests import dynamics_numpy as D
     lin, _ = B.robot_ball_momentum(sim, n, asset)
     root = sim.root_states.reshape(n, 2, 13)[:, 0].astype(np.float64)
     dof = sim.dof_state.reshape(n, 18, 2).astype(np.float64)
     f = np.float64
-    links = CM.model_of(asset)["links"]
+    links = D.model_of(asset)["links"]
     E, r, a, m, c, I = CM._configuration(links, root[:, 3:7], dof[:, :, 0], np.ones((n, len(links))), f)
     com = sum(m[i][:, None] * c[i] for i in range(len(links))) / sum(m)[:, None]
     w, v = CM._velocities(links, r, a, c, root[:, 7:10], root[:, 10:13], dof[:, :, 1])

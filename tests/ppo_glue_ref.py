@@ -22,6 +22,7 @@ import math
 import zlib
 
 import numpy as np
+import torch
 
 F16, F32, F64 = np.float16, np.float32, np.float64
 EPS64 = 2.0 ** -53
@@ -647,3 +648,21 @@ def gae_data(h, n, pattern):
     last[0] = 7.5
     last[-1] = -6.25 if n > 1 else 7.5
     return dict(rew=rng.normal(size=(h, n)).astype(F32), val=(rng.normal(size=(h, n)) * 2.0).astype(F32), mb_dones=mbd, dones=dones, last=last)
+
+
+def _torch_loss(mu, logstd, value, mb, e, critic_coef, entropy_coef, bounds_coef, clip_value):
+    from bez_isaacgym_amd.ppo.a2c_continuous import ModelA2CContinuousLogStd, policy_kl
+    sigma = torch.exp(logstd).unsqueeze(0).expand_as(mu)
+    neglogp = ModelA2CContinuousLogStd.neglogp(mb["actions"], mu, sigma, logstd.unsqueeze(0).expand_as(mu))
+    entropy = (0.5 + 0.5 * math.log(2 * math.pi) + logstd.unsqueeze(0).expand_as(mu)).sum(-1)
+    ratio = torch.exp(mb["old_logp"] - neglogp)
+    a_loss = torch.max(-mb["advantages"] * ratio, -mb["advantages"] * torch.clamp(ratio, 1 - e, 1 + e))
+    if clip_value:
+        vclip = mb["old_values"] + (value - mb["old_values"]).clamp(-e, e)
+        c_loss = torch.max((value - mb["returns"]) ** 2, (vclip - mb["returns"]) ** 2)
+    else:
+        c_loss = (mb["returns"] - value) ** 2
+    b_loss = (torch.clamp_min(mu - 1.1, 0.0) ** 2 + torch.clamp_max(mu + 1.1, 0.0) ** 2).sum(-1)
+    loss = a_loss.mean() + 0.5 * c_loss.mean() * critic_coef - entropy.mean() * entropy_coef + b_loss.mean() * bounds_coef
+    kl = policy_kl(mu.detach(), sigma.detach(), mb["mu"], mb["sigma"])
+    return loss, a_loss.mean(), c_loss.mean(), b_loss.mean(), kl, entropy.mean()

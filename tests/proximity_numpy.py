@@ -17,6 +17,8 @@ import os
 
 import numpy as np
 
+from tests.limb_ik_numpy import quat_to_mat
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODEL = json.load(open(os.path.join(ROOT, "bez_isaacgym_amd", "model", "bez_model.json")))
 ASSETS = ("default", "cleats", "box", "box_cleats")
@@ -62,17 +64,6 @@ def tables(asset, mutate=None):
     elif mutate == "ground_point":
         T["pt_pos"][9, 2] += 0.5e-3
     return T
-
-
-def quat_to_mat(q, f):
-    """(n, 4) xyzw, used as given -> (n, 3, 3)"""
-    x, y, z, w = (q[:, k] for k in range(4))
-    one, two = f(1), f(2)
-    R = np.empty((q.shape[0], 3, 3), f)
-    R[:, 0, 0] = one - two * (y * y + z * z); R[:, 0, 1] = two * (x * y - z * w); R[:, 0, 2] = two * (x * z + y * w)
-    R[:, 1, 0] = two * (x * y + z * w); R[:, 1, 1] = one - two * (x * x + z * z); R[:, 1, 2] = two * (y * z - x * w)
-    R[:, 2, 0] = two * (x * z - y * w); R[:, 2, 1] = two * (y * z + x * w); R[:, 2, 2] = one - two * (x * x + y * y)
-    return R
 
 
 def _mv(M, v):

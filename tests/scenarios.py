@@ -7,6 +7,7 @@ import os
 
 import numpy as np
 
+from bez_isaacgym_amd import abi
 from bez_isaacgym_amd.utils.trajectories import JOINT_ORDER, Trajectory
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -217,3 +218,28 @@ def leg_press(sim, n, model, steps=90, rng=None):
     q = sim.dof_state.reshape(n, 18, 2)[:, :, 0]
     return dict(dp=float(dp.max()), dL=float(dL.max()), penetration=float(pen.max()), on_limit=on_limit, over_limit=over_limit,
                 finite=bool(np.isfinite(q).all()), hip_roll=[float(q[:, 5].min()), float(q[:, 13].min())])
+
+
+def _free_space_cfg(n, seed=3, substeps=2):
+    cfg = abi.default_config(n, seed=seed)
+    cfg.gravity[:] = [0.0, 0.0, 0.0]
+    cfg.substeps = substeps
+    return cfg
+
+
+def _pressed_state(model, rng):
+    """Legs overlapping by a few millimetres (both hip rolls 0.25 rad inward: the capsules meet at 0.22 each), six leg joints just below the speed limit with
+    their targets far ahead (saturated drives pushing them over it), the torso tumbling."""
+    dflt = np.asarray(model["dof_default"], float)
+    q = dflt + rng.uniform(-0.05, 0.05, 18)
+    q[5] = dflt[5] - 0.25; q[13] = dflt[13] - 0.25
+    qd = rng.uniform(-1.0, 1.0, 18)
+    fast = [6, 7, 8, 14, 15, 16]
+    sign = rng.choice([-1.0, 1.0], len(fast))
+    qd[fast] = sign * 6.1
+    target = dflt.copy()
+    target[fast] = q[fast] + sign * 1.5
+    target[5] = dflt[5] - 0.8; target[13] = dflt[13] - 0.8   # hip drives saturated inward
+    v0 = np.concatenate([rng.uniform(-1, 1, 3), rng.uniform(-0.3, 0.3, 3)])
+    quat = rng.normal(size=4); quat /= np.linalg.norm(quat)
+    return q, qd, target, v0, quat, fast, sign

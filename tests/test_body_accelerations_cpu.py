@@ -1,6 +1,6 @@
 """CPU: the C ABI declares, lists and exports bez_sim_body_accelerations; its kernel compiles for gfx950 without spills or scratch; and the
 reference that pins it on the GPU (tests/body_accel_numpy.acc_ref) is what it says it is -- held to things it was not built from, on the
-states of tests/test_state_tensors_cpu.generate_states in fp64 -- and notices the mistakes it is there to catch."""
+states of tests/state_sets.generate_states in fp64 -- and notices the mistakes it is there to catch."""
 import ctypes as C
 import os
 import re
@@ -10,7 +10,7 @@ import pytest
 
 from bez_isaacgym_amd import abi
 from tests import body_accel_numpy as BA
-from tests.test_state_tensors_cpu import _expm_skew, generate_states, quat_mat
+from tests.state_sets import _expm_skew, generate_states, quat_mat
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "bez_sim.h")).read()

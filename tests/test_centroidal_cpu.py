@@ -14,7 +14,7 @@ from bez_isaacgym_amd import abi
 from tests import centroidal_numpy as CM
 from tests import dynamics_numpy as D
 from tests import inverse_dynamics_numpy as ID
-from tests.test_state_tensors_cpu import generate_states
+from tests.centroidal_numpy import centroidal_states
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "bez_sim.h")).read()
@@ -22,17 +22,6 @@ ARMATURE = float(abi.default_config(1).armature)
 G = np.array([0.3, -0.2, -9.81])   # not along an axis: a dropped or permuted component shows
 TOL = 1e-9
 NG = 24
-
-
-def centroidal_states(n, seed=31):
-    """the states of tests/test_state_tensors_cpu.generate_states (seams, joint limits, random roots; |w| up to 10 rad/s, |qd| up to
-    20 rad/s) with the root a few metres from the origin, so that COM carries a real offset without drowning it: fp32 (n, 13), (n, 18, 2)"""
-    root, dof, _ = generate_states(n)
-    rng = np.random.default_rng(seed)
-    root = root.copy()
-    root[:, 0:2] = rng.uniform(-3, 3, (n, 2))
-    root[:, 2] = rng.uniform(0.2, 2, n)
-    return root.astype(np.float32), dof.astype(np.float32)
 
 
 def test_abi_declares_lists_and_exports_the_centroidal_call():

@@ -144,7 +144,7 @@ class _ActuatorFakeEnv:
 
 def _agent(env, n, horizon):
     from bez_isaacgym_amd.ppo.a2c_continuous import A2CAgent
-    from tests.test_ppo_cpu import _params
+    from tests.fake_env import _params
     agent = A2CAgent(_params(n, 4 * n, horizon=horizon), env, "cpu")
     agent.obs = agent.env_reset()
     return agent

@@ -10,8 +10,8 @@ import pytest
 from bez_isaacgym_amd import abi
 from tests import dynamics_numpy as D
 from tests import rbd_numpy as R
-from tests.test_state_tensors_cpu import generate_states
-from tests.test_tasks import make_cfg
+from tests.sim_cfg import make_cfg
+from tests.state_sets import generate_states
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "bez_sim.h")).read()

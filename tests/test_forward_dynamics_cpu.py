@@ -12,7 +12,7 @@ from bez_isaacgym_amd import abi
 from tests import dynamics_numpy as D
 from tests import forward_dynamics_numpy as FD
 from tests import inverse_dynamics_numpy as ID
-from tests.test_state_tensors_cpu import generate_states, ulp32
+from tests.state_sets import generate_states, ulp32
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "bez_sim.h")).read()

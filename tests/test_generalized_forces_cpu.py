@@ -1,6 +1,6 @@
 """CPU: the C ABI declares, lists and exports bez_sim_generalized_forces; its kernel compiles for gfx950 without spills or scratch; and the
 reference that pins it on the GPU (tests/generalized_forces_numpy.gf_ref) is what it says it is -- held to identities it was not built
-from, on the states of tests/test_state_tensors_cpu.generate_states in fp64 -- and notices the mistakes it is there to catch."""
+from, on the states of tests/state_sets.generate_states in fp64 -- and notices the mistakes it is there to catch."""
 import ctypes as C
 import os
 import re
@@ -12,7 +12,7 @@ from bez_isaacgym_amd import abi
 from tests import dynamics_numpy as D
 from tests import generalized_forces_numpy as GF
 from tests import inverse_dynamics_numpy as ID
-from tests.test_state_tensors_cpu import generate_states
+from tests.state_sets import generate_states
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "bez_sim.h")).read()

@@ -21,9 +21,9 @@ import torch
 
 from bez_isaacgym_amd import abi
 from tests import body_accel_numpy as BA
-from tests.test_gpu_state_tensors import ASSETS, _dev, _host, _sim, _write_states
-from tests.test_state_tensors_cpu import ball_states, generate_states, ulp32
-from tests.test_tasks import make_cfg
+from tests.gpu_util import ASSETS, _bits, _dev, _free, _host, _sim, _write_states
+from tests.sim_cfg import make_cfg
+from tests.state_sets import ball_states, generate_states, ulp32
 
 pytestmark = pytest.mark.gpu
 
@@ -64,10 +64,6 @@ def _refs(asset, randomized, cfg):
                 out[terms, space] = (r64, bar)
         _CACHE[key] = out
     return _CACHE[key]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _call(sim, udot, terms, space=abi.SPACE_ENV):
@@ -169,11 +165,6 @@ def test_exact_structure(asset):
         assert zero(_call(sim, udot, abi.ACC_GRAVITY, space))                    # a zero gravity row
     np.testing.assert_array_equal(_bits(_call(sim, udot, abi.ACC_ALL)), _bits(parts[abi.ACC_UDOT]))   # ... and what is left is the UDOT term
     sim.close()
-
-
-def _free():
-    torch.cuda.synchronize()
-    return torch.cuda.mem_get_info(0)[0]
 
 
 def test_contract():

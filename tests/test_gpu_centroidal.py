@@ -23,10 +23,10 @@ import torch
 from bez_isaacgym_amd import abi
 from tests import centroidal_numpy as CM
 from tests import dynamics_numpy as D
-from tests.test_centroidal_cpu import centroidal_states
-from tests.test_gpu_state_tensors import ASSETS, _dev, _host, _sim, _write_states
-from tests.test_state_tensors_cpu import ball_states, ulp32
-from tests.test_tasks import make_cfg
+from tests.centroidal_numpy import centroidal_states
+from tests.gpu_util import ASSETS, _bits, _dev, _free, _host, _sim, _write_states
+from tests.sim_cfg import make_cfg
+from tests.state_sets import ball_states, ulp32
 
 pytestmark = pytest.mark.gpu
 
@@ -78,10 +78,6 @@ def _refs(asset, randomized, cfg):
         r32 = CM.cm_ref(*a, dtype=np.float32, armature=float(cfg.armature))
         _CACHE[key] = (r64, _bars(r64, r32))
     return _CACHE[key]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _no_bits(a):
@@ -250,11 +246,6 @@ def test_momentum_closes_on_the_step(model, kernel, monkeypatch):
           "gross momentum sum_j |A_G[:, j] u_j|: linear %.3g, angular %.3g; largest |u1| %.3g"
           % ((kernel,) + res["lin_mom"] + res["ang_mom"] + (float(gross[:, 0:3].max()), float(gross[:, 3:6].max()), float(np.abs(u1).max()))))
     assert np.abs(u1[:, 6:]).max() > 1.0 and gross[:, 0:3].max() > 1e-2 and gross[:, 3:6].max() > 1e-3   # not vacuous: the drives moved the joints
-
-
-def _free():
-    torch.cuda.synchronize()
-    return torch.cuda.mem_get_info(0)[0]
 
 
 def test_contract():

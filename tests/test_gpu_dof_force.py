@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 from bez_isaacgym_amd import abi  # noqa: E402
 from tests import dof_force_numpy as D  # noqa: E402
 from tests import rbd_numpy as R  # noqa: E402
-from tests.test_oracle_round6 import _free_space_cfg, _pressed_state  # noqa: E402
+from tests.scenarios import _free_space_cfg, _pressed_state   # noqa: E402
 
 KERNELS = ["ws8", "ws8q", "lane"]
 

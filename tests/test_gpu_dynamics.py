@@ -1,11 +1,11 @@
 """GPU: the dynamics tensors (include/bez_sim.h "Dynamics tensors": the robot's Jacobian (N*NB, 6, 24) and mass matrix (N, 24, 24))
-against the fp64 references of tests/dynamics_numpy.py, on the state set of tests/test_state_tensors_cpu.py.
+against the fp64 references of tests/dynamics_numpy.py, on the state set of tests/state_sets.py.
 
 Sizes: the rigid-body refresh's 1, 63, 64, 65, 300 and, around the kernel's 16-env tile, 15, 16, 17.  Assets default, cleats, box; the
 kick (ball actor) and walk (no ball) layouts.  No outlier budget anywhere: every element of every env is held to its bar.
 
   J   per field (rows 0:3 linear, 3:6 angular): 3x the fp32 oracle's worst error on the same unit-velocity rows + 2 fp32 ulps of the
-      value, as tests/test_gpu_state_tensors._bars builds its own.
+      value, as tests/gpu_util._bars builds the rigid-body rows'.
   M   3x the worst error of the sum J^T M J route evaluated in np.float32 against fp64 on the same states + 2 fp32 ulps of
       sqrt(M_ii M_jj); the worst error is the largest absolute one over every element and state, as _bars takes its own.  The error
       relative to each element's own sqrt(M_ii M_jj) is printed beside it as a measurement, not asserted: the kernel's recursion sums
@@ -23,9 +23,9 @@ import torch
 
 from bez_isaacgym_amd import abi
 from tests import dynamics_numpy as D
-from tests.test_gpu_state_tensors import ASSETS, _bars, _dev, _host, _ids, _sim, _write_states
-from tests.test_state_tensors_cpu import FIELDS, ball_states, field_errors, generate_states, oracle_rows, ulp32
-from tests.test_tasks import make_cfg
+from tests.gpu_util import ASSETS, _bars, _bits, _dev, _free, _host, _ids, _sim, _write_states
+from tests.sim_cfg import make_cfg
+from tests.state_sets import FIELDS, ball_states, field_errors, generate_states, oracle_rows, ulp32
 
 pytestmark = pytest.mark.gpu
 
@@ -74,10 +74,6 @@ def _M_refs(asset, root, dof, scale, armature, key):
         bar_abs = 3.0 * float(err.max()) + 2.0 * ulp32(size)
         _CACHE[key] = (M64, bar_abs, size)
     return _CACHE[key]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _check_J_structure(J, asset):
@@ -194,11 +190,6 @@ def test_after_motion():
 
 
 # ---------------------------------------------------------------- the contract of the two entry points
-
-def _free():
-    torch.cuda.synchronize()
-    return torch.cuda.mem_get_info(0)[0]
-
 
 def test_refresh_contract():
     """refresh before the acquisition, a zero mask and an unknown bit: rc -1 with a message; after the acquisitions ten refreshes leave

@@ -1,12 +1,12 @@
 """Why episodes end, on the GPU (include/bez_sim.h: BEZ_END_*, BezEpisodeTensor, BEZ_FLAG_REWARD_TERMS): the step kernels' cause bits
-against the numpy restatement (tests/test_episode_stats_cpu.py) on the golden sets and along random rollouts, one scripted env per cause
+against the numpy restatement (tests/episode_stats_ref.py) on the golden sets and along random rollouts, one scripted env per cause
 in one sim, the reward-term sums, bit-identical outputs with the flag on and off, and the PPO epoch row."""
 import numpy as np
 import pytest
 import torch
 
 from bez_isaacgym_amd import abi
-from tests.test_episode_stats_cpu import GOLDEN_SETS, end_causes, golden_inputs, kick_params, task_params
+from tests.episode_stats_ref import GOLDEN_SETS, end_causes, golden_inputs, kick_params, task_params
 
 pytestmark = pytest.mark.gpu
 
@@ -17,7 +17,7 @@ TASKS = {"kick": abi.TASK_KICK, "walk": abi.TASK_WALK, "orient": abi.TASK_ORIENT
 def _cfg(n, task=abi.TASK_KICK, cleats=False, terms=False, seed=11):
     c = abi.default_config(n, seed=seed)
     c.task = task
-    if task != abi.TASK_KICK:   # bez_walk.yaml / bez_orient.yaml (tests/test_tasks.py make_cfg)
+    if task != abi.TASK_KICK:   # bez_walk.yaml / bez_orient.yaml (tests/sim_cfg.py make_cfg)
         c.max_episode_length = 600
         c.goal[:] = [2.0, 0.0]
         c.goal_angle = 1.5708

@@ -25,10 +25,9 @@ from bez_isaacgym_amd import abi
 from tests import dynamics_numpy as D
 from tests import forward_dynamics_numpy as FD
 from tests import inverse_dynamics_numpy as ID
-from tests.test_gpu_inverse_dynamics import _bits, _free, _prepared, _states
-from tests.test_gpu_state_tensors import ASSETS, _dev, _host, _sim, _write_states
-from tests.test_state_tensors_cpu import ulp32
-from tests.test_tasks import make_cfg
+from tests.gpu_util import ASSETS, _bits, _dev, _free, _host, _prepared, _sim, _states, _write_states
+from tests.sim_cfg import make_cfg
+from tests.state_sets import ulp32
 
 pytestmark = pytest.mark.gpu
 

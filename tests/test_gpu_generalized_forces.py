@@ -23,9 +23,9 @@ from bez_isaacgym_amd import abi
 from tests import dynamics_numpy as D
 from tests import generalized_forces_numpy as GF
 from tests import inverse_dynamics_numpy as ID
-from tests.test_gpu_state_tensors import ASSETS, _dev, _host, _sim, _write_states
-from tests.test_state_tensors_cpu import ball_states, generate_states, ulp32
-from tests.test_tasks import make_cfg
+from tests.gpu_util import ASSETS, _bits, _dev, _free, _host, _sim, _write_states
+from tests.sim_cfg import make_cfg
+from tests.state_sets import ball_states, generate_states, ulp32
 
 pytestmark = pytest.mark.gpu
 
@@ -74,10 +74,6 @@ def _ref(asset, kind, space, mode):
             bar[sl] = 3.0 * e32[k] + 2.0 * float(ulp32(np.abs(r64[:, sl]).max()))
         _CACHE[key] = (r64, bar)
     return _CACHE[key]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _rows(sim, a, n):
@@ -341,11 +337,6 @@ def test_exact_structure(asset, task):
         np.testing.assert_array_equal(_bits(got[keep]), _bits(want_s[keep]))
         assert np.isnan(got[17, 0:6]).any() and np.isfinite(got[keep]).all()
     sim.close()
-
-
-def _free():
-    torch.cuda.synchronize()
-    return torch.cuda.mem_get_info(0)[0]
 
 
 def test_contract():

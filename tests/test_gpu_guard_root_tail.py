@@ -5,7 +5,7 @@ and the health bit -- and the next step must perform the ordinary reset.  The tw
 import pytest
 
 from bez_isaacgym_amd import abi
-from tests.test_gpu_nonfinite_guard import _twin
+from tests.guard_util import _twin
 
 pytestmark = pytest.mark.gpu
 

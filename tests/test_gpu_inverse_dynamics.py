@@ -23,9 +23,9 @@ from bez_isaacgym_amd import abi
 from tests import dof_force_numpy as DF
 from tests import dynamics_numpy as D
 from tests import inverse_dynamics_numpy as ID
-from tests.test_gpu_state_tensors import ASSETS, _dev, _host, _sim, _write_states
-from tests.test_state_tensors_cpu import ball_states, generate_states, ulp32
-from tests.test_tasks import make_cfg
+from tests.gpu_util import ASSETS, _bits, _dev, _free, _host, _prepared, _sim, _states, _write_states
+from tests.sim_cfg import make_cfg
+from tests.state_sets import ulp32
 
 pytestmark = pytest.mark.gpu
 
@@ -35,18 +35,6 @@ NMAX = max(SIZES)
 NG = abi.NUM_GEN
 TERMS = (abi.ID_ALL, abi.ID_INERTIA, abi.ID_VELOCITY, abi.ID_GRAVITY)
 _CACHE = {}
-
-
-def _states():
-    if "states" not in _CACHE:
-        root, dof, _ = generate_states(NMAX)
-        rng = np.random.default_rng(29)
-        # udot of O(10) in mixed SI units: m/s^2, rad/s^2
-        udot = rng.uniform(-10, 10, (NMAX, NG)).astype(np.float32)
-        scale = rng.uniform(0.5, 1.5, (NMAX, 19)).astype(np.float32)
-        gravity = (np.array([0.0, 0.0, -9.81]) + rng.uniform(-2, 2, (NMAX, 3))).astype(np.float32)
-        _CACHE["states"] = dict(root=root, dof=dof, ball=ball_states(NMAX), udot=udot, scale=scale, gravity=gravity)
-    return _CACHE["states"]
 
 
 def _refs(asset, randomized, cfg):
@@ -69,22 +57,8 @@ def _refs(asset, randomized, cfg):
     return _CACHE[key]
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def _call(sim, udot, terms):
     return _host(sim.inverse_dynamics(udot, terms))
-
-
-def _prepared(cfg, n, randomized):
-    st = _states()
-    sim = _sim(cfg)
-    _write_states(sim, st["root"][:n], st["dof"][:n], st["ball"][:n])
-    if randomized:
-        sim.set_env_params(abi.PARAM_MASS_SCALE, _dev(st["scale"][:n]))
-        sim.set_env_params(abi.PARAM_GRAVITY, _dev(st["gravity"][:n]))
-    return sim, _dev(st["udot"][:n]).view(n, NG)
 
 
 @pytest.mark.parametrize("randomized", [False, True], ids=["default_params", "mass_scale_and_gravity_rows"])
@@ -215,11 +189,6 @@ def test_terms_add_up(asset):
           "block's largest sum |terms| in the env: %.2f ulps" % (asset, ratio[e, k], e, k, resid[e, k], [float(p[e, k]) for p in parts],
                                                                  float((resid / ulp32(block)).max())))
     assert (resid <= 4.0 * ulp32(total)).all(), float(ratio.max())
-
-
-def _free():
-    torch.cuda.synchronize()
-    return torch.cuda.mem_get_info(0)[0]
 
 
 def test_contract():

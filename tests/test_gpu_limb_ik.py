@@ -7,7 +7,7 @@ layouts.  No outlier budget anywhere: every element of every env is held to its 
 
   known answer   per block (each chain's q, the position rows, the rotation rows): 3x the worst absolute error of limb_ik_ref evaluated
                  in np.float32 against fp64 on the same inputs + 2 fp32 ulps of the block's largest |reference|.
-  convergence    the weighted residual after 30 iterations at the lambda of tests/test_limb_ik_cpu.CONV against the reference's + the
+  convergence    the weighted residual after 30 iterations at the lambda of tests/limb_ik_inputs.CONV against the reference's + the
                  known-answer bars of the error rows taken through the residual's norm.
   duality        dq of one unlimited step against (J^T W J + lambda^2 I)^-1 J^T W e with the refreshed Jacobian tensor's columns in
                  the root's axes, solved in fp64: the Jacobian test's per-entry bar and the bar of the error rows (the iters = 0 call's,
@@ -22,10 +22,10 @@ import torch
 
 from bez_isaacgym_amd import abi
 from tests import limb_ik_numpy as IK
-from tests.test_gpu_state_tensors import ASSETS, _dev, _host, _sim, _write_states
-from tests.test_limb_ik_cpu import CONV, convergence_inputs
-from tests.test_state_tensors_cpu import ball_states, generate_states, ulp32
-from tests.test_tasks import make_cfg
+from tests.gpu_util import ASSETS, _bits, _dev, _host, _sim, _write_states
+from tests.limb_ik_inputs import CONV, convergence_inputs
+from tests.sim_cfg import make_cfg
+from tests.state_sets import ball_states, generate_states, ulp32
 
 pytestmark = pytest.mark.gpu
 
@@ -129,10 +129,6 @@ def _call(sim, targets, weights=WEIGHTS, offsets=None, damping=DAMPING, max_step
 def _run(sim, asset, space_name, space, cfg, n):
     it, off, step, _ = cfg
     return _call(sim, _targets(asset, space, off), WEIGHTS, OFFSETS if off else None, DAMPING, STEP if step else 0.0, it, space_name)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 @pytest.mark.parametrize("task", ["bez_kick", "bez_walk"])

@@ -14,11 +14,9 @@ import pytest
 import torch
 
 from tests import policy_ref as R
+from tests.gpu_util import DEV, GUARD, Guarded, SENT
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-SENT = 7.0      # sentinel of every output buffer (an fp16 number; no case produces a tensor of sevens)
-GUARD = 3       # sentinel rows behind row n
 REPORT = {}
 
 
@@ -30,24 +28,6 @@ def _report():
         with open(path, "a") as f:
             for key in sorted(REPORT):
                 f.write("%-44s %s\n" % (key, "  ".join("%s=%s" % kv for kv in REPORT[key].items())))
-
-
-class Guarded:
-    """(n, cols) output filled with the sentinel, with GUARD more sentinel rows behind it"""
-
-    def __init__(self, n, cols=None, dtype=torch.float32):
-        self.n = n
-        self.full = torch.full((n + GUARD,) if cols is None else (n + GUARD, cols), SENT, device=DEV, dtype=dtype)
-        self.t = self.full[:n]
-
-    def band_untouched(self):
-        return bool((self.full[self.n:] == SENT).all())
-
-    def untouched(self):
-        return bool((self.full == SENT).all())
-
-    def np(self):
-        return self.t.double().cpu().numpy()
 
 
 def _check(key, name, got, ref, bound, mode):

@@ -1,10 +1,10 @@
 """GPU: the PPO glue kernels (csrc/bez_ppo.hip, C ABI bez_ppo_*) against the plain torch formulation of the same
 rl_games a2c_continuous arithmetic (bez_isaacgym_amd/ppo/a2c_continuous.py) -- term by term, then a whole optimiser step."""
-import math
-
 import numpy as np
 import pytest
 import torch
+
+from tests.ppo_glue_ref import _torch_loss
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -207,24 +207,6 @@ def test_policy_rollout_step_equals_forward_then_rollout_pre(n, normalize_value,
     assert float(got["env_act"].abs().max()) <= 1.0
     if n >= 333:
         assert float((got["act"].abs() > 1.0).float().mean()) > 0.01  # the clamp did something
-
-
-def _torch_loss(mu, logstd, value, mb, e, critic_coef, entropy_coef, bounds_coef, clip_value):
-    from bez_isaacgym_amd.ppo.a2c_continuous import ModelA2CContinuousLogStd, policy_kl
-    sigma = torch.exp(logstd).unsqueeze(0).expand_as(mu)
-    neglogp = ModelA2CContinuousLogStd.neglogp(mb["actions"], mu, sigma, logstd.unsqueeze(0).expand_as(mu))
-    entropy = (0.5 + 0.5 * math.log(2 * math.pi) + logstd.unsqueeze(0).expand_as(mu)).sum(-1)
-    ratio = torch.exp(mb["old_logp"] - neglogp)
-    a_loss = torch.max(-mb["advantages"] * ratio, -mb["advantages"] * torch.clamp(ratio, 1 - e, 1 + e))
-    if clip_value:
-        vclip = mb["old_values"] + (value - mb["old_values"]).clamp(-e, e)
-        c_loss = torch.max((value - mb["returns"]) ** 2, (vclip - mb["returns"]) ** 2)
-    else:
-        c_loss = (mb["returns"] - value) ** 2
-    b_loss = (torch.clamp_min(mu - 1.1, 0.0) ** 2 + torch.clamp_max(mu + 1.1, 0.0) ** 2).sum(-1)
-    loss = a_loss.mean() + 0.5 * c_loss.mean() * critic_coef - entropy.mean() * entropy_coef + b_loss.mean() * bounds_coef
-    kl = policy_kl(mu.detach(), sigma.detach(), mb["mu"], mb["sigma"])
-    return loss, a_loss.mean(), c_loss.mean(), b_loss.mean(), kl, entropy.mean()
 
 
 @pytest.mark.parametrize("b,a", [(32768, 18), (1000, 7)])  # config 3's minibatch; a ragged batch (partial workgroup) of another action width

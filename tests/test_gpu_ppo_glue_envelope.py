@@ -16,7 +16,7 @@ import pytest
 import torch
 
 from tests import ppo_glue_ref as R
-from tests.test_gpu_policy_envelope import DEV, GUARD, SENT, Guarded      # (the guard-band helper is the policy envelope's)
+from tests.gpu_util import DEV, GUARD, Guarded, SENT
 
 pytestmark = pytest.mark.gpu
 F16, F32, F64 = np.float16, np.float32, np.float64

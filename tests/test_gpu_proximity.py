@@ -4,7 +4,7 @@ bit.
 
 Sizes: 1, 15, 16, 17 (the kernel's 16-env tile), 33, 65, 300 (many tiles, ragged last tile).  Assets default / cleats / box and box +
 cleats (the asset whose right ankle's joint origin moves) in the kick and walk layouts.  State sets: "generated"
-(tests.test_state_tensors_cpu.generate_states: roots up to 100 m out, every attitude seam, joints at their limits; the ball far away) and
+(tests.state_sets.generate_states: roots up to 100 m out, every attitude seam, joints at their limits; the ball far away) and
 "contact" (proximity_numpy.contact_states: every pair overlapping and apart, every box through a face, an edge, a corner and with the
 centre inside, every ground point above and below the plane).  No outlier budget anywhere.
 
@@ -21,9 +21,9 @@ import torch
 from bez_isaacgym_amd import abi
 from tests import ball_contact_ref as BC
 from tests import proximity_numpy as P
-from tests.test_gpu_state_tensors import ASSETS, _host, _sim, _write_states
-from tests.test_state_tensors_cpu import ball_states, generate_states, ulp32
-from tests.test_tasks import make_cfg
+from tests.gpu_util import ASSETS, _bits, _host, _sim, _write_states
+from tests.sim_cfg import make_cfg
+from tests.state_sets import ball_states, generate_states, ulp32
 
 pytestmark = pytest.mark.gpu
 
@@ -84,10 +84,6 @@ def _call(sim, **kw):
 
 def _ratios(got, ref, cond, bars, n):
     return {k: v / bars[k] for k, v in P.block_errors(got, ref, cond, n).items()}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _env(sim, n):

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from bez_isaacgym_amd import abi
+from tests.gpu_util import _agent
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -225,20 +226,6 @@ def test_domain_randomization_parity_full_size():
         act = rng.uniform(-1, 1, (256, 18)).astype(np.float32)
         base_o.step(act); lim_o.step(act)
     assert np.abs(base_o.dof_state - lim_o.dof_state).max() > 1e-2
-
-
-def _agent(num_envs, minibatch, randomize=False, **cfg_over):
-    from bez_isaacgym_amd.ppo.a2c_continuous import A2CAgent
-    from bez_isaacgym_amd.utils.config import load_config
-    from bez_isaacgym_amd.utils.rlgames_utils import RLGPUEnv, get_rlgames_env_creator
-    args = ["task=bez_kick", "num_envs=%d" % num_envs, "headless=True"] + (["task.task.randomize=True"] if randomize else [])
-    cfg = load_config(args)
-    cfg["task"]["seed"] = 42
-    creator = get_rlgames_env_creator(cfg["task"], "bez_kick", "cuda:0", "cuda:0", 0, True)
-    venv = RLGPUEnv("rlgpu", num_envs, env_creator=creator)
-    params = cfg["train"]["params"]
-    params["config"].update(minibatch_size=minibatch, save_frequency=0, save_best_after=10 ** 9, **cfg_over)
-    return A2CAgent(params, venv, "cuda:0")
 
 
 def test_ppo_config3_full_size():

@@ -28,7 +28,7 @@ def test_set_flags_refuses_oracle_only_variants():
 
 def _twin_agents(**over_b):
     """Two agents with the same weights, rollout dataset and normaliser state; `over_b` = config overrides of the second one."""
-    from tests.test_gpu_round2 import _agent
+    from tests.gpu_util import _agent
     a = _agent(512, 4096, hip_graphs=False, **over_b)
     b = _agent(512, 4096, hip_graphs=False)
     b.model.load_state_dict(a.model.state_dict())

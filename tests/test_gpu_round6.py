@@ -8,7 +8,7 @@ pytestmark = pytest.mark.gpu
 from bez_isaacgym_amd import abi  # noqa: E402
 from tests import rbd_numpy as R  # noqa: E402
 from tests.scenarios import capsule_penetration, leg_press  # noqa: E402
-from tests.test_oracle_round6 import _free_space_cfg, _pressed_state  # noqa: E402
+from tests.scenarios import _free_space_cfg, _pressed_state   # noqa: E402
 
 
 def _adapter(cfg, kernel, monkeypatch):
@@ -18,7 +18,7 @@ def _adapter(cfg, kernel, monkeypatch):
 
 
 def _inject(sim, n, model, seed):
-    """n pressed states (tests/test_oracle_round6._pressed_state) through the Isaac-layout setters; returns them"""
+    """n pressed states (tests/scenarios._pressed_state) through the Isaac-layout setters; returns them"""
     rng = np.random.default_rng(seed)
     dflt = np.asarray(model["dof_default"], float)
     rs = sim.root_states.reshape(n, 2, 13).copy()

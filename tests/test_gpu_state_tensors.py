@@ -1,7 +1,7 @@
 """GPU: the state-tensor boundary of bez_sim.hip -- what rl_games and the task code see -- against references that leave no room for
 an outlier budget.
 
-  * refresh_rigid_body_kernel<CL> (FK + mat_to_quat): the state set of tests/test_state_tensors_cpu.py (random SO(3) roots with both
+  * refresh_rigid_body_kernel<CL> (FK + mat_to_quat): the state set of tests/state_sets.py (random SO(3) roots with both
     signs, mat_to_quat's branch seams, joints over their range and at their limits, fast joints and roots, |x|, |y| to 100 m) on the
     default, cleats and box assets x the kick (ball row) and walk / orient (no ball) layouts, at sizes around the 64-thread blocks;
     against the fp64 FD reference (default asset) and the fp64 oracle (every asset).  Bar per field: 3x the fp32 oracle's worst error
@@ -20,33 +20,14 @@ import pytest
 import torch
 
 from bez_isaacgym_amd import abi
-from tests.test_state_tensors_cpu import (FIELDS, NB, DOF_LOWER, DOF_UPPER, align_quat, ball_states, fd_reference, field_errors,
-                                          generate_states, oracle_rows, ulp32)
-from tests.test_tasks import make_cfg
+from tests.state_sets import DOF_LOWER, DOF_UPPER, FIELDS, NB, align_quat, ball_states, fd_reference, field_errors, generate_states, oracle_rows, ulp32
+from tests.gpu_util import ASSETS, _bars, _dev, _host, _ids, _sim, _write_states
+from tests.sim_cfg import make_cfg
 
 pytestmark = pytest.mark.gpu
 
-ASSETS = {"default": {}, "cleats": dict(cleats=True), "box": dict(box=True)}
 SIZES = (1, 63, 64, 65, 300)
 NMAX = max(SIZES)
-
-
-def _sim(cfg):
-    from bez_isaacgym_amd.sim import BezSim
-    return BezSim(cfg, 0)
-
-
-def _dev(a, dtype=torch.float32):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to("cuda:0").reshape(-1).contiguous()
-
-
-def _ids(a):
-    return torch.as_tensor(np.asarray(a, np.int64).astype(np.int32)).to("cuda:0").contiguous()
-
-
-def _host(t):
-    torch.cuda.synchronize()
-    return t.detach().cpu().numpy().copy()
 
 
 @pytest.fixture(scope="module")
@@ -54,22 +35,6 @@ def gen():
     root, dof, cases = generate_states(NMAX)
     ball = ball_states(NMAX)
     return dict(root=root, dof=dof, ball=ball, cases=cases, fd=fd_reference(root, dof))
-
-
-def _write_states(sim, root, dof, ball):
-    n, nact = sim.num_envs, sim.num_actors
-    rs = np.zeros((n, nact, 13), np.float32)
-    rs[:, 0] = root
-    if nact == 2:
-        rs[:, 1] = ball
-    sim.set_actor_root_state_tensor_indexed(_dev(rs), _ids(np.arange(n * nact)))
-    sim.set_dof_state_tensor_indexed(_dev(dof), _ids(np.arange(0, n * nact, nact)))
-    return rs
-
-
-def _bars(err32, ref):
-    """per field: 3x the fp32 oracle's worst error on these states + 2 fp32 ulps of the value (elementwise)"""
-    return {name: 3.0 * float(err32[name].max()) + 2.0 * ulp32(ref[..., sl]) for name, sl in FIELDS}
 
 
 def _check(rows, ref, bars, what):

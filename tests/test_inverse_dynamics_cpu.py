@@ -1,6 +1,6 @@
 """CPU: the C ABI declares, lists and exports bez_sim_inverse_dynamics; and the reference that pins it on the GPU
 (tests/inverse_dynamics_numpy.id_ref) is what it says it is -- held to identities it was not built from, on the states of
-tests/test_state_tensors_cpu.generate_states in fp64 -- and notices the mistakes it is there to catch."""
+tests/state_sets.generate_states in fp64 -- and notices the mistakes it is there to catch."""
 import ctypes as C
 import os
 import re
@@ -12,7 +12,7 @@ from bez_isaacgym_amd import abi
 from tests import dynamics_numpy as D
 from tests import inverse_dynamics_numpy as ID
 from tests import rbd_numpy as R
-from tests.test_state_tensors_cpu import generate_states
+from tests.state_sets import generate_states
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "bez_sim.h")).read()

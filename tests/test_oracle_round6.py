@@ -11,32 +11,7 @@ import pytest
 from bez_isaacgym_amd import abi
 from oracle.bez_oracle import Oracle
 from tests import rbd_numpy as R
-from tests.scenarios import capsule_penetration, leg_press, make_backend
-
-
-def _free_space_cfg(n, seed=3, substeps=2):
-    cfg = abi.default_config(n, seed=seed)
-    cfg.gravity[:] = [0.0, 0.0, 0.0]
-    cfg.substeps = substeps
-    return cfg
-
-
-def _pressed_state(model, rng):
-    """Legs overlapping by a few millimetres (both hip rolls 0.25 rad inward: the capsules meet at 0.22 each), six leg joints just below the speed limit with
-    their targets far ahead (saturated drives pushing them over it), the torso tumbling."""
-    dflt = np.asarray(model["dof_default"], float)
-    q = dflt + rng.uniform(-0.05, 0.05, 18)
-    q[5] = dflt[5] - 0.25; q[13] = dflt[13] - 0.25
-    qd = rng.uniform(-1.0, 1.0, 18)
-    fast = [6, 7, 8, 14, 15, 16]
-    sign = rng.choice([-1.0, 1.0], len(fast))
-    qd[fast] = sign * 6.1
-    target = dflt.copy()
-    target[fast] = q[fast] + sign * 1.5
-    target[5] = dflt[5] - 0.8; target[13] = dflt[13] - 0.8   # hip drives saturated inward
-    v0 = np.concatenate([rng.uniform(-1, 1, 3), rng.uniform(-0.3, 0.3, 3)])
-    quat = rng.normal(size=4); quat /= np.linalg.norm(quat)
-    return q, qd, target, v0, quat, fast, sign
+from tests.scenarios import capsule_penetration, _free_space_cfg, leg_press, make_backend, _pressed_state
 
 
 def test_locked_joints_and_pressed_legs_need_no_base_wrench(model):

@@ -11,15 +11,7 @@ import torch.multiprocessing as mp
 
 from bez_isaacgym_amd.ppo.a2c_continuous import (A2CAgent, ModelA2CContinuousLogStd, RunningMeanStd, discount_values)
 from bez_isaacgym_amd.utils.config import load_config
-from tests.fake_env import FakeVecEnv
-
-
-def _params(num_actors, minibatch, horizon=8, epochs=3):
-    cfg = load_config(["task=bez_kick"], resolve=True)
-    p = cfg["train"]["params"]
-    p["config"].update(num_actors=num_actors, minibatch_size=minibatch, horizon_length=horizon, max_epochs=epochs,
-                       mixed_precision=False, save_frequency=0, save_best_after=10 ** 9)
-    return p
+from tests.fake_env import FakeVecEnv, _params
 
 
 def test_network_matches_reference_checkpoint_shapes():

@@ -104,7 +104,7 @@ def test_rollout_bookkeeping_and_fold():
 
 
 def _torch_loss64(d, cfg):
-    from tests.test_gpu_ppo_fused import _torch_loss
+    from tests.ppo_glue_ref import _torch_loss
     t = {k: T(d[k]) for k in R.LOSS_KEYS}
     mu, logstd, value = t["mu"].requires_grad_(), t["logstd"].requires_grad_(), t["value"].reshape(-1, 1).requires_grad_()
     mb = dict(actions=t["actions"], old_logp=t["old_logp"], advantages=t["advantages"], old_values=t["old_values"].reshape(-1, 1),

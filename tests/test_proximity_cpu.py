@@ -13,7 +13,7 @@ import pytest
 from bez_isaacgym_amd import abi
 from tests import ball_contact_ref as BC
 from tests import proximity_numpy as P
-from tests.test_state_tensors_cpu import ball_states, generate_states
+from tests.state_sets import ball_states, generate_states
 
 N = 300
 PAIR_CAP, BALL_CAP = 0.25, 0.05

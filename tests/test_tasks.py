@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-from bez_isaacgym_amd import abi
+from tests.sim_cfg import make_cfg, oracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 64
@@ -16,25 +16,6 @@ VARIANTS = [("bez_kick", True), ("bez_walk", False), ("bez_walk", True), ("bez_o
 @pytest.fixture(scope="module")
 def TG():
     return np.load(os.path.join(ROOT, "tests", "golden", "tasks_golden.npz"))
-
-
-def make_cfg(n, task="bez_kick", cleats=False, seed=42, box=False, **kw):
-    c = abi.default_config(n, seed=seed, **kw)
-    c.task = abi.TASK_IDS[task]
-    if task != "bez_kick":
-        c.max_episode_length = 600      # bez_walk.yaml / bez_orient.yaml: episodeLength_s 10
-        c.goal[:] = [2.0, 0.0]
-        c.goal_angle = 1.5708
-    if cleats:
-        c.flags |= abi.FLAG_CLEATS
-    if box:
-        c.flags |= abi.FLAG_BOX_ASSET
-    return c
-
-
-def oracle(n, **kw):
-    from oracle.bez_oracle import Oracle
-    return Oracle(make_cfg(n, **kw))
 
 
 def hip(n, **kw):
@@ -195,7 +176,6 @@ def test_hip_task_golden(TG, task, tag): check_task(hip(N, task="bez_" + task), 
 
 @pytest.mark.gpu
 def test_hip_box_asset_rest_height(): check_box_asset_rest_height(hip)
-
 
 
 @pytest.mark.gpu

@@ -6,7 +6,7 @@ import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np
 from tests.sim_adapter import SimAdapter
-from tests.test_tasks import make_cfg
+from tests.sim_cfg import make_cfg
 n = 200
 os.environ["BEZ_SIM_KERNEL"] = "ws8"; a = SimAdapter(make_cfg(n, seed=31, task="bez_kick"))
 os.environ["BEZ_SIM_KERNEL"] = "ws8q"; b = SimAdapter(make_cfg(n, seed=31, task="bez_kick"))

@@ -4,7 +4,7 @@ normalisers and Adam's moments.  Two builds that print the same line for a confi
 
   python tools/agent_digests.py [--randomize] [--train] [--dist] [switch=value ...]      e.g.  fused_ops=False hip_graphs=False
 
-The agent is tests.test_gpu_round2._agent(512, 4096, **switches).  --train: the epochs run through train(max_epochs=5) (pipelined epochs)
+The agent is tests.gpu_util._agent(512, 4096, **switches).  --train: the epochs run through train(max_epochs=5) (pipelined epochs)
 instead of train_epoch(); --dist: a 1-rank RCCL process group with BEZ_PPO_FORCE_DIST=1 (the data-parallel path on one GPU).  One
 configuration per process (profiles/agent_refactor_digests.txt)."""
 import ast
@@ -40,7 +40,7 @@ def main(argv):
         os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1", BEZ_PPO_FORCE_DIST="1")
         torch.cuda.set_device(0)
         dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-    from tests.test_gpu_round2 import _agent
+    from tests.gpu_util import _agent
     a = _agent(512, 4096, randomize="--randomize" in flags, **over)
     if "--train" in flags:
         a.train(max_epochs=5, log=lambda line: None)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """SHA-256 digests of what the dynamics queries write, on the seeded states, udot and parameter rows of the GPU tests
-(tests.test_gpu_inverse_dynamics._prepared: generate_states through _write_states).  Two builds that print the same lines compute the same bits:
+(tests.gpu_util._prepared: generate_states through _write_states).  Two builds that print the same lines compute the same bits:
 
   BEZ_SIM_LIB=build_ab/parent.so python tools/dynamics_digests.py        (one process per library; profiles/dynamics_refactor_digests.txt, profiles/dynamics_chains_digests.txt)
 
@@ -22,7 +22,8 @@ import bez_isaacgym_amd   # noqa: E402,F401  (before anything initialises HIP: D
 import torch   # noqa: E402
 
 from bez_isaacgym_amd import abi   # noqa: E402
-from tests.test_gpu_inverse_dynamics import ASSETS, _prepared, make_cfg   # noqa: E402
+from tests.gpu_util import ASSETS, _prepared   # noqa: E402
+from tests.sim_cfg import make_cfg   # noqa: E402
 
 SIZES = (1, 15, 16, 17, 65, 300)
 NG = abi.NUM_GEN

@@ -4,7 +4,7 @@ import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np
 from tests.sim_adapter import SimAdapter
-from tests.test_tasks import make_cfg
+from tests.sim_cfg import make_cfg
 n = 200
 for variant in ("kick", "kick_cleats", "walk", "orient", "orient_cleats"):
     for other in ("lane",):

@@ -6,7 +6,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import numpy as np
 import torch
 from tests.sim_adapter import SimAdapter
-from tests.test_tasks import make_cfg
+from tests.sim_cfg import make_cfg
 from bez_isaacgym_amd import abi
 
 
