@@ -255,6 +255,14 @@ static void goal_draw(uint64_t seed, uint64_t counter, uint32_t kind, float out[
 }
 
 /* ------------------------------------------------------------------ per-env state */
+/* Joint decisions of one substep, a test aid like vmargin (read, never fed back): per DOF the decision word -- bits 0..3 as
+ * BEZ_ACTUATOR_STATUS (saturated + / -, locked + / -), bit 4 q below lo, bit 5 q above hi -- and how far each decision quantity is from
+ * its boundary: tau_drive from +-effort (N m), v_pred from +-vel_limit (rad/s), q from lo and from hi (rad), |qd| from jfric_veps (rad/s);
+ * then the two predictors themselves, tau_drive and v_pred. */
+enum { BEZ_JD_WORD, BEZ_JD_M_TAU, BEZ_JD_M_VEL, BEZ_JD_M_LO, BEZ_JD_M_HI, BEZ_JD_M_FRIC, BEZ_JD_TAU_DRIVE, BEZ_JD_V_PRED, BEZ_JD_COLS };
+#define BEZ_JD_MAXSUB 8
+#define BEZ_JD_BELOW_LO 16
+#define BEZ_JD_ABOVE_HI 32
 typedef struct {
   real root_pos[3], root_quat[4], root_lin[3], root_ang[3];
   real q[ND], qd[ND];
@@ -272,6 +280,10 @@ typedef struct {
   real friction, kp_scale[ND], kd_scale[ND], mass_scale[NL], gravity[3], lim_lo[ND], lim_hi[ND];
   real ftrans[ND]; /* BEZ_FLAG_TGS_SOLVER: size of the spatial force each joint transmitted in the previous substep */
   real vmargin;    /* test aid: smallest distance of a speed-limit predictor from its decision boundary over the last control step, rad/s */
+  /* test aid (bez_oracle_get_joint_decisions): the joint decisions of the first BEZ_JD_MAXSUB substeps of the last control step, and the
+   * means over its substeps of the drive torque and the net joint force as include/bez_sim.h "Actuator tensors" defines them */
+  int jd_n; real jd[BEZ_JD_MAXSUB][ND][BEZ_JD_COLS];
+  real act_drive[ND], act_net[ND];
 } Env;
 
 typedef struct {
@@ -313,6 +325,8 @@ typedef struct {
   V3 ball_lin_acc, ball_ang_acc; /* classical */
   real contact_force[NBMAX][3];
   real vmargin;
+  real jd[ND][BEZ_JD_COLS];            /* test aid: the joint decisions of this evaluation (mode 0) */
+  real act_drive[ND], act_net[ND];     /* test aid: drive torque and net joint force of this evaluation (mode 0) */
 } Dyn;
 
 typedef struct { int link, body; V3 x; real fn0, kn, ct, ftx0, fty0; } GroundHit;
@@ -525,6 +539,7 @@ static void dynamics_x(const BezSimConfig* c, const Env* e, real h, int mode, co
   memset(pS, 0, sizeof(pS)); memset(Wself, 0, sizeof(Wself)); memset(cfs, 0, sizeof(cfs));
   memset(out->contact_force, 0, sizeof(out->contact_force));
   out->vmargin = (real)1e9;
+  memset(out->jd, 0, sizeof(out->jd)); memset(out->act_drive, 0, sizeof(out->act_drive)); memset(out->act_net, 0, sizeof(out->act_net));
 
   /* contacts (implicit spring-dampers folded into IA / pA) */
   GroundHit hits[BEZ_NPT + BEZ_NXPT];
@@ -699,6 +714,17 @@ static void dynamics_x(const BezSimConfig* c, const Env* e, real h, int mode, co
       if (force_lock) { lock = force_lock[d] != 0; if (lock) qdd_fix = ((force_lock[d] > 0 ? vl : -vl) - e->qd[d]) / h; }
       else if (v_pred > vl) { lock = 1; qdd_fix = (vl - e->qd[d]) / h; }
       else if (v_pred < -vl) { lock = 1; qdd_fix = (-vl - e->qd[d]) / h; }
+      { /* test aid: the decisions just taken and their distances from the boundaries (written, never read, by the dynamics) */
+        real* jd = out->jd[d];
+        int word = (tau_drive > eff ? BEZ_ACTUATOR_SATURATED_POS : 0) | (tau_drive < -eff ? BEZ_ACTUATOR_SATURATED_NEG : 0)
+                 | (e->q[d] < lo ? BEZ_JD_BELOW_LO : 0) | (e->q[d] > hi ? BEZ_JD_ABOVE_HI : 0);
+        if (lock) word |= qdd_fix * h + e->qd[d] > 0 ? BEZ_ACTUATOR_LOCKED_POS : BEZ_ACTUATOR_LOCKED_NEG;
+        jd[BEZ_JD_WORD] = (real)word;
+        jd[BEZ_JD_M_TAU] = fabs(fabs(tau_drive) - eff); jd[BEZ_JD_M_VEL] = fabs(fabs(v_pred) - vl);
+        jd[BEZ_JD_M_LO] = fabs(e->q[d] - lo); jd[BEZ_JD_M_HI] = fabs(e->q[d] - hi);
+        jd[BEZ_JD_M_FRIC] = fabs(fabs(e->qd[d]) - (real)c->jfric_veps);
+        jd[BEZ_JD_TAU_DRIVE] = tau_drive; jd[BEZ_JD_V_PRED] = v_pred;
+      }
     } else {
       tau = tau_in ? tau_in[d] : 0;
       D = J;
@@ -733,6 +759,21 @@ static void dynamics_x(const BezSimConfig* c, const Env* e, real h, int mode, co
     real qdd = wj[l] - gj[l] * sv_dot(U[l], ap);
     out->qdd[l - 1] = qdd;
     acc[l] = sv_add(ap, sv_scale(S[l], qdd));
+    if (mode == 0) { /* test aid: the actuator record of include/bez_sim.h "Actuator tensors", from the solved acceleration */
+      const int d = l - 1, word = (int)out->jd[d][BEZ_JD_WORD];
+      const real vn = e->qd[d] + h * qdd, qn = e->q[d] + h * vn;
+      real drive = (real)c->kp * e->kp_scale[d] * (e->target[d] - qn) - (real)c->kd * e->kd_scale[d] * vn;
+      if (word & BEZ_ACTUATOR_SATURATED_POS) drive = (real)c->effort;
+      else if (word & BEZ_ACTUATOR_SATURATED_NEG) drive = -(real)c->effort;
+      const real cf = (real)c->joint_friction / fmax(fabs(e->qd[d]), (real)c->jfric_veps);
+      real tl = stop_tau[l] - stop_k[l] * qdd;
+      if (word & BEZ_JD_BELOW_LO) tl += (real)c->limit_k * (e->lim_lo[d] - qn) - (real)c->limit_d * vn;
+      else if (word & BEZ_JD_ABOVE_HI) tl += (real)c->limit_k * (e->lim_hi[d] - qn) - (real)c->limit_d * vn;
+      out->act_drive[d] = drive;
+      if (word & (BEZ_ACTUATOR_LOCKED_POS | BEZ_ACTUATOR_LOCKED_NEG)) /* the constraint's reaction (J holds the armature) */
+        out->act_net[d] = sv_dot(S[l], pA[l]) + sc * sv_dot(S[l], pS[l]) + sv_dot(U[l], ap) + (sv_dot(S[l], U[l]) + (real)c->armature) * qdd;
+      else out->act_net[d] = drive - cf * vn + tl;
+    }
   }
   /* contact forces actually applied (implicit part resolved with the link accelerations) */
   out->ball_lin_acc = v3(0, 0, 0); out->ball_ang_acc = v3(0, 0, 0);
@@ -789,6 +830,13 @@ static void dynamics_x(const BezSimConfig* c, const Env* e, real h, int mode, co
  * locks are only added) instead of by the predictor -- the reference the predictor's misses are measured against. */
 static void dynamics(const BezSimConfig* c, const Env* e, real h, int mode, const real* tau_in, Dyn* out) {
   const int npass = (int)c->tune[22];
+  if (mode == 0 && npass < 0) { /* tune[22] = -1 (ORACLE ONLY, tests/joint_drive_ref.py): a planted error -- every lock the predictor takes is put on the opposite limit */
+    int flipped[ND];
+    dynamics_x(c, e, h, mode, tau_in, out, NULL);
+    for (int d = 0; d < ND; ++d) { int w = (int)out->jd[d][BEZ_JD_WORD]; flipped[d] = (w & BEZ_ACTUATOR_LOCKED_POS) ? -1 : ((w & BEZ_ACTUATOR_LOCKED_NEG) ? 1 : 0); }
+    dynamics_x(c, e, h, mode, tau_in, out, flipped);
+    return;
+  }
   if (mode != 0 || npass <= 0) { dynamics_x(c, e, h, mode, tau_in, out, NULL); return; }
   int lock[ND]; memset(lock, 0, sizeof(lock));
   for (int it = 0; it < npass; ++it) {
@@ -1192,6 +1240,14 @@ static void substep(const BezSimConfig* c, Env* e, real h, int first, real wgt) 
   }
   quat_integrate(e->ball_quat, e->ball_ang, h);
   e->vmargin = first ? d.vmargin : (d.vmargin < e->vmargin ? d.vmargin : e->vmargin);
+  if (first) e->jd_n = 0;
+  if (e->jd_n < BEZ_JD_MAXSUB) memcpy(e->jd[e->jd_n], d.jd, sizeof(d.jd));
+  e->jd_n += 1;
+  for (int j = 0; j < ND; ++j) { /* the mean over the substeps, like the contact rows */
+    const real w1 = (real)1 / (real)c->substeps;
+    e->act_drive[j] = first ? d.act_drive[j] * w1 : e->act_drive[j] + d.act_drive[j] * w1;
+    e->act_net[j] = first ? d.act_net[j] * w1 : e->act_net[j] + d.act_net[j] * w1;
+  }
   /* physx.contact_collection 2 = CC_ALL_SUBSTEPS (bez_kick.yaml:147): the tensor holds the mean force over the control step [ext] */
   for (int b = 0; b < NBMAX; ++b) for (int i = 0; i < 3; ++i) e->contact_force[b][i] = first ? d.contact_force[b][i] * wgt : e->contact_force[b][i] + d.contact_force[b][i] * wgt;
 }
@@ -1602,6 +1658,24 @@ void bez_oracle_get_obs(void* h, float* out) { Oracle* o = (Oracle*)h; const int
 void bez_oracle_get_feet(void* h, float* out) { Oracle* o = (Oracle*)h; for (int i = 0; i < o->n; ++i) for (int k = 0; k < 8; ++k) out[(size_t)i * 8 + k] = (float)o->env[i].feet[k]; }
 /* test aid (tests/: which envs sat within rounding of a speed-limit decision in the last control step) */
 void bez_oracle_get_vlim_margin(void* h, float* out) { Oracle* o = (Oracle*)h; for (int i = 0; i < o->n; ++i) out[i] = (float)o->env[i].vmargin; }
+/* test aid: out (n, maxsub, 18, BEZ_JD_COLS) fp64, the joint decisions of the first min(substeps, maxsub, BEZ_JD_MAXSUB) substeps of the
+ * last control step (rows beyond them: zero); returns the number of substeps that control step took */
+int bez_oracle_get_joint_decisions(void* h, double* out, int maxsub) {
+  Oracle* o = (Oracle*)h;
+  int taken = 0;
+  for (int i = 0; i < o->n; ++i) {
+    const Env* e = &o->env[i];
+    if (e->jd_n > taken) taken = e->jd_n;
+    for (int s = 0; s < maxsub; ++s) for (int d = 0; d < ND; ++d) for (int k = 0; k < BEZ_JD_COLS; ++k)
+      out[(((size_t)i * maxsub + s) * ND + d) * BEZ_JD_COLS + k] = (s < e->jd_n && s < BEZ_JD_MAXSUB) ? (double)e->jd[s][d][k] : 0.0;
+  }
+  return taken;
+}
+/* test aid: out (n, 2, 18) fp64, the means over the substeps of the last control step of the drive torque and of the net joint force */
+void bez_oracle_get_actuators(void* h, double* out) {
+  Oracle* o = (Oracle*)h;
+  for (int i = 0; i < o->n; ++i) for (int d = 0; d < ND; ++d) { out[((size_t)i * 2) * ND + d] = (double)o->env[i].act_drive[d]; out[((size_t)i * 2 + 1) * ND + d] = (double)o->env[i].act_net[d]; }
+}
 void bez_oracle_get_rew(void* h, float* out) { Oracle* o = (Oracle*)h; for (int i = 0; i < o->n; ++i) out[i] = (float)o->env[i].rew; }
 void bez_oracle_get_reset(void* h, int64_t* out) { Oracle* o = (Oracle*)h; for (int i = 0; i < o->n; ++i) out[i] = o->env[i].reset; }
 void bez_oracle_set_reset(void* h, const int64_t* in) { Oracle* o = (Oracle*)h; for (int i = 0; i < o->n; ++i) o->env[i].reset = in[i]; }

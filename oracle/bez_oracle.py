@@ -89,6 +89,29 @@ class Oracle:
     rew = property(lambda s: s._get("rew", (s.n,)))
     vlim_margin = property(lambda s: s._get("vlim_margin", (s.n,)))   # rad/s: how close a speed-limit decision of the last step came to its boundary
     reset_buf = property(lambda s: s._get("reset", (s.n,), np.int64))
+
+    JD_MAXSUB = 8
+    JD_COLUMNS = ("word", "m_tau", "m_vel", "m_lo", "m_hi", "m_fric", "tau_drive", "v_pred")
+    JD_BELOW_LO, JD_ABOVE_HI = 16, 32
+
+    def joint_decisions(self):
+        """Test aid, like vlim_margin: {column: (n, substeps, 18)} of the last control step (its first JD_MAXSUB substeps).  word (int): bits
+        0..3 as BEZ_ACTUATOR_STATUS (saturated + / -, locked + / -), JD_BELOW_LO, JD_ABOVE_HI; m_*: distance of tau_drive from +-effort
+        (N m), of v_pred from +-vel_limit (rad/s), of q from lo and from hi (rad), of |qd| from jfric_veps (rad/s); the two predictors."""
+        out = np.zeros((self.n, self.JD_MAXSUB, NUM_DOFS, len(self.JD_COLUMNS)))
+        self.lib.bez_oracle_get_joint_decisions.restype = C.c_int
+        taken = min(int(self.lib.bez_oracle_get_joint_decisions(self.h, _fp(out), C.c_int(self.JD_MAXSUB))), self.JD_MAXSUB)
+        d = {k: out[:, :taken, :, i].copy() for i, k in enumerate(self.JD_COLUMNS)}
+        d["word"] = d["word"].astype(np.int32)
+        return d
+
+    def actuators(self):
+        """Test aid: (drive torque, net joint force), fp64 (n, 18) each: the means over the substeps of the last control step, as
+        include/bez_sim.h "Actuator tensors" defines them"""
+        out = np.zeros((self.n, 2, NUM_DOFS))
+        self.lib.bez_oracle_get_actuators(self.h, _fp(out))
+        return out[:, 0].copy(), out[:, 1].copy()
+
     progress_buf = property(lambda s: s._get("progress", (s.n,), np.int64))
     timeout_buf = property(lambda s: s._get("timeout", (s.n,), np.int64))
 
