@@ -415,3 +415,35 @@ def ik_params(weights, offsets=None, damping=0.05, max_step=0.0, iters=1, space=
         raise ValueError("iters must be an integer in 0 .. %d" % IK_MAX_ITERS)
     p.damping, p.max_step, p.iters, p.space = damping, max_step, iters, ik_space(space)
     return p
+
+
+class BezOpSpaceParams(C.Structure):
+    """include/bez_sim.h BezOpSpaceParams, passed to bez_sim_operational_space by pointer and to its kernel by value"""
+    _fields_ = [
+        ("offset", (C.c_float * 3) * IK_CHAINS),
+        ("mode", C.c_uint32),
+    ]
+
+
+def op_space_params(offsets=None, fixed_base=False):
+    """The BezOpSpaceParams of a bez_sim_operational_space call, checked here (ValueError) before the library sees it.  offsets:
+    (IK_CHAINS, 3), finite, or None for zero: the controlled frame of chain c is its end body (IK_END_BODIES) displaced by offsets[c] in that
+    body's axes.  fixed_base: hold the root (FD_FIXED_BASE)."""
+    p = BezOpSpaceParams()
+    if offsets is not None:
+        try:
+            rows = [list(r) for r in offsets]
+        except TypeError:
+            rows = None
+        if rows is None or len(rows) != IK_CHAINS or any(len(r) != 3 for r in rows):
+            raise ValueError("offsets must be (%d, 3) or None" % IK_CHAINS)
+        for c, r in enumerate(rows):
+            for k, o in enumerate(r):
+                o = float(o)
+                if not math.isfinite(o):
+                    raise ValueError("offsets[%d][%d] must be finite, got %r" % (c, k, o))
+                p.offset[c][k] = o
+    if not isinstance(fixed_base, (bool, int)):
+        raise ValueError("fixed_base must be True or False, got %r" % (fixed_base,))
+    p.mode = FD_FIXED_BASE if fixed_base else 0
+    return p

@@ -1,5 +1,5 @@
 // bez_dynamics.h -- the kernels that run forward kinematics outside the control step (rigid-body refresh, dynamics tensors, inverse, forward and
-// centroidal dynamics, body accelerations, external wrenches, limb inverse kinematics, proximity).  Included by bez_sim.hip only.
+// centroidal dynamics, body accelerations, external wrenches, limb inverse kinematics, operational space, proximity).  Included by bez_sim.hip only.
 // What they share, each defined once and named, not restated, in the kernels' own comments:
 //   body_frame, for_each_body_of_link      a body's link, offset and centre of mass; the bodies fixed to one link
 //   chain_first / chain_len, for_each_chain the tree's five chains off the torso, derived from BEZ_LINK_PARENT, in either order
@@ -1133,6 +1133,363 @@ __global__ void __launch_bounds__(FD_THREADS) forward_dynamics_kernel(DynArgs D,
   });
   __syncthreads();
   tile_store<DYN_NG, FD_RSTRIDE, FD_THREADS>(frows, out + (size_t)e0 * DYN_NG, ne);
+}
+
+// ---- bez_sim_operational_space (definition: include/bez_sim.h "Operational space"): the 30 columns J_E^T of the five controlled frames
+// solved on forward_dynamics_kernel's one factorisation of the block arrow.  Column block c of J_E^T is non-zero on the base rows (X_c^T,
+// X_c = [I -skew(x); 0 I]) and on chain c's rows (J_cc^T) alone, so with y_c = M_cc^-1 J_cc^T, Z_c = M_cc^-1 B_c and S = L L^T the Schur
+// complement:
+//     P_c = X_c - J_cc Z_c  (= G_c^T, G_c = X_c^T - B_c^T y_c),   Q_c = L^-1 P_c^T,   x_0^(c) = S^-1 P_c^T = L^-T Q_c,
+//     chain a's rows of M^-1 J_c^T:  delta_ac y_c - Z_a x_0^(c),
+//     W_ab = X_a x_0^(b) + J_aa x_a^(b) = Q_a^T Q_b + delta_ab J_aa y_a,     Lambda_c = W_cc^-1.
+// W in the Q form is a Gram matrix plus the chain's own block: it is symmetric term by term, and what is left of S's rounding enters
+// both factors alike.  J_cc's levers are a_j x (p - r_j) from the joint's own origin in the root's axes (ik_chain's), turned to world
+// axes by the root's rotation as whole vectors.
+// The tile, the units and phase 1 are forward_dynamics_kernel's.  Unit 4 leaves M00 and the F_l in the env's MS_* words; then every chain's
+// unit walks its chain twice (fd_chain_block for M_cc, still_chain_walk for J_cc and the controlled point), factors M_cc and leaves Z_c,
+// y_c, J_cc, x, tri(B_c^T Z_c) and tri(J_cc y_c) in the env's OS_* words, keeping P_c in registers; unit 0 factors S and publishes the
+// tri-packed factor and its reciprocals; the chains' units solve their own six columns for Q_c and x_0^(c), finish their own rows
+// y_c - Z_c x_0^(c) and W_cc in place, and invert W_cc by a 6 x 6 Cholesky.  Last, all lanes form the outputs element by element from the
+// env's words in the order of the tile's contiguous output ranges and store them as float4 (refresh_dynamics_kernel's phase 2; a range
+// that is not 16-byte aligned: the scalar path to the same bits): a tile's outputs are 161 KB, and none of them is staged.  Both
+// triangles of w take one value: every element is formed from the sorted pair of its indices.
+// The words of phase 1 (and the chains' B^T Z) are dead once S is factored: Q, x_0 and Lambda are laid over them, which keeps the
+// tile under 64 KB.  BEZ_FD_FIXED_BASE: no phase 1, no Z, no S; x_0 = 0, W_cc = J_cc y_c, and every structural zero is a literal.
+// An env's values pass through that env's lanes and LDS words only.
+constexpr int OS_TILE = FD_TILE, OS_THREADS = FD_THREADS, OS_NF = 6 * BEZ_IK_CHAINS;
+constexpr int OS_BZ = DYN_STRIDE;                                                                       // live until S is factored
+constexpr int OS_Q = 0, OS_X0 = OS_Q + 36 * BEZ_IK_CHAINS, OS_LAM = OS_X0 + 36 * BEZ_IK_CHAINS;         // laid over them afterwards
+constexpr int OS_SF = (OS_BZ > OS_LAM ? OS_BZ : OS_LAM) + 21 * BEZ_IK_CHAINS;                           // tri(L), 1 / diag(L); then tri(S)
+constexpr int OS_S0 = OS_SF + 27, OS_Z = OS_S0 + 21, OS_XC = OS_Z + 6 * BEZ_ND, OS_JL = OS_XC + 6 * BEZ_ND, OS_JA = OS_JL + 3 * BEZ_ND, OS_XP = OS_JA + 3 * BEZ_ND;
+constexpr int OS_WD = OS_XP + 3 * BEZ_IK_CHAINS, OS_STRIDE = (OS_WD + 21 * BEZ_IK_CHAINS) | 1;          // odd, as DYN_STRIDE
+static_assert(OS_TILE * OS_STRIDE * sizeof(float) <= 65536, "the tile's words fit the static LDS limit");
+constexpr int os_chain_of_dof(int d) { int c = 0; for (int k = 1; k < BEZ_IK_CHAINS; ++k) c += d >= chain_first(k) - 1; return c; }
+// the two halves of chol_solve
+template <int K>
+BEZ_DEV void chol_forward(const float (&A)[K][K], const float (&inv)[K], float (&x)[K]) {
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+#pragma unroll
+    for (int k = 0; k < i; ++k) x[i] = fmaf(-A[i][k], x[k], x[i]);
+    x[i] *= inv[i];
+  }
+}
+template <int K>
+BEZ_DEV void chol_backward(const float (&A)[K][K], const float (&inv)[K], float (&x)[K]) {
+#pragma unroll
+  for (int i = K - 1; i >= 0; --i) {
+#pragma unroll
+    for (int k = i + 1; k < K; ++k) x[i] = fmaf(-A[k][i], x[k], x[i]);
+    x[i] *= inv[i];
+  }
+}
+// Chain C of one env up to the Schur complement.  O: the env's words; P: P_C, kept for os_chain_finish (floating base alone)
+template <bool CL, int C>
+BEZ_DEV void os_chain_reduce(const DynArgs& D, int e, const BezOpSpaceParams& Pm, bool floating, float* O, float (&P)[6][6]) {
+  constexpr int FIRST = chain_first(C), LEN = chain_len(C), D0 = FIRST - 1, R0 = 5 + FIRST;
+  float A[LEN][LEN], inv[LEN], x[LEN];
+  fd_chain_block<CL, C>(D, e, A);
+  float A0[LEN][LEN];   // M_cc itself, for the residuals of Z_c
+#pragma unroll
+  for (int i = 0; i < LEN; ++i) {
+#pragma unroll
+    for (int j = 0; j <= i; ++j) A0[i][j] = A0[j][i] = A[i][j];
+  }
+  chol_factor<LEN>(A, inv);
+  // J_cc = [E0 (a_j x (p - r_j)); E0 a_j] and the controlled point x = E0 p
+  float J[6][LEN];
+  V3 xw;
+  {
+    M3 E = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    V3 r = mk(0.f, 0.f, 0.f), a[LEN], ro[LEN];
+    still_chain_walk<FIRST, LEN>(E, r, quirk_rz<CL>(D.flags), [&](auto Lk) { return state_at(D, F_Q + decltype(Lk)::value - 1, e); }, [&](auto Lk, const SV& S) {
+      a[decltype(Lk)::value - FIRST] = S.a; ro[decltype(Lk)::value - FIRST] = r;
+    });
+    const BodyFrame bf = body_frame<CL>(link_body<CL>(FIRST + LEN - 1));
+    const V3 p = r + mul(E, bf.off + mk(Pm.offset[C][0], Pm.offset[C][1], Pm.offset[C][2]));
+    const M3 E0 = root_rotation(D, e);
+    xw = mul(E0, p);
+    dyn_put3(O, OS_XP + 3 * C, xw);
+#pragma unroll
+    for (int i = 0; i < LEN; ++i) {
+      const V3 jl = mul(E0, cross(a[i], p - ro[i])), ja = mul(E0, a[i]);
+      J[0][i] = jl.x; J[1][i] = jl.y; J[2][i] = jl.z; J[3][i] = ja.x; J[4][i] = ja.y; J[5][i] = ja.z;
+      dyn_put3(O, OS_JL + 3 * (D0 + i), jl);
+      dyn_put3(O, OS_JA + 3 * (D0 + i), ja);
+    }
+  }
+  if (floating) {
+    const float* Ms = O + DYN_MS;
+    float B[LEN][6], Z[LEN][6];
+    static_for<LEN>([&](auto I) {
+      constexpr int i = decltype(I)::value;
+      static_for<6>([&](auto K) { B[i][decltype(K)::value] = mass_at<R0 + i, decltype(K)::value>(Ms); });
+    });
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+#pragma unroll
+      for (int i = 0; i < LEN; ++i) x[i] = B[i][k];
+      chol_solve<LEN>(A, inv, x);
+      // one step of refinement on the column, the residual against M_cc in fp64: P_c = X_c - J_cc Z_c is what is left of X_c
+      float d[LEN];
+#pragma unroll
+      for (int i = 0; i < LEN; ++i) {
+        double r = B[i][k];
+#pragma unroll
+        for (int m = 0; m < LEN; ++m) r = fma(-(double)A0[i][m], (double)x[m], r);
+        d[i] = (float)r;
+      }
+      chol_solve<LEN>(A, inv, d);
+#pragma unroll
+      for (int i = 0; i < LEN; ++i) { x[i] += d[i]; Z[i][k] = x[i]; O[OS_Z + 6 * (D0 + i) + k] = x[i]; }
+    }
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+#pragma unroll
+      for (int b = 0; b <= a; ++b) {
+        double s = 0.0;   // (fp64: the products of two floats are exact, and S is what is left of M00 after these are taken off)
+#pragma unroll
+        for (int i = 0; i < LEN; ++i) s = fma((double)B[i][a], (double)Z[i][b], s);
+        O[OS_BZ + 21 * C + fd_tri(a, b)] = (float)s;
+      }
+    }
+    const float X[3][3] = {{0.f, xw.z, -xw.y}, {-xw.z, 0.f, xw.x}, {xw.y, -xw.x, 0.f}};   // -skew(x)
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        float s = (i < 3 && k >= 3) ? X[i % 3][k % 3] : (i == k ? 1.f : 0.f);
+#pragma unroll
+        for (int r = 0; r < LEN; ++r) s = fmaf(-J[i][r], Z[r][k], s);
+        P[i][k] = s;
+      }
+    }
+  }
+  // y_c column by column, and the lower triangle of J_cc y_c
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+#pragma unroll
+    for (int r = 0; r < LEN; ++r) x[r] = J[i][r];
+    chol_solve<LEN>(A, inv, x);
+#pragma unroll
+    for (int r = 0; r < LEN; ++r) O[OS_XC + 6 * (D0 + r) + i] = x[r];
+#pragma unroll
+    for (int j = 0; j <= i; ++j) {
+      float s = 0.f;
+#pragma unroll
+      for (int r = 0; r < LEN; ++r) s = fmaf(J[j][r], x[r], s);
+      O[OS_WD + 21 * C + fd_tri(i, j)] = s;
+    }
+  }
+}
+// S = M00 - sum_c B_c^T Z_c of one env (fd_base_solve's sum), factored; the factor's lower triangle and reciprocals go to OS_SF
+BEZ_DEV void os_base_factor(float* O) {
+  const float* Ms = O + DYN_MS;
+  float S[6][6], inv[6];
+  static_for<6>([&](auto I) {
+    constexpr int i = decltype(I)::value;
+    static_for<i + 1>([&](auto Jc) {
+      constexpr int j = decltype(Jc)::value;
+      double s = mass_at<i, j>(Ms);
+#pragma unroll
+      for (int c = 0; c < BEZ_IK_CHAINS; ++c) s -= (double)O[OS_BZ + 21 * c + fd_tri(i, j)];
+      S[i][j] = (float)s;
+      O[OS_S0 + fd_tri(i, j)] = S[i][j];
+    });
+  });
+  chol_factor<6>(S, inv);
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+#pragma unroll
+    for (int j = 0; j <= i; ++j) O[OS_SF + fd_tri(i, j)] = S[i][j];
+    O[OS_SF + 21 + i] = inv[i];
+  }
+}
+// Chain C of one env behind the Schur complement: Q_C and x_0^(C), the chain's own rows y_C - Z_C x_0^(C) over y_C, W_CC over J_CC y_C,
+// Lambda_C where it is asked for
+template <int C>
+BEZ_DEV void os_chain_finish(bool floating, bool want_lambda, float* O, const float (&P)[6][6]) {
+  constexpr int LEN = chain_len(C), D0 = chain_first(C) - 1;
+  float Wc[6][6];
+  double Wd[6][6];   // W_CC before its rounding to fp32, for Lambda's residual
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+#pragma unroll
+    for (int j = 0; j <= i; ++j) { Wc[i][j] = O[OS_WD + 21 * C + fd_tri(i, j)]; Wd[i][j] = Wd[j][i] = Wc[i][j]; }
+  }
+  if (floating) {
+    float S[6][6], S0[6][6], inv[6], Q[6][6], X0[6][6], x[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+      for (int j = 0; j <= i; ++j) { S[i][j] = O[OS_SF + fd_tri(i, j)]; S0[i][j] = S0[j][i] = O[OS_S0 + fd_tri(i, j)]; }
+      inv[i] = O[OS_SF + 21 + i];
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) x[k] = P[i][k];
+      chol_forward<6>(S, inv, x);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) { Q[k][i] = x[k]; O[OS_Q + 36 * C + 6 * k + i] = x[k]; }
+      chol_backward<6>(S, inv, x);
+      // one step of refinement on the column: the residual against S in fp64
+      float d[6];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        double r = P[i][k];
+#pragma unroll
+        for (int m = 0; m < 6; ++m) r = fma(-(double)S0[k][m], (double)x[m], r);
+        d[k] = (float)r;
+      }
+      chol_solve<6>(S, inv, d);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) { x[k] += d[k]; X0[k][i] = x[k]; O[OS_X0 + 36 * C + 6 * k + i] = x[k]; }
+    }
+#pragma unroll
+    for (int r = 0; r < LEN; ++r) {
+      float z[6];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) z[k] = O[OS_Z + 6 * (D0 + r) + k];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        float s = O[OS_XC + 6 * (D0 + r) + i];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s = fmaf(-z[k], X0[k][i], s);
+        O[OS_XC + 6 * (D0 + r) + i] = s;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+      for (int j = 0; j <= i; ++j) {
+        double s = Wc[i][j];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s = fma((double)Q[k][i], (double)Q[k][j], s);
+        Wd[i][j] = Wd[j][i] = s;
+        Wc[i][j] = (float)s;
+        O[OS_WD + 21 * C + fd_tri(i, j)] = Wc[i][j];
+      }
+    }
+  }
+  if (want_lambda) {
+    // Lambda = W_cc^-1 column by column from the factor of the rounded block, then one Newton step Lambda += Lambda (I - W_cc Lambda)
+    // whose residual is formed in fp64 against the UNROUNDED W_cc (Wd): cond(W_cc) reaches 6e3, and what Lambda loses is the rounding of
+    // W_cc's entries to fp32, not the inversion -- measured on MI355X 1.43 of the known-answer bar with the residual against the
+    // rounded block, 0.86 against Wd
+    float Lm[6][6], inv[6], x[6];
+    chol_factor<6>(Wc, inv);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) x[k] = k == j ? 1.f : 0.f;
+      chol_solve<6>(Wc, inv, x);
+#pragma unroll
+      for (int i = j; i < 6; ++i) Lm[i][j] = Lm[j][i] = x[i];
+    }
+    float R[6][6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        double r = k == j ? 1.0 : 0.0;
+#pragma unroll
+        for (int m = 0; m < 6; ++m) r = fma(-Wd[k][m], (double)Lm[m][j], r);
+        R[k][j] = (float)r;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+#pragma unroll
+      for (int i = j; i < 6; ++i) {
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s = fmaf(Lm[i][k], R[k][j], s);
+        O[OS_LAM + 21 * C + fd_tri(i, j)] = Lm[i][j] + s;
+      }
+    }
+  }
+}
+// Element i of an env's output from its words O: jac (5, 6, 24), jminv (5, 6, 24), w (30, 30), lambda (5, 6, 6)
+BEZ_DEV float os_jac_at(const float* O, int i) {
+  const int col = i % DYN_NG, row = (i / DYN_NG) % 6, c = i / (6 * DYN_NG);
+  if (col < 6) return jacobian_entry(O, 0u, lds3(O + OS_XP + 3 * c), row, col);
+  const int d = col - 6;
+  if (os_chain_of_dof(d) != c) return 0.f;
+  return row < 3 ? O[OS_JL + 3 * d + row] : O[OS_JA + 3 * d + row - 3];
+}
+BEZ_DEV float os_jminv_at(const float* O, int i, bool floating) {
+  const int col = i % DYN_NG, row = (i / DYN_NG) % 6, b = i / (6 * DYN_NG);
+  if (col < 6) return floating ? O[OS_X0 + 36 * b + 6 * col + row] : 0.f;
+  const int d = col - 6;
+  if (os_chain_of_dof(d) == b) return O[OS_XC + 6 * d + row];
+  if (!floating) return 0.f;
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) s = fmaf(-O[OS_Z + 6 * d + k], O[OS_X0 + 36 * b + 6 * k + row], s);
+  return s;
+}
+BEZ_DEV float os_w_at(const float* O, int i, bool floating) {
+  const int r = i / OS_NF, c = i % OS_NF, lo = min(r, c), hi = max(r, c), a = lo / 6, ia = lo % 6, b = hi / 6, ib = hi % 6;
+  if (a == b) return O[OS_WD + 21 * a + fd_tri(ib, ia)];
+  if (!floating) return 0.f;
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) s = fmaf(O[OS_Q + 36 * a + 6 * k + ia], O[OS_Q + 36 * b + 6 * k + ib], s);
+  return s;
+}
+BEZ_DEV float os_lambda_at(const float* O, int i) {
+  const int r = (i / 6) % 6, c = i % 6;
+  return O[OS_LAM + 21 * (i / 36) + fd_tri(max(r, c), min(r, c))];
+}
+// the tile's contiguous range of `ne` x PER_ENV elements, each formed by at(the env's words, its index within the env)
+template <int PER_ENV, typename At>
+BEZ_DEV void os_emit(const float* lds, float* __restrict__ out, int ne, At&& at) {
+  static_assert(PER_ENV % 4 == 0, "whole float4s per env");
+  auto v = [&](int i) { return at(lds + (i / PER_ENV) * OS_STRIDE, i % PER_ENV); };
+  const int count = ne * PER_ENV;
+  if ((reinterpret_cast<uintptr_t>(out) & 15u) == 0) {
+    float4* o4 = reinterpret_cast<float4*>(out);
+    for (int i = threadIdx.x; i < count / 4; i += OS_THREADS) o4[i] = make_float4(v(4 * i), v(4 * i + 1), v(4 * i + 2), v(4 * i + 3));
+  } else {
+    for (int i = threadIdx.x; i < count; i += OS_THREADS) out[i] = v(i);
+  }
+}
+template <bool CL>
+__global__ void __launch_bounds__(OS_THREADS) operational_space_kernel(DynArgs D, BezOpSpaceParams Pm, float* __restrict__ jac, float* __restrict__ jminv,
+                                                                       float* __restrict__ w, float* __restrict__ lam) {
+  __shared__ float lds[OS_TILE * OS_STRIDE];
+  const int n = D.n, e0 = blockIdx.x * OS_TILE, ne = min(OS_TILE, n - e0);
+  const int el = threadIdx.x % OS_TILE, unit = threadIdx.x / OS_TILE;
+  const bool mine = el < ne, floating = !(Pm.mode & BEZ_FD_FIXED_BASE);
+  const int e = e0 + el;
+  float* O = lds + el * OS_STRIDE;
+  if (mine && unit == 4 && floating) {
+    EnvState S;
+    load_state(D.st, n, e, S);
+    M3 E[BEZ_NL]; V3 r[BEZ_NL]; SV V[BEZ_NL];
+    link_frames<CL, false>(S, D.flags, E, r, V);
+    dyn_joint_words(O, E, r);
+    dyn_mass_words<CL, false>(D, e, O, E, r);
+  }
+  __syncthreads();
+  float P[6][6];
+  static_for<BEZ_IK_CHAINS>([&](auto Ci) {
+    constexpr int c = decltype(Ci)::value;
+    if (mine && unit == fd_unit(c)) os_chain_reduce<CL, c>(D, e, Pm, floating, O, P);
+  });
+  __syncthreads();
+  if (mine && unit == 0 && floating) os_base_factor(O);
+  __syncthreads();
+  static_for<BEZ_IK_CHAINS>([&](auto Ci) {
+    constexpr int c = decltype(Ci)::value;
+    if (mine && unit == fd_unit(c)) os_chain_finish<c>(floating, lam != nullptr, O, P);
+  });
+  __syncthreads();
+  if (jac) os_emit<OS_NF * DYN_NG>(lds, jac + (size_t)e0 * (OS_NF * DYN_NG), ne, [](const float* Oe, int i) { return os_jac_at(Oe, i); });
+  if (jminv) os_emit<OS_NF * DYN_NG>(lds, jminv + (size_t)e0 * (OS_NF * DYN_NG), ne, [&](const float* Oe, int i) { return os_jminv_at(Oe, i, floating); });
+  if (w) os_emit<OS_NF * OS_NF>(lds, w + (size_t)e0 * (OS_NF * OS_NF), ne, [&](const float* Oe, int i) { return os_w_at(Oe, i, floating); });
+  if (lam) os_emit<36 * BEZ_IK_CHAINS>(lds, lam + (size_t)e0 * (36 * BEZ_IK_CHAINS), ne, [](const float* Oe, int i) { return os_lambda_at(Oe, i); });
 }
 
 // ---- bez_sim_proximity (definition: include/bez_sim.h "Proximity"): the step's three narrow phases -- link_ground_points, test_box_at /

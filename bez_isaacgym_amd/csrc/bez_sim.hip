@@ -785,6 +785,19 @@ int bez_sim_forward_dynamics(BezSim* s, const float* force_dev, uint32_t bias, u
   return LAUNCH_ASSET(s, forward_dynamics_kernel, FD_TILE, FD_THREADS, (hipStream_t)stream, dyn_args(s), force_dev, out_dev, bias,
                       (int)(mode & BEZ_FD_FIXED_BASE));
 }
+int bez_sim_operational_space(BezSim* s, const BezOpSpaceParams* params, float* jac_dev, float* jminv_dev, float* w_dev, float* lambda_dev, void* stream) {
+  if (!s) return fail(s, -1, "bez_sim_operational_space: sim is null");
+  if (!params) return fail(s, -1, "bez_sim_operational_space: params is null");
+  if (!jac_dev && !jminv_dev && !w_dev && !lambda_dev) return fail(s, -1, "bez_sim_operational_space: all four outputs are null (nothing to write)");
+  const BezOpSpaceParams p = *params;
+  if (p.mode & ~(uint32_t)BEZ_FD_FIXED_BASE) return fail(s, -1, "bez_sim_operational_space: mode must be 0 or BEZ_FD_FIXED_BASE");
+  for (int c = 0; c < BEZ_IK_CHAINS; ++c)
+    for (int k = 0; k < 3; ++k)
+      if (!std::isfinite(p.offset[c][k])) return fail(s, -1, "bez_sim_operational_space: an offset is not finite");
+  if ((p.mode & BEZ_FD_FIXED_BASE) && lambda_dev)
+    return fail(s, -1, "bez_sim_operational_space: lambda_dev with BEZ_FD_FIXED_BASE (W_cc of a held root is singular by structure)");
+  return LAUNCH_ASSET(s, operational_space_kernel, OS_TILE, OS_THREADS, (hipStream_t)stream, dyn_args(s), p, jac_dev, jminv_dev, w_dev, lambda_dev);
+}
 int bez_sim_centroidal(BezSim* s, float* state_dev, float* matrix_dev, void* stream) {
   if (!s) return fail(s, -1, "bez_sim_centroidal: sim is null");
   if (!state_dev && !matrix_dev) return fail(s, -1, "bez_sim_centroidal: state_dev and matrix_dev are both null (nothing to write)");

@@ -61,6 +61,7 @@ SIGS = {
     "bez_sim_refresh_dynamics_tensors": (C.c_int, [vp, u32, vp]),
     "bez_sim_inverse_dynamics": (C.c_int, [vp, fp, u32, fp, vp]),
     "bez_sim_forward_dynamics": (C.c_int, [vp, fp, u32, u32, fp, vp]),
+    "bez_sim_operational_space": (C.c_int, [vp, C.POINTER(abi.BezOpSpaceParams), fp, fp, fp, fp, vp]),
     "bez_sim_centroidal": (C.c_int, [vp, fp, fp, vp]),
     "bez_sim_body_accelerations": (C.c_int, [vp, fp, u32, i32, fp, vp]),
     "bez_sim_generalized_forces": (C.c_int, [vp, fp, fp, fp, i32, fp, vp]),
@@ -275,6 +276,47 @@ class BezSim:
         self._check(self.lib.bez_sim_forward_dynamics(self.h, None if force is None else self._ptr(force, torch.float32, n), bias,
                                                       abi.FD_FIXED_BASE if fixed_base else 0, self._ptr(out, torch.float32, n), self._stream()))
         return out
+
+    # ---- operational space: end-frame Jacobians, J M^-1, the Delassus matrix J M^-1 J^T and the operational-space inertias
+    def operational_space(self, offsets=None, fixed_base=False, jac=None, jminv=None, w=None, lam=None, want=("jac", "jminv", "w", "lambda")):
+        """(jac, jminv, w, lam) of the current state in one launch on the current stream (include/bez_sim.h "Operational space"), for the
+        five frames limb_ik controls (abi.IK_CHAIN_NAMES, end bodies abi.IK_END_BODIES, each displaced by `offsets[c]` in the body's axes;
+        (5, 3) or None for zero).  jac (N, 5, 6, 24) float32: J_c in u = [root_lin, root_ang, qd], rows [linear; angular] in world axes.
+        jminv (N, 5, 6, 24): J_c M^-1.  w (N, 30, 30): J_E M^-1 J_E^T, block (a, b) 6 x 6 in chain order, bitwise symmetric.  lam
+        (N, 5, 6, 6): W_cc^-1.  `fixed_base`: hold the root (M becomes M[6:, 6:]; the off-diagonal blocks of w and jminv[..., 0:6] are
+        zero); W_cc is then singular by structure and "lambda" must not be wanted.  `want`: which of the four to compute; an output that
+        is not wanted is None in the result and is not written.  `jac`, `jminv`, `w`, `lam`: contiguous float32 tensors on the sim's device
+        to write into (a given tensor is wanted); None: one buffer of each kind per sim, allocated by the first call that needs it and
+        overwritten by every later one.  Everything is checked before the library is called."""
+        n = self.num_envs
+        shapes = {"jac": (n, abi.IK_CHAINS, 6, abi.NUM_GEN), "jminv": (n, abi.IK_CHAINS, 6, abi.NUM_GEN),
+                  "w": (n, 6 * abi.IK_CHAINS, 6 * abi.IK_CHAINS), "lambda": (n, abi.IK_CHAINS, 6, 6)}
+        try:
+            params = abi.op_space_params(offsets, fixed_base)
+        except ValueError as e:
+            raise BezSimError("operational_space: %s" % e)
+        if isinstance(want, str):
+            want = (want,)
+        for k in want:
+            if k not in shapes:
+                raise BezSimError("operational_space: want holds %r, expected a subset of %s" % (k, tuple(shapes)))
+        out = {}
+        for name, t in (("jac", jac), ("jminv", jminv), ("w", w), ("lambda", lam)):
+            if t is not None:
+                out[name] = self._checked("lam" if name == "lambda" else name, t, (shapes[name],))
+            else:
+                out[name] = name in want or None
+        if all(t is None for t in out.values()):
+            raise BezSimError("operational_space: nothing is wanted (want is empty and no output tensor is given)")
+        if fixed_base and out["lambda"] is not None:
+            raise BezSimError("operational_space: 'lambda' with fixed_base (W_cc of a held root is singular by structure)")
+        ptrs = []
+        for name in ("jac", "jminv", "w", "lambda"):
+            if out[name] is True:
+                out[name] = self._scratch("operational_space_" + name, shapes[name])
+            ptrs.append(None if out[name] is None else self._ptr(out[name], torch.float32, torch.Size(shapes[name]).numel()))
+        self._check(self.lib.bez_sim_operational_space(self.h, C.byref(params), ptrs[0], ptrs[1], ptrs[2], ptrs[3], self._stream()))
+        return out["jac"], out["jminv"], out["w"], out["lambda"]
 
     # ---- centroidal dynamics: centre of mass, momentum about it, the momentum matrix A_G, mechanical energy
     def centroidal(self, state=None, matrix=None, want_matrix=False):

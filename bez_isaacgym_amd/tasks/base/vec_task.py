@@ -234,6 +234,35 @@ class VecTask(Env):
         """(N, 24): M(q)^-1 b for a generalised force b (N, 24)"""
         return self.forward_dynamics(b, 0)
 
+    # ---- operational space of the current state (include/bez_sim.h "Operational space"), for the five frames limb_ik controls; each
+    # method is one launch, and what it returns is the sim's one result buffer of that kind: the next call overwrites it
+    def operational_space(self, offsets=None, fixed_base=None, want=("jac", "jminv", "w", "lambda")):
+        """(jac (N, 5, 6, 24), jminv (N, 5, 6, 24), w (N, 30, 30), lam (N, 5, 6, 6)): J_c, J_c M^-1, J_E M^-1 J_E^T and W_cc^-1 of the frames
+        of abi.IK_CHAIN_NAMES, each the chain's end body displaced by offsets[c] (5, 3) in its own axes (None: zero); None for what `want`
+        leaves out.  fixed_base: hold the root, None: as the task's urdfAsset.fixBaseLink says; "lambda" cannot be wanted with it"""
+        from ... import abi
+        if fixed_base is None:
+            fixed_base = bool(int(self.sim.cfg.flags) & abi.FLAG_FIX_BASE)
+        return self.sim.operational_space(offsets, fixed_base, want=want)
+
+    def end_effector_jacobian(self, offsets=None):
+        """(N, 5, 6, 24): the Jacobians of the five controlled frames, rows [linear; angular] in world axes"""
+        return self.operational_space(offsets, want=("jac",))[0]
+
+    def delassus_matrix(self, offsets=None):
+        """(N, 30, 30): W = J_E M^-1 J_E^T, what a wrench on one controlled frame does to every other; bitwise symmetric"""
+        return self.operational_space(offsets, want=("w",))[2]
+
+    def operational_space_inertia(self, offsets=None):
+        """(N, 5, 6, 6): Lambda_c = (J_c M^-1 J_c^T)^-1 of each controlled frame (floating base alone)"""
+        return self.operational_space(offsets, want=("lambda",))[3]
+
+    def dynamically_consistent_inverse(self, offsets=None):
+        """(N, 5, 24, 6): Jbar_c = M^-1 J_c^T Lambda_c of each controlled frame, J_c @ Jbar_c = I (floating base alone): the launch and one
+        matmul on its outputs"""
+        _, jminv, _, lam = self.operational_space(offsets, want=("jminv", "lambda"))
+        return torch.matmul(lam, jminv).transpose(-1, -2)
+
     # ---- centroidal dynamics of the current state (include/bez_sim.h "Centroidal dynamics"); each method is one launch, and what it
     # returns is (a view of) the sim's one result buffer of that kind: the next call overwrites it
     def centroidal_state(self):

@@ -393,6 +393,47 @@ int bez_sim_inverse_dynamics(BezSim* sim, const float* udot_dev, uint32_t terms,
 #define BEZ_FD_FIXED_BASE 1u   /* hold the root: udot[0:6] = 0, solve the joint block alone */
 int bez_sim_forward_dynamics(BezSim* sim, const float* force_dev, uint32_t bias, uint32_t mode, float* out_dev, void* stream);
 
+/* Operational space: the quantities of operational-space control for the five frames that bez_sim_limb_ik controls (head, two hands, two
+ * feet), in one launch on the factorisation of the call above:
+ *       J_c,   J_c M^-1,   W = J_E M^-1 J_E^T (the Delassus matrix, J_E the five J_c stacked),   Lambda_c = W_cc^-1.
+ * (The Isaac Gym route: both dynamics tensors, slicing and shifting rows by hand, torch.linalg.solve on N dense 24 x 24 systems, two bmm.)
+ *   Chains, end bodies and params->offset[c] are those of bez_sim_limb_ik: the controlled frame of chain c is the chain's end body
+ *     displaced by offset[c] in that body's axes.
+ *   Coordinates are those of the dynamics tensors: u = [root_lin(3), root_ang(3), qd(18)]; rows 0:3 of a frame are the linear velocity of
+ *     the controlled point, rows 3:6 its angular velocity, world axes.  M is the matrix of BEZ_DYNAMICS_MASS_MATRIX (armature, the env's
+ *     BEZ_PARAM_MASS_SCALE row, the asset's model, the joint origin box + cleats moves).  The state is read as it stands on `stream`.  The
+ *     ball takes no part.  BEZ_FLAG_FIX_BASE changes nothing, as in every sibling call.
+ *   Outputs, f32, env-major, each may be NULL (not written); all four NULL is an error:
+ *     jac_dev    (N, 5, 6, 24)  J_c of the controlled frame; with offset 0 the rows of the end body in BEZ_DYNAMICS_JACOBIAN.  The base block
+ *                is exact as there (I, I, 0, -skew(x - root_pos)); the columns of the other four chains are +0.0f.  The mode does not
+ *                change it.
+ *     jminv_dev  (N, 5, 6, 24)  J_c M^-1: jminv[c] @ f is the frame's acceleration response to a generalised force f, and
+ *                Lambda_c @ jminv[c] is the transpose of the dynamically consistent inverse.
+ *     w_dev      (N, 30, 30)    W, block (a, b) 6 x 6 in chain order; both triangles are written from one computed value (bitwise symmetric).
+ *                W is singular by structure (rank <= 24): the call never returns its full inverse.
+ *     lambda_dev (N, 5, 6, 6)   W_cc^-1 by a 6 x 6 Cholesky factorisation, bitwise symmetric.
+ *   mode == BEZ_FD_FIXED_BASE holds the root, M becomes M[6:,6:]: jminv[..., 0:6] and the other chains' columns are +0.0f, the off-diagonal
+ *     blocks of w are +0.0f, W_cc = J_cc M_cc^-1 J_cc^T.  Those blocks are singular by structure (rank 2 for the head and the arms, a
+ *     straight knee for a leg): a non-NULL lambda_dev in this mode is an error.
+ *   To the bit: block (a, b) of w and chain c's jac, jminv and lambda do not depend on any other chain's offset; an env's bits depend
+ *     neither on N, nor on its place, nor on the buffers' alignment (4-byte-aligned pointers give the same bits); which outputs are asked
+ *     for does not change the others; a non-finite state is written through for its own env and changes no bit of any other env.
+ *   One kernel launch with params in its arguments.  The call allocates nothing, never synchronises, reads nothing on the host and writes
+ *   only the given outputs: it captures into a HIP graph.  rc -1 with a message, and nothing written: a null sim or params, all outputs
+ *   NULL, an unknown mode bit, a non-finite offset, lambda_dev with BEZ_FD_FIXED_BASE. */
+#ifndef BEZ_IK_CHAINS
+#define BEZ_IK_CHAINS 5
+#endif
+typedef struct BezOpSpaceParams {
+  float offset[BEZ_IK_CHAINS][3];   /* controlled frame = the chain's end body displaced by this, in that body's axes */
+  uint32_t mode;                    /* 0, or BEZ_FD_FIXED_BASE */
+} BezOpSpaceParams;
+int bez_sim_operational_space(BezSim* sim, const BezOpSpaceParams* params,
+                              float* jac_dev    /* (N,5,6,24) or NULL */,
+                              float* jminv_dev  /* (N,5,6,24) or NULL */,
+                              float* w_dev      /* (N,30,30)  or NULL */,
+                              float* lambda_dev /* (N,5,6,6)  or NULL */, void* stream);
+
 /* Centroidal dynamics: the robot's centre of mass, its momentum about it, the map from u to that momentum, and the mechanical energy --
  * what balance controllers, capture-point and angular-momentum rewards and energy diagnostics read.
  *   Coordinates: u = [root_lin(3), root_ang(3), qd(18)] of the dynamics tensors above; world (env) axes throughout.

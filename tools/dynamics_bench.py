@@ -1,6 +1,6 @@
 """Times one of the dynamics queries at num_envs = 4096 beside its yardsticks in the same run.  Prints one JSON line.
 
-  python tools/dynamics_bench.py {tensors,inverse_dynamics,centroidal,body_accelerations,generalized_forces,limb_ik,proximity,forward_dynamics} [--num-envs 4096] [--launches 200] [--warmup 20] [--cleats]
+  python tools/dynamics_bench.py {tensors,inverse_dynamics,centroidal,body_accelerations,generalized_forces,limb_ik,proximity,forward_dynamics,operational_space} [--num-envs 4096] [--launches 200] [--warmup 20] [--cleats]
   python tools/dynamics_bench.py inverse_dynamics > profiles/inverse_dynamics_bench.json      (the committed records)
   python tools/dynamics_bench.py centroidal > profiles/centroidal_bench.json
   python tools/dynamics_bench.py body_accelerations > profiles/body_accelerations_bench.json
@@ -32,6 +32,10 @@ collision shapes from bez_model.json on the body rows and compute the same 23 + 
 forward_dynamics: bez_sim_forward_dynamics (floating base with all bias; fixed base; the plain mass solve) beside bez_sim_inverse_dynamics
 with all terms -- whose walk is one of its two front ends -- beside the mass-matrix refresh -- the other -- and the route the call
 replaces: a mass-matrix refresh, bez_sim_inverse_dynamics for h and torch.linalg.solve.
+operational_space: bez_sim_operational_space (all four outputs, floating base; w alone; the fixed base without lambda) beside
+bez_sim_forward_dynamics -- whose factorisation it shares -- and the route the call replaces: a rigid-body, a Jacobian and a mass-matrix
+refresh, the five end bodies' rows sliced and their linear rows shifted to the controlled points in torch, torch.linalg.solve on the 24 x 24
+systems with 30 right-hand sides, torch.bmm for W (and, counted apart, torch.linalg.inv of the five diagonal blocks for Lambda).
 
 Each figure is the median over --launches (>= 200) single launches, each between its own pair of events on one stream, after --warmup
 launches.  Nothing flushes the caches between launches, for a call and its yardsticks alike.
@@ -414,9 +418,60 @@ def forward_dynamics(sim, n, t):
     return res
 
 
+def operational_space(sim, n, t):
+    sim.step(torch.rand(n * 18, device=DEV) * 2 - 1)   # a state off the reset pose, in motion
+    model = json.load(open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bez_isaacgym_amd", "model", "bez_model.json")))
+    ends = torch.tensor([model["body_names"].index(b) for b in abi.IK_END_BODIES], device=DEV)
+    offsets = [[0, 0, .03], [0, 0, -.05], [.02, 0, -.01], [0, 0, -.05], [.02, 0, -.01]]
+    off = torch.tensor(offsets, device=DEV, dtype=torch.float32)
+    nb = sim.num_bodies - (1 if sim.has_ball else 0)
+    nch, nf, ng = abi.IK_CHAINS, 6 * abi.IK_CHAINS, abi.NUM_GEN
+    outs = [torch.zeros(s, device=DEV) for s in ((n, nch, 6, ng), (n, nch, 6, ng), (n, nf, nf), (n, nch, 6, 6))]
+    Jt, M = sim.dynamics_tensor("jacobian"), sim.dynamics_tensor("mass_matrix")
+    force, udot = torch.rand(n, ng, device=DEV) - 0.5, torch.zeros(n, ng, device=DEV)
+    route = {}
+
+    def replaced(with_lambda):
+        def run():
+            rb = sim.refresh(abi.TENSOR_RIGID_BODY_STATE).view(n, sim.num_bodies, 13)
+            sim.refresh_dynamics_tensors(["jacobian", "mass_matrix"])
+            q = rb[:, ends, 3:7]
+            qv, qw = q[..., 0:3], q[..., 3:4]
+            o = off.unsqueeze(0).expand(n, nch, 3)
+            d = o + 2.0 * torch.cross(qv, torch.cross(qv, o, dim=-1) + qw * o, dim=-1)        # the offsets in world axes
+            J = Jt.view(n, nb, 6, ng)[:, ends].clone()
+            J[:, :, 0:3] += torch.cross(J[:, :, 3:6], d.unsqueeze(3).expand(n, nch, 3, ng), dim=2)   # v + w x d, column by column
+            JE = J.view(n, nf, ng)
+            T = torch.linalg.solve(M, JE.transpose(1, 2))
+            route["jac"], route["jminv"], route["w"] = J, T.transpose(1, 2), torch.bmm(JE, T)
+            if with_lambda:
+                route["lambda"] = torch.linalg.inv(torch.stack([route["w"][:, 6 * c:6 * c + 6, 6 * c:6 * c + 6] for c in range(nch)], dim=1))
+        return run
+
+    res = {"operational_space_all_outputs": t(lambda: sim.operational_space(offsets, False, *outs)),
+           "operational_space_w_alone": t(lambda: sim.operational_space(offsets, False, w=outs[2], want=())),
+           "operational_space_fixed_base": t(lambda: sim.operational_space(offsets, True, outs[0], outs[1], outs[2], want=())),
+           "forward_dynamics_mass_solve": t(lambda: sim.forward_dynamics(force, 0, False, udot)),
+           "refreshes_slice_shift_linalg_solve_bmm": t(replaced(False)),
+           "refreshes_slice_shift_linalg_solve_bmm_plus_linalg_inv": t(replaced(True))}
+    mine = res["operational_space_all_outputs"]["median_us"]
+    res["ratio_to_forward_dynamics_mass_solve"] = round(mine / res["forward_dynamics_mass_solve"]["median_us"], 3)
+    res["ratio_to_replaced_route"] = round(mine / res["refreshes_slice_shift_linalg_solve_bmm"]["median_us"], 4)
+    res["ratio_to_replaced_route_with_lambda"] = round(mine / res["refreshes_slice_shift_linalg_solve_bmm_plus_linalg_inv"]["median_us"], 4)
+    # the two routes agree
+    sim.operational_space(offsets, False, *outs)
+    replaced(True)()
+    torch.cuda.synchronize()
+    for k, mine_t in zip(("jac", "jminv", "w", "lambda"), outs):
+        res["max_abs_difference_of_" + k] = float((mine_t - route[k].reshape(mine_t.shape)).abs().max())
+        res["max_abs_" + k] = float(mine_t.abs().max())
+        assert torch.isfinite(mine_t).all()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("call", choices=["tensors", "inverse_dynamics", "centroidal", "body_accelerations", "generalized_forces", "limb_ik", "proximity", "forward_dynamics"])
+    ap.add_argument("call", choices=["tensors", "inverse_dynamics", "centroidal", "body_accelerations", "generalized_forces", "limb_ik", "proximity", "forward_dynamics", "operational_space"])
     ap.add_argument("--num-envs", type=int, default=4096)
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
