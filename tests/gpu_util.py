@@ -1,10 +1,14 @@
 """Device helpers the GPU tests and the digest tool share: simulations of every asset, host <-> device copies, the state writer, the
-per-field bars of the rigid-body rows, and the seeded states, udot and parameter rows of the inverse- and forward-dynamics tests
-(_states / _prepared; tools/dynamics_digests.py digests what the queries write on exactly these).  Importing this initialises no GPU."""
+per-field bars of the rigid-body rows and of the Jacobian (_J_refs), the seeded states, udot and parameter rows of the inverse- and
+forward-dynamics tests (_states / _prepared; tools/dynamics_digests.py digests what the queries write on exactly these), an oracle /
+HIP pair on one config (_pair), a SimAdapter on a named step kernel (_adapter), the randomisation config of the DR tests (_dr_cfg),
+and the PPO agent on the HIP simulator (_agent).  Importing this initialises no GPU."""
 import numpy as np
 import torch
 
 from bez_isaacgym_amd import abi
+from tests import dynamics_numpy as D
+from tests.sim_cfg import make_cfg
 from tests.state_sets import FIELDS, ball_states, generate_states, ulp32
 
 ASSETS = {"default": {}, "cleats": dict(cleats=True), "box": dict(box=True)}
@@ -90,6 +94,48 @@ def _agent(num_envs, minibatch, randomize=False, **cfg_over):
     params = cfg["train"]["params"]
     params["config"].update(minibatch_size=minibatch, save_frequency=0, save_best_after=10 ** 9, **cfg_over)
     return A2CAgent(params, venv, "cuda:0")
+
+
+def _pair(n, **kw):
+    from oracle.bez_oracle import Oracle
+    from tests.sim_adapter import SimAdapter
+    return Oracle(abi.default_config(n, **kw)), SimAdapter(abi.default_config(n, **kw))
+
+
+def _adapter(cfg, kernel, monkeypatch):
+    from tests.sim_adapter import SimAdapter
+    monkeypatch.setenv("BEZ_SIM_KERNEL", kernel)
+    return SimAdapter(cfg)
+
+
+def _dr_cfg(freq=5, sched=40):
+    r = lambda a, b, s=sched: {"range": [a, b], "schedule": "linear", "schedule_steps": s}
+    return abi.dr_config_from_params({
+        "frequency": freq,
+        "observations": {"range": [0, .002], "operation": "additive", "distribution": "gaussian"},
+        "actions": {"range": [0., .02], "operation": "additive", "distribution": "gaussian", "schedule": "linear", "schedule_steps": sched},
+        "sim_params": {"gravity": dict(r(0, 0.4), operation="additive", distribution="gaussian")},
+        "actor_params": {"bez": {
+            "rigid_shape_properties": {"friction": dict(r(0.7, 1.3), num_buckets=500, operation="scaling", distribution="uniform")},
+            "dof_properties": {"damping": dict(r(0.5, 1.5), operation="scaling", distribution="uniform"),
+                               "stiffness": dict(r(0.5, 1.5), operation="scaling", distribution="uniform"),
+                               "lower": dict(r(0, 0.01), operation="additive", distribution="gaussian"),
+                               "upper": dict(r(0, 0.01), operation="additive", distribution="gaussian")}}}})
+
+
+def _J_refs(asset, root, dof, key):
+    """(fp64 J_ref, per-field bars) of an asset from the oracle's unit-velocity rows; computed once per key and left unchanged"""
+    if key not in _CACHE:
+        cfg = lambda n: make_cfg(n, task="bez_walk", seed=5, **ASSETS[asset])
+        nb = 29 if asset == "cleats" else 21
+        J64 = D.J_ref_oracle(cfg, "f64", root, dof, nb)
+        J32 = D.J_ref_oracle(cfg, "f32", root, dof, nb)
+        err32 = np.abs(J32 - J64)
+        bars = np.empty_like(J64)
+        for sl in (slice(0, 3), slice(3, 6)):
+            bars[:, :, sl] = 3.0 * float(err32[:, :, sl].max()) + 2.0 * ulp32(J64[:, :, sl])
+        _CACHE[key] = (J64, bars)
+    return _CACHE[key]
 
 
 DEV = "cuda"

@@ -1,7 +1,8 @@
 """Scripted physics scenarios shared by the tests and by tools/getup_probe.py: the reference's three get-up tables played from lying
 starts (resources/library/trajectories/trajectories/simulation_getup{front,back,side}.csv via tests/golden/trajectories.json,
-`soccer_trajectories.py:56-91`) and the per-DOF limit sweep of `bez_isaacgym/test/test_kick_env.py:142-186`.  Both run through the
-SPLIT entry points (pre_physics + simulate) of an Oracle / SimAdapter object, so no fall reset interferes."""
+`soccer_trajectories.py:56-91`) and the per-DOF limit sweep of `bez_isaacgym/test/test_kick_env.py:142-186` with the bars both back
+ends are held to.  Both run through the SPLIT entry points (pre_physics + simulate) of an Oracle / SimAdapter object, so no fall
+reset interferes."""
 import json
 import os
 
@@ -74,8 +75,6 @@ def play(sim, n, name, model, settle=60, hold=120, trace_env=None):
     return dict(steps=len(seq), final_z=float(np.median(z)), final_up=float(np.median(up)), max_z=float(np.median(max_z)),
                 max_up=float(np.median(max_up)), standing=float(((z > 0.28) & (up > 0.9) & ok).mean()), finite=float(ok.mean()),
                 final_z_minmax=[float(z.min()), float(z.max())], trace=rows)
-
-
 
 
 def dof_sweep(sim, n, model, speed=3.0, hold=25, dofs=range(18)):
@@ -243,3 +242,53 @@ def _pressed_state(model, rng):
     v0 = np.concatenate([rng.uniform(-1, 1, 3), rng.uniform(-0.3, 0.3, 3)])
     quat = rng.normal(size=4); quat /= np.linalg.norm(quat)
     return q, qd, target, v0, quat, fast, sign
+
+
+def _lie_on_back(b, n, count=None):
+    """The first `count` envs (default: all): robot on its back (torso -x down), ball far away, joints at rest."""
+    m = n if count is None else count
+    rs = np.array(b.root_states, dtype=np.float32).reshape(n, b.nact, 13).copy()
+    rs[:m, 0, 0:3] = [0.0, 0.0, 0.12]
+    rs[:m, 0, 3:7] = [0.0, -np.sin(np.pi / 4), 0.0, np.cos(np.pi / 4)]   # xyzw: -90 deg about y -> torso +x points up
+    rs[:m, 0, 7:13] = 0
+    if b.nact > 1:
+        rs[:m, 1, 0:3] = [5.0, 5.0, 0.0795]; rs[:m, 1, 7:13] = 0   # resting in contact (exactly z = R would sit on the contact on/off edge)
+    b.set_root_states(rs.reshape(-1, 13))
+    ds = np.array(b.dof_state, dtype=np.float32).reshape(n, 18, 2).copy(); ds[:m, :, 1] = 0
+    b.set_dof_state(ds.reshape(-1, 2))
+    b.set_reset(np.zeros(n, np.int64)); b.set_progress(np.zeros(n, np.int64))
+
+
+def check_dof_sweep(rows):
+    """Every actuated DOF reaches both limits and returns (zero gravity, floating base) -- except where the model says it cannot:
+    the head joints never receive an action (kick_env.py:414), a hip rolling INWARD meets the other leg (collision_filter 0,
+    kick_env.py:365-366: the foot plates, 8 mm apart in the default pose, touch first) 0.6 rad short of its -0.785 rad limit, and a hip
+    yawing to its lower limit swings the hip box into the other leg 0.1 rad short of -1.309.  (Round 5's 3000 N/m explicit spring let
+    the saturated drive push 2 cm into the other leg: its hip roll stopped 0.34 rad short, at the thighs.)"""
+    for r in rows:
+        assert r["finite"], r
+        if r["dof"] < 2:
+            assert r["miss_default"] < 1e-3 and r["miss_lower"] > 1.5, r       # did not move
+        elif r["name"].endswith("leg_motor_1"):
+            assert 0.5 < r["miss_lower"] < 0.72 and r["miss_upper"] < 0.05 and r["miss_default"] < 0.05, r
+        elif r["name"].endswith("leg_motor_0"):
+            assert 0.03 < r["miss_lower"] < 0.2 and r["miss_upper"] < 0.05 and r["miss_default"] < 0.05, r
+        else:
+            assert r["miss_lower"] < 0.05 and r["miss_upper"] < 0.05 and r["miss_default"] < 0.05, r
+
+
+def check_fixed_base_sweep(rows, root_before, root_after):
+    """The reference's form of the sweep ("better when fixBaseLink = True", test/test_kick_env.py:142-186): gravity on, the torso welded one
+    metre above the plane.  The torso does not move by a bit; every actuated DOF reaches both limits under its limb's weight and returns,
+    with the same exceptions as the floating sweep (head joints never commanded, a hip rolling inward or yawing to its lower limit meets the other leg)."""
+    assert np.array_equal(root_before, root_after)
+    for r in rows:
+        assert r["finite"], r
+        if r["dof"] < 2:
+            assert r["miss_default"] < 1e-3 and r["miss_lower"] > 1.5, r
+        elif r["name"].endswith("leg_motor_1"):
+            assert 0.5 < r["miss_lower"] < 0.72 and r["miss_upper"] < 0.06 and r["miss_default"] < 0.06, r
+        elif r["name"].endswith("leg_motor_0"):
+            assert 0.03 < r["miss_lower"] < 0.2 and r["miss_upper"] < 0.06 and r["miss_default"] < 0.06, r
+        else:
+            assert r["miss_lower"] < 0.06 and r["miss_upper"] < 0.06 and r["miss_default"] < 0.06, r

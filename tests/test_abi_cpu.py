@@ -72,7 +72,7 @@ def test_create_argument_errors(lib):
 def test_oracle_only_model_variants_are_refused(lib):
     """BEZ_FLAG_HARD_CONTACT, BEZ_FLAG_TGS_SOLVER and BezSimConfig.tune[] select solver experiments that exist only in the CPU
     oracle (include/bez_sim.h): the HIP library must say so (rc -5, before it even looks for a device) instead of stepping
-    the compliant model under a flag it ignores.  bez_sim_set_flags applies the same rule (GPU: tests/test_gpu_round3.py)."""
+    the compliant model under a flag it ignores.  bez_sim_set_flags applies the same rule (GPU: tests/test_gpu_round4.py)."""
     for mutate in (lambda c: setattr(c, "flags", c.flags | abi.FLAG_HARD_CONTACT),
                    lambda c: setattr(c, "flags", c.flags | abi.FLAG_TGS_SOLVER),
                    lambda c: setattr(c, "flags", c.flags | abi.FLAG_ANKLE_STOP | abi.FLAG_CLEATS),          # (round 6: both run on the lane kernel -- for the stl asset without cleats only)

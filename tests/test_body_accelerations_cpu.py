@@ -42,7 +42,7 @@ def test_abi_declares_lists_and_exports_the_body_acceleration_call():
 
 
 def test_the_kernel_of_both_assets_has_no_spills_and_no_scratch(tmp_path):
-    from tests.test_body_forces_cpu import kernel_resources
+    from tests.kernel_resources import kernel_resources
     res = kernel_resources(os.path.join(ROOT, "bez_isaacgym_amd", "csrc", "bez_sim.hip"), str(tmp_path))
     mine = {k: v for k, v in res.items() if "body_accelerations_kernel" in k}
     assert len(mine) == 2, sorted(res)

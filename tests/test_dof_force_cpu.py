@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from bez_isaacgym_amd import abi
+from tests.fake_env import _ActuatorFakeEnv, _agent
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "bez_sim.h")).read()
@@ -127,27 +128,6 @@ def test_vec_task_attributes_exist_only_with_the_key():
 
 
 # ---- PPO epoch row and observer (tests/fake_env.py)
-class _ActuatorFakeEnv:
-    """mixin over FakeVecEnv: the env side of the actuator statistics (VecTask.dof_force_on / actuator_snapshot) with known numbers"""
-    dof_force_on = True
-
-    def actuator_snapshot(self):
-        self.snapshots = getattr(self, "snapshots", 0) + 1
-        n = self.n
-        drive = torch.zeros(n, 18); drive[:, 0] = 100.0           # head: not a driven joint, must not count
-        drive[:, 2] = 2.5; drive[:, 3] = -1.5
-        status = torch.zeros(n, 18, dtype=torch.int32); status[:, 0] = 15
-        status[:, 2] = abi.ACTUATOR_SATURATED_POS; status[: n // 2, 4] = abi.ACTUATOR_LOCKED_NEG
-        qd = torch.zeros(n, 18); qd[:, 2] = 2.0; qd[:, 3] = 1.0   # power: 5 W on joint 2, negative (no contribution) on joint 3
-        return drive, status, qd
-
-
-def _agent(env, n, horizon):
-    from bez_isaacgym_amd.ppo.a2c_continuous import A2CAgent
-    from tests.fake_env import _params
-    agent = A2CAgent(_params(n, 4 * n, horizon=horizon), env, "cpu")
-    agent.obs = agent.env_reset()
-    return agent
 
 
 def test_epoch_row_gains_actuators_only_with_the_flag():
@@ -190,7 +170,7 @@ def test_observer_writes_the_actuator_tags(tmp_path):
 # ---- the recording translation units
 @pytest.fixture(scope="module")
 def resources(tmp_path_factory):
-    from tests.test_body_forces_cpu import kernel_resources
+    from tests.kernel_resources import kernel_resources
     d = tmp_path_factory.mktemp("dfres")
     with cf.ThreadPoolExecutor(len(TUS)) as ex:
         res = list(ex.map(lambda tu: kernel_resources(os.path.join(CSRC, tu + ".hip"), str(d)), TUS))
@@ -223,7 +203,7 @@ def test_restated_net_joint_force_is_the_inverse_dynamics_torque(model, precisio
     from tests import dof_force_numpy as D
     from tests import rbd_numpy as R
     from tests.scenarios import make_backend
-    from tests.test_oracle_round6 import _free_space_cfg, _pressed_state
+    from tests.scenarios import _free_space_cfg, _pressed_state
     n = 64
     cfg = _free_space_cfg(n, substeps=1)
     cfg.flags |= abi.FLAG_NO_SELF_COLLISION

@@ -90,13 +90,13 @@ def test_kinetic_energy_is_half_uMu(states, scales, M_routes):
 def test_J_ref_routes_agree_and_have_the_documented_structure(states):
     """the oracle's unit-velocity rows and the finite-difference FK of the URDF fixture give the same Jacobian; J u is the body rows'
     velocity; the base blocks and the non-ancestor columns are what the header says"""
-    from tests.test_state_tensors_cpu import oracle_rows
+    from tests.state_sets import oracle_rows
     root, dof = states
     Jo = D.J_ref_oracle(lambda n: make_cfg(n, seed=5), "f64", root, dof, 21)
     Jf = D.J_ref_fd(root, dof)
     assert Jo.shape == Jf.shape == (N, 21, 6, 24)
     # the oracle's rows are fp32 outputs (half an ulp); the central differences with step 1e-5 in fp64 are good to 1e-9
-    from tests.test_state_tensors_cpu import ulp32
+    from tests.state_sets import ulp32
     bad = np.abs(Jo - Jf) > 0.51 * ulp32(Jf) + 1e-9
     assert not bad.any(), (float(np.abs(Jo - Jf).max()), np.argwhere(bad)[:5])
     rows = oracle_rows(make_cfg(N, seed=5), "f64", root, dof)[:, :21].astype(np.float64)

@@ -6,11 +6,10 @@ import os
 import re
 
 import numpy as np
-import torch
 
 from bez_isaacgym_amd import abi
 from tests.episode_stats_ref import GOLDEN_SETS, end_causes, golden_inputs, kick_params, task_params
-from tests.fake_env import FakeVecEnv
+from tests.fake_env import _CountingFakeEnv, _agent
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = open(os.path.join(ROOT, "include", "bez_sim.h")).read()
@@ -114,38 +113,6 @@ def test_debug_rewards_key_maps_to_the_flag():
 
 
 # ---------------------------------------------------------------------------------------------------- PPO epoch row and observer
-class _CountingFakeEnv(FakeVecEnv):
-    """FakeVecEnv with the simulator's episode statistics: every ended episode bumps episode_end_counts[cause, env] with a cause drawn
-    from the env index and the step, and (terms on) the reward goes into slot 5 on ended steps, split over slots 0 / 2 otherwise."""
-
-    def __init__(self, *a, terms=False, **kw):
-        super().__init__(*a, **kw)
-        self.episode_end_counts = torch.zeros(abi.END_CAUSES, self.n, dtype=torch.int64)
-        self.reward_terms_buf = torch.zeros(abi.END_CAUSES, self.n, dtype=torch.float32)
-        self.reward_terms_on = terms
-        self.calls, self.ended = 0, []
-
-    def step(self, actions):
-        obs, rew, done, info = super().step(actions)
-        causes = (torch.arange(self.n) + self.calls) % 3 + abi.END_FALL
-        idx = done.nonzero().squeeze(-1)
-        self.episode_end_counts[causes[idx], idx] += 1
-        self.ended.append(done.sum().item())
-        if self.reward_terms_on:
-            d = done.bool()
-            self.reward_terms_buf[5] += torch.where(d, rew, torch.zeros_like(rew))
-            self.reward_terms_buf[0] += torch.where(d, torch.zeros_like(rew), 0.25 * rew)
-            self.reward_terms_buf[2] += torch.where(d, torch.zeros_like(rew), rew - 0.25 * rew)
-        self.calls += 1
-        return obs, rew, done, info
-
-
-def _agent(env, n, horizon):
-    from bez_isaacgym_amd.ppo.a2c_continuous import A2CAgent
-    from tests.fake_env import _params
-    agent = A2CAgent(_params(n, 4 * n, horizon=horizon), env, "cpu")
-    agent.obs = agent.env_reset()
-    return agent
 
 
 def test_epoch_row_carries_episode_ends():

@@ -52,7 +52,7 @@ def test_abi_declares_lists_and_exports_the_generalized_force_call():
 def test_the_kernel_of_both_assets_has_no_spills_and_no_scratch(tmp_path):
     """and sits well below inverse dynamics' 256 VGPRs (there are no inertias or velocities to carry): at most 168, the budget of three
     waves per SIMD where 256 leaves room for one"""
-    from tests.test_body_forces_cpu import kernel_resources
+    from tests.kernel_resources import kernel_resources
     res = kernel_resources(os.path.join(ROOT, "bez_isaacgym_amd", "csrc", "bez_sim.hip"), str(tmp_path))
     mine = {k: v for k, v in res.items() if "generalized_forces_kernel" in k}
     assert len(mine) == 2, sorted(res)
@@ -127,7 +127,7 @@ def test_duality_with_the_finite_difference_jacobian(cases):
     Jacobian of tests/body_accel_numpy.J_ref (forward kinematics alone; up to 1.7e-7 on these fp32 states, whose quaternion J_ref_fd
     normalises), times sum |w|, + 1e-12 sum |J| |w|.  The reference is handed the same normalised quaternion."""
     from tests import body_accel_numpy as BA
-    from tests.test_state_tensors_cpu import quat_mat
+    from tests.state_sets import quat_mat
     c = cases[0]
     J = D.J_ref_fd(c["root"].astype(np.float32), c["dof"].astype(np.float32))
     c = dict(c, root=c["root"].astype(np.float32).astype(np.float64), dof=c["dof"].astype(np.float32).astype(np.float64))

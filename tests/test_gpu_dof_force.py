@@ -15,15 +15,10 @@ pytestmark = pytest.mark.gpu
 from bez_isaacgym_amd import abi  # noqa: E402
 from tests import dof_force_numpy as D  # noqa: E402
 from tests import rbd_numpy as R  # noqa: E402
+from tests.gpu_util import _adapter  # noqa: E402
 from tests.scenarios import _free_space_cfg, _pressed_state   # noqa: E402
 
 KERNELS = ["ws8", "ws8q", "lane"]
-
-
-def _adapter(cfg, kernel, monkeypatch):
-    from tests.sim_adapter import SimAdapter
-    monkeypatch.setenv("BEZ_SIM_KERNEL", kernel)
-    return SimAdapter(cfg)
 
 
 def _actuators(sim):

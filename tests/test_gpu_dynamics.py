@@ -23,7 +23,7 @@ import torch
 
 from bez_isaacgym_amd import abi
 from tests import dynamics_numpy as D
-from tests.gpu_util import ASSETS, _bars, _bits, _dev, _free, _host, _ids, _sim, _write_states
+from tests.gpu_util import ASSETS, _J_refs, _bars, _bits, _dev, _free, _host, _ids, _sim, _write_states
 from tests.sim_cfg import make_cfg
 from tests.state_sets import FIELDS, ball_states, field_errors, generate_states, oracle_rows, ulp32
 
@@ -42,21 +42,6 @@ def _states():
         scale = np.random.default_rng(17).uniform(0.5, 1.5, (NMAX, 19)).astype(np.float32)
         _CACHE["states"] = dict(root=root, dof=dof, ball=ball_states(NMAX), scale=scale)
     return _CACHE["states"]
-
-
-def _J_refs(asset, root, dof, key):
-    """(fp64 J_ref, per-field bars) of an asset from the oracle's unit-velocity rows; computed once per key and left unchanged"""
-    if key not in _CACHE:
-        cfg = lambda n: make_cfg(n, task="bez_walk", seed=5, **ASSETS[asset])
-        nb = 29 if asset == "cleats" else 21
-        J64 = D.J_ref_oracle(cfg, "f64", root, dof, nb)
-        J32 = D.J_ref_oracle(cfg, "f32", root, dof, nb)
-        err32 = np.abs(J32 - J64)
-        bars = np.empty_like(J64)
-        for sl in (slice(0, 3), slice(3, 6)):
-            bars[:, :, sl] = 3.0 * float(err32[:, :, sl].max()) + 2.0 * ulp32(J64[:, :, sl])
-        _CACHE[key] = (J64, bars)
-    return _CACHE[key]
 
 
 def _M_refs(asset, root, dof, scale, armature, key):

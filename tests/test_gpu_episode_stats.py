@@ -234,7 +234,7 @@ def test_rollout_bits_counts_and_restatement(monkeypatch, kernel, task):
 @pytest.mark.parametrize("variant", ["default", "randomised"])
 @pytest.mark.parametrize("kernel", KERNELS)
 def test_reward_terms_twin(monkeypatch, kernel, variant):
-    from tests.test_gpu_nonfinite_guard import _snap
+    from tests.guard_util import _snap
     n, steps = 4096, 200
     on = _sim(monkeypatch, n, kernel, variant=variant, terms=True)
     off = _sim(monkeypatch, n, kernel, variant=variant, terms=False)

@@ -129,7 +129,7 @@ def test_known_answer(asset, task):
 def test_duality_with_the_jacobian_tensor_and_power(asset):
     """at="origin", ENV: out[e, c] == sum_{b, r} J[e, b, r, c] w[e, b, r] with the refreshed Jacobian tensor, and u . out == the power of
     the wrenches at the velocities RIGID_BODY_STATE reports"""
-    from tests.test_gpu_dynamics import _J_refs
+    from tests.gpu_util import _J_refs
     st = _states()
     J64, barsJ = _J_refs(asset, st["root"], st["dof"], ("J", asset))
     nb = J64.shape[1]
@@ -217,7 +217,7 @@ def test_closure_on_the_step(model, kernel, space, monkeypatch):
     identity here.  Compared: the joints whose ACTUATOR_STATUS carries no lock bit (4 | 8) in the substep."""
     from tests import dof_force_numpy as DF
     from tests.sim_adapter import SimAdapter
-    from tests.test_oracle_round6 import _free_space_cfg, _pressed_state
+    from tests.scenarios import _free_space_cfg, _pressed_state
     n = 64
     monkeypatch.setenv("BEZ_SIM_KERNEL", kernel)
     gmodel = GF.model_of("default")

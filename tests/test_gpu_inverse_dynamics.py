@@ -112,7 +112,7 @@ def test_equation_of_motion_closes_on_the_step(model, kernel, monkeypatch):
     nothing touches the robot), one substep with BEZ_FLAG_DOF_FORCE: the call on the PRE-step state (restored with the setters) with udot = (u1 - u0) / h gives DOF_FORCE
     on rows 6:24 and zero on rows 0:6.  The project measured 6.7e-6 N m for the joint rows with the fp64 RNEA."""
     from tests.sim_adapter import SimAdapter
-    from tests.test_oracle_round6 import _free_space_cfg, _pressed_state
+    from tests.scenarios import _free_space_cfg, _pressed_state
     n = 64
     cfg = _free_space_cfg(n, substeps=1)
     cfg.flags |= abi.FLAG_NO_SELF_COLLISION | abi.FLAG_DOF_FORCE

@@ -193,7 +193,7 @@ def test_convergence():
 def test_duality_with_the_jacobian_tensor(asset):
     """iters = 1, no step limit, limits out of reach: q_out - q against (J^T W J + lambda^2 I)^-1 J^T W e, J the refreshed Jacobian
     tensor's columns of the chain for its end body turned into the root's axes, e the call's own err_out at iters = 0, solved in fp64"""
-    from tests.test_gpu_dynamics import _J_refs
+    from tests.gpu_util import _J_refs
     st = _states()
     _, barsJ = _J_refs(asset, st["root"], st["dof"], ("J", asset))
     model = _model(asset)

@@ -7,6 +7,7 @@ import torch
 
 from bez_isaacgym_amd import abi
 from tests import golden_checks as GC
+from tests.gpu_util import _pair
 from tests.parity_util import EnvOutliers
 
 pytestmark = pytest.mark.gpu
@@ -32,13 +33,6 @@ def test_golden_reward_normal(sim64, golden): GC.check_reward(sim64, golden, "no
 def test_golden_reward_edge(sim64, golden): GC.check_reward(sim64, golden, "edge")
 def test_golden_pre_physics(sim64, golden): GC.check_pre_physics(sim64, golden)
 def test_golden_step_sequence(sim64, golden): GC.check_step_sequence(sim64, golden)
-
-
-def _pair(n, **kw):
-    from oracle.bez_oracle import Oracle
-    from tests.sim_adapter import SimAdapter
-    cfg_a, cfg_b = abi.default_config(n, **kw), abi.default_config(n, **kw)
-    return Oracle(cfg_a), SimAdapter(cfg_b)
 
 
 def test_reset_state_bit_exact():

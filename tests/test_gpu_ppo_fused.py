@@ -356,7 +356,7 @@ def test_adam_step_kernel_matches_torch_amp_clip_adam():
 def test_fused_and_plain_optimiser_step_agree():
     """Two agents with identical weights and an identical rollout dataset: one optimiser step through the fused kernels and
     one through the plain torch formulation leave the same parameters (AMP on, as bez_kickPPO.yaml)."""
-    from tests.test_gpu_round2 import _agent
+    from tests.gpu_util import _agent
     plain = _agent(512, 4096, fused_ops=False, hip_graphs=False)
     fused = _agent(512, 4096, fused_ops=True, hip_graphs=False)
     assert fused.fused and not plain.fused
@@ -488,7 +488,7 @@ def test_train_forward_kernel_and_manual_backward_match_autograd_path(fused_back
     """A PPO minibatch's gradient through (a) the one-launch MFMA forward that keeps the ELU outputs + the backward chain called
     directly (its input-gradient half per layer, or as the one-launch MFMA backward kernel) and (b) the torch GEMM forward + autograd through _HalfLinearEluFn / _HalfLinearFn: same dataset, same weights.
     The forwards differ by fp16 roundings of the ELU (exp in fp32 either way) -- the flat gradients agree to that level."""
-    from tests.test_gpu_round2 import _agent
+    from tests.gpu_util import _agent
     a = _agent(512, 4096, hip_graphs=False, fused_train_forward=False)
     b = _agent(512, 4096, hip_graphs=False, fused_train_forward=True, fused_policy_backward=fused_backward)
     assert (b._policy_bwd is not None) == fused_backward
@@ -522,7 +522,7 @@ def test_segmented_graphs_equal_the_monolithic_update():
     """World > 1 replays collective-free graph SEGMENTS with the RCCL calls in between.  Forced on one GPU (world = 2 pretended,
     no process group): from identical weights and an identical dataset the segmented update must leave the same parameters
     as the monolithic captured update."""
-    from tests.test_gpu_round2 import _agent
+    from tests.gpu_util import _agent
     # constant learning rate: with the per-step adaptive rule a last-bit difference in a KL near a threshold (the loss kernel's sums are
     # float atomics) moves one agent's lr by 1.5x and the comparison would measure the schedule, not the graph segmentation
     mono, segm = _agent(512, 4096, lr_schedule="constant"), _agent(512, 4096, lr_schedule="constant")
@@ -570,7 +570,7 @@ import bez_isaacgym_amd   # before anything initialises HIP: graph replay is onl
 os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="%d", RANK="0", WORLD_SIZE="1", BEZ_PPO_FORCE_DIST="1")
 torch.cuda.set_device(0)
 dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-from tests.test_gpu_round2 import _agent
+from tests.gpu_util import _agent
 a = _agent(512, 4096)
 assert a._segmented and a.world == 1
 a.obs = a.env_reset()
@@ -606,7 +606,7 @@ def test_training_is_bit_reproducible():
     """Same seed, same build, same GPU -> the same weights: two agents trained independently for 2 eager + 1 capturing + 2 replayed
     epochs end bit-identical (parameters, Adam moments, loss scale, normalisers).  What makes this hold: no float atomic on the path
     from the rollout to the weights -- loss sums, bias gradients, weight gradients and the gradient norm are fixed-order reductions."""
-    from tests.test_gpu_round2 import _agent
+    from tests.gpu_util import _agent
     snaps = []
     for _ in range(2):
         torch.manual_seed(123); torch.cuda.manual_seed_all(123)
@@ -755,3 +755,41 @@ def test_wgrad_mfma_matches_fp32_reference(rows, shapes):
         odd = F.WgradMfma([torch.zeros(2048, o, device=DEV, dtype=torch.float16)], [torch.zeros(2048, i, device=DEV, dtype=torch.float16)],
                           [torch.zeros(o, i, device=DEV)])
         assert not odd.ok and odd(accumulate=False) is False
+
+
+def test_in_launch_gradient_norm_on_a_capped_grid_and_its_residency_guard():
+    """Round-5 advisor finding (medium): the optimiser launch's in-launch norm is a grid barrier.  (a) bez_ppo_adam_grid_capacity reports
+    what the device can hold at once and what the launch uses; on a whole MI355X the 256-workgroup cap fits.  (b) n > 256 * 2048 parameters:
+    the grid is capped at 256 workgroups and every workgroup walks several slices -- the step must equal the norm-shares path there too (the
+    round-5 test stopped at 61 workgroups).  (c) the counter is back at zero: the buffer serves the next launch."""
+    import ctypes as C
+    import torch
+    from bez_isaacgym_amd.ppo import fused as F
+    DEV = "cuda:0"
+    cap, g = C.c_int32(0), C.c_int32(0)
+    assert F.lib().bez_ppo_adam_grid_capacity(124237, C.addressof(cap), C.addressof(g)) == 0
+    assert g.value == 61 and cap.value >= 256 and F.adam_grid_fits(124237)
+    n = 256 * 2048 * 3 + 1234 + 1
+    assert F.lib().bez_ppo_adam_grid_capacity(n, C.addressof(cap), C.addressof(g)) == 0 and g.value == 256 and F.adam_grid_fits(n)
+    torch.manual_seed(3)
+    gs = (torch.randn(n + 3, device=DEV)[:n] * 3.0 * 1024.0).contiguous()
+    p0 = torch.randn(n, device=DEV)
+    grid_buf = torch.zeros(F.ADAM_GRIDNORM_FLOATS, device=DEV)
+
+    def step(grid):
+        p, m, v = p0.clone(), torch.zeros(n, device=DEV), torch.zeros(n, device=DEV)
+        steps, lr = torch.zeros(1, device=DEV), torch.tensor([3e-4], device=DEV)
+        scale, gt = torch.tensor([1024.0], device=DEV), torch.zeros(1, device=DEV, dtype=torch.int32)
+        work = torch.zeros(F.ADAM_WORK_FLOATS, device=DEV)
+        parts = None if grid else F.grad_norm_parts(gs, torch.zeros((n // 4 + 3 + 1023) // 1024 + 1, 2, device=DEV))
+        F.adam_step(p, gs, m, v, steps, lr, (0.9, 0.999), 1e-8, 0.0, 1.0, scale, gt, 2.0, 0.5, 2000, work, norm_parts=parts,
+                    grid_norm=grid_buf if grid else None)
+        torch.cuda.synchronize()
+        return p, m
+    p_ref, m_ref = step(False)
+    for _ in range(2):
+        p_g, m_g = step(True)
+        # (the two norms add 1.5 M squares in different fixed orders: the clip coefficient may differ in its last bit, an ulp in 0.1 % of the elements)
+        torch.testing.assert_close(p_g, p_ref, rtol=3e-7, atol=2e-9); torch.testing.assert_close(m_g, m_ref, rtol=1e-6, atol=1e-9)
+        assert int(grid_buf[512:513].view(torch.int32)) == 0
+    assert not torch.equal(p_ref, p0)

@@ -9,16 +9,10 @@ import pytest
 import torch
 
 from bez_isaacgym_amd import abi
-from tests.gpu_util import _agent
+from tests.gpu_util import _agent, _pair
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _pair(n, **kw):
-    from oracle.bez_oracle import Oracle
-    from tests.sim_adapter import SimAdapter
-    return Oracle(abi.default_config(n, **kw)), SimAdapter(abi.default_config(n, **kw))
 
 
 def _sync(o, g):
@@ -55,7 +49,7 @@ def test_ws_kernel_post_physics_pinned_against_lane_kernel(task, asset):
     reward with the LANE kernel's obs-only pass on the very same resulting state -- for every task x asset: obs[0:36] must equal
     the dof state exactly, the remaining slots and the reward to 1e-6 of their scale, reset flags and feet flags exactly."""
     from tests.sim_adapter import SimAdapter
-    from tests.test_tasks import make_cfg
+    from tests.sim_cfg import make_cfg
     n = 448
     kw = dict(task=task, cleats=(asset == "cleats"), box=(asset == "box"), seed=23)
     a, b = SimAdapter(make_cfg(n, **kw)), SimAdapter(make_cfg(n, **kw))
@@ -91,7 +85,7 @@ def test_fused_step_kernels_agree(other, variant, monkeypatch):
     16-env workgroups) and one env per lane (BEZ_SIM_KERNEL=lane) -- compute the same physics in a different order.  From an identical state, with the same actions, resynchronised every step:
     integers exact, fp32 quantities to a few ulp of their scale.  N is not a multiple of the 64-env workgroup."""
     from tests.sim_adapter import SimAdapter
-    from tests.test_tasks import make_cfg
+    from tests.sim_cfg import make_cfg
     n = 200
     task = "bez_walk" if variant.startswith("walk") else ("bez_orient" if variant.startswith("orient") else "bez_kick")
     kw = dict(seed=31, task=task, cleats=variant.endswith("_cleats"), box=variant.endswith("_box"))
@@ -101,7 +95,7 @@ def test_fused_step_kernels_agree(other, variant, monkeypatch):
     b = SimAdapter(make_cfg(n, **kw))
     monkeypatch.delenv("BEZ_SIM_KERNEL", raising=False)
     if variant.endswith("_box"):   # the box asset differs in the upper-body contact points: put a third of the envs on their back
-        from tests.test_tasks import _lie_on_back
+        from tests.scenarios import _lie_on_back
         _lie_on_back(a, n, n // 3)
     rng = np.random.default_rng(8)
     nres = 0

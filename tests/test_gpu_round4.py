@@ -120,7 +120,7 @@ def test_rollout_bookkeeping_inside_the_policy_launch_changes_nothing():
     every rollout row, the dataset, the running episode sums and the statistics are bit-identical over two rollouts (the second
     one starts from the state the first one's LAST, separately launched, bookkeeping left)."""
     import torch
-    from tests.test_gpu_round2 import _agent
+    from tests.gpu_util import _agent
     a = _agent(512, 4096, hip_graphs=False, fold_rollout_post=False)
     b = _agent(512, 4096, hip_graphs=False)
     b.model.load_state_dict(a.model.state_dict())
@@ -199,7 +199,7 @@ def test_eager_work_and_checkpoint_saves_between_graph_replays_change_nothing(fu
     import os
     import torch
     import bez_isaacgym_amd
-    from tests.test_gpu_round2 import _agent
+    from tests.gpu_util import _agent
     assert os.environ.get("DEBUG_CLR_GRAPH_PACKET_CAPTURE") == "0" and bez_isaacgym_amd.GRAPH_REPLAY_SAFE
     x = torch.ones(100, device="cuda")
     out = []
@@ -288,7 +288,7 @@ def test_dataset_prep_in_four_launches_equals_the_separate_launches():
     """bez_ppo_dataset_prep against the path it replaces (per-minibatch moments, value / return moments, two RunningMeanStd updates, two
     normalisations, advantage + its normalisation, env-major transposes): same dataset and the same normaliser statistics after a rollout."""
     import torch
-    from tests.test_gpu_round2 import _agent
+    from tests.gpu_util import _agent
     out = []
     for fused_prep in (False, True):
         torch.manual_seed(11)
@@ -317,7 +317,7 @@ def test_loss_in_front_of_the_backward_chain_changes_nothing():
     LDS) against bez_ppo_loss + bez_ppo_policy_backward: the same code on the same numbers -- weights, Adam moments, loss scale and the
     dataset's updated mu / sigma are bit-identical after four epochs (80 optimiser steps, update_mu_sigma and adaptive lr included)."""
     import torch
-    from tests.test_gpu_round2 import _agent
+    from tests.gpu_util import _agent
     out = []
     for fused in (False, True):
         torch.manual_seed(5)

@@ -51,8 +51,7 @@ def test_dof_sweep_hip(model):
     """`test_motor_action_agent` (bez_isaacgym/test/test_kick_env.py:142-186) on the HIP simulator: every DOF to its lower limit, its
     upper limit and back, zero gravity, floating base; the same bars as the oracle's run (tests/test_scenarios.py)."""
     from bez_isaacgym_amd import abi
-    from tests.scenarios import dof_sweep, make_backend
-    from tests.test_scenarios import check_dof_sweep
+    from tests.scenarios import check_dof_sweep, dof_sweep, make_backend
     n = 64
     cfg = abi.default_config(n, seed=3)
     cfg.gravity[:] = [0.0, 0.0, 0.0]
@@ -128,7 +127,7 @@ torch.cuda.init(); torch.zeros(1, device="cuda:0")
 sys.path.insert(0, %r)
 import bez_isaacgym_amd
 assert not bez_isaacgym_amd.GRAPH_REPLAY_SAFE
-from tests.test_gpu_round2 import _agent
+from tests.gpu_util import _agent
 with warnings.catch_warnings(record=True) as w:
     warnings.simplefilter("always")
     a = _agent(256, 2048)
@@ -152,7 +151,7 @@ def test_external_weight_writes_reach_the_mfma_kernels():
     model's load_state_dict hook fires.  An in-place write to the fp32 master weights between epochs (p.mul_, an EMA tool, a late
     broadcast) must reach the rollout's MFMA forward too: play_steps() notices it from the parameters' version counters (host only)."""
     import torch
-    from tests.test_gpu_round2 import _agent
+    from tests.gpu_util import _agent
     a = _agent(256, 2048, hip_graphs=False)
     a.obs = a.env_reset()
     a.train_epoch()
@@ -175,7 +174,7 @@ def test_dr_hand_out_can_be_taken_back():
     import torch
     from bez_isaacgym_amd import abi
     from bez_isaacgym_amd.sim import BezSim, BezSimError
-    from tests.test_gpu_round3 import _dr_cfg
+    from tests.gpu_util import _dr_cfg
     n = 256
     a, b = BezSim(abi.default_config(n, seed=9), 0), BezSim(abi.default_config(n, seed=9), 0)
     for s in (a, b):
@@ -317,7 +316,7 @@ import bez_isaacgym_amd   # before anything initialises HIP: graph replay is onl
 os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="%d", RANK="0", WORLD_SIZE="1", BEZ_PPO_FORCE_DIST="1")
 torch.cuda.set_device(0)
 dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-from tests.test_gpu_round2 import _agent
+from tests.gpu_util import _agent
 snaps = []
 for capture in (False, True):
     torch.manual_seed(77); torch.cuda.manual_seed_all(77)
@@ -343,8 +342,7 @@ def test_fixed_base_hip_equals_oracle_and_the_torso_does_not_move(model):
     steps through the split entry points against the fp64 oracle on the same states: the torso rows stay bit-equal to their start, the joints
     agree within the usual bars; (b) the reference's form of the per-DOF sweep (gravity on, torso welded a metre up) with the oracle's bars."""
     from bez_isaacgym_amd import abi
-    from tests.scenarios import dof_sweep, make_backend
-    from tests.test_scenarios import check_fixed_base_sweep
+    from tests.scenarios import check_fixed_base_sweep, dof_sweep, make_backend
     n = 128
     mk = lambda backend: make_backend(backend, (lambda c: (setattr(c, "flags", c.flags | abi.FLAG_FIX_BASE), c)[1])(abi.default_config(n, seed=5)))
     h, o = mk("hip"), mk("oracle")
@@ -376,7 +374,7 @@ def test_pipelined_epochs_train_to_the_same_bits_and_report_the_same_numbers():
     same stream order as train_epoch() one epoch at a time -- same weights, Adam moments and normaliser bit for bit through eager, capturing and
     replayed epochs, and the same per-epoch report (KL, losses, learning rate, finished-episode sums cleared in stream order, not a report late)."""
     import torch
-    from tests.test_gpu_round2 import _agent
+    from tests.gpu_util import _agent
     n_ep = 7
     reports = {}
     states = {}

@@ -44,7 +44,7 @@ def test_abi_declares_lists_and_exports_the_call():
 
 def test_the_kernel_of_both_assets_has_no_spills_and_no_scratch(tmp_path):
     import os
-    from tests.test_body_forces_cpu import kernel_resources
+    from tests.kernel_resources import kernel_resources
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = kernel_resources(os.path.join(root, "bez_isaacgym_amd", "csrc", "bez_sim.hip"), str(tmp_path))
     mine = {k: v for k, v in res.items() if "limb_ik_kernel" in k}

@@ -3,10 +3,8 @@ task-config flag, and the PPO epoch row's nonfinite_resets."""
 import os
 import re
 
-import torch
-
 from bez_isaacgym_amd import abi
-from tests.fake_env import FakeVecEnv
+from tests.fake_env import FakeVecEnv, _GuardedFakeEnv
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = open(os.path.join(ROOT, "include", "bez_sim.h")).read()
@@ -67,24 +65,9 @@ def test_task_config_honours_nonfinite_guard_key():
     assert c.flags & abi.FLAG_IMU_PREV_ALIAS   # nothing else changes
 
 
-class _GuardedFakeEnv(FakeVecEnv):
-    """FakeVecEnv with the simulator's trip counters: `trips[k]` = {env: increments} made during the k-th step() call."""
-
-    def __init__(self, *a, trips=None, **kw):
-        super().__init__(*a, **kw)
-        self.nonfinite_buf = torch.zeros(self.n, dtype=torch.int64)
-        self.calls, self.trips = 0, trips or {}
-
-    def step(self, actions):
-        for e, k in self.trips.get(self.calls, {}).items():
-            self.nonfinite_buf[e] += k
-        self.calls += 1
-        return super().step(actions)
-
-
 def test_epoch_row_carries_nonfinite_resets():
     from bez_isaacgym_amd.ppo.a2c_continuous import A2CAgent
-    from tests.test_ppo_cpu import _params
+    from tests.fake_env import _params
     horizon = 8
     # epoch 0: none; epoch 1: env 3 twice and env 5 once (3 increments); epoch 2: env 0 once
     env = _GuardedFakeEnv(32, seed=7, trips={horizon + 2: {3: 1}, horizon + 5: {3: 1, 5: 1}, 2 * horizon: {0: 1}})
@@ -98,7 +81,7 @@ def test_epoch_row_carries_nonfinite_resets():
 
 def test_epoch_row_without_counters_reports_zero():
     from bez_isaacgym_amd.ppo.a2c_continuous import A2CAgent
-    from tests.test_ppo_cpu import _params
+    from tests.fake_env import _params
     agent = A2CAgent(_params(16, 64, horizon=4), FakeVecEnv(16, seed=2), "cpu")
     agent.obs = agent.env_reset()
     row = agent.train_epoch()

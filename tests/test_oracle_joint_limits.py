@@ -1,5 +1,5 @@
-"""Round 6 (missing 2 / next 1): the joint speed limit as a constraint inside the ABA and the leg <-> leg contact with
-an implicit joint-space part -- known answers on the CPU oracle.  The same scenarios run on the HIP simulator in tests/test_gpu_round6.py.
+"""The joint speed limit as a constraint inside the ABA and the leg <-> leg contact with an implicit joint-space part -- known answers
+on the CPU oracle.  The same scenarios run on the HIP simulator in tests/test_gpu_joint_limits.py.
 
 * `kick_env.py:327` gives every DOF a velocity limit of 2 pi rad/s; `kick_env.py:365-366` creates the robot with collision filter 0.
 * What "the reaction reaches the parent" means, exactly: the accelerations one evaluation of the dynamics returns, put into an

@@ -106,9 +106,7 @@ def test_epoch_report_layout_is_pinned_and_grows_with_mini_epochs():
         assert all((lay.view(buf, k) == i + 1).all() for i, k in enumerate(names))
         assert lay.view(buf, "loss", "kl").numel() == 2 + me
 
-    from tests.test_dof_force_cpu import _ActuatorFakeEnv
-    from tests.test_episode_stats_cpu import _CountingFakeEnv
-    from tests.test_nonfinite_guard_cpu import _GuardedFakeEnv
+    from tests.fake_env import _ActuatorFakeEnv, _CountingFakeEnv, _GuardedFakeEnv
 
     class _Actuators(_ActuatorFakeEnv, FakeVecEnv):
         pass

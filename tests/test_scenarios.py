@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from bez_isaacgym_amd import abi
-from tests.scenarios import dof_sweep, lay_down, make_backend, play
+from tests.scenarios import check_dof_sweep, check_fixed_base_sweep, dof_sweep, lay_down, make_backend, play
 
 
 def _getup(name, n=8, flags=None):
@@ -57,24 +57,6 @@ def test_all_ground_shapes_let_the_back_getup_roll_over_oracle():
     assert a["max_z"] < 0.12 and b["max_z"] > 0.20 and b["max_up"] > 0.75, (a, b)
 
 
-def check_dof_sweep(rows):
-    """Every actuated DOF reaches both limits and returns (zero gravity, floating base) -- except where the model says it cannot:
-    the head joints never receive an action (kick_env.py:414), a hip rolling INWARD meets the other leg (collision_filter 0,
-    kick_env.py:365-366: the foot plates, 8 mm apart in the default pose, touch first) 0.6 rad short of its -0.785 rad limit, and a hip
-    yawing to its lower limit swings the hip box into the other leg 0.1 rad short of -1.309.  (Round 5's 3000 N/m explicit spring let
-    the saturated drive push 2 cm into the other leg: its hip roll stopped 0.34 rad short, at the thighs.)"""
-    for r in rows:
-        assert r["finite"], r
-        if r["dof"] < 2:
-            assert r["miss_default"] < 1e-3 and r["miss_lower"] > 1.5, r       # did not move
-        elif r["name"].endswith("leg_motor_1"):
-            assert 0.5 < r["miss_lower"] < 0.72 and r["miss_upper"] < 0.05 and r["miss_default"] < 0.05, r
-        elif r["name"].endswith("leg_motor_0"):
-            assert 0.03 < r["miss_lower"] < 0.2 and r["miss_upper"] < 0.05 and r["miss_default"] < 0.05, r
-        else:
-            assert r["miss_lower"] < 0.05 and r["miss_upper"] < 0.05 and r["miss_default"] < 0.05, r
-
-
 def test_dof_sweep_oracle(model):
     n = 2
     cfg = abi.default_config(n, seed=3)
@@ -109,23 +91,6 @@ def test_separating_axis_test_of_the_pair_log():
     Rx = quat_to_mat(qx)
     d = sep([0, 0, 0], I, [1.0, 0.05, 0.05], [0, 0.0, 0.4], Rx, [0.05, 1.0, 0.05])
     assert d == pytest.approx(0.4 / np.sqrt(2.0) - 0.05 * np.sqrt(2.0) - 0.05, abs=1e-9)
-
-
-def check_fixed_base_sweep(rows, root_before, root_after):
-    """The reference's form of the sweep ("better when fixBaseLink = True", test/test_kick_env.py:142-186): gravity on, the torso welded one
-    metre above the plane.  The torso does not move by a bit; every actuated DOF reaches both limits under its limb's weight and returns,
-    with the same exceptions as the floating sweep (head joints never commanded, a hip rolling inward or yawing to its lower limit meets the other leg)."""
-    assert np.array_equal(root_before, root_after)
-    for r in rows:
-        assert r["finite"], r
-        if r["dof"] < 2:
-            assert r["miss_default"] < 1e-3 and r["miss_lower"] > 1.5, r
-        elif r["name"].endswith("leg_motor_1"):
-            assert 0.5 < r["miss_lower"] < 0.72 and r["miss_upper"] < 0.06 and r["miss_default"] < 0.06, r
-        elif r["name"].endswith("leg_motor_0"):
-            assert 0.03 < r["miss_lower"] < 0.2 and r["miss_upper"] < 0.06 and r["miss_default"] < 0.06, r
-        else:
-            assert r["miss_lower"] < 0.06 and r["miss_upper"] < 0.06 and r["miss_default"] < 0.06, r
 
 
 def test_dof_sweep_with_a_fixed_base_oracle(model):

@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+from tests.scenarios import _lie_on_back
 from tests.sim_cfg import make_cfg, oracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -103,21 +104,6 @@ def test_oracle_walk_goal_is_shared_per_reset_call_and_shard_invariant():
 # ------------------------------------------------------------------ GPU: HIP path through the C ABI
 @pytest.mark.gpu
 def test_hip_cleats_feet(TG): check_cleats_feet(hip(N, cleats=True), TG)
-
-
-def _lie_on_back(b, n, count=None):
-    """The first `count` envs (default: all): robot on its back (torso -x down), ball far away, joints at rest."""
-    m = n if count is None else count
-    rs = np.array(b.root_states, dtype=np.float32).reshape(n, b.nact, 13).copy()
-    rs[:m, 0, 0:3] = [0.0, 0.0, 0.12]
-    rs[:m, 0, 3:7] = [0.0, -np.sin(np.pi / 4), 0.0, np.cos(np.pi / 4)]   # xyzw: -90 deg about y -> torso +x points up
-    rs[:m, 0, 7:13] = 0
-    if b.nact > 1:
-        rs[:m, 1, 0:3] = [5.0, 5.0, 0.0795]; rs[:m, 1, 7:13] = 0   # resting in contact (exactly z = R would sit on the contact on/off edge)
-    b.set_root_states(rs.reshape(-1, 13))
-    ds = np.array(b.dof_state, dtype=np.float32).reshape(n, 18, 2).copy(); ds[:m, :, 1] = 0
-    b.set_dof_state(ds.reshape(-1, 2))
-    b.set_reset(np.zeros(n, np.int64)); b.set_progress(np.zeros(n, np.int64))
 
 
 def check_box_asset_rest_height(make):
