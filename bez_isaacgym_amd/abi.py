@@ -309,15 +309,23 @@ def config_from_task_cfg(cfg, seed=42, env_id_offset=0, strict_reference_quirks=
     return c
 
 
+def _enum(value, names, ids, bad_name, bad_id):
+    """The id of an enum value from the int or from its name (any case, blanks around it stripped; a bool is no int).  `names`: name -> id,
+    `ids`: the ints taken as they are.  Anything else raises ValueError: `bad_name` % the value for a string, `bad_id` % it otherwise."""
+    if isinstance(value, str):
+        key = value.strip().lower()
+        if key not in names:
+            raise ValueError(bad_name % (value,))
+        return names[key]
+    if isinstance(value, bool) or not isinstance(value, int) or value not in ids:
+        raise ValueError(bad_id % (value,))
+    return int(value)
+
+
 def _tensor_id(kind, names, which):
     """The id of a `kind` tensor from the int or from its name (any case); `names`: the names in id order."""
-    if isinstance(which, str):
-        if which.strip().lower() not in names:
-            raise ValueError("%s tensor must be one of %s, got %r" % (kind, sorted(names), which))
-        return names.index(which.strip().lower())
-    if isinstance(which, bool) or not isinstance(which, int) or not 0 <= which < len(names):
-        raise ValueError("%s tensor id must be in [0, %d), got %r" % (kind, len(names), which))
-    return int(which)
+    return _enum(which, {k: i for i, k in enumerate(names)}, range(len(names)), "%s tensor must be one of %s, got %%r" % (kind, sorted(names)),
+                 "%s tensor id must be in [0, %d), got %%r" % (kind, len(names)))
 
 
 def actuator_tensor_id(which):
@@ -330,26 +338,22 @@ def dynamics_tensor_id(which):
     return _tensor_id("dynamics", ("jacobian", "mass_matrix"), which)
 
 
+_SPACE_NAMES = {"env": SPACE_ENV, "env_space": SPACE_ENV, "local": SPACE_LOCAL, "local_space": SPACE_LOCAL}
+_AT_NAMES = {"com": 0, "origin": GF_AT_ORIGIN}
+_IK_SPACE_NAMES = {"env": IK_SPACE_ENV, "root": IK_SPACE_ROOT}
+
+
 def body_force_space(space):
     """SPACE_ENV / SPACE_LOCAL from the int or from "env" / "local" (any case); anything else raises ValueError."""
-    if isinstance(space, str):
-        key = space.strip().lower()
-        if key in ("env", "env_space"):
-            return SPACE_ENV
-        if key in ("local", "local_space"):
-            return SPACE_LOCAL
-        raise ValueError("space must be 'env' or 'local', got %r" % space)
-    if isinstance(space, bool) or not isinstance(space, int) or space not in (SPACE_ENV, SPACE_LOCAL):
-        raise ValueError("space must be SPACE_ENV (0) or SPACE_LOCAL (1), got %r" % (space,))
-    return int(space)
+    return _enum(space, _SPACE_NAMES, (SPACE_ENV, SPACE_LOCAL), "space must be 'env' or 'local', got %r",
+                 "space must be SPACE_ENV (0) or SPACE_LOCAL (1), got %r")
 
 
 def generalized_force_space(space, at="com"):
     """the `space` word of bez_sim_generalized_forces: body_force_space(space), with GF_AT_ORIGIN OR-ed in for at="origin" (at="com",
     the default point of application of apply_body_forces, adds nothing); any other `at` raises ValueError."""
-    if not isinstance(at, str) or at.strip().lower() not in ("com", "origin"):
-        raise ValueError("at must be 'com' or 'origin', got %r" % (at,))
-    return body_force_space(space) | (GF_AT_ORIGIN if at.strip().lower() == "origin" else 0)
+    at = _enum(at, _AT_NAMES, (), "at must be 'com' or 'origin', got %r", "at must be 'com' or 'origin', got %r")   # a name only
+    return body_force_space(space) | at
 
 
 class BezIkParams(C.Structure):
@@ -366,14 +370,26 @@ class BezIkParams(C.Structure):
 
 def ik_space(space):
     """IK_SPACE_ENV / IK_SPACE_ROOT from the int or from "env" / "root" (any case); anything else raises ValueError."""
-    if isinstance(space, str):
-        key = space.strip().lower()
-        if key in ("env", "root"):
-            return IK_SPACE_ENV if key == "env" else IK_SPACE_ROOT
-        raise ValueError("space must be 'env' or 'root', got %r" % space)
-    if isinstance(space, bool) or not isinstance(space, int) or space not in (IK_SPACE_ENV, IK_SPACE_ROOT):
-        raise ValueError("space must be IK_SPACE_ENV (0) or IK_SPACE_ROOT (1), got %r" % (space,))
-    return int(space)
+    return _enum(space, _IK_SPACE_NAMES, (IK_SPACE_ENV, IK_SPACE_ROOT), "space must be 'env' or 'root', got %r",
+                 "space must be IK_SPACE_ENV (0) or IK_SPACE_ROOT (1), got %r")
+
+
+def _read_offsets(offsets, dst):
+    """`offsets`, (IK_CHAINS, 3) and finite, into the `offset` field `dst` of a parameter struct; None leaves it zero"""
+    if offsets is None:
+        return
+    try:
+        rows = [list(r) for r in offsets]
+    except TypeError:
+        rows = None
+    if rows is None or len(rows) != IK_CHAINS or any(len(r) != 3 for r in rows):
+        raise ValueError("offsets must be (%d, 3) or None" % IK_CHAINS)
+    for c, r in enumerate(rows):
+        for k, o in enumerate(r):
+            o = float(o)
+            if not math.isfinite(o):
+                raise ValueError("offsets[%d][%d] must be finite, got %r" % (c, k, o))
+            dst[c][k] = o
 
 
 def ik_params(weights, offsets=None, damping=0.05, max_step=0.0, iters=1, space=IK_SPACE_ENV):
@@ -392,16 +408,7 @@ def ik_params(weights, offsets=None, damping=0.05, max_step=0.0, iters=1, space=
             if not math.isfinite(w) or w < 0.0:
                 raise ValueError("weights[%d][%d] must be finite and >= 0, got %r" % (c, k, w))
             p.weight[c][k] = w
-    if offsets is not None:
-        rows = [list(r) for r in offsets]
-        if len(rows) != IK_CHAINS or any(len(r) != 3 for r in rows):
-            raise ValueError("offsets must be (%d, 3) or None" % IK_CHAINS)
-        for c, r in enumerate(rows):
-            for k, o in enumerate(r):
-                o = float(o)
-                if not math.isfinite(o):
-                    raise ValueError("offsets[%d][%d] must be finite, got %r" % (c, k, o))
-                p.offset[c][k] = o
+    _read_offsets(offsets, p.offset)
     damping, max_step = float(damping), float(max_step)
     if not math.isfinite(damping) or damping <= 0.0:
         raise ValueError("damping must be a positive finite number, got %r" % damping)
@@ -430,19 +437,7 @@ def op_space_params(offsets=None, fixed_base=False):
     (IK_CHAINS, 3), finite, or None for zero: the controlled frame of chain c is its end body (IK_END_BODIES) displaced by offsets[c] in that
     body's axes.  fixed_base: hold the root (FD_FIXED_BASE)."""
     p = BezOpSpaceParams()
-    if offsets is not None:
-        try:
-            rows = [list(r) for r in offsets]
-        except TypeError:
-            rows = None
-        if rows is None or len(rows) != IK_CHAINS or any(len(r) != 3 for r in rows):
-            raise ValueError("offsets must be (%d, 3) or None" % IK_CHAINS)
-        for c, r in enumerate(rows):
-            for k, o in enumerate(r):
-                o = float(o)
-                if not math.isfinite(o):
-                    raise ValueError("offsets[%d][%d] must be finite, got %r" % (c, k, o))
-                p.offset[c][k] = o
+    _read_offsets(offsets, p.offset)
     if not isinstance(fixed_base, (bool, int)):
         raise ValueError("fixed_base must be True or False, got %r" % (fixed_base,))
     p.mode = FD_FIXED_BASE if fixed_base else 0

@@ -17,13 +17,15 @@ class BezSimError(RuntimeError):
 
 
 vp, i32, i64, u32, u64, fp = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_void_p
+# a getter of a sim-owned buffer: sim, which -> pointer, shape, rank, dtype (the episode getter's line stays spelled out: a test reads it)
+_GETTER = [vp, C.c_int, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(C.c_int)]
 # (restype, argtypes) of every bez_sim_* entry point of include/bez_sim.h (the bez_ppo_* ones of the same library: ppo/fused.py)
 SIGS = {
     "bez_sim_default_config": (C.c_int, [C.POINTER(abi.BezSimConfig), i32]),
     "bez_sim_create": (C.c_int, [C.POINTER(abi.BezSimConfig), C.c_int, C.POINTER(vp)]),
     "bez_sim_destroy": (C.c_int, [vp]),
     "bez_sim_last_error": (C.c_char_p, [vp]),
-    "bez_sim_get_tensor": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bez_sim_get_tensor": (C.c_int, _GETTER),
     "bez_sim_refresh_tensor": (C.c_int, [vp, C.c_int, vp]),
     "bez_sim_get_episode_tensor": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bez_sim_set_actor_root_state_tensor_indexed": (C.c_int, [vp, fp, vp, i32, vp]),
@@ -55,9 +57,9 @@ SIGS = {
     "bez_sim_calibrate": (C.c_int, [vp, u64, i32, vp]),
     "bez_sim_time_steps": (C.c_int, [vp, fp, i32, vp, C.POINTER(C.c_float)]),
     "bez_sim_apply_body_forces": (C.c_int, [vp, fp, fp, fp, i32, vp]),
-    "bez_sim_get_actuator_tensor": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bez_sim_get_actuator_tensor": (C.c_int, _GETTER),
     "bez_sim_refresh_actuator_tensors": (C.c_int, [vp, vp]),
-    "bez_sim_get_dynamics_tensor": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bez_sim_get_dynamics_tensor": (C.c_int, _GETTER),
     "bez_sim_refresh_dynamics_tensors": (C.c_int, [vp, u32, vp]),
     "bez_sim_inverse_dynamics": (C.c_int, [vp, fp, u32, fp, vp]),
     "bez_sim_forward_dynamics": (C.c_int, [vp, fp, u32, u32, fp, vp]),
@@ -159,12 +161,56 @@ class BezSim:
             raise BezSimError("%s: expected shape %s, got %s" % (name, " or ".join(str(s) for s in shapes), tuple(t.shape)))
         return t
 
-    def _scratch(self, key, shape):
-        """the sim's own float32 result buffer `key`: allocated by the first call that needs it, overwritten by every later one"""
+    # the query calls resolve their tensors in two steps, every method in the same order: first _in / _out / _wanted for each argument
+    # (is it a tensor, has it an accepted shape -- the shape fixes the element count --, which buffer takes a result), then, when
+    # every other argument is checked too, _f32 for each pointer (dtype, layout, device)
+    def _in(self, name, t, *shapes):
+        """an optional input: None, or t once it is _checked against the shapes it may have"""
+        return None if t is None else self._checked(name, t, shapes)
+
+    def _out(self, name, t, key, shape):
+        """an output: the caller's tensor once it is _checked against `shape`; None: the sim's own float32 result buffer `key` of that
+        shape, allocated by the first call that needs it, overwritten by every later one"""
+        if t is not None:
+            return self._checked(name, t, (shape,))
         bufs = self.__dict__.setdefault("_buffers", {})
         if key not in bufs:
             bufs[key] = torch.zeros(shape, device=self.device, dtype=torch.float32)
         return bufs[key]
+
+    def _f32(self, t):
+        """what the library is handed for a resolved tensor: NULL for None, else the pointer of a contiguous float32 tensor on the device"""
+        return None if t is None else self._ptr(t, torch.float32)
+
+    def _wanted(self, method, shapes, given, want, prefix, refused=None):
+        """The outputs of a call that computes a chosen subset of them.  `shapes`: output name -> shape, in the library's order;
+        `given`: (keyword, tensor or None) per output in that order, a given tensor is wanted and written; `want`: the names (or one
+        name) to compute into the scratch buffers `prefix` + name; `refused`: None or (name, why) of an output this call must not want.
+        Returns ({name: tensor or None}, [pointer or NULL per output])."""
+        if isinstance(want, str):
+            want = (want,)
+        for k in want:
+            if k not in shapes:
+                raise BezSimError("%s: want holds %r, expected a subset of %s" % (method, k, tuple(shapes)))
+        out = {name: (name in want or None) if t is None else self._checked(keyword, t, (shapes[name],)) for name, (keyword, t) in zip(shapes, given)}
+        if all(t is None for t in out.values()):
+            raise BezSimError("%s: nothing is wanted (want is empty and no output tensor is given)" % method)
+        if refused is not None and out[refused[0]] is not None:
+            raise BezSimError("%s: %s" % (method, refused[1]))
+        ptrs = []
+        for name, t in out.items():
+            if t is True:
+                t = out[name] = self._out(name, None, prefix + name, shapes[name])
+            ptrs.append(self._f32(t))
+        return out, ptrs
+
+    def _body_vectors(self, forces, torques, positions):
+        """the pointers (NULL for None) of the three per-body vector tensors of apply_body_forces and generalized_forces, each float32 on
+        the sim's device, contiguous, (N*B, 3) or (N, B, 3)"""
+        n, nb = self.num_envs, self.num_bodies
+        shapes = ((n * nb, 3), (n, nb, 3))
+        return [None if t is None else self._ptr(self._checked(name, t, shapes), torch.float32)
+                for name, t in (("forces", forces), ("torques", torques), ("positions", positions))]
 
     def _describe(self, getter, which):
         """(device pointer, shape, typestr) of a sim-owned buffer"""
@@ -242,14 +288,8 @@ class BezSim:
         `out`: the same kind of tensor to write into; None: one buffer per sim, allocated by the first such call and overwritten by
         every later one.  One launch on the current stream."""
         shape = (self.num_envs, abi.NUM_GEN)
-        for name, t in (("udot", udot), ("out", out)):
-            if t is not None:
-                self._checked(name, t, (shape,))
-        if out is None:
-            out = self._scratch("inverse_dynamics", shape)
-        n = shape[0] * shape[1]
-        self._check(self.lib.bez_sim_inverse_dynamics(self.h, None if udot is None else self._ptr(udot, torch.float32, n), int(terms),
-                                                      self._ptr(out, torch.float32, n), self._stream()))
+        udot, out = self._in("udot", udot, shape), self._out("out", out, "inverse_dynamics", shape)
+        self._check(self.lib.bez_sim_inverse_dynamics(self.h, self._f32(udot), int(terms), self._f32(out), self._stream()))
         return out
 
     # ---- forward dynamics: udot = M(q)^-1 (f - h(q, u)) of the current state without forming M
@@ -262,19 +302,14 @@ class BezSim:
         such call and overwritten by every later one.  One launch on the current stream; everything is checked before the library is
         called."""
         shape = (self.num_envs, abi.NUM_GEN)
-        for name, t in (("force", force), ("out", out)):
-            if t is not None:
-                self._checked(name, t, (shape,))
+        force, out = self._in("force", force, shape), self._out("out", out, "forward_dynamics", shape)
         bias = int(bias)
         if bias & ~(abi.ID_VELOCITY | abi.ID_GRAVITY):
             raise BezSimError("forward_dynamics: bias must be a subset of abi.ID_VELOCITY | abi.ID_GRAVITY, got %d" % bias)
         if bias == 0 and force is None:
             raise BezSimError("forward_dynamics: bias is 0 and force is None (nothing to solve for)")
-        if out is None:
-            out = self._scratch("forward_dynamics", shape)
-        n = shape[0] * shape[1]
-        self._check(self.lib.bez_sim_forward_dynamics(self.h, None if force is None else self._ptr(force, torch.float32, n), bias,
-                                                      abi.FD_FIXED_BASE if fixed_base else 0, self._ptr(out, torch.float32, n), self._stream()))
+        self._check(self.lib.bez_sim_forward_dynamics(self.h, self._f32(force), bias, abi.FD_FIXED_BASE if fixed_base else 0, self._f32(out),
+                                                      self._stream()))
         return out
 
     # ---- operational space: end-frame Jacobians, J M^-1, the Delassus matrix J M^-1 J^T and the operational-space inertias
@@ -295,27 +330,9 @@ class BezSim:
             params = abi.op_space_params(offsets, fixed_base)
         except ValueError as e:
             raise BezSimError("operational_space: %s" % e)
-        if isinstance(want, str):
-            want = (want,)
-        for k in want:
-            if k not in shapes:
-                raise BezSimError("operational_space: want holds %r, expected a subset of %s" % (k, tuple(shapes)))
-        out = {}
-        for name, t in (("jac", jac), ("jminv", jminv), ("w", w), ("lambda", lam)):
-            if t is not None:
-                out[name] = self._checked("lam" if name == "lambda" else name, t, (shapes[name],))
-            else:
-                out[name] = name in want or None
-        if all(t is None for t in out.values()):
-            raise BezSimError("operational_space: nothing is wanted (want is empty and no output tensor is given)")
-        if fixed_base and out["lambda"] is not None:
-            raise BezSimError("operational_space: 'lambda' with fixed_base (W_cc of a held root is singular by structure)")
-        ptrs = []
-        for name in ("jac", "jminv", "w", "lambda"):
-            if out[name] is True:
-                out[name] = self._scratch("operational_space_" + name, shapes[name])
-            ptrs.append(None if out[name] is None else self._ptr(out[name], torch.float32, torch.Size(shapes[name]).numel()))
-        self._check(self.lib.bez_sim_operational_space(self.h, C.byref(params), ptrs[0], ptrs[1], ptrs[2], ptrs[3], self._stream()))
+        held = ("lambda", "'lambda' with fixed_base (W_cc of a held root is singular by structure)") if fixed_base else None
+        out, ptrs = self._wanted("operational_space", shapes, (("jac", jac), ("jminv", jminv), ("w", w), ("lam", lam)), want, "operational_space_", held)
+        self._check(self.lib.bez_sim_operational_space(self.h, C.byref(params), *ptrs, self._stream()))
         return out["jac"], out["jminv"], out["w"], out["lambda"]
 
     # ---- centroidal dynamics: centre of mass, momentum about it, the momentum matrix A_G, mechanical energy
@@ -326,16 +343,10 @@ class BezSim:
         written only when a `matrix` tensor is given or want_matrix is set, and is None in the result otherwise.  `state`, `matrix`:
         contiguous float32 tensors on the sim's device to write into; None: one buffer of each kind per sim, allocated by the first
         call that needs it and overwritten by every later one."""
-        shapes = {"state": (self.num_envs, abi.CM_WORDS), "matrix": (self.num_envs, 6, abi.NUM_GEN)}
-        for name, t in (("state", state), ("matrix", matrix)):
-            if t is not None:
-                self._checked(name, t, (shapes[name],))
-        if state is None:
-            state = self._scratch("centroidal_state", shapes["state"])
-        if matrix is None and want_matrix:
-            matrix = self._scratch("centroidal_matrix", shapes["matrix"])
-        self._check(self.lib.bez_sim_centroidal(self.h, self._ptr(state, torch.float32, state.numel()),
-                                                None if matrix is None else self._ptr(matrix, torch.float32, matrix.numel()), self._stream()))
+        state = self._out("state", state, "centroidal_state", (self.num_envs, abi.CM_WORDS))
+        if matrix is not None or want_matrix:
+            matrix = self._out("matrix", matrix, "centroidal_matrix", (self.num_envs, 6, abi.NUM_GEN))
+        self._check(self.lib.bez_sim_centroidal(self.h, self._f32(state), self._f32(matrix), self._stream()))
         return state, matrix
 
     # ---- body accelerations: J udot + Jdot u of every rigid body of the robot, and what an accelerometer on it reads
@@ -349,14 +360,8 @@ class BezSim:
         overwritten by every later one.  One launch on the current stream."""
         space = abi.body_force_space(space)
         n, nb = self.num_envs, self.num_bodies - (1 if self.has_ball else 0)
-        if udot is not None:
-            self._checked("udot", udot, ((n, abi.NUM_GEN),))
-        if out is None:
-            out = self._scratch("body_accelerations", (n, nb, 6))
-        else:
-            self._checked("out", out, ((n, nb, 6),))
-        self._check(self.lib.bez_sim_body_accelerations(self.h, None if udot is None else self._ptr(udot, torch.float32, n * abi.NUM_GEN), int(terms),
-                                                        space, self._ptr(out, torch.float32, n * nb * 6), self._stream()))
+        udot, out = self._in("udot", udot, (n, abi.NUM_GEN)), self._out("out", out, "body_accelerations", (n, nb, 6))
+        self._check(self.lib.bez_sim_body_accelerations(self.h, self._f32(udot), int(terms), space, self._f32(out), self._stream()))
         return out
 
     # ---- generalised forces: sum over bodies of J_b^T [f; t], the map from wrenches on rigid bodies to forces on u
@@ -370,19 +375,13 @@ class BezSim:
         tensor of the result's kind to write into; None: one buffer per sim, allocated by the first such call and overwritten by every
         later one.  One launch on the current stream; everything is checked before the library is called."""
         space = abi.generalized_force_space(space, at)
-        n, nb = self.num_envs, self.num_bodies
         if forces is None and torques is None:
             raise BezSimError("generalized_forces: forces and torques are both None (nothing to map)")
         if positions is not None and space & abi.GF_AT_ORIGIN:
             raise BezSimError("generalized_forces: at='origin' is the point of application when positions is None")
-        ptrs = [None if t is None else self._ptr(self._checked(name, t, ((n * nb, 3), (n, nb, 3))), torch.float32, n * nb * 3)
-                for name, t in (("forces", forces), ("torques", torques), ("positions", positions))]
-        if out is None:
-            out = self._scratch("generalized_forces", (n, abi.NUM_GEN))
-        else:
-            self._checked("out", out, ((n, abi.NUM_GEN),))
-        self._check(self.lib.bez_sim_generalized_forces(self.h, ptrs[0], ptrs[1], ptrs[2], space, self._ptr(out, torch.float32, n * abi.NUM_GEN),
-                                                        self._stream()))
+        ptrs = self._body_vectors(forces, torques, positions)
+        out = self._out("out", out, "generalized_forces", (self.num_envs, abi.NUM_GEN))
+        self._check(self.lib.bez_sim_generalized_forces(self.h, *ptrs, space, self._f32(out), self._stream()))
         return out
 
     # ---- limb inverse kinematics: damped least squares on each of the five chains off the torso
@@ -403,17 +402,8 @@ class BezSim:
             raise BezSimError("limb_ik: %s" % e)
         n = self.num_envs
         self._checked("targets", targets, ((n, abi.IK_CHAINS, 7), (n * abi.IK_CHAINS, 7)))
-        if out is None:
-            out = self._scratch("limb_ik_q", (n, abi.NUM_DOFS))
-        else:
-            self._checked("out", out, ((n, abi.NUM_DOFS),))
-        if err_out is None:
-            err_out = self._scratch("limb_ik_err", (n, abi.IK_CHAINS, 6))
-        else:
-            self._checked("err_out", err_out, ((n, abi.IK_CHAINS, 6),))
-        self._check(self.lib.bez_sim_limb_ik(self.h, self._ptr(targets, torch.float32, n * abi.IK_CHAINS * 7), C.byref(params),
-                                             self._ptr(out, torch.float32, n * abi.NUM_DOFS),
-                                             self._ptr(err_out, torch.float32, n * abi.IK_CHAINS * 6), self._stream()))
+        out, err_out = self._out("out", out, "limb_ik_q", (n, abi.NUM_DOFS)), self._out("err_out", err_out, "limb_ik_err", (n, abi.IK_CHAINS, 6))
+        self._check(self.lib.bez_sim_limb_ik(self.h, self._f32(targets), C.byref(params), self._f32(out), self._f32(err_out), self._stream()))
         return out, err_out
 
     # ---- proximity: the contact geometry of the step -- ground points, ball against boxes, leg against leg -- as distances
@@ -429,21 +419,8 @@ class BezSim:
         that needs it and overwritten by every later one."""
         n = self.num_envs
         shapes = {"ground": (n, abi.PROX_GROUND_ROWS, 3), "ball": (n, abi.PROX_BOXES, abi.PROX_WORDS), "pairs": (n, abi.PROX_PAIRS, abi.PROX_WORDS)}
-        if isinstance(want, str):
-            want = (want,)
-        for w in want:
-            if w not in shapes:
-                raise BezSimError("proximity: want holds %r, expected a subset of %s" % (w, tuple(shapes)))
-        out = {}
-        for name, t in (("ground", ground), ("ball", ball), ("pairs", pairs)):
-            if t is not None:
-                out[name] = self._checked(name, t, (shapes[name],))
-            else:
-                out[name] = self._scratch("proximity_" + name, shapes[name]) if name in want else None
-        if all(t is None for t in out.values()):
-            raise BezSimError("proximity: nothing is wanted (want is empty and no output tensor is given)")
-        ptrs = [None if out[k] is None else self._ptr(out[k], torch.float32, torch.Size(shapes[k]).numel()) for k in ("ground", "ball", "pairs")]
-        self._check(self.lib.bez_sim_proximity(self.h, ptrs[0], ptrs[1], ptrs[2], self._stream()))
+        out, ptrs = self._wanted("proximity", shapes, (("ground", ground), ("ball", ball), ("pairs", pairs)), want, "proximity_")
+        self._check(self.lib.bez_sim_proximity(self.h, *ptrs, self._stream()))
         return out["ground"], out["ball"], out["pairs"]
 
     def refresh(self, which):
@@ -489,10 +466,7 @@ class BezSim:
         Each tensor: float32 on the sim's device, contiguous, (N*B, 3) or (N, B, 3) in RIGID_BODY_STATE order, or None.  `space`:
         abi.SPACE_ENV / abi.SPACE_LOCAL or "env" / "local".  Everything is checked before the library is called."""
         space = abi.body_force_space(space)
-        n, nb = self.num_envs, self.num_bodies
-        ptrs = [None if t is None else self._ptr(self._checked(name, t, ((n * nb, 3), (n, nb, 3))), torch.float32, n * nb * 3)
-                for name, t in (("forces", forces), ("torques", torques), ("positions", positions))]
-        self._check(self.lib.bez_sim_apply_body_forces(self.h, ptrs[0], ptrs[1], ptrs[2], space, self._stream()))
+        self._check(self.lib.bez_sim_apply_body_forces(self.h, *self._body_vectors(forces, torques, positions), space, self._stream()))
 
     # ---- the non-finite guard (abi.FLAG_NONFINITE_GUARD)
     def health(self, clear=False):

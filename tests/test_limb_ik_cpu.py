@@ -136,7 +136,7 @@ def test_ik_params_rejects_each_bad_argument():
     nan_w = [list(r) for r in W_ALL]; nan_w[0][0] = math.nan
     inf_o = [[0.0, 0.0, 0.0] for _ in range(5)]; inf_o[3][1] = math.inf
     for kw in (dict(weights=W_ALL[:4]), dict(weights=None), dict(weights=bad_w), dict(weights=nan_w), dict(weights=W_ALL, offsets=inf_o),
-               dict(weights=W_ALL, offsets=[[0.0, 0.0]] * 5), dict(weights=W_ALL, damping=0.0), dict(weights=W_ALL, damping=-0.1),
+               dict(weights=W_ALL, offsets=[[0.0, 0.0]] * 5), dict(weights=W_ALL, offsets=3), dict(weights=W_ALL, damping=0.0), dict(weights=W_ALL, damping=-0.1),
                dict(weights=W_ALL, damping=math.inf), dict(weights=W_ALL, damping=math.nan), dict(weights=W_ALL, max_step=math.nan),
                dict(weights=W_ALL, iters=-1), dict(weights=W_ALL, iters=abi.IK_MAX_ITERS + 1), dict(weights=W_ALL, iters=1.5),
                dict(weights=W_ALL, iters=True), dict(weights=W_ALL, iters=np.float64(2.0)), dict(weights=W_ALL, iters=np.int64(65)),
