@@ -263,6 +263,12 @@ enum { BEZ_JD_WORD, BEZ_JD_M_TAU, BEZ_JD_M_VEL, BEZ_JD_M_LO, BEZ_JD_M_HI, BEZ_JD
 #define BEZ_JD_MAXSUB 8
 #define BEZ_JD_BELOW_LO 16
 #define BEZ_JD_ABOVE_HI 32
+/* One pending external wrench (bez_oracle_apply_body_forces): force and torque in world axes, acting at the point p
+ * of the frame of `link` (NL: the ball, its own frame about its centre).  Kept entry by entry -- never folded into a moment matrix. */
+typedef struct { int link; real p[3], F[3], T[3]; real arm0[3]; /* planted slips only: the world moment arm of the first substep */ } ExtEntry;
+/* planted errors of tests/body_wrench_ref.py (ORACLE ONLY, bez_oracle_set_ext_slip): 0 = none */
+enum { EXT_SLIP_NONE, EXT_SLIP_POINT_2MM, EXT_SLIP_FRAME_FROZEN, EXT_SLIP_LOCAL_AS_ENV, EXT_SLIP_OFFSET_DROPPED, EXT_SLIP_BALL_POINT_FIXED,
+       EXT_SLIP_ACTS_TWICE, EXT_SLIP_PREDICTOR_BLIND };
 typedef struct {
   real root_pos[3], root_quat[4], root_lin[3], root_ang[3];
   real q[ND], qd[ND];
@@ -284,6 +290,8 @@ typedef struct {
    * means over its substeps of the drive torque and the net joint force as include/bez_sim.h "Actuator tensors" defines them */
   int jd_n; real jd[BEZ_JD_MAXSUB][ND][BEZ_JD_COLS];
   real act_drive[ND], act_net[ND];
+  /* external wrenches pending for the next env_simulate, which drops them behind its last substep */
+  int ext_n, ext_cap, ext_first, ext_slip; ExtEntry* ext;
 } Env;
 
 typedef struct {
@@ -485,6 +493,21 @@ static void ankle_stop(const BezSimConfig* c, const Env* e, real h, const Kin* k
   }
 }
 
+/* A pending external wrench about the frame's reference point (links: the torso origin O; the ball: its centre), world axes, with the
+ * frame (E, r) of this substep: the force stays fixed in world axes, its point of application r + E p moves with the body. */
+static V3 v3of(const real a[3]) { return v3(a[0], a[1], a[2]); }
+static SV ext_wrench_of(const Env* e, const ExtEntry* x, const M3* E, V3 r) {
+  const int frozen = !e->ext_first && (x->link < NL ? e->ext_slip == EXT_SLIP_FRAME_FROZEN : e->ext_slip == EXT_SLIP_BALL_POINT_FIXED);
+  const V3 arm = frozen ? v3of(x->arm0) : v3add(r, m3mulv(E, v3of(x->p)));
+  return sv(v3add(v3of(x->T), v3cross(arm, v3of(x->F))), v3of(x->F));
+}
+/* the sum over the entries of link l, taken entry by entry */
+static SV ext_link_wrench(const Env* e, const Kin* k, int l) {
+  SV W; memset(&W, 0, sizeof(W));
+  for (int i = 0; i < e->ext_n; ++i) if (e->ext[i].link == l) W = sv_add(W, ext_wrench_of(e, &e->ext[i], &k->E[l], k->r[l]));
+  return W;
+}
+
 /* pass 1 of the ABA: kinematics, link velocities, bias accelerations, rigid-body inertias and bias forces (gravity included) */
 typedef struct { Kin k; SV V[NL], S[NL], cb[NL], pA[NL]; M6 IA[NL]; } Pass1;
 static void aba_pass1(const BezSimConfig* c, const Env* e, Pass1* P) {
@@ -518,6 +541,8 @@ static void aba_pass1(const BezSimConfig* c, const Env* e, Pass1* P) {
     pA[l] = crf(V[l], hmom);
     SV fg = wrench_at(cw, v3scale(g, m));
     pA[l] = sv_add(pA[l], sv_scale(fg, -1));
+    /* external wrenches: bias forces like gravity, so that everything downstream of pA sees them */
+    if (e->ext_n && e->ext_slip != EXT_SLIP_PREDICTOR_BLIND) pA[l] = sv_add(pA[l], sv_scale(ext_link_wrench(e, k, l), -1));
   }
 }
 
@@ -537,6 +562,9 @@ static void dynamics_x(const BezSimConfig* c, const Env* e, real h, int mode, co
   SV Wself[NL]; real cfs[NBMAX][3]; /* the same as wrenches ON the links, and the contact-force rows they report: both scaled by self_contact_scale */
   M6* IA = P1.IA;
   memset(pS, 0, sizeof(pS)); memset(Wself, 0, sizeof(Wself)); memset(cfs, 0, sizeof(cfs));
+  SV pX[NL]; real wX[NL]; /* planted slip EXT_SLIP_PREDICTOR_BLIND only: the external wrenches propagated next to pA like pS, unseen by the predictors */
+  memset(pX, 0, sizeof(pX)); memset(wX, 0, sizeof(wX));
+  if (mode == 0 && e->ext_n && e->ext_slip == EXT_SLIP_PREDICTOR_BLIND) for (int l = 0; l < NL; ++l) pX[l] = sv_scale(ext_link_wrench(e, &k, l), -1);
   memset(out->contact_force, 0, sizeof(out->contact_force));
   out->vmargin = (real)1e9;
   memset(out->jd, 0, sizeof(out->jd)); memset(out->act_drive, 0, sizeof(out->act_drive)); memset(out->act_net, 0, sizeof(out->act_net));
@@ -733,20 +761,22 @@ static void dynamics_x(const BezSimConfig* c, const Env* e, real h, int mode, co
     if (lock) { gj[l] = 0; wj[l] = qdd_fix; qdd_hp[l] = qdd_fix; }
     else { gj[l] = 1 / D; wj[l] = u_main * gj[l]; qdd_hp[l] = (u_main - Ucb) * gj[l]; }
     wS[l] = du * gj[l];
+    wX[l] = -sv_dot(S[l], pX[l]) * gj[l];
     M6 Ia = IA[l];
     for (int i = 0; i < 6; ++i) for (int j = 0; j < 6; ++j) Ia.m[i][j] -= U[l].v[i] * U[l].v[j] * gj[l];
     SV pa = sv_add(pA[l], sv_add(m6mulv(&Ia, cb[l]), sv_scale(U[l], wj[l])));
     for (int i = 0; i < 6; ++i) for (int j = 0; j < 6; ++j) IA[p].m[i][j] += Ia.m[i][j];
     pA[p] = sv_add(pA[p], pa);
     pS[p] = sv_add(pS[p], sv_add(pS[l], sv_scale(U[l], wS[l])));
+    pX[p] = sv_add(pX[p], sv_add(pX[l], sv_scale(U[l], wX[l])));
   }
   /* the leg<->leg forces' common scale, then their (linear) share of the joint accelerations and of the torso's bias */
   const real sc = mode == 0 ? self_contact_scale(c, h, S, Wself, F2self, gj, qdd_hp) : 0;
-  for (int l = 1; l < NL; ++l) wj[l] += sc * wS[l];
+  for (int l = 1; l < NL; ++l) wj[l] += sc * wS[l] + wX[l];
   for (int b = 0; b < NBMAX; ++b) for (int i = 0; i < 3; ++i) out->contact_force[b][i] += sc * cfs[b][i];
   /* root */
   M6 I0 = IA[0];
-  SV a0 = sv_scale(sv_add(pA[0], sv_scale(pS[0], sc)), -1);
+  SV a0 = sv_scale(sv_add(sv_add(pA[0], pX[0]), sv_scale(pS[0], sc)), -1);
   chol6_solve(&I0, &a0, 1);
   if (c->flags & BEZ_FLAG_FIX_BASE) memset(&a0, 0, sizeof(a0)); /* urdfAsset.fixBaseLink (kick_env.py:287): the torso is welded to the world */
   out->a0 = a0;
@@ -811,6 +841,10 @@ static void dynamics_x(const BezSimConfig* c, const Env* e, real h, int mode, co
     }
     /* ball: Mb ab = -pb - Jb^T fl */
     SV rhs = sv_add(sv_scale(pb, -1), sv_scale(wrench_at(bl_xb, fl), -1));
+    if (e->ext_n) { /* the ball's external wrench about its centre joins its free-body solve here: the ball <-> robot contact operands above (gb) do not see it */
+      const M3 Eb = quat_to_mat(e->ball_quat);
+      for (int i = 0; i < e->ext_n; ++i) if (e->ext[i].link == NL) rhs = sv_add(rhs, ext_wrench_of(e, &e->ext[i], &Eb, v3(0, 0, 0)));
+    }
     M6 Mc = Mb;
     chol6_solve(&Mc, &rhs, 1);
     out->ball_ang_acc = sv_ang(rhs); out->ball_lin_acc = sv_lin(rhs);
@@ -1481,10 +1515,21 @@ static void env_post_physics(const BezSimConfig* c, Env* e, int64_t genv, int us
 static void env_simulate(const BezSimConfig* c, Env* e) {
   real h = (real)c->dt / (real)c->substeps;
   const int last_only = (c->flags & BEZ_FLAG_CF_LAST_SUBSTEP) != 0;
+  if (e->ext_n && (e->ext_slip == EXT_SLIP_FRAME_FROZEN || e->ext_slip == EXT_SLIP_BALL_POINT_FIXED)) { /* planted slips: the moment arms of the first substep */
+    Kin k; forward_kinematics(c, e, &k);
+    const M3 Eb = quat_to_mat(e->ball_quat);
+    for (int i = 0; i < e->ext_n; ++i) {
+      ExtEntry* x = &e->ext[i];
+      const V3 arm = x->link < NL ? v3add(k.r[x->link], m3mulv(&k.E[x->link], v3of(x->p))) : m3mulv(&Eb, v3of(x->p));
+      for (int a = 0; a < 3; ++a) x->arm0[a] = arm.v[a];
+    }
+  }
   for (int s = 0; s < c->substeps; ++s) {
+    e->ext_first = s == 0;
     if (last_only) substep(c, e, h, 1, 1);
     else substep(c, e, h, s == 0, (real)1 / (real)c->substeps);
   }
+  if (e->ext_slip != EXT_SLIP_ACTS_TWICE) e->ext_n = 0; /* one launch: the wrenches acted through every substep and are dropped */
 }
 
 /* ------------------------------------------------------------------ domain randomisation (vec_task.py:505-725)
@@ -1596,7 +1641,7 @@ void* bez_oracle_create(const BezSimConfig* cfg) {
   }
   return o;
 }
-void bez_oracle_destroy(void* h) { Oracle* o = (Oracle*)h; free(o->env); free(o); }
+void bez_oracle_destroy(void* h) { Oracle* o = (Oracle*)h; for (int i = 0; i < o->n; ++i) free(o->env[i].ext); free(o->env); free(o); }
 int bez_oracle_real_size(void) { return (int)sizeof(real); }
 
 void bez_oracle_get_root_states(void* h, float* out) {
@@ -1725,6 +1770,79 @@ void bez_oracle_get_rigid_body_states(void* h, float* out) {
     for (int a = 0; a < 3; ++a) { r[a] = (float)e->ball_pos[a]; r[7 + a] = (float)e->ball_lin[a]; r[10 + a] = (float)e->ball_ang[a]; }
     for (int a = 0; a < 4; ++a) r[3 + a] = (float)e->ball_quat[a];
   }
+}
+
+/* bez_sim_apply_body_forces restated from DESIGN.md 4.3c: external forces / torques on the rigid bodies for the NEXT env_simulate.
+ * forces / torques / positions: doubles (n * rows, 3) in RIGID_BODY_STATE order (the fp32 values the simulator is given, widened; a
+ * test may hand over more digits), any of them NULL.  Everything is resolved here, against
+ * the state the oracle holds now: a LOCAL vector is rotated into world axes by the body's frame (a fixed body has its link's), the
+ * point of application -- default: the body's own centre of mass, BEZ_BODY_OFFSET + BEZ_BODY_COM in its link's frame -- is turned
+ * into a point of the link's frame (the ball: of its own frame about its centre).  Every loaded row becomes one entry of its env's
+ * pending list.  Returns 0, or 1 for a solver family that has no external wrenches (nothing is changed), 2 for an unknown space. */
+static const double* m_body_com(const BezSimConfig* c, int b) { return m_cl(c) ? BEZ_BODY_COM_CL[b] : BEZ_BODY_COM[b]; }
+int bez_oracle_apply_body_forces(void* h, const double* forces, const double* torques, const double* positions, int space) {
+  Oracle* o = (Oracle*)h;
+  const BezSimConfig* c = &o->cfg;
+  if (c->flags & (BEZ_FLAG_HARD_CONTACT | BEZ_FLAG_TGS_SOLVER)) return 1;
+  if (space != BEZ_SPACE_ENV && space != BEZ_SPACE_LOCAL) return 2;
+  if (!forces && !torques) return 0;
+  const int nb = m_nb(c), nbe = m_nbe(c), local = space == BEZ_SPACE_LOCAL;
+  for (int i = 0; i < o->n; ++i) {
+    Env* e = &o->env[i];
+    Kin k;
+    forward_kinematics(c, e, &k);
+    const M3 Eb = quat_to_mat(e->ball_quat);
+    const int slip = e->ext_slip;
+    for (int b = 0; b < nbe; ++b) {
+      const size_t row = ((size_t)i * nbe + b) * 3;
+      real f[3] = {0, 0, 0}, t[3] = {0, 0, 0};
+      int loaded = 0;
+      for (int a = 0; a < 3; ++a) {
+        if (forces) f[a] = (real)forces[row + a];
+        if (torques) t[a] = (real)torques[row + a];
+        loaded |= (f[a] != 0) | (t[a] != 0); /* (a NaN is != 0: it goes in, and is the non-finite guard's business) */
+      }
+      if (!loaded) continue;
+      ExtEntry x; memset(&x, 0, sizeof(x));
+      const M3* E; V3 p;
+      if (b < nb) {
+        x.link = m_body_link(c, b);
+        E = &k.E[x.link];
+        V3 off = v3of((const real[3]){(real)m_body_offset(c, b)[0], (real)m_body_offset(c, b)[1], (real)m_body_offset(c, b)[2]});
+        if (slip == EXT_SLIP_OFFSET_DROPPED && (b == 4 || b == 13)) off = v3(0, 0, 0); /* planted: /camera's and the first cleat's */
+        if (!positions) p = v3add(off, v3((real)m_body_com(c, b)[0], (real)m_body_com(c, b)[1], (real)m_body_com(c, b)[2]));
+        else if (local) p = v3add(off, v3((real)positions[row], (real)positions[row + 1], (real)positions[row + 2]));
+        else p = m3Tmulv(E, v3sub(v3sub(v3((real)positions[row], (real)positions[row + 1], (real)positions[row + 2]), v3of(e->root_pos)), k.r[x.link]));
+      } else {
+        x.link = NL;
+        E = &Eb;
+        if (!positions) p = v3(0, 0, 0);
+        else if (local) p = v3((real)positions[row], (real)positions[row + 1], (real)positions[row + 2]);
+        else p = m3Tmulv(E, v3sub(v3((real)positions[row], (real)positions[row + 1], (real)positions[row + 2]), v3of(e->ball_pos)));
+      }
+      if (slip == EXT_SLIP_POINT_2MM) p.v[0] += (real)0.002;
+      const V3 F = local && slip != EXT_SLIP_LOCAL_AS_ENV ? m3mulv(E, v3of(f)) : v3of(f);
+      const V3 T = local && slip != EXT_SLIP_LOCAL_AS_ENV ? m3mulv(E, v3of(t)) : v3of(t);
+      for (int a = 0; a < 3; ++a) { x.p[a] = p.v[a]; x.F[a] = F.v[a]; x.T[a] = T.v[a]; }
+      if (e->ext_n == e->ext_cap) {
+        e->ext_cap = e->ext_cap ? 2 * e->ext_cap : 8;
+        e->ext = (ExtEntry*)realloc(e->ext, (size_t)e->ext_cap * sizeof(ExtEntry));
+      }
+      e->ext[e->ext_n++] = x;
+    }
+  }
+  return 0;
+}
+/* ORACLE ONLY (tests/body_wrench_ref.py): a planted error of the external wrenches, EXT_SLIP_*; 0 = none */
+void bez_oracle_set_ext_slip(void* h, int slip) { Oracle* o = (Oracle*)h; for (int i = 0; i < o->n; ++i) o->env[i].ext_slip = slip; }
+/* test aid: the pending entries of one env as rows of 10 doubles (link, p, F, T); returns how many there are */
+int bez_oracle_get_ext_entries(void* h, int env, double* out, int max) {
+  const Env* e = &((Oracle*)h)->env[env];
+  for (int i = 0; i < e->ext_n && i < max; ++i) {
+    out[i * 10] = e->ext[i].link;
+    for (int a = 0; a < 3; ++a) { out[i * 10 + 1 + a] = e->ext[i].p[a]; out[i * 10 + 4 + a] = e->ext[i].F[a]; out[i * 10 + 7 + a] = e->ext[i].T[a]; }
+  }
+  return e->ext_n;
 }
 
 void bez_oracle_pre_physics(void* h, const float* actions) {

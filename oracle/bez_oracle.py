@@ -154,6 +154,41 @@ class Oracle:
     def simulate(self):
         self.lib.bez_oracle_simulate(self.h)
 
+    EXT_SLIPS = ("none", "point_2mm", "frame_frozen", "local_as_env", "fixed_body_offset_dropped", "ball_point_fixed_in_world", "acts_twice",
+                 "predictor_blind")
+
+    def apply_body_forces(self, forces=None, torques=None, positions=None, space=0):
+        """External forces / torques on the rigid bodies for the NEXT simulate() / step() only, with the argument rules of
+        BezSim.apply_body_forces: numpy, (n, rows, 3) or (n * rows, 3) in RIGID_BODY_STATE order, or None; space: abi.SPACE_ENV /
+        abi.SPACE_LOCAL or "env" / "local".  None forces and torques: nothing happens.  Points and LOCAL vectors are resolved now,
+        against the state the oracle holds; calls before one launch add up.  A HARD_CONTACT / TGS_SOLVER oracle raises, unchanged."""
+        from bez_isaacgym_amd import abi
+        space = abi.body_force_space(space)
+        args = []
+        for name, a in (("forces", forces), ("torques", torques), ("positions", positions)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)   # fp32 inputs, as the simulator takes them, are kept exactly
+                if a.shape not in ((self.n * self.nbe, 3), (self.n, self.nbe, 3)):
+                    raise ValueError("%s must be (%d, 3) or (%d, %d, 3), got %r" % (name, self.n * self.nbe, self.n, self.nbe, a.shape))
+            args.append(a)
+        self.lib.bez_oracle_apply_body_forces.restype = C.c_int
+        rc = self.lib.bez_oracle_apply_body_forces(self.h, *[None if a is None else _fp(a) for a in args], C.c_int(space))
+        if rc == 1:
+            raise RuntimeError("apply_body_forces: the HARD_CONTACT / TGS_SOLVER solver families have no external wrenches")
+        if rc:
+            raise ValueError("apply_body_forces: error %d" % rc)
+
+    def set_ext_slip(self, slip):
+        """Test aid (tests/body_wrench_ref.py): plant one error of EXT_SLIPS in the external wrenches; "none" removes it"""
+        self.lib.bez_oracle_set_ext_slip(self.h, C.c_int(self.EXT_SLIPS.index(slip)))
+
+    def ext_entries(self, env):
+        """Test aid: the pending list of one env, (k, 10) fp64 rows of (link; 19 = the ball, point in the link frame, world force, world torque)"""
+        out = np.zeros((256, 10))
+        self.lib.bez_oracle_get_ext_entries.restype = C.c_int
+        k = int(self.lib.bez_oracle_get_ext_entries(self.h, C.c_int(env), _fp(out), C.c_int(256)))
+        return out[:min(k, 256)].copy()
+
     def post_physics(self):
         self.lib.bez_oracle_post_physics(self.h)
 

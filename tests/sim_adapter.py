@@ -60,6 +60,11 @@ class SimAdapter:
     def set_env_params(self, param, values):
         self.sim.set_env_params(param, None if values is None else self._t(values).reshape(-1))
 
+    def apply_body_forces(self, forces=None, torques=None, positions=None, space=abi.SPACE_ENV):
+        """numpy (n, rows, 3) or (n * rows, 3) or None each, uploaded to the sim's device: BezSim.apply_body_forces"""
+        up = [None if a is None else self._t(a) for a in (forces, torques, positions)]
+        self.sim.apply_body_forces(*up, space=space)
+
     def pre_physics(self, actions): self.sim.pre_physics(self._t(actions).reshape(-1))
     def simulate(self): self.sim.simulate()
     def post_physics(self): self.sim.post_physics()
