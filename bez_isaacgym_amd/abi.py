@@ -77,6 +77,10 @@ PROX_BOX_BODIES = tuple("/%s_%s" % (s, p) for s in ("left", "right") for p in _P
 _PROX_CAPSULES = tuple("/%s_%s" % (s, p) for s in ("left", "right") for p in _PROX_LEG + ("foot",))   # two capsules per foot
 PROX_PAIRS_CAPSULES = ((0, 6), (0, 7)) + tuple((1, b) for b in range(6, 12)) + tuple((a, b) for a in range(2, 6) for b in range(7, 12))
 PROX_PAIR_BODIES = tuple((_PROX_CAPSULES[a], _PROX_CAPSULES[b]) for a, b in PROX_PAIRS_CAPSULES)
+# query states (include/bez_sim.h "Query states", BezSim.query_state): the tensors a query state owns, (1 << id) in a refresh mask, and the
+# four parameter rows (PARAM_* below) it copies row by row
+QUERY_RIGID_BODY_STATE, QUERY_JACOBIAN, QUERY_MASS_MATRIX, QUERY_TENSOR_COUNT = range(4)
+QUERY_PARAMS = (3, 4, 5, 6)     # PARAM_MASS_SCALE, PARAM_GRAVITY, PARAM_DOF_LOWER, PARAM_DOF_UPPER
 HEALTH_NONFINITE = 1            # health word bits (TENSOR_HEALTH, BezSim.health)
 HEALTH_SPIN_TIMEOUT = 2
 TASK_KICK, TASK_WALK, TASK_ORIENT = 0, 1, 2

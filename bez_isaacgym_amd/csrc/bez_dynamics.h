@@ -1,5 +1,6 @@
 // bez_dynamics.h -- the kernels that run forward kinematics outside the control step (rigid-body refresh, dynamics tensors, inverse, forward and
-// centroidal dynamics, body accelerations, external wrenches, limb inverse kinematics, operational space, proximity).  Included by bez_sim.hip only.
+// centroidal dynamics, body accelerations, external wrenches, limb inverse kinematics, operational space, proximity), and the kernel that fills
+// a query state, the second state they can be run on.  Included by bez_sim.hip only.
 // What they share, each defined once and named, not restated, in the kernels' own comments:
 //   body_frame, for_each_body_of_link      a body's link, offset and centre of mass; the bodies fixed to one link
 //   chain_first / chain_len, for_each_chain the tree's five chains off the torso, derived from BEZ_LINK_PARENT, in either order
@@ -268,6 +269,82 @@ BEZ_DEV void tile_load_or_zero(float* rows, const float* in, int nrows) {
   } else {
     for (int i = threadIdx.x; i < nrows * WIDTH; i += THREADS) rows[tile_word<WIDTH, STRIDE>(i)] = 0.f;
   }
+}
+
+// ---- query states (definitions: include/bez_sim.h "Query states"): a second SoA state of `rows` rows for the kernels of this header,
+// with row-by-row copies of the four parameter rows they read.  The SoA stops where the fields no query reads begin (targets, previous
+// velocity, contact forces, feet, goal): load_state and every state_at of this header stay below F_TARGET.  A query that starts to read
+// a field behind the cut has to move QS_FIELDS -- the assertion ties the cut to the layout, so that a field inserted in front of it or
+// a reordering cannot leave such a read outside the allocation unnoticed.
+constexpr int QS_FIELDS = F_TARGET;
+static_assert(F_ROOT_POS == 0 && F_Q == 13 && F_QD == F_Q + BEZ_ND && F_BALL_POS == F_QD + BEZ_ND && F_BALL_ANG + 3 == QS_FIELDS &&
+              F_PREV > F_TARGET && F_CF > F_TARGET && F_FEET > F_TARGET && F_GOAL > F_TARGET && QS_FIELDS < F_COUNT,
+              "a query state holds root 13, q 18, qd 18, ball 13 in the sim's field order, and nothing a query reads lies behind them");
+constexpr int QS_PARAMS = 4;
+constexpr int QS_PARAM_ID[QS_PARAMS] = {BEZ_PARAM_MASS_SCALE, BEZ_PARAM_GRAVITY, BEZ_PARAM_DOF_LOWER, BEZ_PARAM_DOF_UPPER};
+constexpr int QS_PARAM_WIDTH[QS_PARAMS] = {BEZ_NL, 3, BEZ_ND, BEZ_ND};
+// What the host tells the fill kernels.  dst: the query state; src: the sim's parameter rows (null: never allocated) and, for a capture,
+// its SoA state of n envs; root / dof / ball: the Isaac-layout rows of a set (ball null: ball_rest, the config's pose, at rest);
+// ids: the env of every row (null: none for a set, the row's own index for a capture); g: the config's gravity
+struct QsFill {
+  float* st; int rows;
+  float* param[QS_PARAMS];
+  const float* src_param[QS_PARAMS];
+  const float* src_st; int n;
+  const float *root, *dof, *ball;
+  const int32_t* ids;
+  float ball_rest[7], g[3];
+};
+// bez_query_state_set (CAPTURE false) and bez_query_state_capture (true).  A workgroup takes QS_TILE consecutive rows.
+// Set: all lanes bring the tile's root, DOF and ball rows -- three contiguous ranges -- into LDS with tile_load, side by side in one staged
+// row per env in the sim's field order (the DOF words stay interleaved [q0, qd0, q1, ...] as DOF_STATE has them: qs_word finds a field);
+// then consecutive lanes write consecutive rows of ONE field, so a wave's store is one contiguous 256-byte range of that SoA column, and
+// its LDS reads are QS_STRIDE (odd) words apart: distinct banks.  Capture: SoA to SoA, the same column writes; the reads are the gather
+// by env id itself (contiguous for the identity).  Both: the parameter rows, written as one contiguous range per parameter and read row
+// by row from env ids[i] -- an id outside 0 .. n-1 (or a parameter the sim never allocated) takes the default row in a set, and leaves
+// the whole row, state and parameters, as it is in a capture.  Values are copied as they are.
+constexpr int QS_TILE = 64, QS_THREADS = 256, QS_STRIDE = QS_FIELDS | 1;
+BEZ_DEV int qs_word(int f) { return f < F_Q ? f : f < F_QD ? F_Q + 2 * (f - F_Q) : f < F_BALL_POS ? F_Q + 2 * (f - F_QD) + 1 : f; }
+template <bool CAPTURE>
+__global__ void __launch_bounds__(QS_THREADS) query_state_fill_kernel(QsFill A) {
+  __shared__ float staged[CAPTURE ? 1 : QS_TILE * QS_STRIDE];
+  __shared__ int env[QS_TILE];
+  const int r0 = blockIdx.x * QS_TILE, nr = min(QS_TILE, A.rows - r0);
+  for (int r = threadIdx.x; r < nr; r += QS_THREADS) {
+    const int e = A.ids ? A.ids[r0 + r] : (CAPTURE ? r0 + r : -1);
+    env[r] = (e >= 0 && e < A.n) ? e : -1;
+  }
+  if constexpr (!CAPTURE) {
+    tile_load<13, QS_STRIDE, QS_THREADS>(staged + F_ROOT_POS, A.root + (size_t)r0 * 13, nr);
+    tile_load<2 * BEZ_ND, QS_STRIDE, QS_THREADS>(staged + F_Q, A.dof + (size_t)r0 * 2 * BEZ_ND, nr);
+    if (A.ball) {
+      tile_load<13, QS_STRIDE, QS_THREADS>(staged + F_BALL_POS, A.ball + (size_t)r0 * 13, nr);
+    } else {
+      for (int i = threadIdx.x; i < nr * 13; i += QS_THREADS) staged[F_BALL_POS + tile_word<13, QS_STRIDE>(i)] = i % 13 < 7 ? A.ball_rest[i % 13] : 0.f;
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < QS_FIELDS * QS_TILE; i += QS_THREADS) {
+    const int f = i / QS_TILE, r = i % QS_TILE;
+    if (r >= nr) continue;
+    float* dst = A.st + (size_t)f * A.rows + r0 + r;
+    if constexpr (CAPTURE) {
+      if (env[r] >= 0) *dst = A.src_st[(size_t)f * A.n + env[r]];
+    } else {
+      *dst = staged[r * QS_STRIDE + qs_word(f)];
+    }
+  }
+  static_for<QS_PARAMS>([&](auto P) {
+    constexpr int p = decltype(P)::value, W = QS_PARAM_WIDTH[p];
+    const float* src = A.src_param[p];
+    float* dst = A.param[p] + (size_t)r0 * W;
+    for (int i = threadIdx.x; i < nr * W; i += QS_THREADS) {
+      const int e = env[i / W], k = i % W;
+      if (CAPTURE && e < 0) continue;
+      const float nominal = p == 0 ? 1.f : p == 1 ? (k == 0 ? A.g[0] : k == 1 ? A.g[1] : A.g[2]) : p == 2 ? (float)BEZ_DOF_LOWER[k] : (float)BEZ_DOF_UPPER[k];
+      dst[i] = (src && e >= 0) ? src[(size_t)e * W + k] : nominal;
+    }
+  });
 }
 
 // The composite-rigid-body front end of the mass matrix and of the momentum matrix, in the frame link_inertia uses (world axes about the

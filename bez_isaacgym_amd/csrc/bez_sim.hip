@@ -90,6 +90,23 @@ struct BezSim {
   // dynamics tensors (bez_sim_get_dynamics_tensor allocates each on its first acquisition; bez_sim_refresh_dynamics_tensors fills them)
   float* jacobian = nullptr;     // (N*nb, 6, 24)
   float* mass_matrix = nullptr;  // (N, 24, 24)
+  // query states (bez_query_state_create): the ones alive, and the one the query entry points read instead of the live state (null: none)
+  std::vector<BezQueryState*> queries;
+  BezQueryState* bound = nullptr;
+};
+
+// A query state: `rows` rows of the fields the query kernels read, row-by-row copies of the parameter rows they read, and tensors of its
+// own.  Every buffer is the owning sim's (dev_alloc_zeroed / dev_free); `shown` says which parameter copies the kernels are handed --
+// the others they see as null pointers, the defaults -- and is decided by the last set or capture.
+struct BezQueryState {
+  BezSim* sim = nullptr;
+  int rows = 0;
+  float* state = nullptr;                 // SoA [QS_FIELDS][rows]
+  float* param[QS_PARAMS] = {};           // (rows, QS_PARAM_WIDTH[p]) of BEZ_PARAM_* QS_PARAM_ID[p]
+  bool shown[QS_PARAMS] = {};
+  float* rigid_body = nullptr;            // (rows*nbe, 13)       allocated on first acquisition (bez_query_state_tensor), as the sim's
+  float* jacobian = nullptr;              // (rows*nb, 6, 24)      dynamics tensors are
+  float* mass_matrix = nullptr;           // (rows, 24, 24)
 };
 
 namespace {
@@ -133,9 +150,12 @@ int launch_checked(BezSim* s, const char* what, void (*kernel)(P...), size_t tot
 }
 #define LAUNCH(s, kernel, total, stream, ...) launch_checked<TB>((s), #kernel " launch", kernel, (total), (stream), __VA_ARGS__)
 // The sim's asset picks the instantiation of a kernel template <bool CL>: workgroups of THREADS lanes, each taking TILE consecutive envs
-#define LAUNCH_ASSET(s, kernel, TILE, THREADS, stream, ...)                                                                                      \
-  ((s)->cleats ? launch_checked<THREADS>((s), #kernel " launch", kernel<true>, (size_t)(((s)->n + (TILE) - 1) / (TILE)) * (THREADS), (stream), __VA_ARGS__) \
-               : launch_checked<THREADS>((s), #kernel " launch", kernel<false>, (size_t)(((s)->n + (TILE) - 1) / (TILE)) * (THREADS), (stream), __VA_ARGS__))
+#define LAUNCH_ASSET_ROWS(s, rows, kernel, TILE, THREADS, stream, ...)                                                                            \
+  ((s)->cleats ? launch_checked<THREADS>((s), #kernel " launch", kernel<true>, (size_t)(((rows) + (TILE) - 1) / (TILE)) * (THREADS), (stream), __VA_ARGS__) \
+               : launch_checked<THREADS>((s), #kernel " launch", kernel<false>, (size_t)(((rows) + (TILE) - 1) / (TILE)) * (THREADS), (stream), __VA_ARGS__))
+#define LAUNCH_ASSET(s, kernel, TILE, THREADS, stream, ...) LAUNCH_ASSET_ROWS(s, (s)->n, kernel, TILE, THREADS, stream, __VA_ARGS__)
+// the same over the rows of a StateView (below): the live state's envs, or a query state's rows
+#define LAUNCH_VIEW(s, v, kernel, TILE, THREADS, stream, ...) LAUNCH_ASSET_ROWS(s, (v).n, kernel, TILE, THREADS, stream, __VA_ARGS__)
 
 // host copy of the reset-noise Philox (bez_kernels.h) for the per-call goal draw
 void philox_host(uint32_t c[4], uint32_t k0, uint32_t k1) {
@@ -267,9 +287,23 @@ Params make_params(const BezSim* s, const float* actions) {
   P.ext = s->ext;
   return P;
 }
-DynArgs dyn_args(const BezSim* s) {
+// "The state the queries read", defined once: the SoA state, its row count, the four parameter rows over those rows (null: the defaults)
+// and whether its rigid-body rows end with a ball.  live_view: the sim's own state; view_of: a query state; query_view: what the query
+// entry points launch on -- the bound query state, else the live state.  Nothing but those entry points asks query_view.
+struct StateView { const float *st, *mass_scale, *gravity_rows, *lower, *upper; int n; bool has_ball; };
+StateView live_view(const BezSim* s) {
+  return {s->state, s->dr[BEZ_PARAM_MASS_SCALE], s->dr[BEZ_PARAM_GRAVITY], s->dr[BEZ_PARAM_DOF_LOWER], s->dr[BEZ_PARAM_DOF_UPPER], s->n, s->has_ball};
+}
+StateView view_of(const BezQueryState* q) {
+  static_assert(QS_PARAM_ID[0] == BEZ_PARAM_MASS_SCALE && QS_PARAM_ID[1] == BEZ_PARAM_GRAVITY && QS_PARAM_ID[2] == BEZ_PARAM_DOF_LOWER &&
+                QS_PARAM_ID[3] == BEZ_PARAM_DOF_UPPER, "the order of a StateView's parameter rows");
+  auto row = [&](int p) -> const float* { return q->shown[p] ? q->param[p] : nullptr; };
+  return {q->state, row(0), row(1), row(2), row(3), q->rows, q->sim->has_ball};
+}
+StateView query_view(const BezSim* s) { return s->bound ? view_of(s->bound) : live_view(s); }
+DynArgs dyn_args(const BezSim* s, const StateView& v) {
   const BezSimConfig& c = s->cfg;
-  return {s->state, s->dr[BEZ_PARAM_MASS_SCALE], s->dr[BEZ_PARAM_GRAVITY], s->n, c.flags, c.armature, {c.gravity[0], c.gravity[1], c.gravity[2]}};
+  return {v.st, v.mass_scale, v.gravity_rows, v.n, c.flags, c.armature, {c.gravity[0], c.gravity[1], c.gravity[2]}};
 }
 bool has_dr(const BezSim* s) {
   for (int i = 0; i < BEZ_PARAM_COUNT; ++i) if (s->dr[i]) return true;
@@ -580,7 +614,8 @@ static const char* oracle_only(uint32_t flags, const float* tune) {
 int bez_sim_destroy(BezSim* s) {
   if (!s) return 0;
   (void)hipSetDevice(s->device);
-  for (void** slot : s->owned) (void)hipFree(*slot);
+  for (void** slot : s->owned) (void)hipFree(*slot);   // (the buffers of the query states still alive among them)
+  for (BezQueryState* q : s->queries) delete q;
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
   delete s;
@@ -768,13 +803,15 @@ int bez_sim_refresh_dynamics_tensors(BezSim* s, uint32_t which_mask, void* strea
   float* M = (which_mask & (1u << BEZ_DYNAMICS_MASS_MATRIX)) ? s->mass_matrix : nullptr;
   if (((which_mask & (1u << BEZ_DYNAMICS_JACOBIAN)) && !J) || ((which_mask & (1u << BEZ_DYNAMICS_MASS_MATRIX)) && !M))
     return fail(s, -1, "bez_sim_refresh_dynamics_tensors: a requested tensor was never acquired (bez_sim_get_dynamics_tensor allocates it)");
-  return LAUNCH_ASSET(s, refresh_dynamics_kernel, DYN_TILE, DYN_THREADS, (hipStream_t)stream, dyn_args(s), J, M);
+  const StateView v = live_view(s);
+  return LAUNCH_VIEW(s, v, refresh_dynamics_kernel, DYN_TILE, DYN_THREADS, (hipStream_t)stream, dyn_args(s, v), J, M);
 }
 int bez_sim_inverse_dynamics(BezSim* s, const float* udot_dev, uint32_t terms, float* out_dev, void* stream) {
   if (!s) return -1;
   if (terms == 0u || (terms & ~(uint32_t)BEZ_ID_ALL)) return fail(s, -1, "bez_sim_inverse_dynamics: terms must be a non-empty set of BEZ_ID_INERTIA | BEZ_ID_VELOCITY | BEZ_ID_GRAVITY");
   if (!out_dev) return fail(s, -1, "bez_sim_inverse_dynamics: out_dev is null");
-  return LAUNCH_ASSET(s, inverse_dynamics_kernel, ID_TILE, ID_THREADS, (hipStream_t)stream, dyn_args(s), udot_dev, out_dev, terms);
+  const StateView v = query_view(s);
+  return LAUNCH_VIEW(s, v, inverse_dynamics_kernel, ID_TILE, ID_THREADS, (hipStream_t)stream, dyn_args(s, v), udot_dev, out_dev, terms);
 }
 int bez_sim_forward_dynamics(BezSim* s, const float* force_dev, uint32_t bias, uint32_t mode, float* out_dev, void* stream) {
   if (!s) return fail(s, -1, "bez_sim_forward_dynamics: sim is null");
@@ -782,8 +819,9 @@ int bez_sim_forward_dynamics(BezSim* s, const float* force_dev, uint32_t bias, u
   if (bias == 0u && !force_dev) return fail(s, -1, "bez_sim_forward_dynamics: bias is 0 and force_dev is null (nothing to solve for)");
   if (mode & ~(uint32_t)BEZ_FD_FIXED_BASE) return fail(s, -1, "bez_sim_forward_dynamics: mode must be 0 or BEZ_FD_FIXED_BASE");
   if (!out_dev) return fail(s, -1, "bez_sim_forward_dynamics: out_dev is null");
-  return LAUNCH_ASSET(s, forward_dynamics_kernel, FD_TILE, FD_THREADS, (hipStream_t)stream, dyn_args(s), force_dev, out_dev, bias,
-                      (int)(mode & BEZ_FD_FIXED_BASE));
+  const StateView v = query_view(s);
+  return LAUNCH_VIEW(s, v, forward_dynamics_kernel, FD_TILE, FD_THREADS, (hipStream_t)stream, dyn_args(s, v), force_dev, out_dev, bias,
+                     (int)(mode & BEZ_FD_FIXED_BASE));
 }
 int bez_sim_operational_space(BezSim* s, const BezOpSpaceParams* params, float* jac_dev, float* jminv_dev, float* w_dev, float* lambda_dev, void* stream) {
   if (!s) return fail(s, -1, "bez_sim_operational_space: sim is null");
@@ -796,19 +834,22 @@ int bez_sim_operational_space(BezSim* s, const BezOpSpaceParams* params, float* 
       if (!std::isfinite(p.offset[c][k])) return fail(s, -1, "bez_sim_operational_space: an offset is not finite");
   if ((p.mode & BEZ_FD_FIXED_BASE) && lambda_dev)
     return fail(s, -1, "bez_sim_operational_space: lambda_dev with BEZ_FD_FIXED_BASE (W_cc of a held root is singular by structure)");
-  return LAUNCH_ASSET(s, operational_space_kernel, OS_TILE, OS_THREADS, (hipStream_t)stream, dyn_args(s), p, jac_dev, jminv_dev, w_dev, lambda_dev);
+  const StateView v = query_view(s);
+  return LAUNCH_VIEW(s, v, operational_space_kernel, OS_TILE, OS_THREADS, (hipStream_t)stream, dyn_args(s, v), p, jac_dev, jminv_dev, w_dev, lambda_dev);
 }
 int bez_sim_centroidal(BezSim* s, float* state_dev, float* matrix_dev, void* stream) {
   if (!s) return fail(s, -1, "bez_sim_centroidal: sim is null");
   if (!state_dev && !matrix_dev) return fail(s, -1, "bez_sim_centroidal: state_dev and matrix_dev are both null (nothing to write)");
-  return LAUNCH_ASSET(s, centroidal_kernel, CM_TILE, CM_THREADS, (hipStream_t)stream, dyn_args(s), state_dev, matrix_dev);
+  const StateView v = query_view(s);
+  return LAUNCH_VIEW(s, v, centroidal_kernel, CM_TILE, CM_THREADS, (hipStream_t)stream, dyn_args(s, v), state_dev, matrix_dev);
 }
 int bez_sim_body_accelerations(BezSim* s, const float* udot_dev, uint32_t terms, int32_t space, float* out_dev, void* stream) {
   if (!s) return fail(s, -1, "bez_sim_body_accelerations: sim is null");
   if (terms == 0u || (terms & ~(uint32_t)BEZ_ACC_ALL)) return fail(s, -1, "bez_sim_body_accelerations: terms must be a non-empty set of BEZ_ACC_UDOT | BEZ_ACC_VELOCITY | BEZ_ACC_GRAVITY");
   if (space != BEZ_SPACE_ENV && space != BEZ_SPACE_LOCAL) return fail(s, -1, "bez_sim_body_accelerations: space must be BEZ_SPACE_ENV or BEZ_SPACE_LOCAL");
   if (!out_dev) return fail(s, -1, "bez_sim_body_accelerations: out_dev is null");
-  return LAUNCH_ASSET(s, body_accelerations_kernel, ACC_TILE, ACC_THREADS, (hipStream_t)stream, dyn_args(s), udot_dev, out_dev, terms, (int)space);
+  const StateView v = query_view(s);
+  return LAUNCH_VIEW(s, v, body_accelerations_kernel, ACC_TILE, ACC_THREADS, (hipStream_t)stream, dyn_args(s, v), udot_dev, out_dev, terms, (int)space);
 }
 int bez_sim_generalized_forces(BezSim* s, const float* forces_dev, const float* torques_dev, const float* positions_dev, int32_t space,
                                float* out_dev, void* stream) {
@@ -817,8 +858,9 @@ int bez_sim_generalized_forces(BezSim* s, const float* forces_dev, const float* 
   if ((space & BEZ_GF_AT_ORIGIN) && positions_dev) return fail(s, -1, "bez_sim_generalized_forces: BEZ_GF_AT_ORIGIN needs positions_dev == NULL");
   if (!forces_dev && !torques_dev) return fail(s, -1, "bez_sim_generalized_forces: forces_dev and torques_dev are both null (nothing to map)");
   if (!out_dev) return fail(s, -1, "bez_sim_generalized_forces: out_dev is null");
-  return LAUNCH_ASSET(s, generalized_forces_kernel, GF_TILE, GF_THREADS, (hipStream_t)stream, dyn_args(s), forces_dev, torques_dev, positions_dev,
-                      (int)space, (int)s->has_ball, out_dev);
+  const StateView v = query_view(s);
+  return LAUNCH_VIEW(s, v, generalized_forces_kernel, GF_TILE, GF_THREADS, (hipStream_t)stream, dyn_args(s, v), forces_dev, torques_dev, positions_dev,
+                     (int)space, (int)v.has_ball, out_dev);
 }
 int bez_sim_limb_ik(BezSim* s, const float* targets_dev, const BezIkParams* params, float* q_out_dev, float* err_out_dev, void* stream) {
   if (!s) return fail(s, -1, "bez_sim_limb_ik: sim is null");
@@ -836,14 +878,124 @@ int bez_sim_limb_ik(BezSim* s, const float* targets_dev, const BezIkParams* para
       if (!std::isfinite(p.offset[c][k])) return fail(s, -1, "bez_sim_limb_ik: an offset is not finite");
   }
   if (p.space != BEZ_IK_SPACE_ENV && p.space != BEZ_IK_SPACE_ROOT) return fail(s, -1, "bez_sim_limb_ik: space must be BEZ_IK_SPACE_ENV or BEZ_IK_SPACE_ROOT");
-  return LAUNCH_ASSET(s, limb_ik_kernel, IK_TILE, IK_THREADS, (hipStream_t)stream, dyn_args(s), s->dr[BEZ_PARAM_DOF_LOWER], s->dr[BEZ_PARAM_DOF_UPPER],
-                      targets_dev, p, q_out_dev, err_out_dev);
+  const StateView v = query_view(s);
+  return LAUNCH_VIEW(s, v, limb_ik_kernel, IK_TILE, IK_THREADS, (hipStream_t)stream, dyn_args(s, v), v.lower, v.upper,
+                     targets_dev, p, q_out_dev, err_out_dev);
 }
 int bez_sim_proximity(BezSim* s, float* ground_dev, float* ball_dev, float* pairs_dev, void* stream) {
   if (!s) return fail(s, -1, "bez_sim_proximity: sim is null");
   if (!ground_dev && !ball_dev && !pairs_dev) return fail(s, -1, "bez_sim_proximity: ground_dev, ball_dev and pairs_dev are all null (nothing to write)");
-  return LAUNCH_ASSET(s, proximity_kernel, PX_TILE, PX_THREADS, (hipStream_t)stream, dyn_args(s), ground_dev, ball_dev, pairs_dev);
+  const StateView v = query_view(s);
+  return LAUNCH_VIEW(s, v, proximity_kernel, PX_TILE, PX_THREADS, (hipStream_t)stream, dyn_args(s, v), ground_dev, ball_dev, pairs_dev);
 }
+// ---- query states: include/bez_sim.h "Query states"
+static bool owns(const BezSim* s, const BezQueryState* q) { return std::find(s->queries.begin(), s->queries.end(), q) != s->queries.end(); }
+// the shared front of every call on a query state: both handles, and the state is one of this sim's
+#define QS_TRY(s, q, name)                                                                            \
+  do {                                                                                                \
+    if (!(s)) return fail((s), -1, name ": sim is null");                                             \
+    if (!(q)) return fail((s), -1, name ": the query state is null");                                 \
+    if (!owns((s), (q))) return fail((s), -1, name ": the query state belongs to another sim");       \
+  } while (0)
+
+int bez_query_state_create(BezSim* s, int32_t rows, BezQueryState** out) {
+  if (!s) return fail(s, -1, "bez_query_state_create: sim is null");
+  if (!out) return fail(s, -1, "bez_query_state_create: out is null");
+  *out = nullptr;
+  if (rows <= 0) return fail(s, -1, "bez_query_state_create: rows must be > 0");
+  BezQueryState* q = new (std::nothrow) BezQueryState();
+  if (!q) return fail(s, -4, "out of host memory");
+  q->sim = s; q->rows = rows;
+  s->queries.push_back(q);
+  (void)hipSetDevice(s->device);
+  int rc = dev_alloc_zeroed(s, &q->state, (size_t)rows * QS_FIELDS * sizeof(float));
+  for (int p = 0; p < QS_PARAMS && !rc; ++p) rc = dev_alloc_zeroed(s, &q->param[p], (size_t)rows * QS_PARAM_WIDTH[p] * sizeof(float));
+  if (rc) { const std::string why = s->err; bez_query_state_destroy(s, q); s->err = why; return rc; }
+  *out = q;
+  return 0;
+}
+int bez_query_state_destroy(BezSim* s, BezQueryState* q) {
+  QS_TRY(s, q, "bez_query_state_destroy");
+  if (s->bound == q) return fail(s, -1, "bez_query_state_destroy: the query state is bound (unbind it first: bez_query_state_bind(sim, NULL))");
+  (void)hipSetDevice(s->device);
+  float** slots[] = {&q->state, &q->param[0], &q->param[1], &q->param[2], &q->param[3], &q->rigid_body, &q->jacobian, &q->mass_matrix};
+  for (float** slot : slots) if (*slot) dev_free(s, slot);   // (hipFree waits for the work that may still read the buffer)
+  s->queries.erase(std::remove(s->queries.begin(), s->queries.end(), q), s->queries.end());
+  delete q;
+  return 0;
+}
+}  // extern "C"
+// what set and capture share: the destination, the sim's parameter rows, the config's constants; then the launch over the tiles
+static QsFill fill_args(const BezSim* s, BezQueryState* q, const int32_t* ids) {
+  QsFill A = {};
+  A.st = q->state; A.rows = q->rows; A.n = s->n; A.ids = ids;
+  for (int p = 0; p < QS_PARAMS; ++p) { A.param[p] = q->param[p]; A.src_param[p] = s->dr[QS_PARAM_ID[p]]; }
+  for (int k = 0; k < 7; ++k) A.ball_rest[k] = s->cfg.ball_init[k];
+  for (int k = 0; k < 3; ++k) A.g[k] = s->cfg.gravity[k];
+  return A;
+}
+template <bool CAPTURE>
+static int launch_fill(BezSim* s, const QsFill& A, hipStream_t stream) {
+  return launch_checked<QS_THREADS>(s, "query_state_fill_kernel launch", query_state_fill_kernel<CAPTURE>,
+                                    (size_t)((A.rows + QS_TILE - 1) / QS_TILE) * QS_THREADS, stream, A);
+}
+extern "C" {
+int bez_query_state_set(BezSim* s, BezQueryState* q, const float* root_dev, const float* dof_dev, const float* ball_dev, const int32_t* env_ids_dev,
+                        void* stream) {
+  QS_TRY(s, q, "bez_query_state_set");
+  if (!root_dev || !dof_dev) return fail(s, -1, "bez_query_state_set: root_dev or dof_dev is null");
+  if (ball_dev && !s->has_ball) return fail(s, -1, "bez_query_state_set: ball_dev given, but this task has no ball");
+  QsFill A = fill_args(s, q, env_ids_dev);
+  A.root = root_dev; A.dof = dof_dev; A.ball = ball_dev;
+  // without ids every row is nominal: the kernels see null parameter pointers; with ids, the rows the sim has
+  for (int p = 0; p < QS_PARAMS; ++p) q->shown[p] = env_ids_dev && A.src_param[p];
+  return launch_fill<false>(s, A, (hipStream_t)stream);
+}
+int bez_query_state_capture(BezSim* s, BezQueryState* q, const int32_t* env_ids_dev, void* stream) {
+  QS_TRY(s, q, "bez_query_state_capture");
+  if (!env_ids_dev && q->rows != s->n) return fail(s, -1, "bez_query_state_capture: env_ids_dev is null (row i <- env i), which needs rows == num_envs");
+  QsFill A = fill_args(s, q, env_ids_dev);
+  A.src_st = s->state;
+  for (int p = 0; p < QS_PARAMS; ++p) q->shown[p] = A.src_param[p] != nullptr;
+  return launch_fill<true>(s, A, (hipStream_t)stream);
+}
+int bez_query_state_bind(BezSim* s, BezQueryState* q) {
+  if (!s) return fail(s, -1, "bez_query_state_bind: sim is null");
+  if (q && !owns(s, q)) return fail(s, -1, "bez_query_state_bind: the query state belongs to another sim");
+  s->bound = q;
+  return 0;
+}
+int bez_query_state_tensor(BezSim* s, BezQueryState* q, int which, void** dev_ptr, int64_t shape[3], int* ndim, int* dtype) {
+  QS_TRY(s, q, "bez_query_state_tensor");
+  if (!dev_ptr || !shape || !ndim || !dtype) return fail(s, -1, "bez_query_state_tensor: null argument");
+  float** slot = nullptr;
+  switch (which) {
+    case BEZ_QUERY_RIGID_BODY_STATE: slot = &q->rigid_body; shape[0] = (int64_t)q->rows * s->nbe; shape[1] = 13; shape[2] = 0; *ndim = 2; break;
+    case BEZ_QUERY_JACOBIAN: slot = &q->jacobian; shape[0] = (int64_t)q->rows * s->nb; shape[1] = 6; shape[2] = 6 + BEZ_ND; *ndim = 3; break;
+    case BEZ_QUERY_MASS_MATRIX: slot = &q->mass_matrix; shape[0] = q->rows; shape[1] = shape[2] = 6 + BEZ_ND; *ndim = 3; break;
+    default: return fail(s, -1, "bez_query_state_tensor: unknown tensor id");
+  }
+  if (!*slot) {   // the acquisition: the one place that allocates (and, through hipMemset, waits)
+    (void)hipSetDevice(s->device);
+    RC_TRY(dev_alloc_zeroed(s, slot, (size_t)(shape[0] * shape[1] * (shape[2] ? shape[2] : 1)) * sizeof(float)));
+  }
+  *dev_ptr = *slot; *dtype = BEZ_DTYPE_F32;
+  return 0;
+}
+int bez_query_state_refresh(BezSim* s, BezQueryState* q, uint32_t which_mask, void* stream) {
+  QS_TRY(s, q, "bez_query_state_refresh");
+  if (which_mask == 0u || (which_mask >> BEZ_QUERY_TENSOR_COUNT)) return fail(s, -1, "bez_query_state_refresh: which_mask must be a non-empty set of (1u << BezQueryTensor) bits");
+  const bool rb = which_mask & (1u << BEZ_QUERY_RIGID_BODY_STATE), jac = which_mask & (1u << BEZ_QUERY_JACOBIAN), mm = which_mask & (1u << BEZ_QUERY_MASS_MATRIX);
+  if ((rb && !q->rigid_body) || (jac && !q->jacobian) || (mm && !q->mass_matrix))
+    return fail(s, -1, "bez_query_state_refresh: a requested tensor was never acquired (bez_query_state_tensor allocates it)");
+  const StateView v = view_of(q);
+  if (rb) RC_TRY(LAUNCH_VIEW(s, v, refresh_rigid_body_kernel, 64, 64, (hipStream_t)stream, v.st, q->rigid_body, v.n, (int)v.has_ball, s->cfg.flags));
+  if (jac || mm)
+    RC_TRY(LAUNCH_VIEW(s, v, refresh_dynamics_kernel, DYN_TILE, DYN_THREADS, (hipStream_t)stream, dyn_args(s, v), jac ? q->jacobian : nullptr,
+                       mm ? q->mass_matrix : nullptr));
+  return 0;
+}
+
 int bez_sim_set_obs_calls(BezSim* s, int64_t calls) { if (!s) return -1; s->obs_calls = calls; return 0; }
 
 int bez_sim_pre_physics(BezSim* s, const float* actions_dev, void* stream) {

@@ -71,6 +71,19 @@ SIGS = {
     "bez_sim_proximity": (C.c_int, [vp, fp, fp, fp, vp]),
 }
 EXPORTS = list(SIGS)
+# the bez_query_state_* entry points of the same header ("Query states"): sim, query state, ...
+QUERY_STATE_SIGS = {
+    "bez_query_state_create": (C.c_int, [vp, i32, C.POINTER(vp)]),
+    "bez_query_state_destroy": (C.c_int, [vp, vp]),
+    "bez_query_state_set": (C.c_int, [vp, vp, fp, fp, fp, vp, vp]),
+    "bez_query_state_capture": (C.c_int, [vp, vp, vp, vp]),
+    "bez_query_state_bind": (C.c_int, [vp, vp]),
+    "bez_query_state_tensor": (C.c_int, [vp, vp] + _GETTER[1:]),
+    "bez_query_state_refresh": (C.c_int, [vp, vp, u32, vp]),
+}
+# the entry points a binding redirects (include/bez_sim.h): what a QueryState brackets with bind / unbind
+BOUND_QUERIES = ("bez_sim_inverse_dynamics", "bez_sim_forward_dynamics", "bez_sim_operational_space", "bez_sim_centroidal",
+                 "bez_sim_body_accelerations", "bez_sim_generalized_forces", "bez_sim_limb_ik", "bez_sim_proximity")
 
 
 def load_library():
@@ -83,7 +96,7 @@ def load_library():
         raise BezSimError("libbez_sim.so not built (%s): run `python -m bez_isaacgym_amd.build` -- "
                           "the HIP extension is required, there is no fallback path" % path)
     lib = C.CDLL(path)
-    for name, (res, args) in SIGS.items():
+    for name, (res, args) in list(SIGS.items()) + list(QUERY_STATE_SIGS.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     _LIB = lib
@@ -129,6 +142,8 @@ class BezSim:
     def close(self):
         if getattr(self, "h", None):
             self._views = {}
+            for qs in self.__dict__.pop("_query_states", []):   # bez_sim_destroy frees them: their objects only forget the handles
+                qs._forget()
             self.lib.bez_sim_destroy(self.h)
             self.h = None
 
@@ -423,6 +438,16 @@ class BezSim:
         self._check(self.lib.bez_sim_proximity(self.h, *ptrs, self._stream()))
         return out["ground"], out["ball"], out["pairs"]
 
+    # ---- query states: the queries above on states the caller supplies (include/bez_sim.h "Query states")
+    def query_state(self, rows):
+        """A QueryState of `rows` rows (>= 1, independent of N) owned by this sim: fill it with set() or capture(), then ask it what this
+        sim is asked -- the live state is never written.  close() frees it; closing the sim frees the ones still open."""
+        if isinstance(rows, bool) or not isinstance(rows, int) or rows < 1:
+            raise BezSimError("query_state: rows must be an int >= 1, got %r" % (rows,))
+        qs = QueryState(self, rows)
+        self.__dict__.setdefault("_query_states", []).append(qs)
+        return qs
+
     def refresh(self, which):
         self._check(self.lib.bez_sim_refresh_tensor(self.h, which, self._stream()))
         return self.tensor(which)
@@ -561,3 +586,121 @@ class BezSim:
 
     def seed(self, seed):
         self._check(self.lib.bez_sim_seed(self.h, int(seed)))
+
+
+class _BoundLib:
+    """The library as a QueryState calls it: an entry point of BOUND_QUERIES runs between bez_query_state_bind(sim, qs) and
+    bez_query_state_bind(sim, NULL) -- the unbind also when the call raises --, every other one goes straight through."""
+
+    def __init__(self, lib, sim_h, qs_h):
+        self._lib, self._sim_h, self._qs_h = lib, sim_h, qs_h
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if name not in BOUND_QUERIES:
+            return fn
+
+        def bound(*args):
+            rc = self._lib.bez_query_state_bind(self._sim_h, self._qs_h)
+            if rc != 0:
+                return rc      # (nothing was bound: the query must not run on the live state in this object's name)
+            try:
+                return fn(*args)
+            finally:
+                self._lib.bez_query_state_bind(self._sim_h, None)   # (a successful call leaves the sim's error message alone)
+        self.__dict__[name] = bound
+        return bound
+
+
+class QueryState:
+    """A state of `rows` rows that the caller supplies, asked what a BezSim is asked (BezSim.query_state; include/bez_sim.h "Query
+    states").  set() fills it from Isaac-layout rows, capture() from live envs; the query methods are BezSim's own, with `rows` in
+    the place of N in every shape, and their result buffers are this object's.  Each of them binds the state, calls and unbinds."""
+
+    def __init__(self, sim, rows):
+        self.sim, self.rows, self.num_envs = sim, rows, rows   # (num_envs: what the shared methods size their tensors by)
+        self.cfg, self.device, self.has_ball, self.num_bodies = getattr(sim, "cfg", None), sim.device, sim.has_ball, sim.num_bodies
+        self._stream, self._views, self.h = sim._stream, {}, sim.h
+        qs = C.c_void_p()
+        sim._check(sim.lib.bez_query_state_create(sim.h, rows, C.byref(qs)))
+        self.qs = qs
+        self.lib = _BoundLib(sim.lib, sim.h, qs)
+
+    # the query calls and the argument machinery under them are BezSim's functions, run on this object: nothing is written twice
+    for _name in ("_check", "_ptr", "_checked", "_in", "_out", "_f32", "_wanted", "_body_vectors", "_describe", "_wrap", "inverse_dynamics",
+                  "forward_dynamics", "operational_space", "centroidal", "body_accelerations", "generalized_forces", "limb_ik", "proximity"):
+        locals()[_name] = getattr(BezSim, _name)
+    del _name
+
+    def _forget(self):
+        self.qs, self._views = None, {}
+
+    def close(self):
+        if getattr(self, "qs", None) is not None:
+            self._views = {}
+            self._check(self.lib.bez_query_state_destroy(self.h, self.qs))
+            self._forget()
+            states = self.sim.__dict__.get("_query_states", [])
+            if self in states:
+                states.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _env_ids(self, env_ids):
+        """the pointer of (rows,) int32 env ids on the device, NULL for None"""
+        return None if env_ids is None else self._ptr(self._checked("env_ids", env_ids, ((self.rows,),)), torch.int32)
+
+    def set(self, root, dof, ball=None, env_ids=None):
+        """Fills every row: `root` (M, 13) as ROOT_STATE rows, `dof` (M, 18, 2) or (M*18, 2) as DOF_STATE rows, `ball` (M, 13) or None --
+        None where the task has no ball (a tensor is refused there), the config's ball_init pose at rest on bez_kick.  float32 on the
+        sim's device, contiguous; values are copied as given.  `env_ids` (M,) int32 or None: row i takes the mass-scale, gravity and
+        joint-limit rows of env env_ids[i] as they are now (ids may repeat; an id outside 0 .. N-1: the default rows); None: the asset's
+        nominal parameters for every row.  One launch on the current stream; everything is checked before the library is called."""
+        m = self.rows
+        root, dof = self._checked("root", root, ((m, 13),)), self._checked("dof", dof, ((m, abi.NUM_DOFS, 2), (m * abi.NUM_DOFS, 2)))
+        ball = self._in("ball", ball, (m, 13))
+        if ball is not None and not self.has_ball:
+            raise BezSimError("query state set: ball given, but this task has no ball")
+        ptrs = [self._f32(root), self._f32(dof), self._f32(ball), self._env_ids(env_ids)]
+        self._check(self.lib.bez_query_state_set(self.h, self.qs, *ptrs, self._stream()))
+
+    def capture(self, env_ids=None):
+        """Row i becomes the live state of env env_ids[i] -- root, joints, ball -- with its parameter rows; `env_ids` (M,) int32 on the
+        sim's device, or None for row i <- env i (needs M == N).  A row whose id is outside 0 .. N-1 is left as it was.  One launch on
+        the current stream."""
+        if env_ids is None and self.rows != self.sim.num_envs:
+            raise BezSimError("query state capture: env_ids is None (row i <- env i), which needs rows == num_envs (%d != %d)"
+                              % (self.rows, self.sim.num_envs))
+        self._check(self.lib.bez_query_state_capture(self.h, self.qs, self._env_ids(env_ids), self._stream()))
+
+    # ---- the tensors of its own: RIGID_BODY_STATE rows, Jacobian, mass matrix; each allocated by its first acquisition
+    def _tensor(self, which):
+        return self._wrap(("query", which), lambda h, w, *out: self.lib.bez_query_state_tensor(h, self.qs, w, *out), which)
+
+    def dynamics_tensor(self, which):
+        """BezSim.dynamics_tensor of this state: the Jacobian (M*NB, 6, 24) or the mass matrix (M, 24, 24); refresh_dynamics_tensors() fills it."""
+        return self._tensor((abi.QUERY_JACOBIAN, abi.QUERY_MASS_MATRIX)[abi.dynamics_tensor_id(which)])
+
+    def refresh_dynamics_tensors(self, which=None):
+        """BezSim.refresh_dynamics_tensors of this state: one tensor, a sequence of them, or None for every one acquired so far."""
+        if which is None:
+            ids = [k[1] for k in self._views if k[1] != abi.QUERY_RIGID_BODY_STATE]
+        else:
+            ids = [(abi.QUERY_JACOBIAN, abi.QUERY_MASS_MATRIX)[abi.dynamics_tensor_id(w)] for w in ([which] if isinstance(which, (str, int)) else which)]
+        mask = 0
+        for k in ids:
+            mask |= 1 << k
+        self._check(self.lib.bez_query_state_refresh(self.h, self.qs, mask, self._stream()))
+
+    def refresh(self, which):
+        """BezSim.refresh(abi.TENSOR_RIGID_BODY_STATE) of this state: its (M*NBE, 13) rigid-body rows, refreshed.  A query state has no
+        other Isaac-layout tensor: its root, DOF and ball rows are what set() or capture() were given."""
+        if which != abi.TENSOR_RIGID_BODY_STATE:
+            raise BezSimError("a query state refreshes abi.TENSOR_RIGID_BODY_STATE only, got tensor id %r" % (which,))
+        view = self._tensor(abi.QUERY_RIGID_BODY_STATE)
+        self._check(self.lib.bez_query_state_refresh(self.h, self.qs, 1 << abi.QUERY_RIGID_BODY_STATE, self._stream()))
+        return view

@@ -281,3 +281,35 @@ class SimQueries:
         """Forces at the given points (world coordinates in "env" space, body frame in "local" space; None = the centres of mass)."""
         self.sim.apply_body_forces(forces=forces, torques=None, positions=positions, space=space)
         return True
+
+    # ---- query states (include/bez_sim.h "Query states"): everything above on states the caller supplies, the episode left alone
+    def query_state(self, rows=None):
+        """A StateQueries of `rows` rows (None: num_envs): fill it with set(root, dof, ball=None, env_ids=None) or capture(env_ids=None),
+        then ask it what the task is asked -- bias_forces(), center_of_mass(), foot_clearance(), limb_ik(), acquire_jacobian_tensor() ... --
+        about those rows; env_ids gives row i the randomised masses, gravity and joint limits of env env_ids[i].  close() frees it."""
+        return StateQueries(self.sim.query_state(self.num_envs if rows is None else rows))
+
+
+class StateQueries(SimQueries):
+    """SimQueries over a query state (bez_isaacgym_amd.sim.QueryState) in the place of the sim: `num_envs` is its row count.  What asks
+    about the last physics launch, or acts on the next one, has no meaning on a supplied state and says so."""
+
+    def __init__(self, state):
+        self.sim, self.num_envs = state, state.rows
+        self.set, self.capture, self.close = state.set, state.capture, state.close
+
+    def _not_here(name):
+        def refuse(self, *args, **kwargs):
+            raise AttributeError("%s is about the physics launches of the live simulation; a query state has none "
+                                 "(ask the task, not its query_state())" % name)
+        return refuse
+
+    dof_force_tensor = property(_not_here("dof_force_tensor"))
+    dof_drive_torque = property(_not_here("dof_drive_torque"))
+    dof_status = property(_not_here("dof_status"))
+    refresh_dof_force_tensor = _not_here("refresh_dof_force_tensor()")
+    actuator_snapshot = _not_here("actuator_snapshot()")
+    apply_rigid_body_force_tensors = _not_here("apply_rigid_body_force_tensors()")
+    apply_rigid_body_force_at_pos_tensors = _not_here("apply_rigid_body_force_at_pos_tensors()")
+    query_state = _not_here("query_state()")
+    del _not_here

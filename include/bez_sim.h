@@ -622,6 +622,59 @@ int bez_sim_limb_ik(BezSim* sim, const float* targets_dev /* (N,5,7) */, const B
 int bez_sim_proximity(BezSim* sim, float* ground_dev /* (N,23,3) or NULL */,
                       float* ball_dev /* (N,11,8) or NULL */, float* pairs_dev /* (N,28,8) or NULL */, void* stream);
 
+/* Query states.  Every query above is "of the current state".  A query state is a second state, of M rows with M >= 1 independent of
+ * N, that the same kernels read instead: candidate poses of a planner (M = N x K), logged (q, u) samples, what limb_ik returned.  The
+ * live state is never written.  A BezQueryState is owned by the sim that created it and holds
+ *   - the fields the query kernels read -- root 13, q 18, qd 18, ball 13 -- as M-row SoA columns (no targets, contact forces, goal: no
+ *     query reads them);
+ *   - M-row copies of the four parameter rows those kernels use: BEZ_PARAM_MASS_SCALE, BEZ_PARAM_GRAVITY, BEZ_PARAM_DOF_LOWER,
+ *     BEZ_PARAM_DOF_UPPER;
+ *   - tensors of its own, each allocated when bez_query_state_tensor first hands it out: RIGID_BODY_STATE rows (M*NBE, 13), the Jacobian
+ *     (M*NB, 6, 24) and the mass matrix (M, 24, 24), defined as the sim's.
+ * bez_query_state_create allocates the state and the parameter copies (zeroed: fill it before asking) through the sim's buffer owner;
+ * bez_query_state_destroy frees them, and bez_sim_destroy frees the query states still alive.  A sim that creates none allocates and
+ * launches what it did without them.
+ *
+ * bez_query_state_set fills all M rows from Isaac-layout rows: root_dev (M, 13) as ROOT_STATE rows, dof_dev (M, 18, 2) as DOF_STATE
+ * rows, ball_dev (M, 13) or NULL.  Values are copied as given (no normalisation, no finiteness filter), as the indexed setters do.
+ * ball_dev must be NULL on a task without a ball; NULL on bez_kick is the config's ball_init pose at rest.  env_ids_dev NULL: every row
+ * has the asset's nominal parameters -- the kernels are handed null parameter rows: mass scale 1, the config's gravity, the model's
+ * limits.  env_ids_dev (M) int32: row i has a copy of env env_ids[i]'s four rows as they are when the call runs on `stream`; a parameter
+ * the sim never allocated stays a null row here too; ids may repeat; an id outside 0 .. N-1 gives that row the default row's values
+ * (the kernel checks the range and reads nothing outside the sim's arrays).
+ * bez_query_state_capture sets row i to the live state of env env_ids[i] -- root, joints, ball -- with its parameter rows.  NULL is
+ * the identity and needs M == N.  A row whose id is outside 0 .. N-1 is left as it was, parameters included.
+ * Which parameter rows the kernels are handed is decided by the last set or capture, for the whole query state.
+ *
+ * bez_query_state_bind(sim, qs) redirects the query entry points and nothing else: until bez_query_state_bind(sim, NULL),
+ * bez_sim_inverse_dynamics, _forward_dynamics, _operational_space, _centroidal, _body_accelerations, _generalized_forces, _limb_ik and
+ * _proximity read the bound state, tile over its M rows and take and write M-row tensors where their comments say N.  Stepping, the
+ * setters, the refreshes of the sim's own tensors, resets and randomisation never look at the binding.  The binding is host state: a
+ * launch already enqueued keeps the state it was launched on.
+ * bez_query_state_refresh(sim, qs, which_mask) fills the acquired tensors of the mask ((1u << BezQueryTensor) bits) with the kernels of
+ * bez_sim_refresh_tensor(RIGID_BODY_STATE) and bez_sim_refresh_dynamics_tensors run on the query state; it needs no binding.
+ *
+ * rc -1 with a bez_sim_last_error message: a null sim or query state, a query state of another sim (also when binding it), rows <= 0,
+ * ball_dev on a task without a ball, capture with NULL ids and M != N, destroying the bound query state, refreshing a tensor that was
+ * never acquired.  create, destroy and the first bez_query_state_tensor of a tensor allocate or free (and may wait for the device);
+ * set, capture, refresh and the bound queries are plain kernel launches on `stream` -- one per call, two for a refresh of rigid-body rows
+ * together with a dynamics tensor -- that allocate nothing, never synchronise and capture into a HIP graph. */
+typedef struct BezQueryState BezQueryState;
+typedef enum BezQueryTensor {
+  BEZ_QUERY_RIGID_BODY_STATE = 0, /* f32 (M*NBE, 13): the rows of BEZ_TENSOR_RIGID_BODY_STATE */
+  BEZ_QUERY_JACOBIAN = 1,         /* f32 (M*NB, 6, 24): BEZ_DYNAMICS_JACOBIAN */
+  BEZ_QUERY_MASS_MATRIX = 2,      /* f32 (M, 24, 24): BEZ_DYNAMICS_MASS_MATRIX */
+  BEZ_QUERY_TENSOR_COUNT = 3
+} BezQueryTensor;
+int bez_query_state_create(BezSim* sim, int32_t rows, BezQueryState** out);
+int bez_query_state_destroy(BezSim* sim, BezQueryState* qs);
+int bez_query_state_set(BezSim* sim, BezQueryState* qs, const float* root_dev /* (M,13) */, const float* dof_dev /* (M,18,2) */,
+                        const float* ball_dev /* (M,13) or NULL */, const int32_t* env_ids_dev /* (M) or NULL */, void* stream);
+int bez_query_state_capture(BezSim* sim, BezQueryState* qs, const int32_t* env_ids_dev /* (M) or NULL */, void* stream);
+int bez_query_state_bind(BezSim* sim, BezQueryState* qs /* or NULL */);
+int bez_query_state_tensor(BezSim* sim, BezQueryState* qs, int which, void** dev_ptr, int64_t shape[3], int* ndim, int* dtype);
+int bez_query_state_refresh(BezSim* sim, BezQueryState* qs, uint32_t which_mask, void* stream);
+
 /* gym.refresh_{actor_root_state,dof_state,rigid_body_state,net_contact_force}_tensor
  * (kick_env.py:750-753): materialise the Isaac-layout tensor from the SoA state.  ROOT_STATE, DOF_STATE, RIGID_BODY_STATE,
  * NET_CONTACT_FORCE, DOF_TARGET, PREV_LIN_VEL, FEET and GOAL need it; every other BezTensor is always live (the kernels
