@@ -286,7 +286,7 @@ BEZ_DEV void load_targets(const Params& P, const float* lds, int lane, int e, fl
 }
 
 // ------------------------------------------------------------------------------------------------ roles
-template <int FIRST, bool PRE, bool POST, bool DR, bool CL, bool EXT = false>
+template <bool DF, int FIRST, bool PRE, bool POST, bool DR, bool CL, bool EXT = false>
 BEZ_DEV void leg_role(const Params& P, float* lds, int lane, int e, bool active, int side) {
   constexpr int LEN = 6;
   const bool xp = EXT && ext_pending(P, e);   // external wrenches pending for this env (EXT instantiations)
@@ -352,27 +352,23 @@ BEZ_DEV void leg_role(const Params& P, float* lds, int lane, int e, bool active,
 #if BEZ_WS_SUB == 4
     // lane-group form (bez_ws_quad.inc): the quad's lanes hold one 3 x 3 block of the articulated inertia each
     const Quad Q = quad_of(lane);
-    P3q p3[LEN];
+    P3q<DF> p3[LEN];
     V3 pA;
-#ifdef BEZ_DOF_FORCE
-    uint32_t dfw = 0u;   // the joints' decision bits (actuator record)
-#endif
+    DfWord<DF> dfw{};   // the joints' decision bits (actuator record)
     {
       Blk M;
-      wq_chain_pass2<FIRST, LEN, (!CL && !DR)>(P, Q, lds, lane, side, s + 1, kps, kds, lo, hi, q, qd, target, LI, pAl, Sl, cbl, Kc, pc, mine, sel, p3, M, pA BEZ_DF_WORD_ARG);
+      wq_chain_pass2<DF, FIRST, LEN, (!CL && !DR)>(P, Q, lds, lane, side, s + 1, kps, kds, lo, hi, q, qd, target, LI, pAl, Sl, cbl, Kc, pc, mine, sel, p3, M, pA, dfw);
 #pragma unroll
       for (int i = 0; i < 9; ++i) XS(X_IA + side * 27 + i) = M.m[i];   // the block, in the quad's layout (wq_add_leg_block)
     }
     WS_STAMP(side, 24 + s);
     ws_barrier();  // B1c: both helper parts' leg<->leg contact wrenches are in LDS
-    const float sc = wq_chain_self_correction<LEN, CL>(P, Q, lds, lane, side, s + 1, p3, pA, X_IA + side * 27 + 9 BEZ_DF_WORD_ARG);
+    const float sc = wq_chain_self_correction<DF, LEN, CL>(P, Q, lds, lane, side, s + 1, p3, pA, X_IA + side * 27 + 9, dfw);
 #else
-    P3 p3[LEN];
+    P3<DF> p3[LEN];
     Sym6 IA = sym6zero(); SV pA = svzero();
-#ifdef BEZ_DOF_FORCE
-    uint32_t dfw = 0u;   // the joints' decision bits (actuator record)
-#endif
-    ws_chain_pass2<FIRST, LEN, true>(P, D, kps, kds, lo, hi, q, qd, target, LI, pAl, Sl, cbl, Kc, pc, mine, sel, p3, IA, pA BEZ_DF_WORD_ARG);
+    DfWord<DF> dfw{};   // the joints' decision bits (actuator record)
+    ws_chain_pass2<DF, FIRST, LEN, true>(P, D, kps, kds, lo, hi, q, qd, target, LI, pAl, Sl, cbl, Kc, pc, mine, sel, p3, IA, pA, dfw);
     {  // the chain's articulated inertia goes to its X_IA block NOW (free since B1: the staged actions are consumed): 21 registers
        // less across the barrier and the correction below; the bias follows once the leg<->leg share is in it
       const float* f = (const float*)&IA;
@@ -381,7 +377,7 @@ BEZ_DEV void leg_role(const Params& P, float* lds, int lane, int e, bool active,
     }
     WS_STAMP(side, 24 + s);
     ws_barrier();  // B1c: both helper parts' leg<->leg contact wrenches are in LDS
-    const float sc = ws_chain_self_correction<LEN, CL>(P, lds, lane, side, s + 1, p3, pA BEZ_DF_WORD_ARG);   // (stores the bias part of the chain's X_IA block)
+    const float sc = ws_chain_self_correction<DF, LEN, CL>(P, lds, lane, side, s + 1, p3, pA, dfw);   // (stores the bias part of the chain's X_IA block)
 #endif
     WS_STAMP(side, 4 + 8 * s);
     ws_barrier();  // B2
@@ -393,23 +389,17 @@ BEZ_DEV void leg_role(const Params& P, float* lds, int lane, int e, bool active,
 #pragma unroll
     for (int i = 0; i < LEN; ++i) { q[i] = XS(X_LEGQ + side * 12 + i); qd[i] = XS(X_LEGQ + side * 12 + 6 + i); }
     V3 fl = mk(0, 0, 0), fend = mk(0, 0, 0);
-#ifdef BEZ_DOF_FORCE
-    if (DR) {   // the per-env gains and limits again, in front of their second use (as in front of pass 2: not kept alive across the barriers)
+    if constexpr (DF && DR) {   // the per-env gains and limits again, in front of their second use (as in front of pass 2: not kept alive across the barriers)
       int ei = e;
       asm volatile("" : "+v"(ei));
       load_joint_params<FIRST, LEN, DR>(P, ei, kps, kds, ms, lo, hi);
     }
-#define BEZ_DF_P3_ARGS , dfw, kps, kds, lo, hi, target, e, s, active
-#else
-#define BEZ_DF_P3_ARGS
-#endif
 #if BEZ_WS_SUB == 4
-    SV aend = wq_chain_pass3<FIRST, LEN, CL>(P, Q, p3, q, qd, mine, sel, fl, fend, lds, lane, keep, first, sc BEZ_DF_P3_ARGS);
+    SV aend = wq_chain_pass3<DF, FIRST, LEN, CL>(P, Q, p3, q, qd, mine, sel, fl, fend, lds, lane, keep, first, sc, dfw, kps, kds, lo, hi, target, e, s, active);
 #else
     SV a0 = xs_load_sv(lds, lane, X_A0);
-    SV aend = ws_chain_pass3<FIRST, LEN, true, CL>(P, a0, p3, q, qd, mine, sel, fl, fend, lds, lane, keep, first, sc BEZ_DF_P3_ARGS);
+    SV aend = ws_chain_pass3<DF, FIRST, LEN, true, CL>(P, a0, p3, q, qd, mine, sel, fl, fend, lds, lane, keep, first, sc, dfw, kps, kds, lo, hi, target, e, s, active);
 #endif
-#undef BEZ_DF_P3_ARGS
     if (mine && sel.link >= 0) { xs_store_v3(lds, lane, X_FL, fl); xs_store_v3(lds, lane, X_FL + 3, sel.xb); }
     if (keep) {
       if constexpr (CL) {  // the foot plate only feels the ball / the other leg; the ground acts on the four cleats
@@ -439,13 +429,11 @@ BEZ_DEV void leg_role(const Params& P, float* lds, int lane, int e, bool active,
 }
 
 // A 2-link chain (head / one arm) owned by a role: its state and the three passes, split at the barriers by the caller.
-template <int FIRST, int BLOCK_IA, bool CL, bool EXT = false>
+template <bool DF, int FIRST, int BLOCK_IA, bool CL, bool EXT = false>
 struct Chain2 {
   float q[2], qd[2], target[2], kps[2], kds[2], ms[2], lo[2], hi[2];
-  P3 p3[2];
-#ifdef BEZ_DOF_FORCE
-  uint32_t dfw;   // the two joints' decision bits (actuator record)
-#endif
+  P3<DF> p3[2];
+  DfWord<DF> dfw;   // the two joints' decision bits (actuator record)
   BodyContact bcn;
   Sym6 IAc; SV pAc;  // the chain's contribution as seen by the torso (also stored to its X_IA block)
   BEZ_DEV void up(const Params& P, const ChainDyn& D, float* lds, int lane, int e = 0, bool xp = false) {  // passes 1 + 2, contribution -> X_IA block
@@ -456,10 +444,8 @@ struct Chain2 {
     Sym6 Kc = sym6zero(); SV pc = svzero();
     ws_ground_points<FIRST + 1, CL>(P, D.mu, R.root_z, Ee, re, Ve, Kc, pc);
     Sym6 IA = sym6zero(); SV pA = svzero();
-#ifdef BEZ_DOF_FORCE
-    dfw = 0u;
-#endif
-    ws_chain_pass2<FIRST, 2, false>(P, D, kps, kds, lo, hi, q, qd, target, LI, pAl, Sl, cbl, Kc, pc, false, nosel, p3, IA, pA BEZ_DF_WORD_ARG);
+    dfw = DfWord<DF>{};
+    ws_chain_pass2<DF, FIRST, 2, false>(P, D, kps, kds, lo, hi, q, qd, target, LI, pAl, Sl, cbl, Kc, pc, false, nosel, p3, IA, pA, dfw);
     bcn = body_contact_of(Kc, pc);
     IAc = IA; pAc = pA;
     xs_store_sym6(lds, lane, X_IA + BLOCK_IA * 27, IA, pA);
@@ -467,27 +453,18 @@ struct Chain2 {
   BEZ_DEV void ext_done(const Params& P, int e, bool xp, bool active) {   // the chain's wrenches were for this launch only
     if (EXT && xp && active) { ext_clear(P, e, FIRST); ext_clear(P, e, FIRST + 1); }
   }
-#ifdef BEZ_DOF_FORCE
-#define BEZ_DF_C2_PARAMS , int e, int sub, bool active
-#define BEZ_DF_C2_ARGS , e, s, active
-#define BEZ_DF_C2_P3 , dfw, kps, kds, lo, hi, target, e, sub, active
-#else
-#define BEZ_DF_C2_PARAMS
-#define BEZ_DF_C2_ARGS
-#define BEZ_DF_C2_P3
-#endif
-  BEZ_DEV void down(const Params& P, float* lds, int lane, bool keep, bool first BEZ_DF_C2_PARAMS) {  // pass 3 + the chain-end contact row
+  BEZ_DEV void down(const Params& P, float* lds, int lane, bool keep, bool first, int e, int sub, bool active) {  // pass 3 + the chain-end contact row (e, sub, active: for the actuator record)
     BallSel nosel; nosel.link = -1; nosel.depth = 0.f; nosel.n = nosel.P = nosel.f0p = nosel.x = nosel.xb = mk(0, 0, 0); nosel.A = sym3zero();
     SV a0 = xs_load_sv(lds, lane, X_A0);
     V3 fl = mk(0, 0, 0), fend = mk(0, 0, 0);
-    SV ae = ws_chain_pass3<FIRST, 2, false, CL>(P, a0, p3, q, qd, false, nosel, fl, fend, lds, lane, keep, first, 0.f BEZ_DF_C2_P3);
+    SV ae = ws_chain_pass3<DF, FIRST, 2, false, CL>(P, a0, p3, q, qd, false, nosel, fl, fend, lds, lane, keep, first, 0.f, dfw, kps, kds, lo, hi, target, e, sub, active);
     if (keep) ws_cf_acc(lds, lane, link_body<CL>(FIRST + 1), cf_ground(P, body_contact_force(bcn, ae)), P.cf_w, first);
   }
 };
 
-template <bool PRE, bool POST, bool DR, bool CL, bool EXT = false>
+template <bool DF, bool PRE, bool POST, bool DR, bool CL, bool EXT = false>
 BEZ_DEV void head_role(const Params& P, float* lds, int lane, int e, bool active) {
-  Chain2<1, 2, CL, EXT> C;
+  Chain2<DF, 1, 2, CL, EXT> C;
   const bool xp = EXT && ext_pending(P, e);
   load_joints<1, 2, DR>(P, e, C.q, C.qd, C.kps, C.kds, C.ms, C.lo, C.hi);
   const ChainDyn D = load_chain_dyn<DR>(P, e);
@@ -517,7 +494,7 @@ BEZ_DEV void head_role(const Params& P, float* lds, int lane, int e, bool active
     ws_barrier();  // B1c: head and arm blocks are in LDS (role 4 sums them into block 2 before B2)
     ws_barrier();  // B2
     ws_barrier();  // B3
-    C.down(P, lds, lane, keep, first BEZ_DF_C2_ARGS);
+    C.down(P, lds, lane, keep, first, e, s, active);
     ws_barrier();  // B4
   }
   C.ext_done(P, e, xp, active);
@@ -529,10 +506,10 @@ BEZ_DEV void head_role(const Params& P, float* lds, int lane, int e, bool active
 // roles 4 / 5: the deepest ball<->leg-box candidate of one leg from this wave's own forward kinematics of that leg (window of
 // the leg's pass 1), then the arm of the same side as a chain of its own (window of the leg's pass 2); role 4 finally adds the head and
 // right-arm blocks to its own and leaves the sum in block 2, so that the root role reads three blocks.
-template <int LEG_FIRST, int ARM_FIRST, bool PRE, bool POST, bool DR, bool CL, bool EXT = false>
+template <bool DF, int LEG_FIRST, int ARM_FIRST, bool PRE, bool POST, bool DR, bool CL, bool EXT = false>
 BEZ_DEV void cand_arm_role(const Params& P, float* lds, int lane, int e, bool active, int side) {
   constexpr int ROLE = LEG_FIRST == 5 ? 4 : 5;
-  Chain2<ARM_FIRST, 3 + (LEG_FIRST == 5 ? 0 : 1), CL, EXT> C;
+  Chain2<DF, ARM_FIRST, 3 + (LEG_FIRST == 5 ? 0 : 1), CL, EXT> C;
   const bool xp = EXT && ext_pending(P, e);
   load_joints<ARM_FIRST, 2, DR>(P, e, C.q, C.qd, C.kps, C.kds, C.ms, C.lo, C.hi);
   const ChainDyn D = load_chain_dyn<DR>(P, e);
@@ -575,7 +552,7 @@ BEZ_DEV void cand_arm_role(const Params& P, float* lds, int lane, int e, bool ac
     }
     ws_barrier();  // B2
     ws_barrier();  // B3
-    C.down(P, lds, lane, keep, first BEZ_DF_C2_ARGS);
+    C.down(P, lds, lane, keep, first, e, s, active);
     ws_barrier();  // B4
   }
   C.ext_done(P, e, xp, active);
@@ -968,12 +945,11 @@ BEZ_DEV void root_role(const Params& P, float* lds, int lane, int e, bool active
 
 // ---- the kernel.  grid = ceil(N / 64) workgroups of 512 threads.
 // EXT: the instantiation that reads (and, behind the last substep, clears) the pending external wrenches of bez_sim_apply_body_forces
+// DF = STEP_DF (bez_kernels.h): a translation unit that defines BEZ_DOF_FORCE (bez_step_ws8_df.hip, bez_step_ws8q_df.hip) compiles the
+// recording kernel, under the name its own `#define step_kernel_ws8 step_kernel_ws8_df` gives it
 template <bool PRE, bool POST, bool DR, bool CL, bool EXT = false>
-#ifdef BEZ_DOF_FORCE
-__global__ __launch_bounds__(WS_BLOCK) void step_kernel_ws8(ParamsDF P) {
-#else
-__global__ __launch_bounds__(WS_BLOCK) void step_kernel_ws8(Params P) {
-#endif
+__global__ __launch_bounds__(WS_BLOCK) void step_kernel_ws8(StepParams<STEP_DF> P) {
+  constexpr bool DF = STEP_DF;
   __shared__ __attribute__((aligned(16))) float lds[WS_LDS_FLOATS];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -1014,21 +990,21 @@ __global__ __launch_bounds__(WS_BLOCK) void step_kernel_ws8(Params P) {
   }
   WS_STAMP(role, 18);
 #ifdef BEZ_AB_ONLY_ROLE   // offline diagnostics (tools/role_resources.sh): the register / spill figures of ONE role's code; never launched
-  if (BEZ_AB_ONLY_ROLE == 0) leg_role<5, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 0);
-  if (BEZ_AB_ONLY_ROLE == 1) leg_role<13, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 1);
-  if (BEZ_AB_ONLY_ROLE == 2) head_role<PRE, POST, DR, CL, EXT>(P, lds, lane, e, active);
+  if (BEZ_AB_ONLY_ROLE == 0) leg_role<DF, 5, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 0);
+  if (BEZ_AB_ONLY_ROLE == 1) leg_role<DF, 13, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 1);
+  if (BEZ_AB_ONLY_ROLE == 2) head_role<DF, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active);
   if (BEZ_AB_ONLY_ROLE == 3) root_role<PRE, POST, DR, CL, EXT>(P, lds, lane, e, active);
-  if (BEZ_AB_ONLY_ROLE == 4) cand_arm_role<5, 3, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 0);
-  if (BEZ_AB_ONLY_ROLE == 5) cand_arm_role<13, 11, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 1);
+  if (BEZ_AB_ONLY_ROLE == 4) cand_arm_role<DF, 5, 3, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 0);
+  if (BEZ_AB_ONLY_ROLE == 5) cand_arm_role<DF, 13, 11, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 1);
   if (BEZ_AB_ONLY_ROLE == 6) self_role<0, POST, DR, CL>(P, lds, lane, e, active);
   if (BEZ_AB_ONLY_ROLE == 7) self_role<1, POST, DR, CL>(P, lds, lane, e, active);
 #else
-  if (role == 0) leg_role<5, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 0);
-  else if (role == 1) leg_role<13, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 1);
-  else if (role == 2) head_role<PRE, POST, DR, CL, EXT>(P, lds, lane, e, active);
+  if (role == 0) leg_role<DF, 5, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 0);
+  else if (role == 1) leg_role<DF, 13, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 1);
+  else if (role == 2) head_role<DF, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active);
   else if (role == 3) root_role<PRE, POST, DR, CL, EXT>(P, lds, lane, e, active);
-  else if (role == 4) cand_arm_role<5, 3, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 0);
-  else if (role == 5) cand_arm_role<13, 11, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 1);
+  else if (role == 4) cand_arm_role<DF, 5, 3, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 0);
+  else if (role == 5) cand_arm_role<DF, 13, 11, PRE, POST, DR, CL, EXT>(P, lds, lane, e, active, 1);
   else if (role == 6) self_role<0, POST, DR, CL>(P, lds, lane, e, active);
   else self_role<1, POST, DR, CL>(P, lds, lane, e, active);
 #endif
@@ -1100,6 +1076,29 @@ __global__ __launch_bounds__(WS_BLOCK) void step_kernel_ws8(Params P) {
     }
   }
   WS_STAMP(role, 23);
+}
+
+// ---- host side: the launch ladder over ext, cleats and dr with (PRE, POST) = (PP, PP), for this translation unit's kernel: the plain one
+// (bez_step_ws8.hip, bez_step_ws8q.hip) or the recording one (bez_step_ws8_df.hip, bez_step_ws8q_df.hip; `raw`: the sim's raw actuator
+// buffer, df_record)
+template <bool DF, bool PP>
+void launch_ws8_pp(const StepParams<DF>& P, bool dr, bool cleats, bool ext, hipStream_t stream) {
+  static_assert(DF == STEP_DF, "the recording kernels are instantiated by the translation units that define BEZ_DOF_FORCE");
+  const dim3 grid((P.n + WS_ENVS - 1) / WS_ENVS), block(WS_BLOCK);
+  if (ext) {   // external wrenches (bez_sim_apply_body_forces): per-env parameter loads always on, null = defaults
+    if (cleats) hipLaunchKernelGGL((step_kernel_ws8<PP, PP, true, true, true>), grid, block, 0, stream, P);
+    else hipLaunchKernelGGL((step_kernel_ws8<PP, PP, true, false, true>), grid, block, 0, stream, P);
+  } else if (cleats) hipLaunchKernelGGL((step_kernel_ws8<PP, PP, true, true>), grid, block, 0, stream, P);
+  else if (dr) hipLaunchKernelGGL((step_kernel_ws8<PP, PP, true, false>), grid, block, 0, stream, P);
+  else hipLaunchKernelGGL((step_kernel_ws8<PP, PP, false, false>), grid, block, 0, stream, P);
+}
+template <bool DF>
+void launch_ws8(const Params& P0, float* raw, bool pre_post, bool dr, bool cleats, bool ext, hipStream_t stream) {
+  StepParams<DF> P;
+  static_cast<Params&>(P) = P0;
+  if constexpr (DF) P.dof_force = raw;
+  if (pre_post) launch_ws8_pp<DF, true>(P, dr, cleats, ext, stream);
+  else launch_ws8_pp<DF, false>(P, dr, cleats, ext, stream);
 }
 
 #undef XS

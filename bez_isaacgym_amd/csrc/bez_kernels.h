@@ -14,6 +14,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <type_traits>
 #include <utility>
 
 #include "../../include/bez_sim.h"
@@ -35,19 +36,18 @@ enum : int {
   F_COUNT = F_GOAL + 2
 };
 
-// ---- LDS slots per lane
-#ifdef BEZ_DOF_FORCE
-constexpr int P3_STRIDE = 23;                       // ... + the actuator record's decision word, reaction constant / ankle-stop torque, ankle-stop stiffness (df_record)
-#else
-constexpr int P3_STRIDE = 20;                       // UD(6) uD(1) S(6) cb(6) per joint + the leg<->leg contacts' share of uD (1)
-#endif
+// ---- LDS slots per lane.  DF = the kernel records the actuator quantities (BEZ_FLAG_DOF_FORCE; "actuator record" below): a template
+// parameter of the step kernels and of the device functions under them that the record reaches.
+// UD(6) uD(1) S(6) cb(6) per joint + the leg<->leg contacts' share of uD (1); DF: + the actuator record's decision word, reaction
+// constant / ankle-stop torque, ankle-stop stiffness (df_record)
+template <bool DF> constexpr int P3_STRIDE = DF ? 23 : 20;
 constexpr int LDS_P3 = 0;                           // 18 joints
-constexpr int LDS_HIT = LDS_P3 + BEZ_ND * P3_STRIDE;  // ground-point records, 8 floats each
+template <bool DF> constexpr int LDS_HIT = LDS_P3 + BEZ_ND * P3_STRIDE<DF>;  // ground-point records, 8 floats each
 constexpr int HIT_STRIDE = 8;                       // x(3) fn0 kn ct ftx0 fty0
-constexpr int LDS_STOP = LDS_HIT + BEZ_NPT * HIT_STRIDE;   // BEZ_FLAG_ANKLE_STOP: per leg 4 corner records (Ja, Jf, lam0) + the foot's normal (3)
+template <bool DF> constexpr int LDS_STOP = LDS_HIT<DF> + BEZ_NPT * HIT_STRIDE;   // BEZ_FLAG_ANKLE_STOP: per leg 4 corner records (Ja, Jf, lam0) + the foot's normal (3)
 constexpr int STOP_STRIDE = 15;
-constexpr int LDS_SLOTS = LDS_STOP + 2 * STOP_STRIDE;
-static_assert(LDS_SLOTS * BLOCK * 4 <= 160 * 1024, "LDS budget of the one-env-per-lane kernel");
+template <bool DF> constexpr int LDS_SLOTS = LDS_STOP<DF> + 2 * STOP_STRIDE;
+static_assert(LDS_SLOTS<false> * BLOCK * 4 <= 160 * 1024 && LDS_SLOTS<true> * BLOCK * 4 <= 160 * 1024, "LDS budget of the one-env-per-lane kernel");
 constexpr float STOP_KN = 2.0e5f, STOP_CN = 1.0e3f;   // calf <-> foot-plate contact (oracle: m_stop_kn / m_stop_cn defaults)
 
 // (DrState, the device-resident state of the domain randomisation: bez_dr_noise.h)
@@ -310,12 +310,14 @@ struct EnvDyn {
   float kp_scale[BEZ_ND], kd_scale[BEZ_ND], mass_scale[BEZ_NL], lo[BEZ_ND], hi[BEZ_ND];
 };
 
-#ifdef BEZ_DOF_FORCE
-// ---- actuator record (BEZ_FLAG_DOF_FORCE; include/bez_sim.h "Actuator tensors").  The translation units built with BEZ_DOF_FORCE
-// (bez_step_*_df.hip) compile the same kernels under other names with this code in them; their kernel argument is a Params with the raw
+// ---- actuator record (BEZ_FLAG_DOF_FORCE; include/bez_sim.h "Actuator tensors").  The step kernels are templates over DF; the
+// instantiations with DF = true live in translation units of their own (bez_step_*_df.hip) behind entry points of their own
+// (step_kernel_df, step_kernel_ws8_df), whose kernel argument is a Params with the raw
 // buffer behind it: [substep][quantity: drive torque, net joint force, status word][dof][env], written by the env's owning lane right
 // behind pass 3 of each joint (plain stores, nothing loaded or waited for); bez_sim_refresh_actuator_tensors reduces it.
+// df_buf / df_record are reached from DF = true code only: there P is the Params part of a ParamsDF.
 struct ParamsDF : Params { float* dof_force; };
+template <bool DF> using StepParams = std::conditional_t<DF, ParamsDF, Params>;   // the kernel argument of a step kernel
 BEZ_DEV float* df_buf(const Params& P) { return static_cast<const ParamsDF&>(P).dof_force; }
 // the decision word pass 2 hands to pass 3 (the status bits of BEZ_ACTUATOR_STATUS)
 constexpr uint32_t DF_SAT_POS = 1u, DF_SAT_NEG = 2u, DF_LOCK_POS = 4u, DF_LOCK_NEG = 8u, DF_LOCK = DF_LOCK_POS | DF_LOCK_NEG;
@@ -338,18 +340,13 @@ BEZ_DEV void df_record(const Params& P, int e, int sub, int d, uint32_t bits, fl
   float* o = df_buf(P) + ((size_t)sub * 3 * BEZ_ND + d) * n + e;
   o[0] = drive; o[(size_t)BEZ_ND * n] = net; o[(size_t)2 * BEZ_ND * n] = __uint_as_float(bits);
 }
-#define BEZ_DF_JOINT_OUT , uint32_t& dfb, float& dfc0
-#define BEZ_DF_STOP_PARAMS float stop_tau, float stop_k, uint32_t& dfb, float& dfc0
-#define BEZ_DF_SUB_PARAM , int sub = 0
-#define BEZ_DF_DOWN_PARAMS , const EnvDyn& D, const float* target, int sub
-#define BEZ_DF_DOWN_ARGS , D, target, sub
-#else
-#define BEZ_DF_JOINT_OUT
-#define BEZ_DF_STOP_PARAMS float stop_tau = 0.f, float stop_k = 0.f
-#define BEZ_DF_SUB_PARAM
-#define BEZ_DF_DOWN_PARAMS
-#define BEZ_DF_DOWN_ARGS
-#endif
+// What exists for the record alone between pass 2 and pass 3, as types that are empty without it:
+// one joint's decisions (the DF_* bits) and c0 = the part of a locked joint's reaction that joint_terms / joint_scalar know
+template <bool DF> struct DfJoint {};
+template <> struct DfJoint<true> { uint32_t bits; float c0; };
+// a chain's decision bits in one word, four per joint (the 8-role-wave kernels, whose chains keep pass 3's operands in registers)
+template <bool DF> struct DfWord {};
+template <> struct DfWord<true> { uint32_t w; };
 
 // ---- contact: implicit spring-damper at a point against the ground plane z = 0.
 // Folds the point's implicit stiffness into (IA, pA) of its body and returns the hit record.
@@ -379,13 +376,15 @@ BEZ_DEV V3 hit_force(const Params& P, const Hit& h, SV acc) {
   V3 ap = point_of(acc, h.x);
   return mk(fmaf(-P.h * h.ct, ap.x, h.ftx0), fmaf(-P.h * h.ct, ap.y, h.fty0), fmaf(-h.kn, ap.z, h.fn0));
 }
+template <bool DF>
 BEZ_DEV void lds_store_hit(float* lds, int lane, int idx, const Hit& h) {
-  float* p = lds + (size_t)(LDS_HIT + idx * HIT_STRIDE) * BLOCK + lane;
+  float* p = lds + (size_t)(LDS_HIT<DF> + idx * HIT_STRIDE) * BLOCK + lane;
   p[0 * BLOCK] = h.x.x; p[1 * BLOCK] = h.x.y; p[2 * BLOCK] = h.x.z; p[3 * BLOCK] = h.fn0;
   p[4 * BLOCK] = h.kn; p[5 * BLOCK] = h.ct; p[6 * BLOCK] = h.ftx0; p[7 * BLOCK] = h.fty0;
 }
+template <bool DF>
 BEZ_DEV Hit lds_load_hit(const float* lds, int lane, int idx) {
-  const float* p = lds + (size_t)(LDS_HIT + idx * HIT_STRIDE) * BLOCK + lane;
+  const float* p = lds + (size_t)(LDS_HIT<DF> + idx * HIT_STRIDE) * BLOCK + lane;
   Hit h;
   h.x = mk(p[0 * BLOCK], p[1 * BLOCK], p[2 * BLOCK]); h.fn0 = p[3 * BLOCK];
   h.kn = p[4 * BLOCK]; h.ct = p[5 * BLOCK]; h.ftx0 = p[6 * BLOCK]; h.fty0 = p[7 * BLOCK];
@@ -644,7 +643,7 @@ BEZ_DEV void add_link_inertia(Sym6& IA, const LinkInertia& I) {
 }
 
 // ground points of link L (compile-time filtered), using the link's frame and velocity
-template <int L, bool CL = false>
+template <bool DF, int L, bool CL = false>
 BEZ_DEV void link_ground_points(const Params& P, float mu, float root_z, const M3& E, V3 r, SV V, Sym6& IA, SV& pA,
                                 float* lds, int lane, bool keep) {
 #pragma unroll
@@ -653,29 +652,29 @@ BEZ_DEV void link_ground_points(const Params& P, float mu, float root_z, const M
       V3 pl = mk(pt_pos_of<CL>(P, i, 0), pt_pos_of<CL>(P, i, 1), pt_pos_of<CL>(P, i, 2));
       V3 x = r + mul(E, pl);
       Hit hit = ground_contact(P, P.kn, P.cn, mu, x, root_z + x.z, V, IA, pA);
-      if (keep) lds_store_hit(lds, lane, i, hit);
+      if (keep) lds_store_hit<DF>(lds, lane, i, hit);
     }
   }
 }
-template <int L>
+template <bool DF, int L>
 BEZ_DEV V3 link_ground_forces(const Params& P, SV acc, const float* lds, int lane) {
   V3 f = mk(0, 0, 0);
 #pragma unroll
   for (int i = 0; i < BEZ_NPT; ++i) {
     if (BEZ_PT_LINK[i] == L) {
-      Hit hit = lds_load_hit(lds, lane, i);
+      Hit hit = lds_load_hit<DF>(lds, lane, i);
       if (hit.kn > 0.f) f = f + hit_force(P, hit, acc);
     }
   }
   return f;
 }
 // cleats: every ground point of the foot link reports into its own cleat body's row
-template <int L>
+template <bool DF, int L>
 BEZ_DEV void link_ground_forces_cleats(const Params& P, SV acc, const float* lds, int lane, const CfOut& co, bool first) {
 #pragma unroll
   for (int i = 0; i < BEZ_NPT; ++i) {
     if (BEZ_PT_LINK[i] == L) {
-      Hit hit = lds_load_hit(lds, lane, i);
+      Hit hit = lds_load_hit<DF>(lds, lane, i);
       V3 f = hit.kn > 0.f ? cf_ground(P, hit_force(P, hit, acc)) : mk(0, 0, 0);
       cf_accum(co, BEZ_PT_BODY_CL[i], f, P.cf_w, first);
     }
@@ -742,9 +741,9 @@ BEZ_DEV constexpr bool link_has_xpoints(int l) {
 // forms qdd = w - g U.(a_parent + c)) and the held-parent acceleration qdd_hp = w - g U.c the predictors work with.  A joint whose
 // held-parent rate would end the substep beyond the speed limit (kick_env.py:327) is a prescribed-rate joint: g = 0, w = the
 // acceleration that puts it ON the limit -- same recursion, and the reaction reaches the parent through pA (oracle: dynamics_x).
-template <int L>
+template <int L, bool DF>
 BEZ_DEV void joint_terms(const Params& P, float kp_scale, float kd_scale, float lo, float hi, float q, float qd, float target, const Sym6& IA, SV pA,
-                         SV S, SV cb, SV& U, float& g, float& w, float& qdd_hp, BEZ_DF_STOP_PARAMS) {
+                         SV S, SV cb, SV& U, float& g, float& w, float& qdd_hp, float stop_tau, float stop_k, DfJoint<DF>& df) {
   U = mul(IA, S);
   float J = dot(S, U) + P.armature;
   float kp = P.kp * kp_scale, kdm = P.kd * kd_scale;
@@ -772,19 +771,19 @@ BEZ_DEV void joint_terms(const Params& P, float kp_scale, float kd_scale, float 
   const float ahi = (P.vel_limit - qd) * P.inv_h, alo = (-P.vel_limit - qd) * P.inv_h;
   const float fix = fminf(fmaxf(qdd_hp, alo), ahi);
   const bool lock = fix != qdd_hp;
-#ifdef BEZ_DOF_FORCE
-  // the decisions of this joint, and the part of a locked joint's reaction that is known here: S.pA + (J + armature) qdd (the caller adds U.(a_parent + c))
-  dfb = (tau_drive > P.effort ? DF_SAT_POS : 0u) | (tau_drive < -P.effort ? DF_SAT_NEG : 0u) | (lock ? (fix > qdd_hp ? DF_LOCK_NEG : DF_LOCK_POS) : 0u);
-  dfc0 = fmaf(J, fix, sp);
-#endif
+  if constexpr (DF) {
+    // the decisions of this joint, and the part of a locked joint's reaction that is known here: S.pA + (J + armature) qdd (the caller adds U.(a_parent + c))
+    df.bits = (tau_drive > P.effort ? DF_SAT_POS : 0u) | (tau_drive < -P.effort ? DF_SAT_NEG : 0u) | (lock ? (fix > qdd_hp ? DF_LOCK_NEG : DF_LOCK_POS) : 0u);
+    df.c0 = fmaf(J, fix, sp);
+  }
   w = lock ? fix : w; g = lock ? 0.f : g; qdd_hp = fix;
 }
 
 // The scalar part of joint_terms for the lane-group kernel (bez_step_ws8q.hip), which forms Jraw = S.(IA S), sp = S.pA and
 // ucb = (IA S).cb across a quad of lanes; the same arithmetic in the same order as above.
-template <int L>
+template <int L, bool DF>
 BEZ_DEV void joint_scalar(const Params& P, float kp_scale, float kd_scale, float lo, float hi, float q, float qd, float target, float Jraw, float sp, float ucb,
-                          float& g, float& w, float& qdd_hp BEZ_DF_JOINT_OUT) {
+                          float& g, float& w, float& qdd_hp, DfJoint<DF>& df) {
   float J = Jraw + P.armature;
   float kp = P.kp * kp_scale, kdm = P.kd * kd_scale;
   float tau_pd0 = fmaf(kp, target - q - P.h * qd, -kdm * qd);
@@ -807,11 +806,11 @@ BEZ_DEV void joint_scalar(const Params& P, float kp_scale, float kd_scale, float
   const float ahi = (P.vel_limit - qd) * P.inv_h, alo = (-P.vel_limit - qd) * P.inv_h;
   const float fix = fminf(fmaxf(qdd_hp, alo), ahi);
   const bool lock = fix != qdd_hp;
-#ifdef BEZ_DOF_FORCE
-  // the decisions of this joint, and the part of a locked joint's reaction that is known here: S.pA + (J + armature) qdd (the caller adds U.(a_parent + c))
-  dfb = (tau_drive > P.effort ? DF_SAT_POS : 0u) | (tau_drive < -P.effort ? DF_SAT_NEG : 0u) | (lock ? (fix > qdd_hp ? DF_LOCK_NEG : DF_LOCK_POS) : 0u);
-  dfc0 = fmaf(J, fix, sp);
-#endif
+  if constexpr (DF) {
+    // the decisions of this joint, and the part of a locked joint's reaction that is known here: S.pA + (J + armature) qdd (the caller adds U.(a_parent + c))
+    df.bits = (tau_drive > P.effort ? DF_SAT_POS : 0u) | (tau_drive < -P.effort ? DF_SAT_NEG : 0u) | (lock ? (fix > qdd_hp ? DF_LOCK_NEG : DF_LOCK_POS) : 0u);
+    df.c0 = fmaf(J, fix, sp);
+  }
   w = lock ? fix : w; g = lock ? 0.f : g; qdd_hp = fix;
 }
 
@@ -832,7 +831,7 @@ BEZ_DEV void static_for(F&& f) { static_for_impl(std::make_integer_sequence<int,
 
 // ---- passes 1+2 of one serial chain FIRST..FIRST+LEN-1 hanging off the torso.  Accumulates the chain's
 // articulated inertia / bias into the torso's (IA0, pA0) and stages pass-3 data in LDS.
-template <int FIRST, int LEN, bool CL, bool EXT = false>
+template <bool DF, int FIRST, int LEN, bool CL, bool EXT = false>
 BEZ_DEV void chain_up(const Params& P, const EnvDyn& D, const EnvState& S, const float* target, const M3& E0, SV V0,
                       const BallBody& ball, V3 bc, BallSel& sel, const SV* selfw, Sym6& IA0, SV& pA0, SV& pS0, SelfSums& Z, float* lds, int lane, bool keep, int e,
                       bool xp = false) {
@@ -867,7 +866,7 @@ BEZ_DEV void chain_up(const Params& P, const EnvDyn& D, const EnvState& S, const
       const float ztop = (float)(BEZ_BOX_CENTER[bff][2] + BEZ_BOX_HALF[bff][2]);
       const V3 nf = col(E, 2);   // (E, r are the foot's after pass 1)
       const float kimp = fmaf(P.h * P.h, STOP_KN, P.h * STOP_CN);
-      float* rec = lds + (size_t)(LDS_STOP + side * STOP_STRIDE) * BLOCK + lane;
+      float* rec = lds + (size_t)(LDS_STOP<DF> + side * STOP_STRIDE) * BLOCK + lane;
       int k = 0;
 #pragma unroll
       for (int cx = -1; cx <= 1; cx += 2) {
@@ -896,7 +895,7 @@ BEZ_DEV void chain_up(const Params& P, const EnvDyn& D, const EnvState& S, const
   SV pA = svzero();
   SV pS = svzero();  // leg<->leg contact wrenches (as bias forces), propagated next to pA (the predictors do not see them); their common scale comes later
   SV wsub = svzero();  // the same, summed over the subtree WITHOUT the projections: S . wsub = the contacts' generalised force on the joint
-  link_ground_points<FIRST + LEN - 1, CL>(P, D.mu, S.root_pos.z, E, r, V, IA, pA, lds, lane, keep);
+  link_ground_points<DF, FIRST + LEN - 1, CL>(P, D.mu, S.root_pos.z, E, r, V, IA, pA, lds, lane, keep);
   // pass 2: tip -> root
   static_for<LEN>([&](auto I) {
     constexpr int i = LEN - 1 - decltype(I)::value;
@@ -912,36 +911,35 @@ BEZ_DEV void chain_up(const Params& P, const EnvDyn& D, const EnvState& S, const
     }
     if constexpr (!CL && link_has_xpoints(L)) { if (P.xhit) link_xpoints_fold<L>(P, e, IA, pA); }
     SV U; float Dinv, uD, qhp;
-#ifdef BEZ_DOF_FORCE
-    uint32_t dfb; float dfc0;
-    const float dstop_tau = (LEG && i >= 4) ? stop_tau[i >= 4 ? i - 4 : 0] : 0.f, dstop_k = (LEG && i >= 4) ? stop_k[i >= 4 ? i - 4 : 0] : 0.f;
+    DfJoint<DF> df;
+    // the ankle stop's share of this joint: read in front of joint_terms' other arguments where the record stores it as well, behind them
+    // elsewhere (the orders the two builds were tuned with: either way round one of them allocates its registers differently)
+    auto stop_of = [&](const float* a) { return (LEG && i >= 4) ? a[i >= 4 ? i - 4 : 0] : 0.f; };
+    float dstop_tau = 0.f, dstop_k = 0.f;
+    if constexpr (DF) { dstop_tau = stop_of(stop_tau); dstop_k = stop_of(stop_k); }
     joint_terms<L>(P, D.kp_scale[L - 1], D.kd_scale[L - 1], D.lo[L - 1], D.hi[L - 1], S.q[L - 1], S.qd[L - 1], target[L - 1], IA, pA, Sl[i], cbl[i], U,
-                   Dinv, uD, qhp, dstop_tau, dstop_k, dfb, dfc0);
-#else
-    joint_terms<L>(P, D.kp_scale[L - 1], D.kd_scale[L - 1], D.lo[L - 1], D.hi[L - 1], S.q[L - 1], S.qd[L - 1], target[L - 1], IA, pA, Sl[i], cbl[i], U,
-                   Dinv, uD, qhp, (LEG && i >= 4) ? stop_tau[i >= 4 ? i - 4 : 0] : 0.f, (LEG && i >= 4) ? stop_k[i >= 4 ? i - 4 : 0] : 0.f);
-#endif
+                   Dinv, uD, qhp, DF ? dstop_tau : stop_of(stop_tau), DF ? dstop_k : stop_of(stop_k), df);
     SV UD = U * Dinv;
     const float duD = -dot(Sl[i], pS) * Dinv;
     if constexpr (FIRST == 5 || FIRST == 13) {   // only the legs carry leg<->leg contacts
       const float tq = dot(Sl[i], wsub);         // (sign: wsub holds bias forces = minus the wrenches; tq enters squared and times am's own sign convention below)
       Z.as = fmaf(tq * tq, Dinv, Z.as); Z.am = fmaf(-tq, qhp, Z.am);
     }
-    float* p3 = lds + (size_t)(LDS_P3 + (L - 1) * P3_STRIDE) * BLOCK + lane;
+    float* p3 = lds + (size_t)(LDS_P3 + (L - 1) * P3_STRIDE<DF>) * BLOCK + lane;
     p3[0 * BLOCK] = UD.a.x; p3[1 * BLOCK] = UD.a.y; p3[2 * BLOCK] = UD.a.z; p3[3 * BLOCK] = UD.l.x; p3[4 * BLOCK] = UD.l.y; p3[5 * BLOCK] = UD.l.z;
     p3[6 * BLOCK] = uD;
     p3[7 * BLOCK] = Sl[i].a.x; p3[8 * BLOCK] = Sl[i].a.y; p3[9 * BLOCK] = Sl[i].a.z; p3[10 * BLOCK] = Sl[i].l.x; p3[11 * BLOCK] = Sl[i].l.y; p3[12 * BLOCK] = Sl[i].l.z;
     p3[13 * BLOCK] = cbl[i].a.x; p3[14 * BLOCK] = cbl[i].a.y; p3[15 * BLOCK] = cbl[i].a.z; p3[16 * BLOCK] = cbl[i].l.x; p3[17 * BLOCK] = cbl[i].l.y; p3[18 * BLOCK] = cbl[i].l.z;
     p3[19 * BLOCK] = duD;
-#ifdef BEZ_DOF_FORCE
-    // actuator record: a locked joint (1/D = 0: the six U/D slots and the contacts' share would hold zeros) hands pass 3 U itself and
-    // S.pS instead -- chain_down reads them as zeros for the dynamics -- with its decision word and the reaction's known part
-    if (dfb & DF_LOCK) {
-      p3[0 * BLOCK] = U.a.x; p3[1 * BLOCK] = U.a.y; p3[2 * BLOCK] = U.a.z; p3[3 * BLOCK] = U.l.x; p3[4 * BLOCK] = U.l.y; p3[5 * BLOCK] = U.l.z;
-      p3[19 * BLOCK] = dot(Sl[i], pS);
+    if constexpr (DF) {
+      // actuator record: a locked joint (1/D = 0: the six U/D slots and the contacts' share would hold zeros) hands pass 3 U itself and
+      // S.pS instead -- chain_down reads them as zeros for the dynamics -- with its decision word and the reaction's known part
+      if (df.bits & DF_LOCK) {
+        p3[0 * BLOCK] = U.a.x; p3[1 * BLOCK] = U.a.y; p3[2 * BLOCK] = U.a.z; p3[3 * BLOCK] = U.l.x; p3[4 * BLOCK] = U.l.y; p3[5 * BLOCK] = U.l.z;
+        p3[19 * BLOCK] = dot(Sl[i], pS);
+      }
+      p3[20 * BLOCK] = __uint_as_float(df.bits); p3[21 * BLOCK] = (df.bits & DF_LOCK) ? df.c0 : dstop_tau; p3[22 * BLOCK] = dstop_k;
     }
-    p3[20 * BLOCK] = __uint_as_float(dfb); p3[21 * BLOCK] = (dfb & DF_LOCK) ? dfc0 : dstop_tau; p3[22 * BLOCK] = dstop_k;
-#endif
     // Ia = IA - U U^T / D ;  pa = pA + Ia c + U u / D
     add_outer(IA, U, -Dinv);
     pA = pA + mul(IA, cbl[i]) + U * uD;
@@ -954,9 +952,10 @@ BEZ_DEV void chain_up(const Params& P, const EnvDyn& D, const EnvState& S, const
 
 // ---- pass 3 of one chain: joint accelerations from the torso acceleration; integrates the joints in
 // place (semi-implicit Euler) and resolves contact forces on the way.  sc = the leg<->leg contacts' common scale.
-template <int FIRST, int LEN, bool CL>
+// D, target, sub (the substep's index): read by the actuator record only
+template <bool DF, int FIRST, int LEN, bool CL>
 BEZ_DEV void chain_down(const Params& P, EnvState& S, SV a0, float sc, BallSel& sel, const V3* selfcf, V3& ball_link_force, CfOut& co, const float* lds,
-                        int lane, bool keep, bool first, int e BEZ_DF_DOWN_PARAMS) {
+                        int lane, bool keep, bool first, int e, const EnvDyn& D, const float* target, int sub) {
   SV a = a0;
   constexpr int Lend = FIRST + LEN - 1;
   constexpr bool LEG = (FIRST == 5 || FIRST == 13);
@@ -966,24 +965,23 @@ BEZ_DEV void chain_down(const Params& P, EnvState& S, SV a0, float sc, BallSel& 
   static_for<LEN>([&](auto I) {
     constexpr int i = decltype(I)::value;
     constexpr int L = FIRST + i;
-    const float* p3 = lds + (size_t)(LDS_P3 + (L - 1) * P3_STRIDE) * BLOCK + lane;
+    const float* p3 = lds + (size_t)(LDS_P3 + (L - 1) * P3_STRIDE<DF>) * BLOCK + lane;
     SV UD = mksv(mk(p3[0 * BLOCK], p3[1 * BLOCK], p3[2 * BLOCK]), mk(p3[3 * BLOCK], p3[4 * BLOCK], p3[5 * BLOCK]));
     float uD = fmaf(sc, p3[19 * BLOCK], p3[6 * BLOCK]);
     SV Sj = mksv(mk(p3[7 * BLOCK], p3[8 * BLOCK], p3[9 * BLOCK]), mk(p3[10 * BLOCK], p3[11 * BLOCK], p3[12 * BLOCK]));
     SV cb = mksv(mk(p3[13 * BLOCK], p3[14 * BLOCK], p3[15 * BLOCK]), mk(p3[16 * BLOCK], p3[17 * BLOCK], p3[18 * BLOCK]));
     SV ap = a + cb;
-#ifdef BEZ_DOF_FORCE
-    const uint32_t dfb = __float_as_uint(p3[20 * BLOCK]);
-    const float dUa = dot(UD, ap);   // a locked joint's slots hold U: U.(a_parent + c), the rest of its reaction
-    float qdd = (dfb & DF_LOCK) ? p3[6 * BLOCK] : uD - dUa;
-    {
+    float qdd;
+    if constexpr (DF) {
+      const uint32_t dfb = __float_as_uint(p3[20 * BLOCK]);
+      const float dUa = dot(UD, ap);   // a locked joint's slots hold U: U.(a_parent + c), the rest of its reaction
+      qdd = (dfb & DF_LOCK) ? p3[6 * BLOCK] : uD - dUa;
       const bool lk = (dfb & DF_LOCK) != 0u;
       df_record(P, e, sub, L - 1, dfb, D.kp_scale[L - 1], D.kd_scale[L - 1], D.lo[L - 1], D.hi[L - 1], S.q[L - 1], S.qd[L - 1], target[L - 1], qdd,
                 fmaf(sc, p3[19 * BLOCK], p3[21 * BLOCK] + dUa), lk ? 0.f : p3[21 * BLOCK], lk ? 0.f : p3[22 * BLOCK]);
+    } else {
+      qdd = uD - dot(UD, ap);
     }
-#else
-    float qdd = uD - dot(UD, ap);
-#endif
     a = ap + Sj * qdd;
     float v = fmaf(P.h, qdd, S.qd[L - 1]);   // the speed limit is inside the dynamics (joint_terms): no rate is edited here
     S.qd[L - 1] = v;
@@ -1010,7 +1008,7 @@ BEZ_DEV void chain_down(const Params& P, EnvState& S, SV a0, float sc, BallSel& 
       if constexpr (i == 4) qdd_ankle = qdd;
       if constexpr (i == 5) {
         if (P.flags & BEZ_FLAG_ANKLE_STOP) {
-          const float* rec = lds + (size_t)(LDS_STOP + (FIRST == 5 ? 0 : 1) * STOP_STRIDE) * BLOCK + lane;
+          const float* rec = lds + (size_t)(LDS_STOP<DF> + (FIRST == 5 ? 0 : 1) * STOP_STRIDE) * BLOCK + lane;
           const float kimp = fmaf(P.h * P.h, STOP_KN, P.h * STOP_CN);
           float lam = 0.f;
 #pragma unroll
@@ -1035,9 +1033,9 @@ BEZ_DEV void chain_down(const Params& P, EnvState& S, SV a0, float sc, BallSel& 
     constexpr bool foot = (Lend == BEZ_LFOOT_LINK || Lend == BEZ_RFOOT_LINK);
     if constexpr (CL && foot) {  // the foot plate itself only feels the ball / the other leg; the ground acts on the cleats
       cf_accum(co, link_body<CL>(Lend), fend, P.cf_w, first);
-      link_ground_forces_cleats<Lend>(P, a, lds, lane, co, first);
+      link_ground_forces_cleats<DF, Lend>(P, a, lds, lane, co, first);
     } else {
-      V3 f = fend + cf_ground(P, link_ground_forces<Lend>(P, a, lds, lane));
+      V3 f = fend + cf_ground(P, link_ground_forces<DF, Lend>(P, a, lds, lane));
       if constexpr (Lend == BEZ_LFOOT_LINK) co.lf = first ? f * P.cf_w : fma3(f, P.cf_w, co.lf);
       else if constexpr (Lend == BEZ_RFOOT_LINK) co.rf = first ? f * P.cf_w : fma3(f, P.cf_w, co.rf);
       else cf_accum(co, link_body<CL>(Lend), f, P.cf_w, first);
@@ -1060,9 +1058,10 @@ BEZ_DEV void quat_integrate(float q[4], V3 w, float h) {
 // ---- one substep of the articulated-body dynamics for this lane's env.  When `keep` the net contact force per body of
 // this substep is accumulated (`first`: it starts the mean): foot rows in `co`, all other rows in HBM.
 // EXT: `xp` = this env has external wrenches pending (bez_sim_apply_body_forces): they enter every link's bias force and the ball's.
-template <bool CL, bool EXT = false>
+// `sub` = the substep's index in the control step (the actuator record's row)
+template <bool DF, bool CL, bool EXT = false>
 BEZ_DEV void substep(const Params& P, const EnvDyn& D, EnvState& S, const float* target, CfOut& co, float* lds, int lane, bool keep, bool first, int e,
-                     bool xp = false BEZ_DF_SUB_PARAM) {
+                     bool xp, int sub) {
   const M3 E0 = quat_to_mat(S.rq[0], S.rq[1], S.rq[2], S.rq[3]);
   const SV V0 = mksv(S.root_ang, S.root_lin);
   const V3 bc = S.ball_pos - S.root_pos;  // ball centre rel. O
@@ -1112,18 +1111,18 @@ BEZ_DEV void substep(const Params& P, const EnvDyn& D, EnvState& S, const float*
     link_inertia<0, CL>(D.mass_scale[0], D.g, E0, mk(0, 0, 0), V0, I0, pA0);
     if constexpr (EXT) { if (xp) pA0 = pA0 - ext_wrench(P, e, 0, E0, mk(0, 0, 0)); }
     add_link_inertia(IA0, I0);
-    link_ground_points<0, CL>(P, D.mu, S.root_pos.z, E0, mk(0, 0, 0), V0, IA0, pA0, lds, lane, keep);
+    link_ground_points<DF, 0, CL>(P, D.mu, S.root_pos.z, E0, mk(0, 0, 0), V0, IA0, pA0, lds, lane, keep);
     if (sel.link == 0) {
       ball_link_contact(P, D.mu, S.ball_ang, S.ball_lin, ball, bc, V0, sel);
       if (sel.link == 0) { add_point_stiffness(IA0, sel.x, sel.A); pA0 = pA0 - wrench_at(sel.x, sel.f0p); }
     }
   }
   SV pS0 = svzero(); SelfSums Z; Z.am = Z.as = 0.f; Z.f2 = selff2;
-  chain_up<1, 2, CL, EXT>(P, D, S, target, E0, V0, ball, bc, sel, selfw, IA0, pA0, pS0, Z, lds, lane, keep, e, xp);    // neck, head
-  chain_up<3, 2, CL, EXT>(P, D, S, target, E0, V0, ball, bc, sel, selfw, IA0, pA0, pS0, Z, lds, lane, keep, e, xp);    // left arm
-  chain_up<5, 6, CL, EXT>(P, D, S, target, E0, V0, ball, bc, sel, selfw, IA0, pA0, pS0, Z, lds, lane, keep, e, xp);    // left leg
-  chain_up<11, 2, CL, EXT>(P, D, S, target, E0, V0, ball, bc, sel, selfw, IA0, pA0, pS0, Z, lds, lane, keep, e, xp);   // right arm
-  chain_up<13, 6, CL, EXT>(P, D, S, target, E0, V0, ball, bc, sel, selfw, IA0, pA0, pS0, Z, lds, lane, keep, e, xp);   // right leg
+  chain_up<DF, 1, 2, CL, EXT>(P, D, S, target, E0, V0, ball, bc, sel, selfw, IA0, pA0, pS0, Z, lds, lane, keep, e, xp);    // neck, head
+  chain_up<DF, 3, 2, CL, EXT>(P, D, S, target, E0, V0, ball, bc, sel, selfw, IA0, pA0, pS0, Z, lds, lane, keep, e, xp);    // left arm
+  chain_up<DF, 5, 6, CL, EXT>(P, D, S, target, E0, V0, ball, bc, sel, selfw, IA0, pA0, pS0, Z, lds, lane, keep, e, xp);    // left leg
+  chain_up<DF, 11, 2, CL, EXT>(P, D, S, target, E0, V0, ball, bc, sel, selfw, IA0, pA0, pS0, Z, lds, lane, keep, e, xp);   // right arm
+  chain_up<DF, 13, 6, CL, EXT>(P, D, S, target, E0, V0, ball, bc, sel, selfw, IA0, pA0, pS0, Z, lds, lane, keep, e, xp);   // right leg
   // the leg<->leg contacts' common scale (known before the root solve), then their share of the torso's bias
   const float sc = self_scale(P, Z);
   pA0 = pA0 + pS0 * sc;
@@ -1135,13 +1134,13 @@ BEZ_DEV void substep(const Params& P, const EnvDyn& D, EnvState& S, const float*
   {
     V3 f0 = mk(0, 0, 0);
     if (sel.link == 0) { fl = sel.f0p - mul(sel.A, point_of(a0, sel.x)); f0 = cf_along(P, fl, sel.n); }
-    if (keep) cf_accum(co, 0, f0 + cf_ground(P, link_ground_forces<0>(P, a0, lds, lane)), P.cf_w, first);
+    if (keep) cf_accum(co, 0, f0 + cf_ground(P, link_ground_forces<DF, 0>(P, a0, lds, lane)), P.cf_w, first);
   }
-  chain_down<1, 2, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e BEZ_DF_DOWN_ARGS);
-  chain_down<3, 2, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e BEZ_DF_DOWN_ARGS);
-  chain_down<5, 6, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e BEZ_DF_DOWN_ARGS);
-  chain_down<11, 2, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e BEZ_DF_DOWN_ARGS);
-  chain_down<13, 6, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e BEZ_DF_DOWN_ARGS);
+  chain_down<DF, 1, 2, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e, D, target, sub);
+  chain_down<DF, 3, 2, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e, D, target, sub);
+  chain_down<DF, 5, 6, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e, D, target, sub);
+  chain_down<DF, 11, 2, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e, D, target, sub);
+  chain_down<DF, 13, 6, CL>(P, S, a0, sc, sel, selfcf, fl, co, lds, lane, keep, first, e, D, target, sub);
   // (f) ball: Mb ab = -pb - Jb^T fl (+ its external wrench about the centre: the contact operands above did not foresee it, as they do
   //     not foresee the leg<->leg forces)
   SV fb_ext = svzero();
@@ -1391,13 +1390,19 @@ BEZ_DEV void env_observe_reward(const Params& P, const EnvState& S, CfOut& co, f
 // ---- the fused kernel: PRE (targets) / SIM (substeps) / POST (bookkeeping, reset, obs, reward)
 // EXT (with SIM): the instantiation that reads the pending external wrenches of bez_sim_apply_body_forces and clears them after the
 // last substep (a sim runs these once it has called that function: bez_sim.hip)
-template <bool PRE, bool SIM, bool POST, bool DR, bool CL, bool EXT = false>
+// The entry point is the one place where the preprocessor still selects the recording build: a translation unit that defines BEZ_DOF_FORCE
+// (bez_step_*_df.hip) compiles this kernel with DF = true, a ParamsDF argument and, by its own `#define step_kernel step_kernel_df`, under
+// the recording kernel's name.  Two thin entry points over one body template compile to other machine code than this (the body is then
+// optimised once on its own and once more in its caller: DESIGN.md 4.3d), so the kernel's text stays the entry point's.
 #ifdef BEZ_DOF_FORCE
-__global__ __launch_bounds__(BLOCK) void step_kernel(ParamsDF P) {
+constexpr bool STEP_DF = true;
 #else
-__global__ __launch_bounds__(BLOCK) void step_kernel(Params P) {
+constexpr bool STEP_DF = false;
 #endif
-  __shared__ float lds[SIM ? LDS_SLOTS * BLOCK : 1];
+template <bool PRE, bool SIM, bool POST, bool DR, bool CL, bool EXT = false>
+__global__ __launch_bounds__(BLOCK) void step_kernel(StepParams<STEP_DF> P) {
+  constexpr bool DF = STEP_DF;
+  __shared__ float lds[SIM ? LDS_SLOTS<DF> * BLOCK : 1];
   const int lane = threadIdx.x;
   const int e = blockIdx.x * BLOCK + lane;
   if (e >= P.n) return;
@@ -1460,11 +1465,7 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(Params P) {
     const bool xp = EXT && ext_pending(P, e);
     for (int s = 0; s < P.substeps; ++s) {
       const bool last = (s == P.substeps - 1);
-#ifdef BEZ_DOF_FORCE
-      substep<CL, EXT>(P, D, S, target, co, lds, lane, last_only ? last : true, last_only ? true : (s == 0), e, xp, s);
-#else
-      substep<CL, EXT>(P, D, S, target, co, lds, lane, last_only ? last : true, last_only ? true : (s == 0), e, xp);
-#endif
+      substep<DF, CL, EXT>(P, D, S, target, co, lds, lane, last_only ? last : true, last_only ? true : (s == 0), e, xp, s);
     }
     if (EXT && xp) {   // the wrenches were for this launch only
 #pragma unroll 1
@@ -1545,6 +1546,29 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(Params P) {
   if (tripped) {   // the contact-force rows this thread wrote during the substeps / above: non-finite entries -> 0
     for (int k = 0; k < BEZ_NBE_MAX * 3; ++k) co.base[(size_t)k * n] = finite_or(co.base[(size_t)k * n], 0.f);
   }
+}
+
+// ---- host side: the launch ladder of the physics-carrying forms (PRE, SIM, POST) = (PP, true, PP) over ext, cleats and dr, for this
+// translation unit's kernel: the plain one (bez_step_lane.hip) or the recording one (bez_step_lane_df.hip; `raw`: the sim's raw actuator
+// buffer, df_record)
+template <bool DF, bool PP>
+void launch_lane_pp(const StepParams<DF>& P, bool dr, bool cleats, bool ext, hipStream_t stream) {
+  static_assert(DF == STEP_DF, "the recording kernels are instantiated by the translation units that define BEZ_DOF_FORCE");
+  const dim3 grid((P.n + BLOCK - 1) / BLOCK), block(BLOCK);
+  if (ext) {   // external wrenches (bez_sim_apply_body_forces): per-env parameter loads always on, null = defaults
+    if (cleats) hipLaunchKernelGGL((step_kernel<PP, true, PP, true, true, true>), grid, block, 0, stream, P);
+    else hipLaunchKernelGGL((step_kernel<PP, true, PP, true, false, true>), grid, block, 0, stream, P);
+  } else if (cleats) hipLaunchKernelGGL((step_kernel<PP, true, PP, true, true>), grid, block, 0, stream, P);
+  else if (dr) hipLaunchKernelGGL((step_kernel<PP, true, PP, true, false>), grid, block, 0, stream, P);
+  else hipLaunchKernelGGL((step_kernel<PP, true, PP, false, false>), grid, block, 0, stream, P);
+}
+template <bool DF>
+void launch_lane(const Params& P0, float* raw, bool pre_post, bool dr, bool cleats, bool ext, hipStream_t stream) {
+  StepParams<DF> P;
+  static_cast<Params&>(P) = P0;
+  if constexpr (DF) P.dof_force = raw;
+  if (pre_post) launch_lane_pp<DF, true>(P, dr, cleats, ext, stream);
+  else launch_lane_pp<DF, false>(P, dr, cleats, ext, stream);
 }
 
 }  // namespace bez

@@ -16,7 +16,6 @@
 #include "bez_dynamics.h"
 #include "bez_dr_step.h"
 #include "bez_launch.h"
-#include "bez_launch_df.h"
 
 using namespace bez;
 

@@ -88,23 +88,12 @@ BEZ_DEV RootView load_root_view(const float* lds, int lane) {
 // keeps a value (and the instructions that produce it) where it is written: an empty asm the compiler cannot move code across
 BEZ_DEV void pin(float& x) { asm volatile("" : "+v"(x)); }
 BEZ_DEV void pin(V3& v) { pin(v.x); pin(v.y); pin(v.z); }
-// per-joint data a chain keeps in registers between pass 2 and pass 3
-#ifdef BEZ_DOF_FORCE
-// actuator record (bez_kernels.h df_record): a speed-limit-locked joint (1/D = 0: UD would hold zeros) keeps U itself in UD -- every use for
-// the dynamics reads it as zero -- and c0 = S.pA + U.c + (J + armature) qdd, the part of its reaction that pass 2 knows; the chain's
-// decision bits travel in one word (four bits per joint)
-struct P3 { SV UD; float uD, Dinv; SV S, cb; float c0; };
-#define BEZ_DF_WORD_OUT , uint32_t& dfw
-#define BEZ_DF_WORD_IN , uint32_t dfw
-#define BEZ_DF_WORD_ARG , dfw
-#define BEZ_DF_P3_PARAMS , uint32_t dfw, const float* kps, const float* kds, const float* lo, const float* hi, const float* target, int e, int sub, bool active
-#else
-struct P3 { SV UD; float uD, Dinv; SV S, cb; };
-#define BEZ_DF_WORD_OUT
-#define BEZ_DF_WORD_IN
-#define BEZ_DF_WORD_ARG
-#define BEZ_DF_P3_PARAMS
-#endif
+// per-joint data a chain keeps in registers between pass 2 and pass 3.
+// DF, the actuator record (bez_kernels.h df_record): a speed-limit-locked joint (1/D = 0: UD would hold zeros) keeps U itself in UD -- every
+// use for the dynamics reads it as zero -- and c0 = S.pA + U.c + (J + armature) qdd, the part of its reaction that pass 2 knows; the
+// chain's decision bits travel in one word (DfWord: four bits per joint)
+template <bool DF> struct P3 { SV UD; float uD, Dinv; SV S, cb; };
+template <> struct P3<true> { SV UD; float uD, Dinv; SV S, cb; float c0; };
 // contact rows of a body: F = F0 - (B^T a_ang + C a_lin) for the body's spatial acceleration a
 struct BodyContact { M3 B; Sym3 C; V3 F0; };
 BEZ_DEV BodyContact body_contact_of(const Sym6& Kc, SV pc) { BodyContact b; b.B = Kc.B; b.C = Kc.C; b.F0 = -pc.l; return b; }
@@ -174,10 +163,10 @@ BEZ_DEV void ws_chain_pass1(const Params& P, const ChainDyn& D, const float* ms,
   Eend = E; rend = r; Vend = V;  // chain-end frame / velocity for the ground points
 }
 
-template <int FIRST, int LEN, bool LEG>
+template <bool DF, int FIRST, int LEN, bool LEG>
 BEZ_DEV void ws_chain_pass2(const Params& P, const ChainDyn& D, const float* kps, const float* kds, const float* lo, const float* hi,
                             const float* q, const float* qd, const float* target, const LinkInertia* LI, const SV* pAl, const SV* Sl,
-                            const SV* cbl, const Sym6& Kc, SV pc, bool mine, BallSel& sel, P3* p3, Sym6& IAo, SV& pAo BEZ_DF_WORD_OUT) {
+                            const SV* cbl, const Sym6& Kc, SV pc, bool mine, BallSel& sel, P3<DF>* p3, Sym6& IAo, SV& pAo, DfWord<DF>& dfw) {
   Sym6 IA = Kc;
   SV pA = pc;
   static_for<LEN>([&](auto I) {
@@ -192,20 +181,16 @@ BEZ_DEV void ws_chain_pass2(const Params& P, const ChainDyn& D, const float* kps
       }
     }
     SV U; float Dinv, uD, qhp;
-#ifdef BEZ_DOF_FORCE
-    uint32_t dfb; float dfc0;
-    joint_terms<L>(P, kps[i], kds[i], lo[i], hi[i], q[i], qd[i], target[i], IA, pA, Sl[i], cbl[i], U, Dinv, uD, qhp, 0.f, 0.f, dfb, dfc0);
-    dfw |= dfb << (4 * i);
-#else
-    joint_terms<L>(P, kps[i], kds[i], lo[i], hi[i], q[i], qd[i], target[i], IA, pA, Sl[i], cbl[i], U, Dinv, uD, qhp);   // (a speed-limited joint: Dinv = 0, uD = its prescribed acceleration)
-#endif
+    DfJoint<DF> df;
+    joint_terms<L>(P, kps[i], kds[i], lo[i], hi[i], q[i], qd[i], target[i], IA, pA, Sl[i], cbl[i], U, Dinv, uD, qhp, 0.f, 0.f, df);   // (a speed-limited joint: Dinv = 0, uD = its prescribed acceleration)
+    if constexpr (DF) dfw.w |= df.bits << (4 * i);
     // p3.uD keeps the HELD-PARENT acceleration qhp = uD - (U/D).c: pass 3 then needs no c in its dot product (qdd = qhp - (U/D).a_parent),
     // and the leg<->leg scale reads it as it is
     p3[i].UD = U * Dinv; p3[i].uD = qhp; p3[i].Dinv = Dinv; p3[i].S = Sl[i]; p3[i].cb = cbl[i];
-#ifdef BEZ_DOF_FORCE
-    if (dfb & DF_LOCK) p3[i].UD = U;
-    p3[i].c0 = dfc0 + dot(U, cbl[i]);
-#endif
+    if constexpr (DF) {
+      if (df.bits & DF_LOCK) p3[i].UD = U;
+      p3[i].c0 = df.c0 + dot(U, cbl[i]);
+    }
     add_outer(IA, U, -Dinv);
     pA = pA + mul(IA, cbl[i]) + U * uD;
 #ifdef BEZ_WS_STAMPS
@@ -256,8 +241,8 @@ BEZ_DEV void ws_pair_wait(const float* lds, int side, int seq) {
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
-template <int LEN, bool CL>
-BEZ_DEV float ws_chain_self_correction(const Params& P, float* lds, int lane, int side, int seq, P3* p3, SV& pAo BEZ_DF_WORD_IN) {
+template <bool DF, int LEN, bool CL>
+BEZ_DEV float ws_chain_self_correction(const Params& P, float* lds, int lane, int side, int seq, P3<DF>* p3, SV& pAo, DfWord<DF> dfw) {
   static_assert(LEN == 6, "legs only");
   SV w[LEN];  // all wrenches are fetched up front (one burst of LDS reads): the chain below is serial and would expose each latency
   static_for<LEN>([&](auto I) {
@@ -279,14 +264,14 @@ BEZ_DEV float ws_chain_self_correction(const Params& P, float* lds, int lane, in
     const float tq = dot(p3[i].S, wsub);
     as = fmaf(tq * tq, p3[i].Dinv, as); am = fmaf(-tq, p3[i].uD, am);
     const float sd = -dot(p3[i].S, acc);
-#ifdef BEZ_DOF_FORCE
-    const bool lk = ((dfw >> (4 * i)) & DF_LOCK) != 0u;   // locked: UD holds U (read as zero here); Dinv keeps sd = -S.(the contacts' bias) for the reaction
-    acc = acc + p3[i].UD * (lk ? 0.f : sd);
-    p3[i].Dinv = lk ? sd : sd * p3[i].Dinv;
-#else
-    acc = acc + p3[i].UD * sd;
-    p3[i].Dinv = sd * p3[i].Dinv;   // from here on: the contacts' unscaled share of this joint's acceleration
-#endif
+    if constexpr (DF) {
+      const bool lk = ((dfw.w >> (4 * i)) & DF_LOCK) != 0u;   // locked: UD holds U (read as zero here); Dinv keeps sd = -S.(the contacts' bias) for the reaction
+      acc = acc + p3[i].UD * (lk ? 0.f : sd);
+      p3[i].Dinv = lk ? sd : sd * p3[i].Dinv;
+    } else {
+      acc = acc + p3[i].UD * sd;
+      p3[i].Dinv = sd * p3[i].Dinv;   // from here on: the contacts' unscaled share of this joint's acceleration
+    }
   });
   XS(X_SELFSUM + side * 2) = am; XS(X_SELFSUM + side * 2 + 1) = as;
   ws_pair_publish(lds, side, seq);
@@ -294,39 +279,41 @@ BEZ_DEV float ws_chain_self_correction(const Params& P, float* lds, int lane, in
   SelfSums Z;
   Z.am = XS(X_SELFSUM) + XS(X_SELFSUM + 2); Z.as = XS(X_SELFSUM + 1) + XS(X_SELFSUM + 3); Z.f2 = XS(X_SELFF2) + XS(X_SELFF2 + 1);   // (the helper parts' sums of |force|^2)
   const float sc = self_scale(P, Z);
-#ifdef BEZ_DOF_FORCE
 #pragma unroll
   for (int i = 0; i < LEN; ++i) {
-    const bool lk = ((dfw >> (4 * i)) & DF_LOCK) != 0u;
-    p3[i].uD = fmaf(sc, lk ? 0.f : p3[i].Dinv, p3[i].uD);
-    p3[i].c0 = lk ? fmaf(-sc, p3[i].Dinv, p3[i].c0) : p3[i].c0;
+    if constexpr (DF) {
+      const bool lk = ((dfw.w >> (4 * i)) & DF_LOCK) != 0u;
+      p3[i].uD = fmaf(sc, lk ? 0.f : p3[i].Dinv, p3[i].uD);
+      p3[i].c0 = lk ? fmaf(-sc, p3[i].Dinv, p3[i].c0) : p3[i].c0;
+    } else {
+      p3[i].uD = fmaf(sc, p3[i].Dinv, p3[i].uD);
+    }
   }
-#else
-#pragma unroll
-  for (int i = 0; i < LEN; ++i) p3[i].uD = fmaf(sc, p3[i].Dinv, p3[i].uD);
-#endif
   pAo = pAo + acc * sc;
   xs_store_sv(lds, lane, X_IA + side * 27 + 21, pAo);
   return sc;
 }
 
 // pass 3: joint accelerations, semi-implicit Euler (the speed limit is inside the dynamics: joint_terms); returns the chain-end acceleration.
-// sc = the leg<->leg contacts' common scale (their reported forces carry it too)
-template <int FIRST, int LEN, bool LEG, bool CL>
-BEZ_DEV SV ws_chain_pass3(const Params& P, SV a0, const P3* p3, float* q, float* qd, bool mine, const BallSel& sel, V3& fl, V3& f_end,
-                          float* lds, int lane, bool keep, bool first, float sc BEZ_DF_P3_PARAMS) {
+// sc = the leg<->leg contacts' common scale (their reported forces carry it too).  dfw, the gains, limits and targets, e, sub (the substep's
+// index) and active (the lane owns env e's stores): read by the actuator record only
+template <bool DF, int FIRST, int LEN, bool LEG, bool CL>
+BEZ_DEV SV ws_chain_pass3(const Params& P, SV a0, const P3<DF>* p3, float* q, float* qd, bool mine, const BallSel& sel, V3& fl, V3& f_end,
+                          float* lds, int lane, bool keep, bool first, float sc, DfWord<DF> dfw, const float* kps, const float* kds, const float* lo,
+                          const float* hi, const float* target, int e, int sub, bool active) {
   SV a = a0;
   static_for<LEN>([&](auto I) {
     constexpr int i = decltype(I)::value;
     constexpr int L = FIRST + i;
-#ifdef BEZ_DOF_FORCE
-    const uint32_t dfb = (dfw >> (4 * i)) & 15u;
-    const float dUa = dot(p3[i].UD, a);   // a locked joint's UD holds U: U.a_parent, the rest of its reaction
-    float qdd = (dfb & DF_LOCK) ? p3[i].uD : p3[i].uD - dUa;
-    if (active) df_record(P, e, sub, L - 1, dfb, kps[i], kds[i], lo[i], hi[i], q[i], qd[i], target[i], qdd, p3[i].c0 + dUa);
-#else
-    float qdd = p3[i].uD - dot(p3[i].UD, a);   // (p3.uD = the held-parent acceleration: the bias acceleration c is already in it)
-#endif
+    float qdd;
+    if constexpr (DF) {
+      const uint32_t dfb = (dfw.w >> (4 * i)) & 15u;
+      const float dUa = dot(p3[i].UD, a);   // a locked joint's UD holds U: U.a_parent, the rest of its reaction
+      qdd = (dfb & DF_LOCK) ? p3[i].uD : p3[i].uD - dUa;
+      if (active) df_record(P, e, sub, L - 1, dfb, kps[i], kds[i], lo[i], hi[i], q[i], qd[i], target[i], qdd, p3[i].c0 + dUa);
+    } else {
+      qdd = p3[i].uD - dot(p3[i].UD, a);   // (p3.uD = the held-parent acceleration: the bias acceleration c is already in it)
+    }
     a = a + p3[i].cb + p3[i].S * qdd;
     float v = fmaf(P.h, qdd, qd[i]);
     qd[i] = v;

@@ -146,17 +146,14 @@ BEZ_DEV void blk_add_outer(Blk& M, V3 u, V3 v, float k) {
 }
 
 // per-joint data a leg keeps between pass 2 and pass 3: the lane's row halves of U/D, S and c, the held-parent acceleration, 1/D
-#ifdef BEZ_DOF_FORCE
-struct P3q { V3 UD; float uD, Dinv; V3 S, cb; float c0; };   // (c0, and U in UD of a locked joint: struct P3 of bez_ws_common.inc)
-#else
-struct P3q { V3 UD; float uD, Dinv; V3 S, cb; };
-#endif
+template <bool DF> struct P3q { V3 UD; float uD, Dinv; V3 S, cb; };
+template <> struct P3q<true> { V3 UD; float uD, Dinv; V3 S, cb; float c0; };   // (c0, and U in UD of a locked joint: struct P3 of bez_ws_common.inc)
 
 // ---- pass 2 of a leg (ws_chain_pass2 in the quad form).  Out: the lane's block of the chain's articulated inertia and its half of the bias.
-template <int FIRST, int LEN, bool PKG>
+template <bool DF, int FIRST, int LEN, bool PKG>
 BEZ_DEV void wq_chain_pass2(const Params& P, const Quad& Q, float* lds, int lane, int side, int seq, const float* kps, const float* kds, const float* lo, const float* hi,
                             const float* q, const float* qd, const float* target, const LinkInertia* LI, const SV* pAl, const SV* Sl,
-                            const SV* cbl, const Sym6& Kc, SV pc, bool mine, BallSel& sel, P3q* p3, Blk& Mo, V3& pAo BEZ_DF_WORD_OUT) {
+                            const SV* cbl, const Sym6& Kc, SV pc, bool mine, BallSel& sel, P3q<DF>* p3, Blk& Mo, V3& pAo, DfWord<DF>& dfw) {
   Blk M = blk_of(Kc, Q);
   V3 pA = q_half(pc, Q.r);
   const PkgBase PB = pkg_base(lds, lane, Q);
@@ -187,16 +184,18 @@ BEZ_DEV void wq_chain_pass2(const Params& P, const Quad& Q, float* lds, int lane
     V3 u = blk_mul(M, Sc);
     u = u + qp_flip_c(u);                       // the lane's row half of U = IA S
     float Dinv, uD, qhp;
-#ifdef BEZ_DOF_FORCE
-    uint32_t dfb; float dfc0;
-    const float ucb = q_dot(u, cbr);
-    joint_scalar<L>(P, kps[i], kds[i], lo[i], hi[i], q[i], qd[i], target[i], q_dot(Sr, u), q_dot(Sr, pA), ucb, Dinv, uD, qhp, dfb, dfc0);
-    dfw |= dfb << (4 * i);
-    p3[i].UD = (dfb & DF_LOCK) ? u : u * Dinv; p3[i].uD = qhp; p3[i].Dinv = Dinv; p3[i].S = Sr; p3[i].cb = cbr; p3[i].c0 = dfc0 + ucb;
-#else
-    joint_scalar<L>(P, kps[i], kds[i], lo[i], hi[i], q[i], qd[i], target[i], q_dot(Sr, u), q_dot(Sr, pA), q_dot(u, cbr), Dinv, uD, qhp);
-    p3[i].UD = u * Dinv; p3[i].uD = qhp; p3[i].Dinv = Dinv; p3[i].S = Sr; p3[i].cb = cbr;
-#endif
+    DfJoint<DF> df;
+    // (U.c stands in front of the other two dot products where the record reads it again, behind them elsewhere: the orders the two
+    // builds were tuned with)
+    float ucb;
+    if constexpr (DF) ucb = q_dot(u, cbr);
+    const float Jraw = q_dot(Sr, u), sp = q_dot(Sr, pA);
+    if constexpr (!DF) ucb = q_dot(u, cbr);
+    joint_scalar<L>(P, kps[i], kds[i], lo[i], hi[i], q[i], qd[i], target[i], Jraw, sp, ucb, Dinv, uD, qhp, df);
+    bool locked = false;
+    if constexpr (DF) { dfw.w |= df.bits << (4 * i); locked = (df.bits & DF_LOCK) != 0u; }
+    p3[i].UD = locked ? u : u * Dinv; p3[i].uD = qhp; p3[i].Dinv = Dinv; p3[i].S = Sr; p3[i].cb = cbr;
+    if constexpr (DF) p3[i].c0 = df.c0 + ucb;
     const V3 uo = qp_flip_r(u);
     const V3 uc = mk(Q.diag ? u.x : uo.x, Q.diag ? u.y : uo.y, Q.diag ? u.z : uo.z);   // the column half of U this block needs
     blk_add_outer(M, u, uc, -Dinv);
@@ -211,8 +210,8 @@ BEZ_DEV void wq_chain_pass2(const Params& P, const Quad& Q, float* lds, int lane
 }
 
 // ---- the leg<->leg correction (ws_chain_self_correction in the quad form); pAo: the lane's half of the chain's bias
-template <int LEN, bool CL>
-BEZ_DEV float wq_chain_self_correction(const Params& P, const Quad& Q, float* lds, int lane, int side, int seq, P3q* p3, V3& pAo, int slot_bias BEZ_DF_WORD_IN) {
+template <bool DF, int LEN, bool CL>
+BEZ_DEV float wq_chain_self_correction(const Params& P, const Quad& Q, float* lds, int lane, int side, int seq, P3q<DF>* p3, V3& pAo, int slot_bias, DfWord<DF> dfw) {
   static_assert(LEN == 6, "legs only");
   V3 w[LEN];
   static_for<LEN>([&](auto I) {
@@ -231,14 +230,14 @@ BEZ_DEV float wq_chain_self_correction(const Params& P, const Quad& Q, float* ld
     const float tq = q_dot(p3[i].S, wsub);
     as = fmaf(tq * tq, p3[i].Dinv, as); am = fmaf(-tq, p3[i].uD, am);
     const float sd = -q_dot(p3[i].S, acc);
-#ifdef BEZ_DOF_FORCE
-    const bool lk = ((dfw >> (4 * i)) & DF_LOCK) != 0u;   // (as ws_chain_self_correction)
-    acc = acc + p3[i].UD * (lk ? 0.f : sd);
-    p3[i].Dinv = lk ? sd : sd * p3[i].Dinv;
-#else
-    acc = acc + p3[i].UD * sd;
-    p3[i].Dinv = sd * p3[i].Dinv;
-#endif
+    if constexpr (DF) {
+      const bool lk = ((dfw.w >> (4 * i)) & DF_LOCK) != 0u;   // (as ws_chain_self_correction)
+      acc = acc + p3[i].UD * (lk ? 0.f : sd);
+      p3[i].Dinv = lk ? sd : sd * p3[i].Dinv;
+    } else {
+      acc = acc + p3[i].UD * sd;
+      p3[i].Dinv = sd * p3[i].Dinv;
+    }
   });
   XS(X_SELFSUM + side * 2) = am; XS(X_SELFSUM + side * 2 + 1) = as;
   ws_pair_publish(lds, side, seq);
@@ -246,38 +245,39 @@ BEZ_DEV float wq_chain_self_correction(const Params& P, const Quad& Q, float* ld
   SelfSums Z;
   Z.am = XS(X_SELFSUM) + XS(X_SELFSUM + 2); Z.as = XS(X_SELFSUM + 1) + XS(X_SELFSUM + 3); Z.f2 = XS(X_SELFF2) + XS(X_SELFF2 + 1);
   const float sc = self_scale(P, Z);
-#ifdef BEZ_DOF_FORCE
 #pragma unroll
   for (int i = 0; i < LEN; ++i) {
-    const bool lk = ((dfw >> (4 * i)) & DF_LOCK) != 0u;
-    p3[i].uD = fmaf(sc, lk ? 0.f : p3[i].Dinv, p3[i].uD);
-    p3[i].c0 = lk ? fmaf(-sc, p3[i].Dinv, p3[i].c0) : p3[i].c0;
+    if constexpr (DF) {
+      const bool lk = ((dfw.w >> (4 * i)) & DF_LOCK) != 0u;
+      p3[i].uD = fmaf(sc, lk ? 0.f : p3[i].Dinv, p3[i].uD);
+      p3[i].c0 = lk ? fmaf(-sc, p3[i].Dinv, p3[i].c0) : p3[i].c0;
+    } else {
+      p3[i].uD = fmaf(sc, p3[i].Dinv, p3[i].uD);
+    }
   }
-#else
-#pragma unroll
-  for (int i = 0; i < LEN; ++i) p3[i].uD = fmaf(sc, p3[i].Dinv, p3[i].uD);
-#endif
   pAo = pAo + acc * sc;
   xs_store_v3(lds, lane, slot_bias, pAo);
   return sc;
 }
 
-// ---- pass 3 of a leg (ws_chain_pass3 in the quad form); returns the chain-end acceleration (both halves)
-template <int FIRST, int LEN, bool CL>
-BEZ_DEV SV wq_chain_pass3(const Params& P, const Quad& Q, const P3q* p3, float* q, float* qd, bool mine, const BallSel& sel, V3& fl, V3& f_end,
-                          float* lds, int lane, bool keep, bool first, float sc BEZ_DF_P3_PARAMS) {
+// ---- pass 3 of a leg (ws_chain_pass3 in the quad form, the record's parameters included); returns the chain-end acceleration (both halves)
+template <bool DF, int FIRST, int LEN, bool CL>
+BEZ_DEV SV wq_chain_pass3(const Params& P, const Quad& Q, const P3q<DF>* p3, float* q, float* qd, bool mine, const BallSel& sel, V3& fl, V3& f_end,
+                          float* lds, int lane, bool keep, bool first, float sc, DfWord<DF> dfw, const float* kps, const float* kds, const float* lo,
+                          const float* hi, const float* target, int e, int sub, bool active) {
   V3 a = xs_load_v3(lds, Q.lane_r, X_A0);
   static_for<LEN>([&](auto I) {
     constexpr int i = decltype(I)::value;
     constexpr int L = FIRST + i;
-#ifdef BEZ_DOF_FORCE
-    const uint32_t dfb = (dfw >> (4 * i)) & 15u;
-    const float dUa = q_dot(p3[i].UD, a);
-    const float qdd = (dfb & DF_LOCK) ? p3[i].uD : p3[i].uD - dUa;
-    if (active) df_record(P, e, sub, L - 1, dfb, kps[i], kds[i], lo[i], hi[i], q[i], qd[i], target[i], qdd, p3[i].c0 + dUa);
-#else
-    const float qdd = p3[i].uD - q_dot(p3[i].UD, a);
-#endif
+    float qdd;
+    if constexpr (DF) {
+      const uint32_t dfb = (dfw.w >> (4 * i)) & 15u;
+      const float dUa = q_dot(p3[i].UD, a);
+      qdd = (dfb & DF_LOCK) ? p3[i].uD : p3[i].uD - dUa;
+      if (active) df_record(P, e, sub, L - 1, dfb, kps[i], kds[i], lo[i], hi[i], q[i], qd[i], target[i], qdd, p3[i].c0 + dUa);
+    } else {
+      qdd = p3[i].uD - q_dot(p3[i].UD, a);
+    }
     a = a + p3[i].cb + p3[i].S * qdd;
     const float v = fmaf(P.h, qdd, qd[i]);
     qd[i] = v;
