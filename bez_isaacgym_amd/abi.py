@@ -81,6 +81,13 @@ PROX_PAIR_BODIES = tuple((_PROX_CAPSULES[a], _PROX_CAPSULES[b]) for a, b in PROX
 # four parameter rows (PARAM_* below) it copies row by row
 QUERY_RIGID_BODY_STATE, QUERY_JACOBIAN, QUERY_MASS_MATRIX, QUERY_TENSOR_COUNT = range(4)
 QUERY_PARAMS = (3, 4, 5, 6)     # PARAM_MASS_SCALE, PARAM_GRAVITY, PARAM_DOF_LOWER, PARAM_DOF_UPPER
+# env snapshots (include/bez_sim.h "Env snapshots", BezSim.snapshot): the `what` bits of a restore, the blob's header, and the sections of
+# a row in the blob's order -- each a run of uint32 columns (width, rows), a 64-bit item as (low, high)
+SNAPSHOT_ENVS, SNAPSHOT_GLOBALS = 1, 2
+SNAPSHOT_MAGIC, SNAPSHOT_LAYOUT, SNAPSHOT_HEADER_WORDS, SNAPSHOT_GLOBAL_WORDS = 0x4e535a42, 1, 40, 16
+SNAPSHOT_SECTIONS = ("state", "obs", "rew", "reset", "progress", "timeout", "episode", "randomize", "nonfinite", "end_counts", "reward_terms", "end_bits",
+                     "param_friction", "param_kp_scale", "param_kd_scale", "param_mass_scale", "param_gravity", "param_dof_lower", "param_dof_upper",
+                     "dof_force_record")
 HEALTH_NONFINITE = 1            # health word bits (TENSOR_HEALTH, BezSim.health)
 HEALTH_SPIN_TIMEOUT = 2
 TASK_KICK, TASK_WALK, TASK_ORIENT = 0, 1, 2

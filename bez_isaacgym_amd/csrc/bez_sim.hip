@@ -8,12 +8,14 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <mutex>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "bez_kernels.h"
 #include "bez_dynamics.h"
+#include "bez_snapshot.h"
 #include "bez_dr_step.h"
 #include "bez_launch.h"
 
@@ -22,6 +24,9 @@ using namespace bez;
 namespace {
 
 thread_local std::string g_create_error;
+// every snapshot alive, of any sim: a restore takes a snapshot of another sim, so "is this handle alive" cannot be asked of one sim
+std::mutex g_snapshots_mutex;
+std::vector<const BezSnapshot*> g_snapshots;
 
 }  // namespace
 
@@ -92,6 +97,8 @@ struct BezSim {
   // query states (bez_query_state_create): the ones alive, and the one the query entry points read instead of the live state (null: none)
   std::vector<BezQueryState*> queries;
   BezQueryState* bound = nullptr;
+  // env snapshots (bez_snapshot_create): the ones alive
+  std::vector<BezSnapshot*> snapshots;
 };
 
 // A query state: `rows` rows of the fields the query kernels read, row-by-row copies of the parameter rows they read, and tensors of its
@@ -610,11 +617,13 @@ static const char* oracle_only(uint32_t flags, const float* tune) {
   return nullptr;
 }
 
+static void forget_snapshots(BezSim* s);   // (env snapshots, at the end of this file)
 int bez_sim_destroy(BezSim* s) {
   if (!s) return 0;
   (void)hipSetDevice(s->device);
   for (void** slot : s->owned) (void)hipFree(*slot);   // (the buffers of the query states still alive among them)
   for (BezQueryState* q : s->queries) delete q;
+  forget_snapshots(s);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
   delete s;
@@ -1219,4 +1228,257 @@ int bez_sim_apply_body_forces(BezSim* s, const float* forces_dev, const float* t
 
 int bez_sim_seed(BezSim* s, uint64_t seed) { if (!s) return -1; s->cfg.seed = seed; s->dr_prelaunched = false; return 0; }
 
+}  // extern "C"
+
+// =============================================================================================== env snapshots (include/bez_sim.h)
+// The inventory of "what is an env": one SNAP_TABLE row per per-env buffer of BezSim that a snapshot keeps (DESIGN.md 4.3p lists every
+// buffer, also the derived ones and the ones left alone).  A new per-env buffer that decides how an env continues is one row here, one
+// name in abi.SNAPSHOT_SECTIONS and BEZ_SNAPSHOT_SECTIONS + 1; the rewind tests fail without it.
+namespace {
+enum : int { SNAP_SEC_PARAM0 = 12, SNAP_SEC_DF = SNAP_SEC_PARAM0 + BEZ_PARAM_COUNT };
+static_assert(SNAP_SEC_DF + 1 == BEZ_SNAPSHOT_SECTIONS && BEZ_SNAPSHOT_SECTIONS <= SNAP_MAX_SECTIONS, "the sections of a snapshot");
+struct SnapRow { int kind; int width; /* < 0: by sim, below */ void* (*env)(const BezSim*); };
+enum : int { W_OBS = -1, W_PARAM = -2, W_DF = -3 };
+#define ENV(expr) [](const BezSim* s) -> void* { return (void*)(expr); }
+const SnapRow SNAP_TABLE[BEZ_SNAPSHOT_SECTIONS] = {
+    {SNAP_COL, F_COUNT, ENV(s->state)},
+    {SNAP_ROW, W_OBS, ENV(s->obs)},
+    {SNAP_COL, 1, ENV(s->rew)},
+    {SNAP_COL64, 2, ENV(s->reset)},
+    {SNAP_COL64, 2, ENV(s->progress)},
+    {SNAP_COL64, 2, ENV(s->timeout)},
+    {SNAP_COL, 1, ENV(s->episode)},
+    {SNAP_COL64, 2, ENV(s->randomize)},
+    {SNAP_COL64, 2, ENV(s->nonfinite)},
+    {SNAP_COL64, 2 * BEZ_END_CAUSES, ENV(s->episode_stats)},                                                       // end counts (8, N) i64
+    {SNAP_COL, BEZ_END_CAUSES, ENV(s->episode_stats + (size_t)BEZ_END_CAUSES * s->n)},                             // reward terms (8, N) f32
+    {SNAP_COL, 1, ENV((float*)(s->episode_stats + (size_t)BEZ_END_CAUSES * s->n) + (size_t)BEZ_END_CAUSES * s->n)},   // end bits (N) i32
+    {SNAP_ROW, W_PARAM, ENV(s->dr[0])}, {SNAP_ROW, W_PARAM, ENV(s->dr[1])}, {SNAP_ROW, W_PARAM, ENV(s->dr[2])}, {SNAP_ROW, W_PARAM, ENV(s->dr[3])},
+    {SNAP_ROW, W_PARAM, ENV(s->dr[4])}, {SNAP_ROW, W_PARAM, ENV(s->dr[5])}, {SNAP_ROW, W_PARAM, ENV(s->dr[6])},
+    {SNAP_COL, W_DF, ENV(s->df_raw)},                                                                               // [substep][3][dof][env]
+};
+#undef ENV
+int snap_width(const BezSim* s, int sec) {
+  const int w = SNAP_TABLE[sec].width;
+  return w == W_OBS ? s->nobs : w == W_PARAM ? PARAM_WIDTH[sec - SNAP_SEC_PARAM0] : w == W_DF ? (s->df_raw ? s->cfg.substeps * 3 * BEZ_ND : 0) : w;
+}
+// the sim-global device words, in the order the snapshot keeps them
+constexpr int SNAP_GLOBAL_WORDS[SNAP_GLOBALS] = {2, (int)(sizeof(DrState) / 4), (int)(sizeof(DrSnap) / 4), 2};
+static_assert(SNAP_GLOBAL_WORDS[0] + SNAP_GLOBAL_WORDS[1] + SNAP_GLOBAL_WORDS[2] + SNAP_GLOBAL_WORDS[3] == BEZ_SNAPSHOT_GLOBAL_WORDS &&
+              sizeof(DrState) % 4 == 0 && sizeof(DrSnap) % 4 == 0, "the global device words of a snapshot");
+}  // namespace
+
+struct BezSnapshot {
+  BezSim* sim = nullptr;
+  int rows = 0;
+  uint32_t* data = nullptr;                      // device: `cols` columns of `rows` words, then BEZ_SNAPSHOT_GLOBAL_WORDS
+  int width[BEZ_SNAPSHOT_SECTIONS] = {};
+  uint32_t off[BEZ_SNAPSHOT_SECTIONS] = {}, cols = 0;
+  uint32_t present = 0;                          // bit per section: what the last save found in its sim (0: nothing was saved yet)
+  int64_t obs_calls = 0;                         // the host part of the global block, as the last save found it
+  uint64_t post_calls = 0, reset_calls = 0;
+  uint32_t gravity_uniform = 0, obs_noise_applied = 0;
+  int grid_y = 0;                                // BEZ_SNAPSHOT_GRID_Y at creation, a measurement knob (tools/snapshot_times.py): workgroups over the
+                                                 // chunks of columns per tile of entries; 0: one per chunk (DESIGN.md 4.3p has both timings)
+};
+
+namespace {
+void forget_snapshot(const BezSnapshot* p) {
+  std::lock_guard<std::mutex> lock(g_snapshots_mutex);
+  g_snapshots.erase(std::remove(g_snapshots.begin(), g_snapshots.end(), p), g_snapshots.end());
+}
+bool snapshot_alive(const BezSnapshot* p) {
+  std::lock_guard<std::mutex> lock(g_snapshots_mutex);
+  return std::find(g_snapshots.begin(), g_snapshots.end(), p) != g_snapshots.end();
+}
+// the shared front of the calls on a snapshot
+#define SNAP_TRY(s, p, name, own)                                                                                       \
+  do {                                                                                                                  \
+    if (!(s)) return fail((s), -1, name ": sim is null");                                                               \
+    if (!(p)) return fail((s), -1, name ": the snapshot is null");                                                      \
+    if (!snapshot_alive(p)) return fail((s), -1, name ": the snapshot is not alive (destroyed, or never created)");      \
+    if ((own) && (p)->sim != (s)) return fail((s), -1, name ": the snapshot belongs to another sim");                    \
+  } while (0)
+size_t snap_words(const BezSnapshot* p) { return (size_t)p->cols * p->rows + BEZ_SNAPSHOT_GLOBAL_WORDS; }
+uint32_t snap_asset(const BezSim* s) { return s->cfg.flags & (BEZ_FLAG_CLEATS | BEZ_FLAG_BOX_ASSET); }
+
+void snap_header(const BezSim* s, const BezSnapshot* p, uint32_t h[BEZ_SNAPSHOT_HEADER_WORDS]) {
+  std::memset(h, 0, BEZ_SNAPSHOT_HEADER_WORDS * sizeof(uint32_t));
+  h[0] = BEZ_SNAPSHOT_MAGIC; h[1] = BEZ_SNAPSHOT_LAYOUT; h[2] = (uint32_t)p->rows; h[3] = BEZ_SNAPSHOT_SECTIONS; h[4] = p->present; h[5] = p->cols;
+  h[6] = BEZ_SNAPSHOT_GLOBAL_WORDS;
+  for (int k = 0; k < BEZ_SNAPSHOT_SECTIONS; ++k) h[8 + k] = (uint32_t)p->width[k];
+  uint32_t* g = h + 8 + BEZ_SNAPSHOT_SECTIONS;
+  g[0] = (uint32_t)p->obs_calls; g[1] = (uint32_t)((uint64_t)p->obs_calls >> 32); g[2] = (uint32_t)p->post_calls; g[3] = (uint32_t)(p->post_calls >> 32);
+  g[4] = (uint32_t)p->reset_calls; g[5] = (uint32_t)(p->reset_calls >> 32); g[6] = p->gravity_uniform; g[7] = p->obs_noise_applied;
+  g[8] = (uint32_t)s->cfg.task; g[9] = snap_asset(s); g[10] = s->has_ball ? 1u : 0u; g[11] = (uint32_t)s->nobs;
+}
+static_assert(8 + BEZ_SNAPSHOT_SECTIONS + 12 == BEZ_SNAPSHOT_HEADER_WORDS, "the header of a snapshot blob");
+
+// The launch of a save (SAVE) or a restore on sim `s`: the sections by `mode`, in chunks of columns over the second grid dimension
+template <bool SAVE>
+int launch_snapshot(BezSim* s, const BezSnapshot* p, const int mode[BEZ_SNAPSHOT_SECTIONS], const int32_t* env_ids, const int32_t* row_ids, int count,
+                    bool globals, hipStream_t stream) {
+  SnapArgs A = {};
+  A.snap = p->data; A.rows = p->rows; A.n = s->n; A.env_ids = env_ids; A.row_ids = row_ids; A.count = count;
+  A.glob_snap = p->data + (size_t)p->cols * p->rows;
+  uint32_t* glob[SNAP_GLOBALS] = {(uint32_t*)s->post_calls_dev, (uint32_t*)s->dr_state, (uint32_t*)s->dr_snap, (uint32_t*)s->goal_draw_dev};
+  for (int g = 0; g < SNAP_GLOBALS; ++g) { A.glob[g] = globals ? glob[g] : nullptr; A.glob_words[g] = SNAP_GLOBAL_WORDS[g]; }
+  for (int k = 0; k < BEZ_PARAM_COUNT; ++k)
+    for (int j = 0; j < PARAM_WIDTH[k]; ++j)
+      A.dflt[k][j] = k == BEZ_PARAM_FRICTION ? s->cfg.plane_friction : k == BEZ_PARAM_GRAVITY ? s->cfg.gravity[j] : k == BEZ_PARAM_DOF_LOWER ? (float)BEZ_DOF_LOWER[j]
+                     : k == BEZ_PARAM_DOF_UPPER ? (float)BEZ_DOF_UPPER[j] : 1.0f;   // (the rows of fill_default_params)
+  for (int chunk_words = SNAP_CHUNK;; chunk_words *= 2) {   // (a long actuator record: wider chunks until the table holds them)
+    int nc = 0;
+    for (int k = 0; k < BEZ_SNAPSHOT_SECTIONS && nc <= SNAP_MAX_CHUNKS; ++k) {
+      SnapSection& S = A.sec[k];
+      S.env = (uint32_t*)SNAP_TABLE[k].env(s); S.off = p->off[k]; S.width = p->width[k]; S.kind = SNAP_TABLE[k].kind; S.mode = mode[k];
+      S.dflt = k >= SNAP_SEC_PARAM0 && k < SNAP_SEC_DF ? k - SNAP_SEC_PARAM0 : 0;
+      if (S.mode == SNAP_SKIP || S.width == 0) continue;
+      const int step = S.kind == SNAP_ROW ? S.width : chunk_words;
+      for (int w0 = 0; w0 < S.width; w0 += step, ++nc)
+        if (nc < SNAP_MAX_CHUNKS) A.chunk[nc] = {(int16_t)k, (int16_t)w0, (int16_t)std::min(step, S.width - w0), 0};
+    }
+    if (nc <= SNAP_MAX_CHUNKS) { A.nchunks = nc; break; }
+  }
+  const dim3 grid((unsigned)std::max(1, (count + SNAP_TILE - 1) / SNAP_TILE), (unsigned)std::max(1, p->grid_y > 0 ? std::min(p->grid_y, A.nchunks) : A.nchunks));
+  hipLaunchKernelGGL(snapshot_copy_kernel<SAVE>, grid, dim3(SNAP_THREADS), 0, stream, A);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(s, -2, "snapshot_copy_kernel launch", e);
+}
+}  // namespace
+
+static void forget_snapshots(BezSim* s) {   // bez_sim_destroy: their buffers went with the sim's
+  for (BezSnapshot* p : s->snapshots) { forget_snapshot(p); delete p; }
+  s->snapshots.clear();
+}
+
+extern "C" {
+int bez_snapshot_create(BezSim* s, int32_t rows, BezSnapshot** out) {
+  if (!s) return fail(s, -1, "bez_snapshot_create: sim is null");
+  if (!out) return fail(s, -1, "bez_snapshot_create: out is null");
+  *out = nullptr;
+  if (rows < 1) return fail(s, -1, "bez_snapshot_create: rows must be >= 1");
+  BezSnapshot* p = new (std::nothrow) BezSnapshot();
+  if (!p) return fail(s, -4, "out of host memory");
+  p->sim = s; p->rows = rows;
+  if (const char* v = std::getenv("BEZ_SNAPSHOT_GRID_Y")) p->grid_y = std::atoi(v);
+  for (int k = 0; k < BEZ_SNAPSHOT_SECTIONS; ++k) { p->width[k] = snap_width(s, k); p->off[k] = p->cols; p->cols += (uint32_t)p->width[k]; }
+  (void)hipSetDevice(s->device);
+  if (int rc = dev_alloc_zeroed(s, &p->data, snap_words(p) * sizeof(uint32_t))) { delete p; return rc; }
+  s->snapshots.push_back(p);
+  { std::lock_guard<std::mutex> lock(g_snapshots_mutex); g_snapshots.push_back(p); }
+  *out = p;
+  return 0;
+}
+int bez_snapshot_destroy(BezSim* s, BezSnapshot* p) {
+  SNAP_TRY(s, p, "bez_snapshot_destroy", true);
+  (void)hipSetDevice(s->device);
+  dev_free(s, &p->data);   // (hipFree waits for the work that may still read the buffer)
+  s->snapshots.erase(std::remove(s->snapshots.begin(), s->snapshots.end(), p), s->snapshots.end());
+  forget_snapshot(p);
+  delete p;
+  return 0;
+}
+int bez_snapshot_save(BezSim* s, BezSnapshot* p, const int32_t* env_ids_dev, void* stream) {
+  SNAP_TRY(s, p, "bez_snapshot_save", true);
+  int mode[BEZ_SNAPSHOT_SECTIONS];
+  uint32_t present = 0;
+  for (int k = 0; k < BEZ_SNAPSHOT_SECTIONS; ++k) {
+    const bool has = SNAP_TABLE[k].env(s) != nullptr && p->width[k] > 0 && snap_width(s, k) == p->width[k];
+    mode[k] = has ? SNAP_COPY : SNAP_SKIP;
+    if (has) present |= 1u << k;
+  }
+  RC_TRY(launch_snapshot<true>(s, p, mode, env_ids_dev, nullptr, p->rows, true, (hipStream_t)stream));
+  p->present = present;
+  p->obs_calls = s->obs_calls; p->post_calls = s->post_calls; p->reset_calls = s->reset_calls;
+  p->gravity_uniform = s->gravity_uniform ? 1u : 0u; p->obs_noise_applied = s->obs_noise_applied ? 1u : 0u;
+  return 0;
+}
+int bez_snapshot_restore(BezSim* d, const BezSnapshot* p, const int32_t* env_ids_dev, const int32_t* row_ids_dev, int32_t count, uint32_t what,
+                         void* stream_) {
+  SNAP_TRY(d, p, "bez_snapshot_restore", false);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (count < 0) return fail(d, -1, "bez_snapshot_restore: count must be >= 0");
+  if (!row_ids_dev && count > p->rows) return fail(d, -1, "bez_snapshot_restore: count exceeds the snapshot's rows (row_ids_dev is null: row i)");
+  if (!(what & BEZ_SNAPSHOT_ENVS) || (what & ~(uint32_t)(BEZ_SNAPSHOT_ENVS | BEZ_SNAPSHOT_GLOBALS)))
+    return fail(d, -1, "bez_snapshot_restore: what must be BEZ_SNAPSHOT_ENVS or BEZ_SNAPSHOT_ENVS | BEZ_SNAPSHOT_GLOBALS");
+  if (!p->present) return fail(d, -1, "bez_snapshot_restore: nothing was saved into the snapshot yet");
+  const BezSim* o = p->sim;
+  if (d != o) {
+    if (d->device != o->device) return fail(d, -1, "bez_snapshot_restore: incompatible destination: another device");
+    if (d->cfg.task != o->cfg.task) return fail(d, -1, "bez_snapshot_restore: incompatible destination: another task");
+    if (snap_asset(d) != snap_asset(o)) return fail(d, -1, "bez_snapshot_restore: incompatible destination: another asset (BEZ_FLAG_CLEATS / BEZ_FLAG_BOX_ASSET)");
+    if (d->has_ball != o->has_ball) return fail(d, -1, "bez_snapshot_restore: incompatible destination: ball / no ball");
+    if (d->nobs != o->nobs) return fail(d, -1, "bez_snapshot_restore: incompatible destination: another observation width");
+  }
+  const bool globals = (what & BEZ_SNAPSHOT_GLOBALS) != 0u;
+  if (count == 0 && !globals) return 0;
+  (void)hipSetDevice(d->device);
+  int mode[BEZ_SNAPSHOT_SECTIONS];
+  bool packed = false, gravity = false;
+  for (int k = 0; k < BEZ_SNAPSHOT_SECTIONS; ++k) {
+    const bool in_snap = (p->present >> k) & 1u;
+    const int param = k >= SNAP_SEC_PARAM0 && k < SNAP_SEC_DF ? k - SNAP_SEC_PARAM0 : -1;
+    if (param >= 0 && in_snap && !d->dr[param] && count > 0) {   // the path of bez_sim_set_env_params: default rows for the envs not restored
+      RC_TRY(dev_alloc_zeroed(d, &d->dr[param], (size_t)d->n * PARAM_WIDTH[param] * sizeof(float), stream));
+      if (int rc = fill_default_params(d, param, d->dr[param], stream)) { dev_free(d, &d->dr[param]); return rc; }
+    }
+    const bool in_dst = SNAP_TABLE[k].env(d) != nullptr && snap_width(d, k) == p->width[k];
+    mode[k] = count == 0 ? SNAP_SKIP : (in_snap && in_dst) ? SNAP_COPY : (param >= 0 && in_dst) ? SNAP_DEFAULT : SNAP_SKIP;
+    if (param >= 0 && mode[k] != SNAP_SKIP) {
+      packed |= param == BEZ_PARAM_KP_SCALE || param == BEZ_PARAM_KD_SCALE || param == BEZ_PARAM_DOF_LOWER || param == BEZ_PARAM_DOF_UPPER;
+      gravity |= param == BEZ_PARAM_GRAVITY;
+    }
+  }
+  RC_TRY(launch_snapshot<false>(d, p, mode, env_ids_dev, row_ids_dev, count, globals, stream));
+  if (packed && repack_dr(d, stream)) return fail(d, -2, "bez_snapshot_restore: repack");
+  if (gravity) d->gravity_uniform = false;   // rows written from outside the randomisation kernel may differ from env to env
+  if (globals) {
+    d->obs_calls = p->obs_calls; d->post_calls = p->post_calls; d->reset_calls = p->reset_calls;
+    d->gravity_uniform = p->gravity_uniform != 0u; d->obs_noise_applied = p->obs_noise_applied != 0u;
+  }
+  return 0;
+}
+int bez_snapshot_export(BezSim* s, const BezSnapshot* p, void* blob, int64_t* bytes, void* stream_) {
+  SNAP_TRY(s, p, "bez_snapshot_export", true);
+  if (!bytes) return fail(s, -1, "bez_snapshot_export: bytes is null");
+  const int64_t need = (int64_t)((BEZ_SNAPSHOT_HEADER_WORDS + snap_words(p)) * sizeof(uint32_t)), room = *bytes;
+  *bytes = need;
+  if (!blob) return 0;
+  if (room < need) return fail(s, -1, "bez_snapshot_export: the blob is too small (*bytes is the size needed)");
+  hipStream_t stream = (hipStream_t)stream_;
+  uint32_t h[BEZ_SNAPSHOT_HEADER_WORDS];
+  snap_header(s, p, h);
+  (void)hipSetDevice(s->device);
+  HIP_TRY(s, hipMemcpyAsync(blob, h, sizeof(h), hipMemcpyDefault, stream));
+  HIP_TRY(s, hipMemcpyAsync((uint32_t*)blob + BEZ_SNAPSHOT_HEADER_WORDS, p->data, snap_words(p) * sizeof(uint32_t), hipMemcpyDefault, stream));
+  HIP_TRY(s, hipStreamSynchronize(stream));
+  return 0;
+}
+int bez_snapshot_import(BezSim* s, BezSnapshot* p, const void* blob, int64_t bytes, void* stream_) {
+  SNAP_TRY(s, p, "bez_snapshot_import", true);
+  if (!blob) return fail(s, -1, "bez_snapshot_import: blob is null");
+  const int64_t need = (int64_t)((BEZ_SNAPSHOT_HEADER_WORDS + snap_words(p)) * sizeof(uint32_t));
+  if (bytes < (int64_t)(BEZ_SNAPSHOT_HEADER_WORDS * sizeof(uint32_t))) return fail(s, -1, "bez_snapshot_import: the blob is truncated (shorter than its header)");
+  hipStream_t stream = (hipStream_t)stream_;
+  (void)hipSetDevice(s->device);
+  uint32_t h[BEZ_SNAPSHOT_HEADER_WORDS], mine[BEZ_SNAPSHOT_HEADER_WORDS];
+  HIP_TRY(s, hipMemcpyAsync(h, blob, sizeof(h), hipMemcpyDefault, stream));
+  HIP_TRY(s, hipStreamSynchronize(stream));
+  snap_header(s, p, mine);
+  if (h[0] != BEZ_SNAPSHOT_MAGIC) return fail(s, -1, "bez_snapshot_import: not a snapshot blob (magic word)");
+  if (h[1] != BEZ_SNAPSHOT_LAYOUT) return fail(s, -1, "bez_snapshot_import: the blob has another layout version");
+  if (h[2] != mine[2]) return fail(s, -1, "bez_snapshot_import: the blob has another number of rows");
+  if (h[3] != mine[3] || h[5] != mine[5] || h[6] != mine[6] || std::memcmp(h + 8, mine + 8, BEZ_SNAPSHOT_SECTIONS * sizeof(uint32_t)) != 0)
+    return fail(s, -1, "bez_snapshot_import: the blob's section widths do not fit this snapshot");
+  const uint32_t *g = h + 8 + BEZ_SNAPSHOT_SECTIONS, *gm = mine + 8 + BEZ_SNAPSHOT_SECTIONS;
+  if (std::memcmp(g + 8, gm + 8, 4 * sizeof(uint32_t)) != 0) return fail(s, -1, "bez_snapshot_import: the blob is of another task or asset");
+  if (bytes < need) return fail(s, -1, "bez_snapshot_import: the blob is truncated");
+  HIP_TRY(s, hipMemcpyAsync(p->data, (const uint32_t*)blob + BEZ_SNAPSHOT_HEADER_WORDS, snap_words(p) * sizeof(uint32_t), hipMemcpyDefault, stream));
+  HIP_TRY(s, hipStreamSynchronize(stream));
+  p->present = h[4];
+  p->obs_calls = (int64_t)((uint64_t)g[0] | (uint64_t)g[1] << 32); p->post_calls = (uint64_t)g[2] | (uint64_t)g[3] << 32;
+  p->reset_calls = (uint64_t)g[4] | (uint64_t)g[5] << 32; p->gravity_uniform = g[6]; p->obs_noise_applied = g[7];
+  return 0;
+}
 }  // extern "C"

@@ -81,6 +81,15 @@ QUERY_STATE_SIGS = {
     "bez_query_state_tensor": (C.c_int, [vp, vp] + _GETTER[1:]),
     "bez_query_state_refresh": (C.c_int, [vp, vp, u32, vp]),
 }
+# the bez_snapshot_* entry points of the same header ("Env snapshots"): sim, snapshot, ...
+SNAPSHOT_SIGS = {
+    "bez_snapshot_create": (C.c_int, [vp, i32, C.POINTER(vp)]),
+    "bez_snapshot_destroy": (C.c_int, [vp, vp]),
+    "bez_snapshot_save": (C.c_int, [vp, vp, vp, vp]),
+    "bez_snapshot_restore": (C.c_int, [vp, vp, vp, vp, i32, u32, vp]),
+    "bez_snapshot_export": (C.c_int, [vp, vp, vp, C.POINTER(i64), vp]),
+    "bez_snapshot_import": (C.c_int, [vp, vp, vp, i64, vp]),
+}
 # the entry points a binding redirects (include/bez_sim.h): what a QueryState brackets with bind / unbind
 BOUND_QUERIES = ("bez_sim_inverse_dynamics", "bez_sim_forward_dynamics", "bez_sim_operational_space", "bez_sim_centroidal",
                  "bez_sim_body_accelerations", "bez_sim_generalized_forces", "bez_sim_limb_ik", "bez_sim_proximity")
@@ -96,7 +105,7 @@ def load_library():
         raise BezSimError("libbez_sim.so not built (%s): run `python -m bez_isaacgym_amd.build` -- "
                           "the HIP extension is required, there is no fallback path" % path)
     lib = C.CDLL(path)
-    for name, (res, args) in list(SIGS.items()) + list(QUERY_STATE_SIGS.items()):
+    for name, (res, args) in list(SIGS.items()) + list(QUERY_STATE_SIGS.items()) + list(SNAPSHOT_SIGS.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     _LIB = lib
@@ -144,6 +153,8 @@ class BezSim:
             self._views = {}
             for qs in self.__dict__.pop("_query_states", []):   # bez_sim_destroy frees them: their objects only forget the handles
                 qs._forget()
+            for snap in self.__dict__.pop("_snapshots", []):
+                snap._forget()
             self.lib.bez_sim_destroy(self.h)
             self.h = None
 
@@ -448,6 +459,16 @@ class BezSim:
         self.__dict__.setdefault("_query_states", []).append(qs)
         return qs
 
+    # ---- env snapshots: whole envs saved and put back (include/bez_sim.h "Env snapshots")
+    def snapshot(self, rows):
+        """A Snapshot of `rows` rows (>= 1, independent of N) owned by this sim: save() copies envs into it, restore() copies rows back into
+        envs of this sim or of another one of the same task and asset.  close() frees it; closing the sim frees the ones still open."""
+        if isinstance(rows, bool) or not isinstance(rows, int) or rows < 1:
+            raise BezSimError("snapshot: rows must be an int >= 1, got %r" % (rows,))
+        snap = Snapshot(self, rows)
+        self.__dict__.setdefault("_snapshots", []).append(snap)
+        return snap
+
     def refresh(self, which):
         self._check(self.lib.bez_sim_refresh_tensor(self.h, which, self._stream()))
         return self.tensor(which)
@@ -704,3 +725,117 @@ class QueryState:
         view = self._tensor(abi.QUERY_RIGID_BODY_STATE)
         self._check(self.lib.bez_query_state_refresh(self.h, self.qs, 1 << abi.QUERY_RIGID_BODY_STATE, self._stream()))
         return view
+
+
+class Snapshot:
+    """`rows` whole envs of a BezSim, saved and put back (BezSim.snapshot; include/bez_sim.h "Env snapshots"): everything that decides how
+    an env continues -- the state with targets, contact rows and goal, obs / rew / reset / progress / timeout, the episode counter that
+    keys the reset noise, randomize, the statistics, the parameter rows the sim has, the actuator record -- and, per save, the sim-global
+    counters and randomisation clock.  A restored env keeps the destination's random identity (seed, global env id)."""
+
+    def __init__(self, sim, rows):
+        self.sim, self.rows, self.device, self.lib, self.h = sim, rows, sim.device, sim.lib, sim.h
+        self._stream = sim._stream
+        snap = C.c_void_p()
+        sim._check(sim.lib.bez_snapshot_create(sim.h, rows, C.byref(snap)))
+        self.snap = snap
+
+    for _name in ("_check", "_ptr", "_checked"):
+        locals()[_name] = getattr(BezSim, _name)
+    del _name
+
+    def _forget(self):
+        self.snap = None
+
+    def close(self):
+        if getattr(self, "snap", None) is not None:
+            self._check(self.lib.bez_snapshot_destroy(self.h, self.snap))
+            self._forget()
+            snaps = self.sim.__dict__.get("_snapshots", [])
+            if self in snaps:
+                snaps.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _open(self, what):
+        if getattr(self, "snap", None) is None:
+            raise BezSimError("snapshot %s: the snapshot is closed" % what)
+
+    def _ids(self, name, ids, count):
+        """the pointer of (count,) int32 ids on the device, NULL for None"""
+        return None if ids is None else self._ptr(self._checked(name, ids, ((count,),)), torch.int32)
+
+    def save(self, env_ids=None):
+        """Row i becomes env env_ids[i] as it is now; `env_ids` (rows,) int32 on the sim's device, contiguous, or None for row i <- env i.
+        Ids may repeat; a row whose id is outside 0 .. N-1 keeps what it held.  Also records the sim-global counters and randomisation
+        clock.  One launch on the current stream."""
+        self._open("save")
+        self._check(self.lib.bez_snapshot_save(self.h, self.snap, self._ids("env_ids", env_ids, self.rows), self._stream()))
+
+    def restore(self, sim=None, env_ids=None, row_ids=None, count=None, globals_=False):
+        """Env env_ids[i] of `sim` (None: the owning sim) becomes row row_ids[i], i < count.  `env_ids`, `row_ids`: (count,) int32 on the
+        sim's device, contiguous, or None for env i / row i; `count` None: the length of the ids given, else the snapshot's rows.  Valid
+        env ids must be distinct; an entry with either id out of range is skipped.  `globals_`: also give the sim the snapshot's global
+        block (a rewind of the whole sim); False leaves the sim's own alone.  The Isaac-layout tensors are stale afterwards as after a
+        set_*_indexed call: refresh them.  Everything is checked before the library is called."""
+        self._open("restore")
+        dst = self.sim if sim is None else sim
+        if not isinstance(dst, BezSim):
+            raise BezSimError("snapshot restore: sim must be a BezSim, got %s" % type(dst).__name__)
+        if dst.device != self.device:
+            raise BezSimError("snapshot restore: the destination sim is on %s, the snapshot on %s" % (dst.device, self.device))
+        given = [t for t in (env_ids, row_ids) if isinstance(t, torch.Tensor)]
+        if count is None:
+            count = given[0].numel() if given else self.rows
+        if isinstance(count, bool) or not isinstance(count, int) or count < 0:
+            raise BezSimError("snapshot restore: count must be an int >= 0, got %r" % (count,))
+        if row_ids is None and count > self.rows:
+            raise BezSimError("snapshot restore: count %d exceeds the snapshot's %d rows (row_ids is None: row i)" % (count, self.rows))
+        ptrs = [self._ids("env_ids", env_ids, count), self._ids("row_ids", row_ids, count)]
+        what = abi.SNAPSHOT_ENVS | (abi.SNAPSHOT_GLOBALS if globals_ else 0)
+        dst._check(self.lib.bez_snapshot_restore(dst.h, self.snap, *ptrs, count, what, self._stream()))
+
+    # ---- the snapshot as host data: one self-describing blob (include/bez_sim.h), here cut into its sections
+    def _blob_words(self):
+        size = C.c_int64(0)
+        self._check(self.lib.bez_snapshot_export(self.h, self.snap, None, C.byref(size), self._stream()))
+        return size.value // 4
+
+    def state_dict(self):
+        """{"header": (SNAPSHOT_HEADER_WORDS,), <section>: (width, rows) for every name of abi.SNAPSHOT_SECTIONS, "globals":
+        (SNAPSHOT_GLOBAL_WORDS,)}: int32 CPU tensors holding the 32-bit words of the snapshot (a 64-bit item is two rows of its section,
+        low then high), copies that stay valid.  Waits for the current stream."""
+        self._open("state_dict")
+        words = self._blob_words()
+        blob = torch.empty(words, dtype=torch.int32)
+        size = C.c_int64(words * 4)
+        self._check(self.lib.bez_snapshot_export(self.h, self.snap, C.c_void_p(blob.data_ptr()), C.byref(size), self._stream()))
+        hw = abi.SNAPSHOT_HEADER_WORDS
+        out, at = {"header": blob[:hw].clone()}, hw
+        for k, name in enumerate(abi.SNAPSHOT_SECTIONS):
+            width = int(blob[8 + k])
+            out[name] = blob[at:at + width * self.rows].view(width, self.rows).clone()
+            at += width * self.rows
+        out["globals"] = blob[at:at + abi.SNAPSHOT_GLOBAL_WORDS].clone()
+        return out
+
+    def load_state_dict(self, d):
+        """Fills the snapshot from a state_dict() of a snapshot with the same rows and widths (of this sim or another one of the same
+        task and asset); the library refuses what does not fit and leaves the snapshot as it was."""
+        self._open("load_state_dict")
+        names = ("header",) + abi.SNAPSHOT_SECTIONS + ("globals",)
+        for name in names:
+            if name not in d or not isinstance(d[name], torch.Tensor) or d[name].dtype != torch.int32 or d[name].device.type != "cpu":
+                raise BezSimError("snapshot load_state_dict: %r must be an int32 CPU tensor" % name)
+        blob = torch.cat([d[name].reshape(-1) for name in names]).contiguous()
+        self._check(self.lib.bez_snapshot_import(self.h, self.snap, C.c_void_p(blob.data_ptr()), blob.numel() * 4, self._stream()))

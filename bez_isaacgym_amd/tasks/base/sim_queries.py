@@ -289,6 +289,40 @@ class SimQueries:
         about those rows; env_ids gives row i the randomised masses, gravity and joint limits of env env_ids[i].  close() frees it."""
         return StateQueries(self.sim.query_state(self.num_envs if rows is None else rows))
 
+    # ---- env snapshots (include/bez_sim.h "Env snapshots"): whole envs saved and put back, for planning through the real step and rewinds
+    def save_state(self, env_ids=None):
+        """A sim.Snapshot holding env env_ids[i] in row i ((M,) int32 on the sim's device; None: every env, row i = env i), with the
+        sim-global counters and randomisation clock and what this object itself holds per step (last_step, last_rand_step, the last
+        actions).  close() frees it; load_state() puts it back."""
+        snap = self.sim.snapshot(self.num_envs if env_ids is None else int(env_ids.numel()))
+        snap.save(env_ids)
+        actions = getattr(self, "actions", None)   # (materialises the borrowed action tensor of the last step: KickEnv.actions)
+        snap.host = {"last_step": getattr(self, "last_step", -1), "last_rand_step": getattr(self, "last_rand_step", -1),
+                     "actions": actions.clone() if isinstance(actions, torch.Tensor) else None}
+        return snap
+
+    def load_state(self, snap, env_ids=None, row_ids=None, globals_=None):
+        """Env env_ids[i] becomes row row_ids[i] of `snap` (None: env i / row i), a snapshot of this task's sim or of another sim of the
+        same task and asset.  `globals_`: also take the snapshot's sim-global block and this object's own per-step state -- None: True
+        exactly when every env is restored by the identity (no ids, as many rows as envs), a rewind of the whole sim; a partial restore
+        leaves them alone.  Afterwards every accessor (obs_buf, root_states, net_contact_forces, dof_force_tensor after its refresh ...)
+        shows the restored envs: the lazily refreshed tensors are marked stale, the copies handed out by the last step() are renewed."""
+        whole = env_ids is None and row_ids is None and snap.rows == self.num_envs
+        if globals_ is None:
+            globals_ = whole
+        snap.restore(self.sim, env_ids=env_ids, row_ids=row_ids, globals_=bool(globals_))
+        self._stale = True   # root_states, dof_state, rigid_body, net_contact_forces: refreshed by their next read (kick_env.py)
+        host = getattr(snap, "host", None)
+        if whole and globals_ and host is not None:   # what only a whole-sim restore can put back
+            self.last_step, self.last_rand_step = host["last_step"], host["last_rand_step"]
+            if host["actions"] is not None:
+                self.actions = host["actions"].clone()
+        extras, obs_dict = self.__dict__.get("extras"), self.__dict__.get("obs_dict")
+        if extras is not None and "time_outs" in extras:
+            extras["time_outs"] = self.timeout_buf.to(self.rl_device)
+        if obs_dict is not None and "obs" in obs_dict:
+            obs_dict["obs"] = self._clipped_obs()
+
 
 class StateQueries(SimQueries):
     """SimQueries over a query state (bez_isaacgym_amd.sim.QueryState) in the place of the sim: `num_envs` is its row count.  What asks
@@ -312,4 +346,6 @@ class StateQueries(SimQueries):
     apply_rigid_body_force_tensors = _not_here("apply_rigid_body_force_tensors()")
     apply_rigid_body_force_at_pos_tensors = _not_here("apply_rigid_body_force_at_pos_tensors()")
     query_state = _not_here("query_state()")
+    save_state = _not_here("save_state()")
+    load_state = _not_here("load_state()")
     del _not_here

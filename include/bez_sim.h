@@ -675,6 +675,73 @@ int bez_query_state_bind(BezSim* sim, BezQueryState* qs /* or NULL */);
 int bez_query_state_tensor(BezSim* sim, BezQueryState* qs, int which, void** dev_ptr, int64_t shape[3], int* ndim, int* dtype);
 int bez_query_state_refresh(BezSim* sim, BezQueryState* qs, uint32_t which_mask, void* stream);
 
+/* Env snapshots.  A snapshot holds whole envs -- everything that decides how an env continues -- in M rows, M >= 1 independent of N:
+ * save copies envs into rows, restore copies rows back into envs of the owning sim or of another sim on the same device (a planner's
+ * second sim), a row into as many envs as wanted.  A BezSnapshot is owned by the sim that created it, allocated through the sim's buffer
+ * owner (one device buffer); bez_snapshot_destroy frees it, and bez_sim_destroy frees the snapshots still alive.  A sim that creates none
+ * allocates and launches what it did without them.
+ *
+ * A row holds, as they are when the save runs on `stream` (DESIGN.md 4.3p has the inventory, buffer by buffer):
+ *   - every field of the SoA state: root, joints, ball, position targets, previous velocity, contact-force rows, feet words, goal;
+ *   - obs, rew, reset, progress, timeout, the episode counter, randomize, the non-finite count;
+ *   - the three episode statistics (end counts, reward terms, end bits);
+ *   - every BEZ_PARAM_* row the sim had allocated at the save (the snapshot remembers which: "present"); a save whose sim lacks a
+ *     parameter leaves the snapshot's rows of it alone and clears its presence for the whole snapshot;
+ *   - the actuator record, when the sim had BEZ_FLAG_DOF_FORCE on at bez_snapshot_create (a snapshot created before has no room for it).
+ * The global block holds the host counters of observation passes, post-physics calls and explicit resets, whether the gravity rows are
+ * uniform and whether the last step added the observation noise itself, and the device words: the goal-draw call counter and its last
+ * draw, the randomisation clock with the noise parameters, and the action-noise record.  Every save records it.
+ * Not in a snapshot: the Isaac-layout tensors, actuator tensors, Jacobian and mass matrix (derived: after a restore they are stale exactly
+ * as after a set_*_indexed call, and their refresh calls bring them to the restored state); external wrenches pending for the next physics
+ * launch (a restore does not touch the destination's either); the health word and the diagnostic records; the configuration (gains, time
+ * step, flags, the randomisation's ranges).
+ *
+ * bez_snapshot_save: row i <- env env_ids_dev[i]; NULL: row i <- env i.  Ids may repeat; a row whose id is outside 0 .. N-1 keeps what it
+ *   held (the kernel maps such an id to -1 before anything is indexed with it).
+ * bez_snapshot_restore: env env_ids_dev[i] of `dst` <- row row_ids_dev[i], i < count; NULL env ids: env i, NULL row ids: row i.  An entry
+ *   with either id out of range is skipped.  Valid env ids must be distinct: with duplicates which row wins is undefined, but nothing
+ *   outside the buffers is touched.  `what`: BEZ_SNAPSHOT_ENVS leaves dst's global block alone (a partial restore; dst's "gravity rows are
+ *   uniform" is cleared when gravity rows were written); BEZ_SNAPSHOT_ENVS | BEZ_SNAPSHOT_GLOBALS also gives dst the snapshot's global
+ *   block (a rewind of the whole sim).  A parameter the snapshot has and dst never allocated is allocated as bez_sim_set_env_params does,
+ *   default rows for the envs not restored -- with the same consequence: a HIP graph captured before has to be recaptured.  A parameter
+ *   dst has and the snapshot lacks: the restored envs get dst's default row.  The packed copy of the gains and limits is rebuilt.  The
+ *   actuator record is copied when both sides have it, with the same number of substeps.
+ *   dst may differ from the owner in num_envs, seed, env_id_offset, gains and time step ("what if this env ran with other gains"); it
+ *   must have the same device, task, asset bits (BEZ_FLAG_CLEATS, BEZ_FLAG_BOX_ASSET), ball and observation width.
+ * The random identity of a restored env is the DESTINATION's: the Philox key of its draws stays (dst seed, dst global env id, episode),
+ *   with `episode` the copied counter.  So copies of one row in several envs diverge at their next reset draw, and an env restored into
+ *   its own slot of its own sim replays the draws it would have had.
+ * bez_snapshot_export / bez_snapshot_import move a snapshot as one self-describing blob, in host or device memory: BEZ_SNAPSHOT_HEADER_WORDS
+ *   uint32 words -- magic, layout version, rows, number of sections, presence bits, columns, then the width of every section, the host
+ *   counters and what a compatible sim has in common --, then the sections as (width, rows) uint32 columns, a 64-bit item as (low, high),
+ *   then the global device words.  export with blob NULL only reports the size in *bytes; otherwise *bytes is the room on entry and the
+ *   size on return.  import refuses a blob that is too short or whose magic, layout version, rows, widths or task / asset do not fit, and
+ *   leaves the snapshot as it was.  Both wait for `stream` before they return.
+ * The host counters are read (save) and written (restore with GLOBALS) when the call is made, as a query-state binding is: a launch
+ *   already enqueued and a captured graph keep what they were given.  Snapshot calls are not for use inside a graph capture.
+ *
+ * rc -1 with a bez_sim_last_error message: rows < 1; a null sim; a null or destroyed snapshot; a snapshot of another sim (save, destroy,
+ * export, import); count < 0; count > the snapshot's rows with NULL row ids; a bit in `what` outside the two above, or without
+ * BEZ_SNAPSHOT_ENVS; restoring a snapshot nothing was saved into; an incompatible dst.  create, destroy and a restore that has to allocate
+ * a parameter allocate or free (and may wait for the device); every other save and restore is ONE kernel launch on `stream` (the global
+ * device words move inside it) -- plus the rebuild of the packed gains and limits where dst has any of the four -- that allocates nothing. */
+typedef struct BezSnapshot BezSnapshot;
+#define BEZ_SNAPSHOT_ENVS 1u
+#define BEZ_SNAPSHOT_GLOBALS 2u
+#define BEZ_SNAPSHOT_MAGIC 0x4e535a42u /* "BZSN" */
+#define BEZ_SNAPSHOT_LAYOUT 1
+#define BEZ_SNAPSHOT_HEADER_WORDS 40
+#define BEZ_SNAPSHOT_SECTIONS 20   /* state, obs, rew, reset, progress, timeout, episode, randomize, nonfinite, end_counts, reward_terms, \
+                                      end_bits, the seven BEZ_PARAM_* rows in enum order, the actuator record */
+#define BEZ_SNAPSHOT_GLOBAL_WORDS 16 /* call counter 2, randomisation clock and noise 8, action-noise record 4, goal draw 2 */
+int bez_snapshot_create(BezSim* sim, int32_t rows, BezSnapshot** out);
+int bez_snapshot_destroy(BezSim* sim, BezSnapshot* snap);
+int bez_snapshot_save(BezSim* sim, BezSnapshot* snap, const int32_t* env_ids_dev /* (rows) or NULL */, void* stream);
+int bez_snapshot_restore(BezSim* dst, const BezSnapshot* snap, const int32_t* env_ids_dev /* (count) or NULL */,
+                         const int32_t* row_ids_dev /* (count) or NULL */, int32_t count, uint32_t what, void* stream);
+int bez_snapshot_export(BezSim* sim, const BezSnapshot* snap, void* blob /* host or device, or NULL */, int64_t* bytes, void* stream);
+int bez_snapshot_import(BezSim* sim, BezSnapshot* snap, const void* blob, int64_t bytes, void* stream);
+
 /* gym.refresh_{actor_root_state,dof_state,rigid_body_state,net_contact_force}_tensor
  * (kick_env.py:750-753): materialise the Isaac-layout tensor from the SoA state.  ROOT_STATE, DOF_STATE, RIGID_BODY_STATE,
  * NET_CONTACT_FORCE, DOF_TARGET, PREV_LIN_VEL, FEET and GOAL need it; every other BezTensor is always live (the kernels
