@@ -1,5 +1,6 @@
 """Ball <-> box contact of the fused step: state generators that put the ball against every one of the eleven boxes, an independent
-numpy sphere-box test, and the shared run / compare helpers of tests/test_ball_contact_cpu.py and tests/test_gpu_ball_contact.py.
+numpy sphere-box test, and the oracle's side of the cases of tests/test_ball_contact_cpu.py and tests/test_gpu_ball_contact.py (the
+harness they share with the other step-term suites is tests/step_terms.py).
 
 `depths` reads only the model JSON and the Isaac-visible rigid-body rows: it calls neither the oracle nor the kernels, so its choice of
 the deepest box is evidence about both.  The generators use their own forward kinematics of the model JSON (checked against the
@@ -9,18 +10,13 @@ import os
 
 import numpy as np
 
-from bez_isaacgym_amd import abi
+from tests import step_terms as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODEL = os.path.join(ROOT, "bez_isaacgym_amd", "model", "bez_model.json")
-ASSETS = {"default": 0, "cleats": abi.FLAG_CLEATS, "box": abi.FLAG_BOX_ASSET}
 NBOX = 11
 KEPT_MARGIN = 1e-4   # m: a deepest box that leads by less may be chosen either way by two roundings (DESIGN.md 6 "knife edges")
 PARKED = (0.0, 3.0, 0.08)
-# the project's single-step bars (tests/test_gpu_parity.py): quantity -> (atol, rtol)
-BARS = {"pose": (2e-5, 0.0), "root_vel": (4e-3, 0.0), "ball_lin": (4e-3, 0.0), "ball_spin": (4e-3, 0.0), "q": (1.5e-4, 0.0),
-        "qd": (1.5e-2, 0.0), "cf": (0.04, 0.01), "imu": (1.5e-2, 0.0), "rew": (2e-5, 0.0)}
-QUANTITIES = tuple(BARS)
 
 _model = None
 
@@ -178,14 +174,14 @@ def free_space_states(n, asset, seed):
 
 
 def kick_stance_states(n, asset, seed, reset_root=None, reset_dof=None):
-    """The reset state (as a freshly created sim of make_cfg(n, asset) reports it, bit for bit the same from the oracle and the kernels:
+    """The reset state (as a freshly created sim of step_terms.step_cfg(n, asset) reports it, bit for bit the same from the oracle and the kernels:
     standing on the ground under default gravity) with the ball resting on the ground, at most 2 mm into it, on a circle of radius
     0.06 - 0.125 m around the left foot (even envs) or the right foot (odd envs), rolling at up to 0.5 m/s with up to 3 rad/s of spin."""
     rng = np.random.default_rng(seed)
     R = ball_radius()
     if reset_root is None:
         from oracle.bez_oracle import Oracle
-        fresh = Oracle(make_cfg(n, asset))
+        fresh = Oracle(S.step_cfg(n, asset))
         reset_root, reset_dof = fresh.root_states, fresh.dof_state
     rs = np.asarray(reset_root, np.float64).reshape(n, 2, 13).copy()
     ds = np.asarray(reset_dof, np.float64).reshape(n, 18, 2).copy()
@@ -214,58 +210,7 @@ def park_ball(states, keep):
     return dict(states, root_states=rs)
 
 
-# ---------------------------------------------------------------------------------------------------------------- run and compare
-def make_cfg(n, asset, gravity=True, substeps=2, flags=0, seed=17):
-    cfg = abi.default_config(n, seed=seed)
-    cfg.flags |= ASSETS[asset] | flags
-    cfg.substeps = substeps
-    if not gravity:
-        cfg.gravity[:] = [0.0, 0.0, 0.0]
-    return cfg
-
-
-def dr_params(n, seed):
-    """per-env friction, Kp and Kd scales (the friction feeds the ball contact)"""
-    rng = np.random.default_rng(seed)
-    return {abi.PARAM_FRICTION: rng.uniform(0.7, 1.3, (n, 1)).astype(np.float32),
-            abi.PARAM_KP_SCALE: rng.uniform(0.5, 1.5, (n, 18)).astype(np.float32),
-            abi.PARAM_KD_SCALE: rng.uniform(0.5, 1.5, (n, 18)).astype(np.float32)}
-
-
-def actions(n, seed):
-    return np.random.default_rng(seed).uniform(-1, 1, (n, 18)).astype(np.float32)
-
-
-def inject(sim, states, params=None):
-    """the same state through the Isaac-layout setters of an Oracle or a SimAdapter; the episode starts here"""
-    n = len(states["root_states"])
-    sim.set_root_states(states["root_states"].reshape(-1, 13))
-    sim.set_dof_state(states["dof_state"].reshape(-1, 2))
-    sim.set_reset(np.zeros(n, np.int64)); sim.set_progress(np.zeros(n, np.int64))
-    for k, v in (params or {}).items():
-        sim.set_env_params(k, v)
-
-
-def outputs(sim, n):
-    """everything one step produces, per env"""
-    rs = sim.root_states.reshape(n, 2, 13).astype(np.float64)
-    ds = sim.dof_state.reshape(n, 18, 2).astype(np.float64)
-    return dict(pose=rs[:, :, 0:7].reshape(n, -1), root_vel=rs[:, 0, 7:13], ball_lin=rs[:, 1, 7:10], ball_spin=rs[:, 1, 10:13],
-                q=ds[:, :, 0], qd=ds[:, :, 1], cf=sim.contact_forces.reshape(n, -1).astype(np.float64),
-                imu=sim.obs[:, 36:44].astype(np.float64), rew=sim.rew.reshape(n, 1).astype(np.float64),
-                reset=sim.reset_buf.copy())
-
-
-def env_errors(got, ref, excess=False):
-    """per quantity the largest |got - ref| of every env (inf for a non-finite env); excess=True: beyond the bar's relative part,
-    |got - ref| - rtol |ref|, which is what the bar's absolute part is compared with"""
-    out = {}
-    for k in QUANTITIES:
-        err = np.abs(got[k] - ref[k]) - (BARS[k][1] * np.abs(ref[k]) if excess else 0.0)
-        out[k] = np.where(np.isfinite(got[k]).all(1), err.max(1), np.inf)
-    return out
-
-
+# ---------------------------------------------------------------------------------------------------------------- rows and momentum
 def loaded_rows(cf, asset, tol=0.0):
     """(n, robot bodies) bool: robot rows of the contact-force tensor (n * rows, 3) that carry a force"""
     nb = ball_row(asset)
@@ -281,58 +226,9 @@ def winner_body(d, asset):
 
 
 def robot_ball_momentum(sim, n, asset):
-    """linear momentum of the robot from the rigid-body rows and the URDF masses (as tests/scenarios.body_momenta), and of the ball"""
-    links = asset_links(asset)
-    mass = np.array([L["mass"] for L in links]); com = np.array([L["com"] for L in links]); body = np.array([L["body"] for L in links])
+    """linear momentum of the robot (step_terms.robot_momentum) and of the ball, from the rigid-body rows"""
     rb = sim.rigid_body_states.reshape(n, -1, 13).astype(np.float64)
-    rows = rb[:, body]
-    rc = np.einsum("nlij,lj->nli", quat_to_mat(rows[..., 3:7]), com)
-    vc = rows[..., 7:10] + np.cross(rows[..., 10:13], rc)
-    return (mass[None, :, None] * vc).sum(1), float(model()["ball"]["mass"]) * rb[:, ball_row(asset), 7:10]
-
-
-# ---------------------------------------------------------------------------------------------------------------- the oracle's side of a case
-NEIGHBOUR_ENVS = (0, 15, 16, 63, 64, 127, 191, 192, 199)   # first / last lanes of the 16- and 64-env workgroups, and the last env
-
-
-def case_states(scenario, asset, n):
-    """the states of a scenario: "free" (free_space_states), "kick" (kick_stance_states), "sparse" (free space, the ball parked away
-    from the robot in every env but NEIGHBOUR_ENVS)"""
-    if scenario == "kick":
-        return kick_stance_states(n, asset, 3)
-    st = free_space_states(n, asset, 4)
-    return park_ball(st, NEIGHBOUR_ENVS) if scenario == "sparse" else st
-
-
-_REFERENCES = {}
-
-
-def reference(scenario, asset, n, substeps=2, dr=False, flags=0):
-    """One step of the fp64 oracle and of its fp32 build from the scenario's states, computed once per process and shared by every
-    kernel's test: states, per-env parameters, actions, the numpy depths of the start state, both outputs, the momentum change."""
-    key = (scenario, asset, n, substeps, dr, flags)
-    if key in _REFERENCES:
-        return _REFERENCES[key]
-    from types import SimpleNamespace
-    from oracle.bez_oracle import Oracle
-    ref = SimpleNamespace(scenario=scenario, asset=asset, n=n, substeps=substeps, dr=dr, flags=flags)
-    ref.cfg = lambda: make_cfg(n, asset, gravity=(scenario == "kick"), substeps=substeps, flags=flags)
-    ref.states = case_states(scenario, asset, n)
-    ref.params = dr_params(n, 8) if dr else None
-    ref.actions = actions(n, 2)
-    o64, o32 = Oracle(ref.cfg()), Oracle(ref.cfg(), precision="f32")
-    for o in (o64, o32):
-        inject(o, ref.states, ref.params)
-    ref.depths = depths(o64.rigid_body_states.reshape(n, -1, 13), ref.states["root_states"][:, 1, 0:3], asset)
-    ref.kept = kept(ref.depths)
-    before = [robot_ball_momentum(o, n, asset) for o in (o64, o32)]
-    for o in (o64, o32):
-        o.step(ref.actions)
-    ref.out64, ref.out32 = outputs(o64, n), outputs(o32, n)
-    ref.err32 = env_errors(ref.out32, ref.out64)
-    ref.dp64, ref.dp32 = (momentum_change(b, robot_ball_momentum(o, n, asset)) for b, o in zip(before, (o64, o32)))
-    _REFERENCES[key] = ref
-    return ref
+    return S.robot_momentum(sim, n, asset)[0], float(model()["ball"]["mass"]) * rb[:, ball_row(asset), 7:10]
 
 
 def momentum_change(before, after):
@@ -340,17 +236,29 @@ def momentum_change(before, after):
     return np.abs((after[0] + after[1]) - (before[0] + before[1])).max(1)
 
 
-OUTLIER_BUDGET = 3   # tests.parity_util.EnvOutliers' default budget for one step of up to 2000 envs
+# ---------------------------------------------------------------------------------------------------------------- the oracle's side of a case
+def case_states(scenario, asset, n):
+    """the states of a scenario: "free" (free_space_states), "kick" (kick_stance_states), "sparse" (free space, the ball parked away
+    from the robot in every env but step_terms.NEIGHBOUR_ENVS)"""
+    if scenario == "kick":
+        return kick_stance_states(n, asset, 3)
+    st = free_space_states(n, asset, 4)
+    return park_ball(st, S.NEIGHBOUR_ENVS) if scenario == "sparse" else st
 
 
-def case_bars(ref):
-    """The bars of a case: the project's single-step bars (BARS) where the oracle's own fp32 build, on this case's kept envs, stays under
-    half of one; where it does not, 3 x the fp32 build's worst error against fp64 -- measured on the oracle, never on a kernel.  The
-    fp32 build flips a branch next to a switch as any fp32 implementation does (tests/parity_util.py), so its worst is taken outside the
-    same OUTLIER_BUDGET envs that the kernel is allowed.  Returns quantity -> (atol, rtol, that fp32 worst)."""
-    out = {}
-    excess = env_errors(ref.out32, ref.out64, excess=True)
-    for k, (atol, rtol) in BARS.items():
-        worst = float(np.sort(excess[k][ref.kept])[-1 - OUTLIER_BUDGET])
-        out[k] = (atol if worst <= 0.5 * atol else 3.0 * worst, rtol, worst)
-    return out
+def reference(scenario, asset, n, substeps=2, dr=False, flags=0):
+    """step_terms.reference of a ball case: states, per-env parameters, actions, the numpy depths of the start state, kept, both
+    outputs, the momentum change."""
+    def build(ref):
+        ref.cfg = lambda: S.step_cfg(n, asset, gravity=(scenario == "kick"), substeps=substeps, flags=flags)
+        ref.states = case_states(scenario, asset, n)
+        ref.params = S.dr_params(n, 8) if dr else None
+        ref.actions = S.actions(n, 2)
+        pair = S.oracle_pair(ref)
+        ref.depths = depths(pair[0].rigid_body_states.reshape(n, -1, 13), ref.states["root_states"][:, 1, 0:3], asset)
+        ref.kept = kept(ref.depths)
+        before = [robot_ball_momentum(o, n, asset) for o in pair]
+        S.step_pair(ref, *pair)
+        ref.dp64, ref.dp32 = (momentum_change(b, robot_ball_momentum(o, n, asset)) for b, o in zip(before, pair))
+    return S.reference(("ball", scenario, asset, n, substeps, dr, flags), build,
+                       scenario=scenario, asset=asset, n=n, substeps=substeps, dr=dr, flags=flags)

@@ -1,8 +1,8 @@
 """The external wrenches of the fused step (bez_sim_apply_body_forces), body by body: load patterns that aim every
 rigid body row (fixed bodies, cleats and the ball's row included) in every mode of the call, magnitudes derived from the fp64 mass
 matrix, the oracle's side of a case (oracle.bez_oracle.Oracle.apply_body_forces, written from DESIGN 4.3c with a pending list of
-entries instead of the kernels' moment matrix) and the shared compare of tests/test_body_wrench_cpu.py and
-tests/test_gpu_body_wrench.py.
+entries instead of the kernels' moment matrix), the response bars and the comparison of tests/test_body_wrench_cpu.py and
+tests/test_gpu_body_wrench.py (on the harness of tests/step_terms.py).
 
 Scenarios (`case_states`):
   flight   joint_drive_ref._base: zero gravity, floating base, root at +-0.3 m/s and +-1 rad/s, easy joints, default gains, the ball in
@@ -30,11 +30,10 @@ from tests import forward_dynamics_numpy as FD
 from tests import generalized_forces_numpy as GF
 from tests import ground_contact_ref as G
 from tests import joint_drive_ref as J
-from tests.ball_contact_ref import BARS, case_bars, make_cfg, inject, env_errors, NEIGHBOUR_ENVS, OUTLIER_BUDGET, dr_params, kick_stance_states
-from tests.parity_util import EnvOutliers
+from tests import step_terms as S
+from tests.step_terms import inject, outputs
 
-N = 1000                    # a multiple of neither the 16-env nor the 64-env workgroup
-QUANTITIES = B.QUANTITIES
+N = S.N
 RESPONSE = ("root_vel", "qd", "ball_lin", "ball_spin")
 MODES = ("env_centre", "env_point", "local_centre", "local_point")   # *_centre: force + torque at the body's centre of mass; *_point: a force at a point
 ENV, LOCAL = abi.SPACE_ENV, abi.SPACE_LOCAL
@@ -58,17 +57,6 @@ def tables(asset, task="bez_kick"):
     nb, ball = int(t["num_bodies"]), task == "bez_kick"
     return SimpleNamespace(nb=nb, nbe=nb + int(ball), ball=ball, link=np.asarray(t["body_link"]), off=np.asarray(t["body_offset"], np.float64),
                            com=np.asarray(t["body_com"], np.float64), names=list(t["body_names"]) + (["ball"] if ball else []))
-
-
-def outputs(sim, n):
-    """ball_contact_ref.outputs; a task without a ball reports zeros for it"""
-    if sim.nact == 2:
-        return B.outputs(sim, n)
-    rs = sim.root_states.reshape(n, 1, 13).astype(np.float64)
-    ds = sim.dof_state.reshape(n, 18, 2).astype(np.float64)
-    return dict(pose=rs[:, :, 0:7].reshape(n, -1), root_vel=rs[:, 0, 7:13], ball_lin=np.zeros((n, 3)), ball_spin=np.zeros((n, 3)),
-                q=ds[:, :, 0], qd=ds[:, :, 1], cf=sim.contact_forces.reshape(n, -1).astype(np.float64),
-                imu=sim.obs[:, 36:44].astype(np.float64), rew=sim.rew.reshape(n, 1).astype(np.float64), reset=sim.reset_buf.copy())
 
 
 # ---------------------------------------------------------------------------------------------------------------- states
@@ -96,7 +84,7 @@ def _off_the_ground_edges(st, asset):
     """st with robot and ball moved together, up or down by up to three NUDGEs, in the envs in which a ground point (the ball's
     included: kick_stance_states rests it 0 - 2 mm deep) starts within ground_contact_ref.KEPT_MARGIN of the plane or of fn0 = 0"""
     n = len(st["root_states"])
-    cfg = make_cfg(n, asset)
+    cfg = S.step_cfg(n, asset)
     rs = st["root_states"].copy()
     z0 = rs[:, :, 2].copy()
     todo = ~ground_kept(st, asset, cfg)
@@ -124,10 +112,10 @@ def case_states(scenario, asset, n, task="bez_kick", fixed=False):
         if scenario == "late":
             st = dict(st, first=flight_states(n, asset, seed=22))
     elif scenario == "stance":
-        st = dict(_off_the_ground_edges(kick_stance_states(n, asset, 3), asset), actions=B.actions(n, 2))
+        st = dict(_off_the_ground_edges(B.kick_stance_states(n, asset, 3), asset), actions=S.actions(n, 2))
     else:
         assert scenario == "lying", scenario
-        st = dict(_off_the_ground_edges(G.lying_states(n, asset), asset), actions=B.actions(n, 2))
+        st = dict(_off_the_ground_edges(G.lying_states(n, asset), asset), actions=S.actions(n, 2))
     if task != "bez_kick":   # no ball actor
         st = {k: (v[:, :1].copy() if k == "root_states" else v) for k, v in st.items()}
         if "first" in st:
@@ -232,7 +220,7 @@ def loads(pattern, asset, task, states, seed, level="easy", cfg=None, mass_scale
         body, mode = solo_cells(n, nbe)
         on = np.ones(n, bool)
         if pattern == "sparse":
-            on[:] = False; on[list(NEIGHBOUR_ENVS)] = True
+            on[:] = False; on[list(S.NEIGHBOUR_ENVS)] = True
         F, Tq, P = draw()
         calls = []
         for m, name in enumerate(MODES):
@@ -301,58 +289,53 @@ def run(ref, precision, loaded, slip=None):
     return outputs(o, ref.n), np.concatenate([d["word"] for d in decisions], 1), decisions
 
 
-_REFERENCES = {}
-
-
 def reference(scenario="flight", pattern="solo", level="easy", asset="default", n=N, substeps=2, dr=False, flags=0, task="bez_kick", steps=1):
-    """One control step (steps=2: two, the second without a call) of the fp64 oracle and of its fp32 build, loaded and unloaded, computed
-    once per process and shared by every kernel's test: states, per-env parameters, actions, calls, aimed rows, the four outputs, the
-    decision words, kept, the responses d64 / d32 = loaded - unloaded."""
+    """step_terms.reference of a wrench case, with this module's own runs: one control step (steps=2: two, the second without a call) of
+    the fp64 oracle and of its fp32 build, loaded and unloaded -- states, per-env parameters, actions, calls, aimed rows, the four
+    outputs, the decision words, kept, the responses d64 / d32 = loaded - unloaded."""
     flags &= ~abi.FLAG_DOF_FORCE    # the oracle records its actuators anyway; the sims of the GPU file set the flag themselves
-    key = (scenario, pattern, level, asset, n, substeps, dr, flags, task, steps)
-    if key in _REFERENCES:
-        return _REFERENCES[key]
-    ref = SimpleNamespace(scenario=scenario, pattern=pattern, level=level, asset=asset, n=n, substeps=substeps, dr=dr, flags=flags, task=task,
-                          steps=steps, tables=tables(asset, task))
 
     def cfg():
-        c = make_cfg(n, asset, gravity=scenario in GRAVITY, substeps=substeps, flags=flags)
+        c = S.step_cfg(n, asset, gravity=scenario in GRAVITY, substeps=substeps, flags=flags)
         c.task = abi.TASK_IDS[task]
         return c
-    ref.cfg = cfg
-    fixed = bool(flags & FIXED_BASE)
-    ref.states = case_states(scenario, asset, n, task, fixed)
-    ref.actions = ref.states["actions"]
-    ref.params = None
-    if dr:
-        ref.params = dict(dr_params(n, 8))
-        ref.params[abi.PARAM_MASS_SCALE] = np.random.default_rng(9).uniform(0.8, 1.2, (n, 19)).astype(np.float32)
-    scale = None if not dr else ref.params[abi.PARAM_MASS_SCALE].astype(np.float64)
-    at = ref.states.get("first", ref.states)
-    ref.calls, ref.aimed = loads(pattern, asset, task, at, 31, level, cfg(), scale, (scenario, asset, n, task, fixed, dr))
-    ref.body, ref.mode = solo_cells(n, ref.tables.nbe)
-    ref.out64, ref.words64, dec_l = run(ref, "f64", True)
-    ref.unl64, ref.words64_unl, dec_u = run(ref, "f64", False)
-    ref.out32, ref.words32, _ = run(ref, "f32", True)
-    ref.unl32, _, _ = run(ref, "f32", False)
-    ref.kept = np.ones(n, bool)
-    for d in dec_l + dec_u:
-        ref.kept &= J.kept(d)
-    ref.joints_kept = ref.kept.copy()
-    if scenario in GRAVITY:
-        from oracle.bez_oracle import Oracle
-        o = Oracle(cfg())
-        inject(o, ref.states, ref.params)
-        rb = o.rigid_body_states.reshape(n, -1, 13)
-        ref.kept &= G.kept(G.terms(ref.states, asset, rb, cfg()))
-        if scenario == "stance":
-            ref.kept &= B.kept(B.depths(rb, ref.states["root_states"][:, 1, 0:3], asset))
-    ref.err32 = env_errors(ref.out32, ref.out64)
-    ref.d64 = {q: ref.out64[q] - ref.unl64[q] for q in RESPONSE}
-    ref.d32 = {q: ref.out32[q] - ref.unl32[q] for q in RESPONSE}
-    ref.rerr32 = {q: np.abs(ref.d32[q] - ref.d64[q]).max(1) for q in RESPONSE}
-    _REFERENCES[key] = ref
-    return ref
+
+    def build(ref):
+        ref.cfg = cfg
+        fixed = bool(flags & FIXED_BASE)
+        ref.states = case_states(scenario, asset, n, task, fixed)
+        ref.actions = ref.states["actions"]
+        ref.params = None
+        if dr:
+            ref.params = dict(S.dr_params(n, 8))
+            ref.params[abi.PARAM_MASS_SCALE] = np.random.default_rng(9).uniform(0.8, 1.2, (n, 19)).astype(np.float32)
+        scale = None if not dr else ref.params[abi.PARAM_MASS_SCALE].astype(np.float64)
+        at = ref.states.get("first", ref.states)
+        ref.calls, ref.aimed = loads(pattern, asset, task, at, 31, level, cfg(), scale, (scenario, asset, n, task, fixed, dr))
+        ref.body, ref.mode = solo_cells(n, ref.tables.nbe)
+        ref.out64, ref.words64, dec_l = run(ref, "f64", True)
+        ref.unl64, ref.words64_unl, dec_u = run(ref, "f64", False)
+        ref.out32, ref.words32, _ = run(ref, "f32", True)
+        ref.unl32, _, _ = run(ref, "f32", False)
+        ref.kept = np.ones(n, bool)
+        for d in dec_l + dec_u:
+            ref.kept &= J.kept(d)
+        ref.joints_kept = ref.kept.copy()
+        if scenario in GRAVITY:
+            from oracle.bez_oracle import Oracle
+            o = Oracle(cfg())
+            inject(o, ref.states, ref.params)
+            rb = o.rigid_body_states.reshape(n, -1, 13)
+            ref.kept &= G.kept(G.terms(ref.states, asset, rb, cfg()))
+            if scenario == "stance":
+                ref.kept &= B.kept(B.depths(rb, ref.states["root_states"][:, 1, 0:3], asset))
+        ref.err32 = S.env_errors(ref.out32, ref.out64)
+        ref.d64 = {q: ref.out64[q] - ref.unl64[q] for q in RESPONSE}
+        ref.d32 = {q: ref.out32[q] - ref.unl32[q] for q in RESPONSE}
+        ref.rerr32 = {q: np.abs(ref.d32[q] - ref.d64[q]).max(1) for q in RESPONSE}
+    return S.reference(("wrench", scenario, pattern, level, asset, n, substeps, dr, flags, task, steps), build,
+                       scenario=scenario, pattern=pattern, level=level, asset=asset, n=n, substeps=substeps, dr=dr, flags=flags, task=task,
+                       steps=steps, tables=tables(asset, task))
 
 
 def new_bits(ref):
@@ -366,7 +349,7 @@ def response_bars(ref):
     a kernel"""
     out = {}
     for q in RESPONSE:
-        worst = float(np.sort(ref.rerr32[q][ref.kept])[-1 - OUTLIER_BUDGET])
+        worst = float(np.sort(ref.rerr32[q][ref.kept])[-1 - S.OUTLIER_BUDGET])
         out[q] = (3.0 * worst + 2.0 * float(np.spacing(np.float32(np.abs(ref.out64[q][ref.kept]).max()))), worst)
     return out
 
@@ -382,8 +365,8 @@ def response_errors(ref, out, out_unloaded):
 
 def compare(case, ref, out, out_unloaded, label, report=None, p99=True):
     """One stepped simulator against the fp64 oracle.
-    (a) joint_drive_ref.compare's: every kept env inside ball_contact_ref.case_bars with EnvOutliers' default budget, reset flags equal
-        outside the outliers, per quantity the p99 of |got - f64| at most 2.5 x the fp32 build's + 1e-6 (p99=False: printed only).
+    (a) step_terms.compare: every kept env inside case_bars with EnvOutliers' default budget, reset flags equal outside the outliers,
+        per quantity the p99 of |got - f64| at most 2.5 x the fp32 build's + 1e-6 (p99=False: printed only).
     (b) the response out - out_unloaded (the same simulator stepped from the same state with nothing applied) against the oracle's,
         per quantity of RESPONSE: a loaded kept env beyond response_bars is an outlier of the SAME budget as (a)'s (the fp32 build's
         own worst is taken outside that budget, and a contact's friction kink is no more guarded by `kept` for the response than for
@@ -391,38 +374,21 @@ def compare(case, ref, out, out_unloaded, label, report=None, p99=True):
         mode cannot hide in it.  Per loaded body row the worst error over its kept envs outside the outliers is reported.
     report: a function that receives (errors, outliers, bars, response errors, response bars, {body: {quantity: worst}}) before anything
     is asserted.  -> the mask of the outlier envs"""
-    k = ref.kept
-    T = EnvOutliers(ref.n)
-    assert max(T.floor, int(np.ceil(T.share * ref.n))) == OUTLIER_BUDGET
-    bars = case_bars(ref)
-    for q in QUANTITIES:
-        atol, rtol, _ = bars[q]
-        print("%s %s %-9s bar %.1e + %g%s: fp32 build %.2e" % (case, label, q, atol, rtol,
-                                                               "" if atol == BARS[q][0] else " (raised: 3 x the fp32 build)", bars[q][2]))
-        T.close(out[q], ref.out64[q], atol, rtol=rtol, what=q, rows=k)
-    err = env_errors(out, ref.out64)
     rbars = response_bars(ref)
     rerr = response_errors(ref, out, out_unloaded)
-    for q in RESPONSE:
-        T._bad |= k & ref.aimed.any(1) & ~(rerr[q] <= rbars[q][0])
-    bad = T._bad.copy()
-    bodies = {}
-    for b in range(ref.tables.nbe):
-        envs = k & ~bad & ref.aimed[:, b]
-        if envs.any():
-            bodies[b] = {q: float(rerr[q][envs].max()) for q in RESPONSE}
-    for q in RESPONSE:
-        print("%s %s response %-9s bar %.2e: fp32 build %.2e, here %.2e" % (case, label, q, rbars[q][0], rbars[q][1],
-                                                                           max([v[q] for v in bodies.values()] or [0.0])))
-    if report is not None:
-        report(err, int(bad.sum()), bars, rerr, rbars, bodies)
-    T.end_step(); T.finish()
-    np.testing.assert_array_equal(out["reset"][k & ~bad], ref.out64["reset"][k & ~bad])
-    for q in QUANTITIES:
-        h, c = np.quantile(err[q][k], 0.99), np.quantile(ref.err32[q][k], 0.99)
-        print("%s %s %-9s p99 %.2e, fp32 build %.2e" % (case, label, q, h, c))
-        assert not p99 or h <= 2.5 * c + 1e-6, (case, label, q, h, c)
-    return bad
+    beyond = ref.aimed.any(1) & np.any([~(rerr[q] <= rbars[q][0]) for q in RESPONSE], 0)
+
+    def elements(bars, bad):
+        bodies = {}
+        for b in range(ref.tables.nbe):
+            envs = ref.kept & ~bad & ref.aimed[:, b]
+            if envs.any():
+                bodies[b] = {q: float(rerr[q][envs].max()) for q in RESPONSE}
+        for q in RESPONSE:
+            print("%s %s response %-9s bar %.2e: fp32 build %.2e, here %.2e" % (case, label, q, rbars[q][0], rbars[q][1],
+                                                                               max([v[q] for v in bodies.values()] or [0.0])))
+        return (rerr, rbars, bodies), []
+    return S.compare(case, ref, out, label, report=report, p99=p99, also_outliers=beyond, elements=elements)
 
 
 def cells(ref):
@@ -432,33 +398,27 @@ def cells(ref):
     return out
 
 
-def error_table(ref):
-    """{quantity: (worst, p99)} of the fp32 build against fp64 over the kept envs, and {quantity: (worst, p99)} of its response"""
+def response_table(ref):
+    """{quantity: (worst, p99)} of the fp32 build's response against fp64's over the kept envs (beside step_terms.error_table)"""
     k = ref.kept
-    return ({q: (float(ref.err32[q][k].max()), float(np.quantile(ref.err32[q][k], 0.99))) for q in QUANTITIES},
-            {q: (float(ref.rerr32[q][k].max()), float(np.quantile(ref.rerr32[q][k], 0.99))) for q in RESPONSE})
+    return {q: (float(ref.rerr32[q][k].max()), float(np.quantile(ref.rerr32[q][k], 0.99))) for q in RESPONSE}
 
 
 def report_line(name, ref, err, outliers, bars, rerr, rbars, bodies):
-    """one line of the report: kept / outlier counts, per quantity worst / p99 of the kernel | of the fp32 build, per response quantity
-    the bar, worst / p99 of the kernel | of the fp32 build, the raised bars"""
+    """one line of the report: step_terms.report_words with, before the raised bars, per response quantity the bar, worst / p99 of the
+    kernel | of the fp32 build"""
     k = ref.kept
-    words = ["%-44s kept=%d/%d outliers=%d/%d" % (name, k.sum(), ref.n, outliers, OUTLIER_BUDGET)]
-    for q in QUANTITIES:
-        h, c = err[q][k], ref.err32[q][k]
-        words.append("%s=%.1e/%.1e|%.1e/%.1e" % (q, h.max(), np.quantile(h, 0.99), c.max(), np.quantile(c, 0.99)))
+    words = S.report_words(name, 44, ref, err, outliers, bars)
     for q in RESPONSE:
         h, c = rerr[q][k], ref.rerr32[q][k]
-        words.append("d_%s=bar %.1e %.1e/%.1e|%.1e/%.1e" % (q, rbars[q][0], max([v[q] for v in bodies.values()] or [0.0]), np.quantile(h, 0.99),
-                                                            c.max(), np.quantile(c, 0.99)))
-    raised = ["%s->%.1e" % (q, bars[q][0]) for q in QUANTITIES if bars[q][0] != BARS[q][0]]
-    words.append("raised=%s" % (",".join(raised) or "none"))
+        words.insert(-1, "d_%s=bar %.1e %.1e/%.1e|%.1e/%.1e" % (q, rbars[q][0], max([v[q] for v in bodies.values()] or [0.0]), np.quantile(h, 0.99),
+                                                                c.max(), np.quantile(c, 0.99)))
     return "  ".join(words)
 
 
 # every oracle case of tests/test_gpu_body_wrench.py: name -> reference(**kw)
 CASES = {}
-for _a in B.ASSETS:
+for _a in S.ASSETS:
     for _dr in (False, True):
         CASES["flight-solo-s2-%s %s" % ("dr" if _dr else "plain", _a)] = dict(asset=_a, dr=_dr)
 for _s in (1, 3, 4):
@@ -469,7 +429,7 @@ for _sc in ("stance", "lying"):
     for _a in ("default", "cleats"):
         CASES["%s-solo %s" % (_sc, _a)] = dict(scenario=_sc, asset=_a)
 for _p in ("all", "stacked"):
-    for _a in B.ASSETS:
+    for _a in S.ASSETS:
         CASES["flight-%s %s" % (_p, _a)] = dict(pattern=_p, asset=_a)
 CASES["late-solo default"] = dict(scenario="late")
 CASES["flight-solo walk default"] = dict(task="bez_walk")

@@ -1,8 +1,8 @@
 """Ground contact of the fused step, point by point: state generators that put every one of the 22 ground points (8 foot corners or
 cleats, 8 torso, 4 head and 2 forearm guard points; bez_model.json "ground_points") under the plane, the numpy side (depth, normal
 force at the start of the step, active set, tangential speed and friction regime of every point, from the model JSON and the
-Isaac-visible rows alone), and the shared run / compare helpers of tests/test_ground_contact_cpu.py and
-tests/test_gpu_ground_contact.py.
+Isaac-visible rows alone), and the oracle's side, the comparison and the planted slips of tests/test_ground_contact_cpu.py and
+tests/test_gpu_ground_contact.py (on the harness of tests/step_terms.py).
 
 The contact law: a point at depth d > 0 whose fn0 = kn d - (h kn + cn) v_z is positive is a spring-damper, integrated
 implicitly, with the tangential viscosity ct = min(mu fn0 / max(vt, veps), ct_max).  Three friction regimes: slipping (vt > veps, under
@@ -14,16 +14,14 @@ the cap), capped (ct = ct_max) and inside veps under the cap.  Scenarios (`case_
   lying       default gravity, the robot on its front, back, left or right side within 0.25 rad, joints default +- 1 rad: at least two
               points of at least two bodies under the plane, the lowest by 1 - 8 mm
   torso_ball  lying on the front or back with a torso point under the plane and the ball 0.5 - 10 mm into the torso box from above
-  sparse      free with the robot and the ball lifted 0.5 m clear of the ground everywhere except ball_contact_ref.NEIGHBOUR_ENVS"""
+  sparse      free with the robot and the ball lifted 0.5 m clear of the ground everywhere except step_terms.NEIGHBOUR_ENVS"""
 import numpy as np
 
 from bez_isaacgym_amd import abi
 from tests import proximity_numpy as P
-from tests.ball_contact_ref import (BARS, case_bars, make_cfg, inject, outputs, env_errors, loaded_rows, dr_params, actions,
-                                    NEIGHBOUR_ENVS, OUTLIER_BUDGET)
 from tests import ball_contact_ref as B
-from tests.leg_contact_ref import pair_geometry, CLEAR, robot_momentum
-from tests.parity_util import EnvOutliers
+from tests import step_terms as S
+from tests.leg_contact_ref import pair_geometry, CLEAR
 from tests.proximity_numpy import tables, link_frames
 
 NPT = P.NPT
@@ -39,8 +37,7 @@ SLOW = 0.02               # every fourth block of 22 envs moves at this share of
 LYING_SPEED = 0.25        # the lying scenarios move at this share of free's speeds
 PER_POINT = 46            # postures per point: 1000 envs aim 45 - 46 at each
 CHUNK = 20000
-QUANTITIES = B.QUANTITIES
-N = 1000                  # a multiple of neither the 16-env nor the 64-env workgroup
+N = S.N
 NONE, SLIPPING, CAPPED, INSIDE = 0, 1, 2, 3
 REGIMES = {SLIPPING: "slipping", CAPPED: "capped", INSIDE: "inside_veps"}
 GRAVITY = ("lying", "torso_ball")
@@ -361,7 +358,7 @@ def case_states(scenario, asset, n):
         return torso_ball_states(n, asset)
     st = free_states(n, asset)
     if scenario == "sparse":
-        return lifted(st, NEIGHBOUR_ENVS)
+        return lifted(st, S.NEIGHBOUR_ENVS)
     assert scenario in ("free", "solo"), scenario
     return st
 
@@ -390,58 +387,45 @@ def momentum_residual(before, after, com, point, cf, asset, dt):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the oracle's side of a case
-_REFERENCES = {}
-
-
 def reference(scenario, asset, n, substeps=2, dr=False, flags=0, contact=None, states=None, tag=None):
-    """One step of the fp64 oracle and of its fp32 build from the scenario's states, computed once per process and shared by every
-    kernel's test: states, per-env parameters, actions, the numpy terms of the start state, kept, both outputs, the momentum residuals.
+    """step_terms.reference of a ground case: states, per-env parameters, actions, the numpy terms of the start state, kept, both
+    outputs, the momentum residuals.
     contact: ((BezSimConfig field, value), ...) set in the config of oracle and sim alike.  states / tag: another state set under the
     scenario's config (the planted slips)."""
-    key = (scenario, asset, n, substeps, dr, flags, contact, tag)
-    if key in _REFERENCES:
-        return _REFERENCES[key]
-    from types import SimpleNamespace
-    from oracle.bez_oracle import Oracle
-    ref = SimpleNamespace(scenario=scenario, asset=asset, n=n, substeps=substeps, dr=dr, flags=flags, contact=contact)
-
     def cfg():
-        c = make_cfg(n, asset, gravity=scenario in GRAVITY, substeps=substeps, flags=flags)
+        c = S.step_cfg(n, asset, gravity=scenario in GRAVITY, substeps=substeps, flags=flags)
         for k, v in contact or ():
             setattr(c, k, v)
         return c
-    ref.cfg = cfg
-    ref.states = case_states(scenario, asset, n) if states is None else states
-    ref.aim = ref.states["aim"]
-    ref.params = dr_params(n, 8) if dr else None
-    ref.actions = actions(n, 2)
-    o64, o32 = Oracle(ref.cfg()), Oracle(ref.cfg(), precision="f32")
-    for o in (o64, o32):
-        inject(o, ref.states, ref.params)
-    rb = o64.rigid_body_states.reshape(n, -1, 13)
-    ref.terms = terms(ref.states, asset, rb, ref.cfg(), None if not dr else ref.params[abi.PARAM_FRICTION])
-    ref.kept = kept(ref.terms)
-    if scenario == "torso_ball":
-        ref.depths = B.depths(rb, ref.states["root_states"][:, 1, 0:3], asset)
-        ref.kept &= B.kept(ref.depths)
-    ref.point = ref.states["root_states"][:, 0, 0:3].astype(np.float64) + points_rel(
-        asset, ref.states["root_states"][:, 0, 3:7], ref.states["dof_state"][:, :, 0])[np.arange(n), np.maximum(ref.aim, 0)]
-    before = [robot_momentum(o, n, asset) for o in (o64, o32)]
-    ref.com = robot_com(o64, n, asset)
-    for o in (o64, o32):
-        o.step(ref.actions)
-    ref.out64, ref.out32 = outputs(o64, n), outputs(o32, n)
-    ref.err32 = env_errors(ref.out32, ref.out64)
-    dt = float(ref.cfg().dt)
-    ref.res64, ref.res32 = (momentum_residual(b, robot_momentum(o, n, asset), ref.com, ref.point, out["cf"], asset, dt)
-                            for b, o, out in zip(before, (o64, o32), (ref.out64, ref.out32)))
-    _REFERENCES[key] = ref
-    return ref
+
+    def build(ref):
+        ref.cfg = cfg
+        ref.states = case_states(scenario, asset, n) if states is None else states
+        ref.aim = ref.states["aim"]
+        ref.params = S.dr_params(n, 8) if dr else None
+        ref.actions = S.actions(n, 2)
+        pair = S.oracle_pair(ref)
+        rb = pair[0].rigid_body_states.reshape(n, -1, 13)
+        ref.terms = terms(ref.states, asset, rb, cfg(), None if not dr else ref.params[abi.PARAM_FRICTION])
+        ref.kept = kept(ref.terms)
+        if scenario == "torso_ball":
+            ref.depths = B.depths(rb, ref.states["root_states"][:, 1, 0:3], asset)
+            ref.kept &= B.kept(ref.depths)
+        ref.point = ref.states["root_states"][:, 0, 0:3].astype(np.float64) + points_rel(
+            asset, ref.states["root_states"][:, 0, 3:7], ref.states["dof_state"][:, :, 0])[np.arange(n), np.maximum(ref.aim, 0)]
+        before = [S.robot_momentum(o, n, asset) for o in pair]
+        ref.com = robot_com(pair[0], n, asset)
+        S.step_pair(ref, *pair)
+        dt = float(cfg().dt)
+        ref.res64, ref.res32 = (momentum_residual(b, S.robot_momentum(o, n, asset), ref.com, ref.point, out["cf"], asset, dt)
+                                for b, o, out in zip(before, pair, (ref.out64, ref.out32)))
+    return S.reference(("ground", scenario, asset, n, substeps, dr, flags, contact, tag), build,
+                       scenario=scenario, asset=asset, n=n, substeps=substeps, dr=dr, flags=flags, contact=contact)
 
 
 LAST, FRIC = abi.FLAG_CF_LAST_SUBSTEP, abi.FLAG_CF_WITH_FRICTION
 # every oracle case of tests/test_gpu_ground_contact.py: (scenario, asset, n, substeps, dr, flags, contact)
-CASES = ([("free", a, N, 2, dr, 0, None) for a in B.ASSETS for dr in (False, True)]
+CASES = ([("free", a, N, 2, dr, 0, None) for a in S.ASSETS for dr in (False, True)]
          + [("solo", a, N, 1, False, f, None) for a in ("default", "cleats") for f in (0, FRIC)]
          + [("lying", "default", N, s, False, 0, None) for s in (1, 2, 3, 4)] + [("lying", "default", N, 3, False, LAST | FRIC, None)]
          + [("lying", a, N, 2, False, 0, None) for a in ("cleats", "box")]
@@ -455,55 +439,9 @@ def case_name(scenario, asset, n, substeps, dr, flags, contact):
 
 
 def compare(case, ref, out, label, report=None, p99=True):
-    """The kept envs of one stepped simulator against the fp64 oracle: every env inside the bars of ball_contact_ref.case_bars with
-    EnvOutliers' default budget, reset flags equal outside the outliers, per quantity the p99 of |got - f64| at most 2.5 x the fp32
-    build's + 1e-6 (p99=False: printed only -- the 200-env cases, whose p99 rests on three envs), and per aimed point the worst
-    contact-force error of its kept envs outside the outliers within the cf bar.
-    report: a function that receives (errors per quantity, number of outliers, bars) before anything is asserted.
-    -> the mask of the outlier envs"""
-    k = ref.kept
-    T = EnvOutliers(ref.n)
-    assert max(T.floor, int(np.ceil(T.share * ref.n))) == OUTLIER_BUDGET
-    bars = case_bars(ref)
-    for q in QUANTITIES:
-        atol, rtol, _ = bars[q]
-        print("%s %s %s %-9s bar %.1e + %g%s: fp32 build %.2e" % (case, ref.asset, label, q, atol, rtol,
-                                                                  "" if atol == BARS[q][0] else " (raised: 3 x the fp32 build)", bars[q][2]))
-        T.close(out[q], ref.out64[q], atol, rtol=rtol, what=q, rows=k)
-    bad = T._bad.copy()
-    err = env_errors(out, ref.out64)
-    if report is not None:
-        report(err, int(bad.sum()), bars)
-    T.end_step(); T.finish()
-    np.testing.assert_array_equal(out["reset"][k & ~bad], ref.out64["reset"][k & ~bad])
-    for q in QUANTITIES:
-        h, c = np.quantile(err[q][k], 0.99), np.quantile(ref.err32[q][k], 0.99)
-        print("%s %s %s %-9s p99 %.2e, fp32 build %.2e" % (case, ref.asset, label, q, h, c))
-        assert not p99 or h <= 2.5 * c + 1e-6, (case, ref.asset, label, q, h, c)
-    atol, rtol, _ = bars["cf"]
-    excess = np.abs(out["cf"] - ref.out64["cf"]) - rtol * np.abs(ref.out64["cf"])
-    for p in range(NPT):
-        envs = k & ~bad & (ref.aim == p)
-        if envs.any():
-            assert excess[envs].max() <= atol, (case, ref.asset, label, "point", p, excess[envs].max())
-    return bad
-
-
-def error_table(ref):
-    """{quantity: (worst, p99)} of the oracle's fp32 build against fp64 over the kept envs: the yardstick of the GPU file"""
-    return {q: (float(ref.err32[q][ref.kept].max()), float(np.quantile(ref.err32[q][ref.kept], 0.99))) for q in QUANTITIES}
-
-
-def report_line(name, ref, err, outliers, bars):
-    """one line of the report: kept / outlier counts, per quantity worst / p99 of the kernel | of the fp32 build, raised bars"""
-    k = ref.kept
-    words = ["%-36s kept=%d/%d outliers=%d/%d" % (name, k.sum(), ref.n, outliers, OUTLIER_BUDGET)]
-    for q in QUANTITIES:
-        h, c = err[q][k], ref.err32[q][k]
-        words.append("%s=%.1e/%.1e|%.1e/%.1e" % (q, h.max(), np.quantile(h, 0.99), c.max(), np.quantile(c, 0.99)))
-    raised = ["%s->%.1e" % (q, bars[q][0]) for q in QUANTITIES if bars[q][0] != BARS[q][0]]
-    words.append("raised=%s" % (",".join(raised) or "none"))
-    return "  ".join(words)
+    """step_terms.compare, and per aimed point the worst contact-force error of its kept envs outside the outliers within the cf bar"""
+    return S.compare(case, ref, out, label, report=report, p99=p99,
+                     elements=lambda bars, bad: ((), S.aimed_cf_checks(ref, out, bars, bad, NPT, "point")))
 
 
 def coverage_line(name, ref):

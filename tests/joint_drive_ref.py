@@ -1,7 +1,7 @@
 """The joint terms of the fused step, joint by joint: state generators that aim one joint per env at one branch of joint_terms /
 joint_scalar (bez_kernels.h) -- beyond a limit, saturated, locked on the speed limit, across the friction floor --, the oracle's own
-decision words and decision margins (oracle.bez_oracle.Oracle.joint_decisions), and the shared run / compare helpers of
-tests/test_joint_drive_cpu.py and tests/test_gpu_joint_drive.py.
+decision words and decision margins (oracle.bez_oracle.Oracle.joint_decisions), and the oracle's side, the comparison and the planted
+slips of tests/test_joint_drive_cpu.py and tests/test_gpu_joint_drive.py (on the harness of tests/step_terms.py).
 
 Per joint and substep the step decides (oracle: dynamics_x pass 2):
   below lo / above hi   q against the env's bounds: the implicit limit spring-damper limit_k, limit_d
@@ -21,13 +21,11 @@ import numpy as np
 
 from bez_isaacgym_amd import abi
 from tests import ball_contact_ref as B
-from tests.ball_contact_ref import BARS, case_bars, make_cfg, inject, outputs, env_errors, NEIGHBOUR_ENVS, OUTLIER_BUDGET
+from tests import step_terms as S
 from tests.leg_contact_ref import pair_geometry, CLEAR
-from tests.parity_util import EnvOutliers
 
 ND = 18
-N = 1000                    # a multiple of neither the 16-env nor the 64-env workgroup
-QUANTITIES = B.QUANTITIES
+N = S.N
 LIMIT_MARGIN = 0.03         # rad: the postures stay this far inside the joint limits
 BEYOND = (0.01, 0.1)        # rad beyond the bound
 BOUND_SHIFT = (0.005, 0.02)  # rad: the dr variant's non-aimed bounds lie this far inside the model's
@@ -169,15 +167,10 @@ def limits_states(n, asset, dr, seed=11):
         q32 = q.astype(np.float32).astype(np.float64)
         elo[env, aim] = np.where(regime == BELOW, q32[env, aim] + beyond, elo[env, aim])
         ehi[env, aim] = np.where(regime == ABOVE, q32[env, aim] - beyond, ehi[env, aim])
-        params = dict(dr_gains(n, seed + 1))
+        params = dict(S.dr_params(n, seed + 1))
         params[abi.PARAM_DOF_LOWER] = elo.astype(np.float32)
         params[abi.PARAM_DOF_UPPER] = ehi.astype(np.float32)
     return _finish(rs, q, qd, target, aim=aim, regime=regime, params=params)
-
-
-def dr_gains(n, seed):
-    """per-env friction, Kp and Kd scales, as ball_contact_ref.dr_params draws them"""
-    return B.dr_params(n, seed)
 
 
 def _joint_inertia(asset):
@@ -227,7 +220,7 @@ def drive_states(n, asset, cfg, dr, seed=12, only=None):
     easy = np.zeros(n, bool)
     if only is not None:
         easy[:] = True; easy[np.asarray(only, int)] = False
-    params = dict(dr_gains(n, seed + 1)) if dr else None
+    params = dict(S.dr_params(n, seed + 1)) if dr else None
     kps = params[abi.PARAM_KP_SCALE][env, aim].astype(np.float64) if dr else np.ones(n)
     kds = params[abi.PARAM_KD_SCALE][env, aim].astype(np.float64) if dr else np.ones(n)
     sign = np.where((regime == SAT_POS) | (regime == LOCK_POS), 1.0, -1.0)
@@ -307,7 +300,7 @@ def _case_states(scenario, asset, n, dr, cfg):
         return drive_states(n, asset, cfg, dr, only=())
     if scenario == "drive_sparse":   # drive_none with the envs NEIGHBOUR_ENVS taken from the drive states: the envs are independent
         full, none = case_states("drive", asset, n, dr, cfg), case_states("drive_none", asset, n, dr, cfg)
-        rows = list(NEIGHBOUR_ENVS)
+        rows = list(S.NEIGHBOUR_ENVS)
         out = {k: (None if v is None else v.copy()) for k, v in none.items() if k != "params"}
         for k in ("root_states", "dof_state", "actions", "aim"):
             out[k][rows] = full[k][rows]
@@ -363,61 +356,44 @@ def measure_margins(refs):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the oracle's side of a case
-_REFERENCES = {}
-
-
 def reference(scenario, asset, n, substeps=2, dr=False, flags=0, wrong=None, tag=None):
-    """One step of the fp64 oracle and of its fp32 build from the scenario's states, computed once per process and shared by every
-    kernel's test: states, per-env parameters, actions, both outputs, both builds' decision words (n, substeps, 18), the fp64 build's
-    decisions with their margins, kept, aim (the aimed joint, -1: none) and aimed (n, 18), both actuator records.
+    """step_terms.reference of a joint case: states, per-env parameters, actions, both outputs, both builds' decision words
+    (n, substeps, 18), the fp64 build's decisions with their margins, kept, aim (the aimed joint, -1: none) and aimed (n, 18), both
+    actuator records.
     wrong / tag: a planted slip -- wrong(cfg, params) edits the oracle's config and parameters, the states stay the scenario's."""
     flags &= ~abi.FLAG_DOF_FORCE    # the oracle records its actuators anyway; the sims of the GPU file set the flag themselves
-    key = (scenario, asset, n, substeps, dr, flags, tag)
-    if key in _REFERENCES:
-        return _REFERENCES[key]
-    from types import SimpleNamespace
-    from oracle.bez_oracle import Oracle
-    ref = SimpleNamespace(scenario=scenario, asset=asset, n=n, substeps=substeps, dr=dr, flags=flags)
-    ref.cfg = lambda: make_cfg(n, asset, gravity=family(scenario) in GRAVITY, substeps=substeps, flags=flags)
-    ref.states = case_states(scenario, asset, n, dr, ref.cfg())
-    ref.aim, ref.regime = ref.states["aim"], ref.states["regime"]
-    ref.aimed = np.zeros((n, ND), bool)
-    if family(scenario) == "pressed":
-        ref.aimed[:, list(PRESSED_FAST)] = True
-    else:
-        ref.aimed[np.flatnonzero(ref.aim >= 0), ref.aim[ref.aim >= 0]] = True
-    ref.params = ref.states["params"]
-    if dr and ref.params is None:
-        ref.params = dict(dr_gains(n, 8))
-    ref.actions = ref.states["actions"]
-    ocfg, oparams = ref.cfg(), ref.params
-    if wrong is not None:
-        oparams = None if oparams is None else dict(oparams)
-        oparams = wrong(ocfg, oparams)
-    o64, o32 = Oracle(ocfg), Oracle(ocfg, precision="f32")
-    for o in (o64, o32):
-        inject(o, ref.states, oparams)
-    if family(scenario) in GRAVITY:
-        from tests import ground_contact_ref as G
-        rb = o64.rigid_body_states.reshape(n, -1, 13)
-        ground = G.kept(G.terms(ref.states, asset, rb, ref.cfg()))
-    else:
-        ground = np.ones(n, bool)
-    for o in (o64, o32):
-        o.step(ref.actions)
-    ref.out64, ref.out32 = outputs(o64, n), outputs(o32, n)
-    ref.decisions = o64.joint_decisions()
-    ref.decisions32 = o32.joint_decisions()
-    ref.words64, ref.words32 = ref.decisions["word"], ref.decisions32["word"]
-    ref.ground = ground
-    ref.kept = kept(ref.decisions) & ground
-    ref.act64, ref.act32 = o64.actuators(), o32.actuators()
-    ref.err32 = env_errors(ref.out32, ref.out64)
-    _REFERENCES[key] = ref
-    return ref
+
+    def build(ref):
+        ref.cfg = lambda: S.step_cfg(n, asset, gravity=family(scenario) in GRAVITY, substeps=substeps, flags=flags)
+        ref.states = case_states(scenario, asset, n, dr, ref.cfg())
+        ref.aim, ref.regime = ref.states["aim"], ref.states["regime"]
+        ref.aimed = np.zeros((n, ND), bool)
+        if family(scenario) == "pressed":
+            ref.aimed[:, list(PRESSED_FAST)] = True
+        else:
+            ref.aimed[np.flatnonzero(ref.aim >= 0), ref.aim[ref.aim >= 0]] = True
+        ref.params = ref.states["params"]
+        if dr and ref.params is None:
+            ref.params = dict(S.dr_params(n, 8))
+        ref.actions = ref.states["actions"]
+        ocfg, oparams = ref.cfg(), ref.params
+        if wrong is not None:
+            oparams = wrong(ocfg, None if oparams is None else dict(oparams))
+        o64, o32 = S.oracle_pair(ref, ocfg, oparams)
+        ref.ground = np.ones(n, bool)
+        if family(scenario) in GRAVITY:
+            from tests import ground_contact_ref as G
+            ref.ground = G.kept(G.terms(ref.states, asset, o64.rigid_body_states.reshape(n, -1, 13), ref.cfg()))
+        S.step_pair(ref, o64, o32)
+        ref.decisions, ref.decisions32 = o64.joint_decisions(), o32.joint_decisions()
+        ref.words64, ref.words32 = ref.decisions["word"], ref.decisions32["word"]
+        ref.kept = kept(ref.decisions) & ref.ground
+        ref.act64, ref.act32 = o64.actuators(), o32.actuators()
+    return S.reference(("joint", scenario, asset, n, substeps, dr, flags, tag), build,
+                       scenario=scenario, asset=asset, n=n, substeps=substeps, dr=dr, flags=flags)
 
 
-ASSETS = tuple(B.ASSETS)
+ASSETS = tuple(S.ASSETS)
 # every oracle case of tests/test_gpu_joint_drive.py: (scenario, asset, n, substeps, dr)
 CASES = ([(s, a, N, 2, dr) for s in ("limits", "drive", "friction") for a in ASSETS for dr in (False, True)]
          + [("pressed", "default", N, k, False) for k in (1, 2, 3, 4)]
@@ -448,59 +424,24 @@ def regime_counts(ref):
 
 
 def compare(case, ref, out, label, report=None, p99=True):
-    """The kept envs of one stepped simulator against the fp64 oracle: every env inside the bars of ball_contact_ref.case_bars with
-    EnvOutliers' default budget, reset flags equal outside the outliers, per quantity the p99 of |got - f64| at most 2.5 x the fp32
-    build's + 1e-6 (p99=False: printed only -- the 200-env cases), and per aimed joint the worst q and qd error of that joint in ALL its
-    kept envs -- no outlier budget -- within the q / qd bars.
-    report: a function that receives (errors per quantity, number of outliers, bars, {joint: (q worst, qd worst)}) before anything is
-    asserted.  -> the mask of the outlier envs"""
-    k = ref.kept
-    T = EnvOutliers(ref.n)
-    assert max(T.floor, int(np.ceil(T.share * ref.n))) == OUTLIER_BUDGET
-    bars = case_bars(ref)
-    for q in QUANTITIES:
-        atol, rtol, _ = bars[q]
-        print("%s %s %-9s bar %.1e + %g%s: fp32 build %.2e" % (case, label, q, atol, rtol,
-                                                               "" if atol == BARS[q][0] else " (raised: 3 x the fp32 build)", bars[q][2]))
-        T.close(out[q], ref.out64[q], atol, rtol=rtol, what=q, rows=k)
-    bad = T._bad.copy()
-    err = env_errors(out, ref.out64)
-    joints = {}
-    for j in range(ND):
-        envs = k & ref.aimed[:, j]
-        if envs.any():
-            joints[j] = tuple(float(np.abs(out[x][envs, j] - ref.out64[x][envs, j]).max()) for x in ("q", "qd"))
-    if report is not None:
-        report(err, int(bad.sum()), bars, joints)
-    T.end_step(); T.finish()
-    np.testing.assert_array_equal(out["reset"][k & ~bad], ref.out64["reset"][k & ~bad])
-    for q in QUANTITIES:
-        h, c = np.quantile(err[q][k], 0.99), np.quantile(ref.err32[q][k], 0.99)
-        print("%s %s %-9s p99 %.2e, fp32 build %.2e" % (case, label, q, h, c))
-        assert not p99 or h <= 2.5 * c + 1e-6, (case, label, q, h, c)
-    for j, (eq, eqd) in joints.items():
-        assert np.isfinite(eq) and eq <= bars["q"][0], (case, label, "joint", j, "q", eq)
-        assert np.isfinite(eqd) and eqd <= bars["qd"][0], (case, label, "joint", j, "qd", eqd)
-    return bad
-
-
-def error_table(ref):
-    """{quantity: (worst, p99)} of the oracle's fp32 build against fp64 over the kept envs: the yardstick of the GPU file"""
-    return {q: (float(ref.err32[q][ref.kept].max()), float(np.quantile(ref.err32[q][ref.kept], 0.99))) for q in QUANTITIES}
+    """step_terms.compare, and per aimed joint the worst q and qd error of that joint in ALL its kept envs -- no outlier budget -- within
+    the q / qd bars.  report receives {joint: (q worst, qd worst)} as its fourth argument."""
+    def elements(bars, bad):
+        joints = {}
+        for j in range(ND):
+            envs = ref.kept & ref.aimed[:, j]
+            if envs.any():
+                joints[j] = tuple(float(np.abs(out[x][envs, j] - ref.out64[x][envs, j]).max()) for x in ("q", "qd"))
+        return (joints,), [("joint %d %s" % (j, x), v[i], bars[x][0]) for j, v in joints.items() for i, x in enumerate(("q", "qd"))]
+    return S.compare(case, ref, out, label, report=report, p99=p99, elements=elements)
 
 
 def report_line(name, ref, err, outliers, bars, joints):
-    """one line of the report: kept / outlier counts, per quantity worst / p99 of the kernel | of the fp32 build, the worst aimed-joint
-    errors, raised bars, kept envs per regime (and how many show it)"""
-    k = ref.kept
-    words = ["%-34s kept=%d/%d outliers=%d/%d" % (name, k.sum(), ref.n, outliers, OUTLIER_BUDGET)]
-    for q in QUANTITIES:
-        h, c = err[q][k], ref.err32[q][k]
-        words.append("%s=%.1e/%.1e|%.1e/%.1e" % (q, h.max(), np.quantile(h, 0.99), c.max(), np.quantile(c, 0.99)))
+    """one line of the report: step_terms.report_words with the worst aimed-joint errors before the raised bars, then the kept envs
+    per regime (and how many show it)"""
+    words = S.report_words(name, 34, ref, err, outliers, bars)
     if joints:
-        words.append("aimed_q=%.1e aimed_qd=%.1e" % (max(v[0] for v in joints.values()), max(v[1] for v in joints.values())))
-    raised = ["%s->%.1e" % (q, bars[q][0]) for q in QUANTITIES if bars[q][0] != BARS[q][0]]
-    words.append("raised=%s" % (",".join(raised) or "none"))
+        words.insert(-1, "aimed_q=%.1e aimed_qd=%.1e" % (max(v[0] for v in joints.values()), max(v[1] for v in joints.values())))
     words.append("regimes: " + " ".join("%s=%d(%d)" % (nm, a, b) for nm, (a, b) in regime_counts(ref).items()))
     return "  ".join(words)
 

@@ -1,6 +1,7 @@
 """Leg <-> leg capsule contact of the fused step, pair by pair: state generators that put every one of the 28 left-leg x right-leg
 capsule pairs into contact within the model's joint limits, the numpy side (the fp64 pair geometry of tests/proximity_numpy.py), and
-the shared run / compare helpers of tests/test_leg_contact_cpu.py and tests/test_gpu_leg_contact.py.
+the oracle's side, the comparison and the planted slips of tests/test_leg_contact_cpu.py and tests/test_gpu_leg_contact.py (on the harness
+of tests/step_terms.py).
 
 The pair geometry does not depend on the root's attitude nor on the arm and head joints, so the postures are searched once per process
 (`pool`) with the root at the identity and shared by every scenario and asset (the leg geometry of the three assets is the same table:
@@ -12,13 +13,13 @@ tests/test_leg_contact_cpu.py).  Scenarios (`case_states`):
               foot-plate capsules) overlap at once, up to five pairs; first the envs in which both foot-plate capsules of one foot touch
               the other leg (one link receives two wrenches)
   stance      the reset state on the ground under gravity with both hip rolls turned inward
-  sparse      free with default leg joints everywhere except ball_contact_ref.NEIGHBOUR_ENVS"""
+  sparse      free with default leg joints everywhere except step_terms.NEIGHBOUR_ENVS"""
 import numpy as np
 
 from bez_isaacgym_amd import abi
 from tests import ball_contact_ref as B
 from tests import proximity_numpy as P
-from tests.parity_util import EnvOutliers
+from tests import step_terms as S
 
 NPAIR = P.NPAIR
 LEGS = list(range(4, 10)) + list(range(12, 18))
@@ -34,7 +35,6 @@ DRAWS = 100000
 PARKED_BALL = (0.0, 3.0, 1.0)
 STANCE_BALL = (0.0, 3.0)
 SLOW_LEGS = 0.05          # in three envs of four the leg joints' speeds are scaled by this: a separating speed rejects a contact
-QUANTITIES = B.QUANTITIES
 
 _T = P.tables("default")
 _IA, _IB = _T["pairs"][:, 0], _T["pairs"][:, 1]
@@ -207,11 +207,11 @@ def both_parts_states(n, seed=5):
 
 
 def stance_states(n, asset, seed=6):
-    """the reset state of make_cfg(n, asset) (standing on the ground under gravity) with both hip rolls turned inward by U(0, 0.17) rad,
+    """the reset state of step_terms.step_cfg(n, asset) (standing on the ground under gravity) with both hip rolls turned inward by U(0, 0.17) rad,
     joint speeds U(-0.3, 0.3), the ball at rest 1 mm into the ground at STANCE_BALL"""
     from oracle.bez_oracle import Oracle
     rng = np.random.default_rng(seed)
-    fresh = Oracle(B.make_cfg(n, asset))
+    fresh = Oracle(S.step_cfg(n, asset))
     rs = np.asarray(fresh.root_states, np.float64).reshape(n, 2, 13).copy()
     ds = np.asarray(fresh.dof_state, np.float64).reshape(n, 18, 2).copy()
     ds[:, HIP_ROLLS[0], 0] += HIP_ROLL_INWARD[0] * rng.uniform(0.0, 0.17, n)
@@ -239,7 +239,7 @@ def case_states(scenario, asset, n):
     if scenario == "solo":
         return default_legs(st, st["solo"])
     if scenario == "sparse":
-        keep = np.zeros(n, bool); keep[list(B.NEIGHBOUR_ENVS)] = True
+        keep = np.zeros(n, bool); keep[list(S.NEIGHBOUR_ENVS)] = True
         return default_legs(st, keep)
     assert scenario == "free", scenario
     return st
@@ -251,70 +251,40 @@ def kept(gap):
 
 
 # ---------------------------------------------------------------------------------------------------------------- momentum
-def robot_momentum(sim, n, asset):
-    """(linear momentum (n, 3) of the robot from the rigid-body rows and the URDF masses (ball_contact_ref.robot_ball_momentum), angular
-    momentum (n, 3) about its centre of mass from the root and DOF state and the URDF masses and inertias (tests/centroidal_numpy.cm_ref))"""
-    from tests import centroidal_numpy as CM
-    from tests import dynamics_numpy as D
-    lin, _ = B.robot_ball_momentum(sim, n, asset)
-    root = sim.root_states.reshape(n, 2, 13)[:, 0].astype(np.float64)
-    dof = sim.dof_state.reshape(n, 18, 2).astype(np.float64)
-    f = np.float64
-    links = D.model_of(asset)["links"]
-    E, r, a, m, c, I = CM._configuration(links, root[:, 3:7], dof[:, :, 0], np.ones((n, len(links))), f)
-    com = sum(m[i][:, None] * c[i] for i in range(len(links))) / sum(m)[:, None]
-    w, v = CM._velocities(links, r, a, c, root[:, 7:10], root[:, 10:13], dof[:, :, 1])
-    _, ang, _ = CM._momentum(m, c, I, w, v, com, f)
-    return lin, ang
-
-
 def momentum_change(before, after):
     """(n, 2): largest component of the change of the robot's linear momentum (kg m/s) and of its angular momentum about its centre
-    of mass (kg m^2/s)"""
+    of mass (kg m^2/s), between two step_terms.robot_momentum"""
     return np.stack([np.abs(after[0] - before[0]).max(1), np.abs(after[1] - before[1]).max(1)], 1)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the oracle's side of a case
-_REFERENCES = {}
-
-
 def reference(scenario, asset, n, substeps=2, dr=False, flags=0):
-    """One step of the fp64 oracle and of its fp32 build from the scenario's states, computed once per process and shared by every
-    kernel's test: states, per-env parameters, actions, the numpy pair geometry of the start state, both outputs, the momentum change."""
-    key = (scenario, asset, n, substeps, dr, flags)
-    if key in _REFERENCES:
-        return _REFERENCES[key]
-    from types import SimpleNamespace
-    from oracle.bez_oracle import Oracle
-    ref = SimpleNamespace(scenario=scenario, asset=asset, n=n, substeps=substeps, dr=dr, flags=flags)
-    ref.cfg = lambda: B.make_cfg(n, asset, gravity=(scenario == "stance"), substeps=substeps, flags=flags)
-    ref.states = case_states(scenario, asset, n)
-    ref.aim = ref.states["aim"]
-    ref.params = B.dr_params(n, 8) if dr else None
-    ref.actions = B.actions(n, 2)
-    ref.gap, ref.sin2, ref.normal = pair_geometry(ref.states["root_states"][:, 0, 3:7], ref.states["dof_state"][:, :, 0], asset)
-    ref.kept = kept(ref.gap)
-    o64, o32 = Oracle(ref.cfg()), Oracle(ref.cfg(), precision="f32")
-    for o in (o64, o32):
-        B.inject(o, ref.states, ref.params)
-    before = [robot_momentum(o, n, asset) for o in (o64, o32)]
-    for o in (o64, o32):
-        o.step(ref.actions)
-    ref.out64, ref.out32 = B.outputs(o64, n), B.outputs(o32, n)
-    ref.err32 = B.env_errors(ref.out32, ref.out64)
-    ref.dp64, ref.dp32 = (momentum_change(b, robot_momentum(o, n, asset)) for b, o in zip(before, (o64, o32)))
-    _REFERENCES[key] = ref
-    return ref
+    """step_terms.reference of a leg case: states, per-env parameters, actions, the numpy pair geometry of the start state, kept, both
+    outputs, the momentum change."""
+    def build(ref):
+        ref.cfg = lambda: S.step_cfg(n, asset, gravity=(scenario == "stance"), substeps=substeps, flags=flags)
+        ref.states = case_states(scenario, asset, n)
+        ref.aim = ref.states["aim"]
+        ref.params = S.dr_params(n, 8) if dr else None
+        ref.actions = S.actions(n, 2)
+        ref.gap, ref.sin2, ref.normal = pair_geometry(ref.states["root_states"][:, 0, 3:7], ref.states["dof_state"][:, :, 0], asset)
+        ref.kept = kept(ref.gap)
+        pair = S.oracle_pair(ref)
+        before = [S.robot_momentum(o, n, asset) for o in pair]
+        S.step_pair(ref, *pair)
+        ref.dp64, ref.dp32 = (momentum_change(b, S.robot_momentum(o, n, asset)) for b, o in zip(before, pair))
+    return S.reference(("leg", scenario, asset, n, substeps, dr, flags), build,
+                       scenario=scenario, asset=asset, n=n, substeps=substeps, dr=dr, flags=flags)
 
 
 NS = abi.FLAG_NO_SELF_COLLISION
 NS_SHARE = 0.5
-N = 1000   # a multiple of neither the 16-env nor the 64-env workgroup
+N = S.N
 # every oracle case of tests/test_gpu_leg_contact.py: (scenario, asset, n, substeps, dr, flags)
-CASES = ([("free", a, N, 2, dr, 0) for a in B.ASSETS for dr in (False, True)]
+CASES = ([("free", a, N, 2, dr, 0) for a in S.ASSETS for dr in (False, True)]
          + [("solo", a, N, 1, False, f) for a in ("default", "cleats") for f in (0, abi.FLAG_CF_WITH_FRICTION)]
          + [("both_parts", "default", N, s, False, 0) for s in (1, 2, 3, 4)]
-         + [("stance", a, N, 2, False, 0) for a in B.ASSETS]
+         + [("stance", a, N, 2, False, 0) for a in S.ASSETS]
          + [("free", "default", 200, 2, False, 0), ("sparse", "default", 200, 2, False, 0), ("free", "default", N, 2, False, NS)])
 
 
@@ -334,42 +304,9 @@ def aimed_rows(cf, ref):
 
 
 def compare(case, ref, out, label, report=None, p99=True):
-    """The kept envs of one stepped simulator against the fp64 oracle: every env inside the bars of ball_contact_ref.case_bars with
-    EnvOutliers' default budget, reset flags equal outside the outliers, per quantity the p99 of |got - f64| at most 2.5 x the fp32
-    build's + 1e-6 (p99=False: printed only -- the 200-env cases, whose p99 rests on three envs), and per aimed pair the worst
-    contact-force error of its kept envs outside the outliers within the cf bar.
-    report: a function that receives (errors per quantity, number of outliers, bars) before anything is asserted.
-    -> the mask of the outlier envs"""
-    k = ref.kept
-    T = EnvOutliers(ref.n)
-    assert max(T.floor, int(np.ceil(T.share * ref.n))) == B.OUTLIER_BUDGET
-    bars = B.case_bars(ref)
-    for q in QUANTITIES:
-        atol, rtol, _ = bars[q]
-        print("%s %s %s %-9s bar %.1e + %g: fp32 build %.2e" % (case, ref.asset, label, q, atol, rtol, bars[q][2]))
-        T.close(out[q], ref.out64[q], atol, rtol=rtol, what=q, rows=k)
-    bad = T._bad.copy()
-    err = B.env_errors(out, ref.out64)
-    if report is not None:
-        report(err, int(bad.sum()), bars)
-    T.end_step(); T.finish()
-    np.testing.assert_array_equal(out["reset"][k & ~bad], ref.out64["reset"][k & ~bad])
-    for q in QUANTITIES:
-        h, c = np.quantile(err[q][k], 0.99), np.quantile(ref.err32[q][k], 0.99)
-        print("%s %s %s %-9s p99 %.2e, fp32 build %.2e" % (case, ref.asset, label, q, h, c))
-        assert not p99 or h <= 2.5 * c + 1e-6, (case, ref.asset, label, q, h, c)
-    atol, rtol, _ = bars["cf"]
-    excess = np.abs(out["cf"] - ref.out64["cf"]) - rtol * np.abs(ref.out64["cf"])
-    for p in range(NPAIR):
-        envs = k & ~bad & (ref.aim == p)
-        if envs.any():
-            assert excess[envs].max() <= atol, (case, ref.asset, label, "pair", p, excess[envs].max())
-    return bad
-
-
-def error_table(ref):
-    """{quantity: (worst, p99)} of the oracle's fp32 build against fp64 over the kept envs: the yardstick of the GPU file"""
-    return {q: (float(ref.err32[q][ref.kept].max()), float(np.quantile(ref.err32[q][ref.kept], 0.99))) for q in QUANTITIES}
+    """step_terms.compare, and per aimed pair the worst contact-force error of its kept envs outside the outliers within the cf bar"""
+    return S.compare(case, ref, out, label, report=report, p99=p99,
+                     elements=lambda bars, bad: ((), S.aimed_cf_checks(ref, out, bars, bad, NPAIR, "pair")))
 
 
 def normal_tolerance(ref):

@@ -29,6 +29,14 @@ class EnvOutliers:
         self._bad |= bad
         return bad
 
+    def mark(self, mask):
+        """count the envs of `mask` (n,) bool among this step's envs beyond the bars"""
+        self._bad |= np.asarray(mask, bool)
+
+    def marked(self):
+        """(n,) bool, a copy: the envs beyond the bars in this step so far"""
+        return self._bad.copy()
+
     def end_step(self):
         self.total += int(self._bad.sum()); self.steps += 1
         self._bad[:] = False

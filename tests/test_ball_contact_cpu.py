@@ -7,21 +7,22 @@ import pytest
 from bez_isaacgym_amd import abi
 from oracle.bez_oracle import Oracle
 from tests import ball_contact_ref as B
+from tests import step_terms as S
 
 N = 1056   # 96 envs aim at each box
 SEED = 4
 
 
-@pytest.fixture(scope="module", params=list(B.ASSETS))
+@pytest.fixture(scope="module", params=list(S.ASSETS))
 def free_space(request):
     """free-space states in a one-substep oracle without leg<->leg contact, their depths, and the contact rows of one step"""
     asset = request.param
     st = B.free_space_states(N, asset, SEED)
-    o = Oracle(B.make_cfg(N, asset, gravity=False, substeps=1, flags=abi.FLAG_NO_SELF_COLLISION))
-    B.inject(o, st)
+    o = Oracle(S.step_cfg(N, asset, gravity=False, substeps=1, flags=abi.FLAG_NO_SELF_COLLISION))
+    S.inject(o, st)
     rb = o.rigid_body_states.reshape(N, -1, 13)
     d = B.depths(rb, st["root_states"][:, 1, 0:3], asset)
-    o.pre_physics(B.actions(N, 2)); o.simulate()
+    o.pre_physics(S.actions(N, 2)); o.simulate()
     return asset, st, rb, d, o.contact_forces.reshape(N, -1, 3).astype(np.float64)
 
 
@@ -68,13 +69,13 @@ def test_numpy_winner_is_the_loaded_row(free_space):
     assert 0.02 <= rejected <= 0.15, rejected
 
 
-@pytest.mark.parametrize("asset", list(B.ASSETS))
+@pytest.mark.parametrize("asset", list(S.ASSETS))
 def test_kick_stance_reaches_the_lower_leg_boxes(asset):
     """standing robot, ball on the ground next to a foot: the calf, ankle and foot boxes of both legs each win in >= 3 kept envs (measured:
     calf 289 / 273, ankle 223 / 213, foot 10 / 4 of 1056), and the ball touches the ground"""
     st = B.kick_stance_states(N, asset, 3)
-    o = Oracle(B.make_cfg(N, asset))
-    B.inject(o, st)
+    o = Oracle(S.step_cfg(N, asset))
+    S.inject(o, st)
     d = B.depths(o.rigid_body_states.reshape(N, -1, 13), st["root_states"][:, 1, 0:3], asset)
     k, w = B.kept(d), B.winner(d)
     wins = np.bincount(w[k & (w >= 0)], minlength=B.NBOX)

@@ -13,19 +13,20 @@ from tests import body_wrench_ref as W
 from tests import forward_dynamics_numpy as FD
 from tests import generalized_forces_numpy as GF
 from tests import rbd_numpy as R
+from tests import step_terms as S
 
 N = W.N
 
 
 def _bare_cfg(asset, substeps=1):
     """flight's config with gains, joint friction and the speed limit switched off: the step is the bare articulated body plus armature"""
-    cfg = W.make_cfg(N, asset, gravity=False, substeps=substeps)
+    cfg = S.step_cfg(N, asset, gravity=False, substeps=substeps)
     cfg.kp = cfg.kd = cfg.joint_friction = 0.0
     cfg.vel_limit = 1e9
     return cfg
 
 
-@pytest.mark.parametrize("asset", list(B.ASSETS))
+@pytest.mark.parametrize("asset", list(S.ASSETS))
 def test_the_oracle_wrench_is_what_an_independent_rnea_needs(asset):
     """fp64 oracle, flight, one substep, solo.  The finite-differenced accelerations of the step, put into tests/rbd_numpy.rnea_floating
     at the start state's velocities, need the applied wrench's generalised force (tests/generalized_forces_numpy.gf_ref of the call's own
@@ -39,7 +40,7 @@ def test_the_oracle_wrench_is_what_an_independent_rnea_needs(asset):
     T = W.tables(asset)
     model = GF.model_of(asset)
     o = Oracle(cfg)
-    W.inject(o, st)
+    S.inject(o, st)
     for F, Tq, X, space in calls:
         o.apply_body_forces(F, Tq, X, space)
     o.step(st["actions"])
@@ -85,7 +86,7 @@ def test_the_oracle_wrench_is_what_an_independent_rnea_needs(asset):
         np.testing.assert_allclose(rs1[e, 1, 7:10], lin, rtol=0, atol=2 * np.spacing(np.float32(np.abs(lin).max())), err_msg=str((asset, e)))
         np.testing.assert_allclose(rs1[e, 1, 10:13], spin, rtol=0, atol=2 * np.spacing(np.float32(np.abs(spin).max())), err_msg=str((asset, e)))
     u = Oracle(cfg)
-    W.inject(u, st)
+    S.inject(u, st)
     u.step(st["actions"])
     np.testing.assert_array_equal(rs1[envs, 0], u.root_states.reshape(N, 2, 13)[envs, 0])   # the robot does not feel it
 
@@ -119,14 +120,14 @@ def test_calls_add_up_and_are_resolved_at_the_call():
     ref = W.reference(pattern="stacked", substeps=1)
     a, b = Oracle(ref.cfg()), Oracle(ref.cfg())
     for o in (a, b):
-        W.inject(o, ref.states)
+        S.inject(o, ref.states)
     for F, Tq, X, space in ref.calls:
         a.apply_body_forces(F, Tq, X, space)
     assert max(len(a.ext_entries(e)) for e in range(8)) > 3
     b.apply_body_forces(*_entries_as_one_call(a, "default", ref.states), space=W.ENV)
     a.step(ref.actions); b.step(ref.actions)
-    oa, ob = W.outputs(a, N), W.outputs(b, N)
-    for q in W.QUANTITIES:
+    oa, ob = S.outputs(a, N), S.outputs(b, N)
+    for q in S.QUANTITIES:
         np.testing.assert_allclose(oa[q], ob[q], rtol=1e-12, atol=0, err_msg=q)
     assert np.abs(oa["root_vel"] - ref.unl64["root_vel"]).max() > 0.1   # (something was applied)
     late, flight = W.reference(scenario="late"), W.reference()
@@ -146,7 +147,7 @@ def test_side_effects():
     ref = W.reference()
     o, u = Oracle(ref.cfg()), Oracle(ref.cfg())
     for x in (o, u):
-        W.inject(x, ref.states)
+        S.inject(x, ref.states)
     o.apply_body_forces(None, None, ref.calls[1][2], W.ENV)
     assert all(len(o.ext_entries(e)) == 0 for e in range(N))
     for F, Tq, X, space in ref.calls:
@@ -158,7 +159,7 @@ def test_side_effects():
     moved = np.abs(o.root_states - u.root_states).max() > 1e-3
     assert moved
     np.testing.assert_array_equal(o.contact_forces, u.contact_forces)
-    W.inject(o, ref.states); W.inject(u, ref.states)
+    S.inject(o, ref.states); S.inject(u, ref.states)
     o.simulate(); u.simulate()     # the second launch without a call is unforced
     for name in ("root_states", "dof_state", "contact_forces"):
         np.testing.assert_array_equal(getattr(o, name), getattr(u, name), err_msg=name)
@@ -166,7 +167,7 @@ def test_side_effects():
     for flag in (abi.FLAG_HARD_CONTACT, abi.FLAG_TGS_SOLVER):
         cfg = ref.cfg(); cfg.flags |= flag
         r = Oracle(cfg)
-        W.inject(r, ref.states)
+        S.inject(r, ref.states)
         before = (r.root_states, r.dof_state)
         with pytest.raises(RuntimeError):
             r.apply_body_forces(F)
@@ -194,7 +195,7 @@ def test_kept_share_cells_and_the_hard_pushes():
             c = W.cells(ref)
             every = np.zeros_like(c); np.add.at(every, (ref.body, ref.mode), 1)
             line += "  cells=%d smallest kept cell=%d" % (c.size, c.min())
-            assert c.size == ref.tables.nbe * 4 and every.min() >= 5 and c.min() >= 4 > W.OUTLIER_BUDGET, (name, every.min(), c.min())
+            assert c.size == ref.tables.nbe * 4 and every.min() >= 5 and c.min() >= 4 > S.OUTLIER_BUDGET, (name, every.min(), c.min())
             assert ref.aimed.sum(1).max() == 1 and (ref.aimed[np.arange(ref.n), ref.body]).all()
         if name in W.HARD_CASES:
             share = float(W.new_bits(ref)[ref.kept].mean())
@@ -205,7 +206,7 @@ def test_kept_share_cells_and_the_hard_pushes():
     d, c = W.reference(), W.reference(asset="cleats")
     assert d.tables.nbe * 4 == 88 and c.tables.nbe * 4 == 120
     sparse = W.reference(pattern="sparse", n=200)
-    np.testing.assert_array_equal(np.flatnonzero(sparse.aimed.any(1)), W.NEIGHBOUR_ENVS)
+    np.testing.assert_array_equal(np.flatnonzero(sparse.aimed.any(1)), S.NEIGHBOUR_ENVS)
 
 
 def test_the_fp32_build_inside_the_bars():
@@ -214,9 +215,9 @@ def test_the_fp32_build_inside_the_bars():
     print()
     for name, kw in W.CASES.items():
         ref = W.reference(**kw)
-        tab, rtab = W.error_table(ref)
+        tab, rtab = S.error_table(ref), W.response_table(ref)
         rb = W.response_bars(ref)
-        print("%-36s kept=%d/%d  %s" % (name, ref.kept.sum(), ref.n, "  ".join("%s=%.1e/%.1e" % (q, *tab[q]) for q in W.QUANTITIES)))
+        print("%-36s kept=%d/%d  %s" % (name, ref.kept.sum(), ref.n, "  ".join("%s=%.1e/%.1e" % (q, *tab[q]) for q in S.QUANTITIES)))
         print("%-36s response  %s" % ("", "  ".join("%s=%.1e/%.1e bar %.1e" % (q, *rtab[q], rb[q][0]) for q in W.RESPONSE)))
         W.compare(name, ref, ref.out32, ref.unl32, "fp32 build", p99=ref.n == N)
 

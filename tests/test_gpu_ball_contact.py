@@ -10,7 +10,7 @@ the project's single-step bars (tests/test_gpu_parity.py) with tests.parity_util
 of |HIP - f64| to 2.5 x the p99 of the oracle's own fp32 build + 1e-6.
 
 The bars, and next to them what the oracle's fp32 build shows on these states (CPU, worst over the kept envs outside the same budget of
-3 envs, over all cases of this file; tests/ball_contact_ref.case_bars raises a bar to 3 x that figure if it came within a factor 2 of it,
+3 envs, over all cases of this file; tests/step_terms.case_bars raises a bar to 3 x that figure if it came within a factor 2 of it,
 which it does in no case):
     pose 2e-5 (3.7e-6)   root velocity 4e-3 (3.2e-4)   ball velocity 4e-3 (5.0e-5)   ball spin 4e-3 (4.3e-4)   q 1.5e-4 (3.4e-5)
     qd 1.5e-2 (4.1e-3)   contact forces 0.04 + 1 % (2.9e-6 beyond the 1 %)   obs[36:44] 1.5e-2 (7.7e-4)   reward 2e-5 (9.1e-6)
@@ -19,72 +19,29 @@ misses a contact force by 16 N, as one env of each kernel does; that is what the
 
 BEZ_BALL_CONTACT_REPORT=<file>: every case appends its kept / outlier counts and per quantity the worst and p99 of the HIP kernel and of
 the fp32 build (profiles/ball_contact_errors.txt)."""
-import os
-
 import numpy as np
 import pytest
 
 from bez_isaacgym_amd import abi
 from tests import ball_contact_ref as B
-from tests.parity_util import EnvOutliers
+from tests import step_terms as S
+from tests.step_terms import KERNELS, N, hip_sim as _hip
 
 pytestmark = pytest.mark.gpu
 
-KERNELS = ["ws8", "ws8q", "lane"]
-ASSETS = list(B.ASSETS)
-N = 1000   # a multiple of neither the 16-env nor the 64-env workgroup
+ASSETS = list(S.ASSETS)
 NS = abi.FLAG_NO_SELF_COLLISION
 
 
-def _hip(ref, kernel, monkeypatch, flags=0):
-    """the HIP sim of a case, in the case's start state"""
-    from tests.sim_adapter import SimAdapter
-    monkeypatch.setenv("BEZ_SIM_KERNEL", kernel)   # read once, at bez_sim_create
-    cfg = ref.cfg()
-    cfg.flags |= flags
-    g = SimAdapter(cfg)
-    B.inject(g, ref.states, ref.params)
-    return g
-
-
-def _report(case, ref, kernel, hip_err, outliers):
-    path = os.environ.get("BEZ_BALL_CONTACT_REPORT")
-    if not path:
-        return
-    k = ref.kept
-    words = ["%-34s kept=%d/%d outliers=%d/%d" % ("%s %s %s" % (case, ref.asset, kernel), k.sum(), ref.n, outliers, B.OUTLIER_BUDGET)]
-    for q in B.QUANTITIES:
-        h, c = hip_err[q][k], ref.err32[q][k]
-        words.append("%s=%.1e/%.1e|%.1e/%.1e" % (q, h.max(), np.quantile(h, 0.99), c.max(), np.quantile(c, 0.99)))
-    with open(path, "a") as f:
-        f.write("  ".join(words) + "\n")
-
-
 def _compare(case, ref, kernel, out):
-    """the kept envs of one stepped HIP sim against the fp64 oracle: bars with the outlier budget, reset flags outside the outliers, p99
-    against the fp32 build"""
-    k = ref.kept
-    T = EnvOutliers(ref.n)
-    assert max(T.floor, int(np.ceil(T.share * ref.n))) == B.OUTLIER_BUDGET
-    bars = B.case_bars(ref)
-    for q in B.QUANTITIES:
-        atol, rtol, _ = bars[q]
-        print("%s %s %s %-9s bar %.1e + %g: fp32 build %.2e" % (case, ref.asset, kernel, q, atol, rtol, bars[q][2]))
-        T.close(out[q], ref.out64[q], atol, rtol=rtol, what=q, rows=k)
-    bad = T._bad.copy()
-    hip_err = B.env_errors(out, ref.out64)
-    _report(case, ref, kernel, hip_err, int(bad.sum()))
-    T.end_step(); T.finish()
-    np.testing.assert_array_equal(out["reset"][k & ~bad], ref.out64["reset"][k & ~bad])
-    for q in B.QUANTITIES:
-        h, c = np.quantile(hip_err[q][k], 0.99), np.quantile(ref.err32[q][k], 0.99)
-        assert h <= 2.5 * c + 1e-6, (case, ref.asset, kernel, q, h, c)
-    return bad
+    """step_terms.compare with the case's line of the report (this suite's line has no raised= word)"""
+    def report(err, outliers, bars):
+        S.note("BEZ_BALL_CONTACT_REPORT", "  ".join(S.report_words("%s %s %s" % (case, ref.asset, kernel), 34, ref, err, outliers)))
+    return S.compare("%s %s" % (case, ref.asset), ref, out, kernel, report=report)
 
 
 def _step(g, ref):
-    g.step(ref.actions)
-    return B.outputs(g, ref.n)
+    return S.step_outputs(g, ref, health=False)
 
 
 @pytest.mark.parametrize("dr", [False, True], ids=["plain", "dr"])
@@ -138,7 +95,7 @@ def test_loaded_row_is_the_numpy_winner(kernel, asset, dr, monkeypatch):
     o_loaded = B.loaded_rows(ref.out64["cf"], asset).any(1)
     differ = k & ~bad & (o_loaded != loaded.any(1))
     f = np.maximum(np.abs(cf[:, :nb]).max((1, 2)), np.abs(ref.out64["cf"].reshape(N, -1, 3)[:, :nb]).max((1, 2)))
-    assert (f[differ] <= B.BARS["cf"][0]).all(), (np.flatnonzero(differ), f[differ])
+    assert (f[differ] <= S.BARS["cf"][0]).all(), (np.flatnonzero(differ), f[differ])
     rejected = (~loaded.any(1))[k].mean()
     assert 0.02 <= rejected <= 0.15, rejected
 
@@ -170,7 +127,7 @@ def test_contact_free_neighbours(kernel, monkeypatch):
     dense, sparse = B.reference("free", "default", n), B.reference("sparse", "default", n)
     a, b = _hip(dense, kernel, monkeypatch), _hip(sparse, kernel, monkeypatch)
     oa, ob = _step(a, dense), _step(b, sparse)
-    envs = list(B.NEIGHBOUR_ENVS)
+    envs = list(S.NEIGHBOUR_ENVS)
     assert (B.winner(sparse.depths)[envs] >= 0).all() and (B.winner(sparse.depths) >= 0).sum() == len(envs)
     for name in ("root_states", "dof_state", "contact_forces"):
         x, y = getattr(a, name).reshape(n, -1), getattr(b, name).reshape(n, -1)

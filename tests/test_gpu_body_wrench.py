@@ -8,7 +8,7 @@ Every case is ONE control step from generated states written into an fp64 Oracle
 an empty call first (the EXT instantiations), one loaded and one not.  Envs in which a joint decision of the loaded or the unloaded
 fp64 step, or a contact of the start state, is nearer its boundary than the measured knife-edge margins (joint_drive_ref.kept,
 ball_contact_ref.kept, ground_contact_ref.kept; at most 14 of 1000, tests/test_body_wrench_cpu.py) are left out.  The others are held
-  (a) to the project's single-step bars (ball_contact_ref.BARS through case_bars) with tests.parity_util.EnvOutliers' default budget,
+  (a) to the project's single-step bars (tests/step_terms.BARS through case_bars) with tests.parity_util.EnvOutliers' default budget,
       per quantity the p99 of |HIP - f64| to 2.5 x the p99 of the oracle's own fp32 build + 1e-6, and
   (b) in their RESPONSE, loaded - unloaded of root velocity, joint rates, ball velocity and spin, to the oracle's: 3 x the fp32 build's
       worst response error + 2 ulp32, inside the same budget of 3 envs per case -- (a)'s bars sit two to four orders above the fp32
@@ -49,58 +49,42 @@ the fp32 build's, and no kept env's status differed from the fp64 decision.
 
 BEZ_BODY_WRENCH_REPORT=<file>: every case appends its kept / outlier counts, per quantity the worst and p99 of the HIP kernel and of
 the fp32 build, per response quantity the bar and both builds' worst and p99 (profiles/body_wrench_errors.txt)."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from bez_isaacgym_amd import abi
-from tests import ball_contact_ref as B
 from tests import body_wrench_ref as W
 from tests import joint_drive_ref as J
+from tests import step_terms as S
+from tests.step_terms import KERNELS
 
 pytestmark = pytest.mark.gpu
 
-KERNELS = ["ws8", "ws8q", "lane"]
-ASSETS = list(B.ASSETS)
-N = W.N
+ASSETS = list(S.ASSETS)
 STATE = ("root_states", "dof_state", "contact_forces", "obs", "rew")
 
 
 def _hip(ref, kernel, monkeypatch, flags=0):
     """a HIP sim of a case that has made the empty call: it launches the EXT instantiations from its first step on"""
-    from tests.sim_adapter import SimAdapter
-    if kernel is None:
-        monkeypatch.delenv("BEZ_SIM_KERNEL", raising=False)
-    else:
-        monkeypatch.setenv("BEZ_SIM_KERNEL", kernel)   # read once, at bez_sim_create
-    cfg = ref.cfg()
-    cfg.flags |= flags
-    g = SimAdapter(cfg)
+    g = S.hip_sim(ref, kernel, monkeypatch, flags, inject=False)
     g.apply_body_forces()
     return g
 
 
 def _note(text):
-    path = os.environ.get("BEZ_BODY_WRENCH_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(text + "\n")
+    S.note("BEZ_BODY_WRENCH_REPORT", text)
 
 
 def _step(g, ref, loaded):
     """the case's order of calls on one sim -- state, calls, (late: the second state,) one control step; the health word must stay clear"""
-    W.inject(g, ref.states.get("first", ref.states), ref.params)
+    S.inject(g, ref.states.get("first", ref.states), ref.params)
     if loaded:
         for F, Tq, X, space in ref.calls:
             g.apply_body_forces(F, Tq, X, space)
     if "first" in ref.states:
-        W.inject(g, ref.states, ref.params)
-    g.step(ref.actions)
-    out = W.outputs(g, ref.n)
-    assert g.sim.health() == 0, g.sim.health()
-    return out
+        S.inject(g, ref.states, ref.params)
+    return S.step_outputs(g, ref)
 
 
 def _run(name, ref, kernel, monkeypatch, flags=0, p99=True):
@@ -175,7 +159,7 @@ def test_on_the_ground(kernel, scenario, asset, monkeypatch):
         free &= np.abs(o64["cf"].reshape(ref.n, nbe, 3)[np.arange(ref.n), ref.body]).max(1) == 0
     e = np.flatnonzero(ref.kept & ~bad & free)
     assert len(e) > 0.25 * ref.n
-    atol = W.case_bars(ref)["cf"][0]
+    atol = S.case_bars(ref)["cf"][0]
     got, twin = (x["cf"].reshape(ref.n, nbe, 3)[e, ref.body[e]] for x in (out, unl))
     assert np.abs(got - twin).max() <= atol, (name, kernel, np.abs(got - twin).max())
     assert (np.abs(ref.out64["cf"]).max(1) > 1.0)[ref.kept].mean() > 0.9   # (the envs do stand or lie on something)
@@ -232,14 +216,14 @@ def test_loaded_neighbours(kernel, monkeypatch):
     name = "flight-sparse200 default"
     ref = W.reference(**W.CASES[name])
     a, b, out, unl, _ = _run(name, ref, kernel, monkeypatch, p99=False)
-    envs = list(W.NEIGHBOUR_ENVS)
+    envs = list(S.NEIGHBOUR_ENVS)
     others = np.ones(ref.n, bool); others[envs] = False
     for key in STATE:
         x, y = getattr(a, key).reshape(ref.n, -1), getattr(b, key).reshape(ref.n, -1)
         np.testing.assert_array_equal(x[others].view(np.uint32), y[others].view(np.uint32), err_msg=key)
     assert (np.abs(out["root_vel"][envs] - unl["root_vel"][envs]).max(1) > 1e-3).all()
     for g in (a, b):
-        W.inject(g, ref.states, ref.params)
+        S.inject(g, ref.states, ref.params)
         g.step(ref.actions)
         assert g.sim.health() == 0
     for key in ("root_states", "dof_state", "contact_forces"):

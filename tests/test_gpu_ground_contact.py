@@ -10,7 +10,7 @@ parameters, with contact-free neighbours in the workgroup, and with the DOF-forc
 Every case is ONE control step from generated states written into an fp64 Oracle, its fp32 build and the HIP sim.  Envs in which some
 point is within 0.1 mm of the plane, or its start-of-step normal force within 0.1 mm x kn of zero, are left out
 (ground_contact_ref.kept: at most 34 of 1000, tests/test_ground_contact_cpu.py); the others are held to the project's single-step bars
-(tests/test_gpu_parity.py, through ball_contact_ref.case_bars) with tests.parity_util.EnvOutliers' default budget, per quantity the p99
+(tests/step_terms.BARS through case_bars) with tests.parity_util.EnvOutliers' default budget, per quantity the p99
 of |HIP - f64| to 2.5 x the p99 of the oracle's own fp32 build + 1e-6, and per aimed point the worst contact-force error to the cf
 bar.  The health word stays zero.
 
@@ -24,54 +24,30 @@ substeps one lying env of the fp32 build flips a branch: that is what the budget
 BEZ_GROUND_CONTACT_REPORT=<file>: every case appends its kept / outlier counts, per quantity the worst and p99 of the HIP kernel and of
 the fp32 build, the raised bars, once per case the envs per aimed point, the envs in which each point is active and the regime counts,
 and where they are measured the momentum residuals (profiles/ground_contact_errors.txt)."""
-import os
-
 import numpy as np
 import pytest
 
 from bez_isaacgym_amd import abi
 from tests import ball_contact_ref as B
 from tests import ground_contact_ref as G
+from tests import step_terms as S
+from tests.step_terms import KERNELS, N, hip_sim as _hip, step_outputs as _step
 
 pytestmark = pytest.mark.gpu
 
-KERNELS = ["ws8", "ws8q", "lane"]
-ASSETS = list(B.ASSETS)
-N = G.N
-
-
-def _hip(ref, kernel, monkeypatch, flags=0):
-    """the HIP sim of a case, in the case's start state"""
-    from tests.sim_adapter import SimAdapter
-    monkeypatch.setenv("BEZ_SIM_KERNEL", kernel)   # read once, at bez_sim_create
-    cfg = ref.cfg()
-    cfg.flags |= flags
-    g = SimAdapter(cfg)
-    B.inject(g, ref.states, ref.params)
-    return g
+ASSETS = list(S.ASSETS)
 
 
 def _note(text):
-    path = os.environ.get("BEZ_GROUND_CONTACT_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(text + "\n")
+    S.note("BEZ_GROUND_CONTACT_REPORT", text)
 
 
 def _compare(case, ref, kernel, out, p99=True):
     def report(err, outliers, bars):
-        _note(G.report_line("%s %s %s" % (case, ref.asset, kernel), ref, err, outliers, bars))
+        _note("  ".join(S.report_words("%s %s %s" % (case, ref.asset, kernel), 36, ref, err, outliers, bars)))
         if kernel == KERNELS[0]:   # the case's own coverage, once
             _note(G.coverage_line("%s %s" % (case, ref.asset), ref))
-    return G.compare(case, ref, out, kernel, report=report, p99=p99)
-
-
-def _step(g, ref):
-    """one control step; the health word must stay clear (no non-finite env, no spin wait that gave up)"""
-    g.step(ref.actions)
-    out = B.outputs(g, ref.n)
-    assert g.sim.health() == 0, g.sim.health()
-    return out
+    return G.compare("%s %s" % (case, ref.asset), ref, out, kernel, report=report, p99=p99)
 
 
 @pytest.mark.parametrize("dr", [False, True], ids=["plain", "dr"])
@@ -114,7 +90,7 @@ def test_loaded_rows_are_the_numpy_active_set(kernel, asset, monkeypatch):
         o_rows = ref.out64["cf"].reshape(N, -1, 3)
         f = np.maximum(np.abs(cf[:, :nb]).max((1, 2)), np.abs(o_rows[:, :nb]).max((1, 2)))
         differ = k & ~bad & (loaded != want[:, :nb]).any(1)
-        assert (f[differ] <= B.BARS["cf"][0]).all(), (np.flatnonzero(differ), f[differ])
+        assert (f[differ] <= S.BARS["cf"][0]).all(), (np.flatnonzero(differ), f[differ])
         assert (np.abs(cf[k, nb]).max(1) > 0).all()
         assert loaded.any(1).mean() >= 0.85
         if flags == 0:
@@ -175,7 +151,7 @@ def test_contact_free_neighbours(kernel, monkeypatch):
     dense, sparse = G.reference("free", "default", n), G.reference("sparse", "default", n)
     a, b = _hip(dense, kernel, monkeypatch), _hip(sparse, kernel, monkeypatch)
     oa, ob = _step(a, dense), _step(b, sparse)
-    envs = list(B.NEIGHBOUR_ENVS)
+    envs = list(S.NEIGHBOUR_ENVS)
     np.testing.assert_array_equal(np.flatnonzero((sparse.terms["d"] > 0).any(1)), envs)
     for name in ("root_states", "dof_state", "contact_forces"):
         x, y = getattr(a, name).reshape(n, -1), getattr(b, name).reshape(n, -1)
@@ -194,9 +170,9 @@ def test_momentum(kernel, monkeypatch):
     error, which the oracle shows in both precisions.  The kernel may show 3 x the fp32 build's max and p99 (the leg suite's rule)."""
     ref = G.reference("solo", "default", N, substeps=1, flags=G.FRIC)
     g = _hip(ref, kernel, monkeypatch)
-    before = G.robot_momentum(g, N, "default")
+    before = S.robot_momentum(g, N, "default")
     out = _step(g, ref)
-    res = G.momentum_residual(before, G.robot_momentum(g, N, "default"), ref.com, ref.point, out["cf"], "default", float(ref.cfg().dt))
+    res = G.momentum_residual(before, S.robot_momentum(g, N, "default"), ref.com, ref.point, out["cf"], "default", float(ref.cfg().dt))
     k = ref.kept
     for col, what in ((0, "linear kg m/s"), (1, "angular kg m^2/s")):
         h, c = res[k, col], ref.res32[k, col]

@@ -9,7 +9,7 @@ Every case is ONE control step from generated states written into an fp64 Oracle
 decision quantity of some joint and substep is nearer its boundary than the measured knife-edge margin (joint_drive_ref.kept:
 tau_drive 6.5e-4 N m from +-effort, v_pred 4.7e-4 rad/s from +-vel_limit, q 7e-7 rad from lo / hi, |qd| 6.7e-6 rad/s from jfric_veps;
 at most 13 of 1000, tests/test_joint_drive_cpu.py) are left out; the others are held to the project's single-step bars
-(ball_contact_ref.BARS through case_bars) with tests.parity_util.EnvOutliers' default budget, per quantity the p99 of |HIP - f64| to
+(tests/step_terms.BARS through case_bars) with tests.parity_util.EnvOutliers' default budget, per quantity the p99 of |HIP - f64| to
 2.5 x the p99 of the oracle's own fp32 build + 1e-6, and per aimed joint the worst q and qd error of that joint over ALL its kept envs
 to the q / qd bars.  ACTUATOR_STATUS is held to the fp64 oracle's decision words exactly.  The health word stays zero.
 
@@ -28,53 +28,28 @@ fp32 build's (drive torque 1.4e-5 against 1.3e-5 N m at worst).
 
 BEZ_JOINT_DRIVE_REPORT=<file>: every case appends its kept / outlier counts, per quantity the worst and p99 of the HIP kernel and of
 the fp32 build, the worst aimed-joint errors, the raised bars and the kept envs per regime (profiles/joint_drive_errors.txt)."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from bez_isaacgym_amd import abi
-from tests import ball_contact_ref as B
 from tests import joint_drive_ref as J
+from tests import step_terms as S
+from tests.step_terms import KERNELS, N, hip_sim as _hip, step_outputs as _step
 
 pytestmark = pytest.mark.gpu
 
-KERNELS = ["ws8", "ws8q", "lane"]
 ASSETS = list(J.ASSETS)
-N = J.N
-
-
-def _hip(ref, kernel, monkeypatch, flags=0):
-    """the HIP sim of a case, in the case's start state"""
-    from tests.sim_adapter import SimAdapter
-    monkeypatch.setenv("BEZ_SIM_KERNEL", kernel)   # read once, at bez_sim_create
-    cfg = ref.cfg()
-    cfg.flags |= flags
-    g = SimAdapter(cfg)
-    B.inject(g, ref.states, ref.params)
-    return g
 
 
 def _note(text):
-    path = os.environ.get("BEZ_JOINT_DRIVE_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(text + "\n")
+    S.note("BEZ_JOINT_DRIVE_REPORT", text)
 
 
 def _compare(case, ref, kernel, out, p99=True):
     def report(err, outliers, bars, joints):
         _note(J.report_line("%s %s %s" % (case, ref.asset, kernel), ref, err, outliers, bars, joints))
     return J.compare("%s %s" % (case, ref.asset), ref, out, kernel, report=report, p99=p99)
-
-
-def _step(g, ref):
-    """one control step; the health word must stay clear (no non-finite env, no spin wait that gave up)"""
-    g.step(ref.actions)
-    out = B.outputs(g, ref.n)
-    assert g.sim.health() == 0, g.sim.health()
-    return out
 
 
 def _actuators(g):
@@ -143,7 +118,7 @@ def test_unaimed_neighbours(kernel, monkeypatch):
     for bit: a decision does not leak across lanes or quads.  Both meet the bars on all their envs."""
     n = 200
     some, none = J.reference("drive_sparse", "default", n), J.reference("drive_none", "default", n)
-    envs = list(B.NEIGHBOUR_ENVS)
+    envs = list(S.NEIGHBOUR_ENVS)
     np.testing.assert_array_equal(np.flatnonzero(some.aim >= 0), envs)
     others = np.ones(n, bool); others[envs] = False
     for key in ("root_states", "dof_state", "actions"):

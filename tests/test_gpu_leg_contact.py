@@ -7,7 +7,7 @@ substeps, with contact-free neighbours in the workgroup, with the contact switch
 
 Every case is ONE control step from generated states written into an fp64 Oracle, its fp32 build and the HIP sim.  Envs in which some
 pair is within 0.1 mm of touching are left out (leg_contact_ref.kept: none in the zero-gravity scenarios by construction, 62 of 1000 in
-the stance); the others are held to the project's single-step bars (tests/test_gpu_parity.py, through ball_contact_ref.case_bars) with
+the stance); the others are held to the project's single-step bars (tests/step_terms.BARS through case_bars) with
 tests.parity_util.EnvOutliers' default budget, per quantity the p99 of |HIP - f64| to 2.5 x the p99 of the oracle's own fp32 build + 1e-6,
 and per aimed pair the worst contact-force error to the cf bar.  The health word stays zero: a bounded spin wait that gave up
 (BEZ_HEALTH_SPIN_TIMEOUT) is a failure, not noise.
@@ -22,50 +22,29 @@ the reward's bar (2e-5) to 3 x the fp32 build's worst outside the budget (4.4e-5
 BEZ_LEG_CONTACT_REPORT=<file>: every case appends its kept / outlier counts, per quantity the worst and p99 of the HIP kernel and of the
 fp32 build, the raised bars, and where they are measured the momentum figures and the normal-direction tolerance
 (profiles/leg_contact_errors.txt)."""
-import os
-
 import numpy as np
 import pytest
 
 from bez_isaacgym_amd import abi
 from tests import ball_contact_ref as B
 from tests import leg_contact_ref as L
+from tests import step_terms as S
+from tests.step_terms import KERNELS, N, hip_sim as _hip, step_outputs as _step
 
 pytestmark = pytest.mark.gpu
 
-KERNELS = ["ws8", "ws8q", "lane"]
-ASSETS = list(B.ASSETS)
-N = L.N
-
-
-def _hip(ref, kernel, monkeypatch, flags=0):
-    """the HIP sim of a case, in the case's start state"""
-    from tests.sim_adapter import SimAdapter
-    monkeypatch.setenv("BEZ_SIM_KERNEL", kernel)   # read once, at bez_sim_create
-    cfg = ref.cfg()
-    cfg.flags |= flags
-    g = SimAdapter(cfg)
-    B.inject(g, ref.states, ref.params)
-    return g
+ASSETS = list(S.ASSETS)
 
 
 def _note(text):
-    path = os.environ.get("BEZ_LEG_CONTACT_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(text + "\n")
+    S.note("BEZ_LEG_CONTACT_REPORT", text)
 
 
 def _compare(case, ref, kernel, out, p99=True):
     def report(err, outliers, bars):
-        k = ref.kept
         aimed = np.bincount(ref.aim[ref.aim >= 0], minlength=L.NPAIR)
-        words = ["%-32s kept=%d/%d outliers=%d/%d aimed>=%d" % ("%s %s %s" % (case, ref.asset, kernel), k.sum(), ref.n, outliers, B.OUTLIER_BUDGET, aimed.min())]
-        for q in L.QUANTITIES:
-            h, c = err[q][k], ref.err32[q][k]
-            words.append("%s=%.1e/%.1e|%.1e/%.1e" % (q, h.max(), np.quantile(h, 0.99), c.max(), np.quantile(c, 0.99)))
-        raised = ["%s->%.1e" % (q, bars[q][0]) for q in L.QUANTITIES if bars[q][0] != B.BARS[q][0]]
-        words.append("raised=%s" % (",".join(raised) or "none"))
+        words = S.report_words("%s %s %s" % (case, ref.asset, kernel), 32, ref, err, outliers, bars)
+        words[0] += " aimed>=%d" % aimed.min()
         _note("  ".join(words))
         if kernel == KERNELS[0]:   # the case's own coverage, once
             if ref.scenario in ("both_parts", "stance"):   # no pair is aimed at: the envs in which each overlaps
@@ -74,15 +53,7 @@ def _compare(case, ref, kernel, out, p99=True):
                 short = [p for p in range(L.NPAIR) if aimed[p] < 5] if ref.scenario == "solo" else []
                 _note("%-32s envs aimed at pair 0..27: %s%s" % ("%s %s" % (case, ref.asset), " ".join(map(str, aimed)),
                                                               "  (pairs without 5 solo envs: %s)" % short if short else ""))
-    return L.compare(case, ref, out, kernel, report=report, p99=p99)
-
-
-def _step(g, ref):
-    """one control step; the health word must stay clear (no non-finite env, no spin wait that gave up)"""
-    g.step(ref.actions)
-    out = B.outputs(g, ref.n)
-    assert g.sim.health() == 0, g.sim.health()
-    return out
+    return L.compare("%s %s" % (case, ref.asset), ref, out, kernel, report=report, p99=p99)
 
 
 @pytest.mark.parametrize("dr", [False, True], ids=["plain", "dr"])
@@ -130,7 +101,7 @@ def test_loaded_rows_are_the_numpy_pair(kernel, asset, monkeypatch):
         o_loaded = B.loaded_rows(ref.out64["cf"], asset).any(1)
         differ = ref.kept & ~bad & (o_loaded != loaded.any(1))
         f = np.maximum(np.abs(cf[:, :nb]).max((1, 2)), np.abs(ref.out64["cf"].reshape(N, -1, 3)[:, :nb]).max((1, 2)))
-        assert (f[differ] <= B.BARS["cf"][0]).all(), (np.flatnonzero(differ), f[differ])
+        assert (f[differ] <= S.BARS["cf"][0]).all(), (np.flatnonzero(differ), f[differ])
         assert loaded.any(1)[e].mean() >= 0.5
         if flags == 0:   # the normal force alone: its direction is the numpy normal
             tol, ok = L.normal_tolerance(ref)
@@ -176,7 +147,7 @@ def test_contact_free_neighbours(kernel, monkeypatch):
     dense, sparse = L.reference("free", "default", n), L.reference("sparse", "default", n)
     a, b = _hip(dense, kernel, monkeypatch), _hip(sparse, kernel, monkeypatch)
     oa, ob = _step(a, dense), _step(b, sparse)
-    envs = list(B.NEIGHBOUR_ENVS)
+    envs = list(S.NEIGHBOUR_ENVS)
     np.testing.assert_array_equal(np.flatnonzero((sparse.gap < 0).any(1)), envs)
     for name in ("root_states", "dof_state", "contact_forces"):
         x, y = getattr(a, name).reshape(n, -1), getattr(b, name).reshape(n, -1)
@@ -193,9 +164,9 @@ def test_momentum(kernel, monkeypatch):
     p99 0.062; 0.013 kg m^2/s, p99 0.009).  The kernel may show 3 x the fp32 build's max and p99."""
     ref = L.reference("free", "default", N)
     g = _hip(ref, kernel, monkeypatch)
-    before = L.robot_momentum(g, N, "default")
+    before = S.robot_momentum(g, N, "default")
     _step(g, ref)
-    dp = L.momentum_change(before, L.robot_momentum(g, N, "default"))
+    dp = L.momentum_change(before, S.robot_momentum(g, N, "default"))
     k = ref.kept
     for col, what in ((0, "linear kg m/s"), (1, "angular kg m^2/s")):
         h, c = dp[k, col], ref.dp32[k, col]
@@ -218,7 +189,7 @@ def test_no_self_collision_flag(kernel, monkeypatch):
     assert not B.loaded_rows(out_on["cf"], "default").any()
     out_off = _step(_hip(off_ref, kernel, monkeypatch), off_ref)
     d = np.abs(out_off["qd"] - out_on["qd"]).max(1)
-    share = (d > 10 * B.BARS["qd"][0]).mean()
+    share = (d > 10 * S.BARS["qd"][0]).mean()
     print("on/off difference of qd: median %.2e, share beyond 10 x the bar %.2f" % (np.median(d), share))
     assert share >= L.NS_SHARE
 

@@ -85,7 +85,7 @@ def test_single_step_parity_resynced():
         T.close(g.rew, o.rew, 2e-5, what="rew")
         cf_o, cf_g = o.contact_forces.reshape(n, 22, 3), g.contact_forces.reshape(n, 22, 3)
         bad = T.close(cf_g, cf_o, 0.04, rtol=0.01, what="cf")
-        bad |= T._bad
+        bad |= T.marked()
         np.testing.assert_array_equal(g.reset_buf[~bad], o.reset_buf[~bad])
         # the feet flags are threshold functions of the contact force: compare where the oracle is not within
         # tolerance of a threshold (0.01 N noise gate, 1 N load gate)
@@ -136,7 +136,7 @@ def test_fused_equals_split():
             np.testing.assert_array_equal(getattr(a, name), getattr(b, name), err_msg=name)
         _compare_state(a, b, T)  # two kernels in fp32 (fused 8-wave vs the lane kernel's split entry points): observed 6e-6 / 1.4e-3 / 4e-5 / 4.7e-3
         T.close(a.obs, b.obs, 5e-3, what="obs")
-        bad = T.close(a.rew, b.rew, 5e-4, what="rew") | T._bad
+        bad = T.close(a.rew, b.rew, 5e-4, what="rew") | T.marked()
         np.testing.assert_array_equal(a.reset_buf[~bad], b.reset_buf[~bad])
         T.end_step()
     T.finish()
@@ -248,7 +248,7 @@ def test_domain_randomization_parity():
         act = rng.uniform(-1, 1, (n, 18)).astype(np.float32)
         o.step(act); g.step(act); base_o.step(act)
         _compare_state(o, g, T)
-        bad = T._bad.copy(); T.end_step()
+        bad = T.marked(); T.end_step()
         np.testing.assert_array_equal(g.reset_buf[~bad], o.reset_buf[~bad])
     T.finish()
     assert np.abs(o.dof_state - base_o.dof_state).max() > 1e-2  # the randomisation really changed the dynamics

@@ -126,7 +126,7 @@ def test_fused_step_kernels_agree(other, variant, monkeypatch):
         ok = heading > 0.05   # a torso pointing straight up or down has no heading: the two slots amplify rounding without bound
         T.close(b.obs[:, 42:44], a.obs[:, 42:44], 2e-5, what="orn", rows=ok)
         assert np.mean(b.obs[:, 44:52] == a.obs[:, 44:52]) > 0.995  # threshold flags: a force within an ulp of 1 N / 0.01 N may flip
-        bad = T.close(b.rew, a.rew, 4e-4 if task == "bez_walk" else 2e-5, what="rew") | T._bad  # walk rewards reach 1000
+        bad = T.close(b.rew, a.rew, 4e-4 if task == "bez_walk" else 2e-5, what="rew") | T.marked()  # walk rewards reach 1000
         np.testing.assert_array_equal(b.reset_buf[~bad], a.reset_buf[~bad])
         T.end_step()
     T.finish()
@@ -146,7 +146,7 @@ def test_partial_workgroup_parity():
         o.step(act); g.step(act)
         T.close(g.dof_state.reshape(n, 18, 2)[..., 0], o.dof_state.reshape(n, 18, 2)[..., 0], 2e-4, what="q")
         T.close(g.obs[:, 36:44], o.obs[:, 36:44], 2e-2, what="imu")
-        bad = T.close(g.contact_forces, o.contact_forces, 0.05, rtol=0.02, what="cf") | T._bad
+        bad = T.close(g.contact_forces, o.contact_forces, 0.05, rtol=0.02, what="cf") | T.marked()
         np.testing.assert_array_equal(g.reset_buf[~bad], o.reset_buf[~bad])
         T.end_step()
     T.finish()
@@ -208,7 +208,7 @@ def test_domain_randomization_parity_full_size():
         T.close(dg[..., 0], do[..., 0], 1.5e-4, what="q")
         T.close(dg[..., 1], do[..., 1], 1.5e-2, what="qd")
         ro, rg = o.root_states.reshape(n, 2, 13), g.root_states.reshape(n, 2, 13)
-        bad = T.close(rg[..., 0:7], ro[..., 0:7], 2e-4, what="pose") | T._bad
+        bad = T.close(rg[..., 0:7], ro[..., 0:7], 2e-4, what="pose") | T.marked()
         np.testing.assert_array_equal(g.reset_buf[~bad], o.reset_buf[~bad])
         T.end_step()
     T.finish()

@@ -9,9 +9,10 @@ import pytest
 from tests import ball_contact_ref as B
 from tests import ground_contact_ref as G
 from tests import proximity_numpy as P
+from tests import step_terms as S
 
 N = G.N
-ASSETS = list(B.ASSETS)
+ASSETS = list(S.ASSETS)
 # the oracle's rigid-body rows are fp32: two ulps of a position below 1 m (1.2e-7) and one ulp of each quaternion component (6e-8) on a
 # lever of at most 0.2 m, four components, twice (1e-7), rounded up
 ROW_BAR = 5e-7
@@ -19,8 +20,8 @@ ROW_BAR = 5e-7
 
 def _oracle_rows(st, asset, n):
     from oracle.bez_oracle import Oracle
-    o = Oracle(B.make_cfg(n, asset, gravity=False))
-    B.inject(o, st)
+    o = Oracle(S.step_cfg(n, asset, gravity=False))
+    S.inject(o, st)
     return o.rigid_body_states.reshape(n, -1, 13).astype(np.float64)
 
 
@@ -110,7 +111,7 @@ def test_torso_ball_puts_the_ball_on_the_lying_torso():
 def test_sparse_contact_set_is_the_neighbour_envs():
     n = 200
     dense, sparse = G.reference("free", "default", n), G.reference("sparse", "default", n)
-    envs = list(B.NEIGHBOUR_ENVS)
+    envs = list(S.NEIGHBOUR_ENVS)
     np.testing.assert_array_equal(np.flatnonzero((sparse.terms["d"] > 0).any(1)), envs)
     np.testing.assert_array_equal(np.flatnonzero(sparse.aim >= 0), envs)
     assert (sparse.terms["height"].min(1)[sparse.aim < 0] >= G.LIFT - G.AIM_DEPTH[1] - 1e-6).all()
@@ -176,17 +177,17 @@ def test_every_friction_regime_occurs():
 
 def test_kept_cap_and_the_fp32_build_inside_the_bars():
     """every oracle case of the GPU file: at most a tenth of the envs left out, the fp32 build against fp64 per quantity (printed: the
-    GPU file's yardstick), the bars as ball_contact_ref.case_bars yields them, and the fp32 build passes the comparison it is the
+    GPU file's yardstick), the bars as step_terms.case_bars yields them, and the fp32 build passes the comparison it is the
     yardstick of"""
     print()
     for case in G.CASES:
         ref = G.reference(*case)
         name = G.case_name(*case)
         assert ref.kept.mean() >= 0.90, (name, ref.kept.mean())
-        tab = G.error_table(ref)
-        bars = B.case_bars(ref)
-        raised = {q: "%.1e" % bars[q][0] for q in G.QUANTITIES if bars[q][0] != B.BARS[q][0]}
-        print("%-30s kept=%d/%d  %s  raised=%s" % (name, ref.kept.sum(), ref.n, "  ".join("%s=%.1e/%.1e" % (q, *tab[q]) for q in G.QUANTITIES), raised or "none"))
+        tab = S.error_table(ref)
+        bars = S.case_bars(ref)
+        raised = {q: "%.1e" % bars[q][0] for q in S.QUANTITIES if bars[q][0] != S.BARS[q][0]}
+        print("%-30s kept=%d/%d  %s  raised=%s" % (name, ref.kept.sum(), ref.n, "  ".join("%s=%.1e/%.1e" % (q, *tab[q]) for q in S.QUANTITIES), raised or "none"))
         print("    " + G.coverage_line(name, ref))
         if case[0] in ("free", "solo", "sparse"):
             assert not raised, (name, raised)
@@ -207,9 +208,9 @@ def test_momentum_residual_of_the_oracle():
     impulse = float(ref.cfg().dt) * np.abs(ref.out64["cf"].reshape(N, -1, 3)[:, :B.ball_row("default")].sum(1)).max(1)
     zero = np.zeros_like(ref.out64["cf"])
     from oracle.bez_oracle import Oracle
-    o = Oracle(ref.cfg()); B.inject(o, ref.states)
-    before = G.robot_momentum(o, N, "default"); o.step(ref.actions)
-    bare = G.momentum_residual(before, G.robot_momentum(o, N, "default"), ref.com, ref.point, zero, "default", float(ref.cfg().dt))
+    o = Oracle(ref.cfg()); S.inject(o, ref.states)
+    before = S.robot_momentum(o, N, "default"); o.step(ref.actions)
+    bare = G.momentum_residual(before, S.robot_momentum(o, N, "default"), ref.com, ref.point, zero, "default", float(ref.cfg().dt))
     big = k & (impulse > 2 * ref.res64[k, 0].max())
     print("impulse median %.3e kg m/s; %d envs beyond twice the residual's max" % (np.median(impulse), big.sum()))
     assert big.sum() >= 300 and (ref.res64[big, 0] < bare[big, 0]).all()

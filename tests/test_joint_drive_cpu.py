@@ -7,6 +7,7 @@ import pytest
 
 from bez_isaacgym_amd import abi
 from tests import joint_drive_ref as J
+from tests import step_terms as S
 
 N = J.N
 AIMED = [c for c in J.CASES if c[0] in ("limits", "drive", "friction")]
@@ -101,7 +102,7 @@ def test_the_oracle_actuator_record_is_the_restated_one():
     for scenario, dr in (("limits", True), ("drive", False)):
         ref = J.reference(scenario, "default", N, substeps=1, dr=dr)
         o = Oracle(ref.cfg())
-        B.inject(o, ref.states, ref.params)
+        S.inject(o, ref.states, ref.params)
         ds0 = ref.states["dof_state"].astype(np.float64)
         o.step(ref.actions)
         ds1 = o.dof_state.reshape(N, 18, 2).astype(np.float64)
@@ -122,15 +123,15 @@ def test_the_oracle_actuator_record_is_the_restated_one():
 
 def test_the_fp32_build_inside_the_bars():
     """every oracle case of the GPU file: the fp32 build against fp64 per quantity (printed: the GPU file's yardstick), no bar raised
-    by ball_contact_ref.case_bars, and the fp32 build passes the comparison it is the yardstick of"""
+    by step_terms.case_bars, and the fp32 build passes the comparison it is the yardstick of"""
     print()
     for case in J.CASES:
         ref = J.reference(*case)
         name = J.case_name(*case)
-        tab = J.error_table(ref)
-        bars = J.case_bars(ref)
-        raised = {q: "%.1e" % bars[q][0] for q in J.QUANTITIES if bars[q][0] != J.BARS[q][0]}
-        print("%-34s kept=%d/%d  %s  raised=%s" % (name, ref.kept.sum(), ref.n, "  ".join("%s=%.1e/%.1e" % (q, *tab[q]) for q in J.QUANTITIES),
+        tab = S.error_table(ref)
+        bars = S.case_bars(ref)
+        raised = {q: "%.1e" % bars[q][0] for q in S.QUANTITIES if bars[q][0] != S.BARS[q][0]}
+        print("%-34s kept=%d/%d  %s  raised=%s" % (name, ref.kept.sum(), ref.n, "  ".join("%s=%.1e/%.1e" % (q, *tab[q]) for q in S.QUANTITIES),
                                                    raised or "none"))
         assert not raised, (name, raised)
         J.compare(name, ref, ref.out32, "fp32 build", p99=True)

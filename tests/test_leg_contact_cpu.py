@@ -9,6 +9,7 @@ from bez_isaacgym_amd import abi
 from tests import ball_contact_ref as B
 from tests import leg_contact_ref as L
 from tests import proximity_numpy as P
+from tests import step_terms as S
 
 N = L.N
 # the pairs the standing reset pose reaches with the hip rolls turned inward by up to 0.17 rad, each leg by its own draw: 16 of 28;
@@ -94,7 +95,7 @@ def test_both_parts():
                                                                                np.bincount(ov.sum(1), minlength=6)[2:].tolist()))
 
 
-@pytest.mark.parametrize("asset", list(B.ASSETS))
+@pytest.mark.parametrize("asset", list(S.ASSETS))
 def test_stance_keeps_nine_in_ten_and_reaches_half_the_pairs(asset):
     ref = L.reference("stance", asset, N)
     assert ref.kept.mean() >= 0.90, ref.kept.mean()
@@ -140,7 +141,7 @@ def test_numpy_gaps_say_which_rows_the_oracle_loads(asset):
 
 def test_no_env_resets_and_the_fp32_build_stays_inside_the_bars():
     """every oracle case of the GPU file: no env resets, and the fp32 build against fp64 per quantity (printed: the GPU file's yardstick);
-    the bars as ball_contact_ref.case_bars yields them -- raised nowhere in the zero-gravity scenarios up to two substeps, where the
+    the bars as step_terms.case_bars yields them -- raised nowhere in the zero-gravity scenarios up to two substeps, where the
     fp32 build sits 30 - 100 x below them, and in the stance only for the reward"""
     print()
     for case in L.CASES:
@@ -149,10 +150,10 @@ def test_no_env_resets_and_the_fp32_build_stays_inside_the_bars():
         assert not ref.out64["reset"].any() and not ref.out32["reset"].any(), name
         if case[0] in ("free", "solo", "both_parts"):
             assert ref.kept.all(), name
-        tab = L.error_table(ref)
-        bars = B.case_bars(ref)
-        raised = {q: "%.1e" % bars[q][0] for q in L.QUANTITIES if bars[q][0] != B.BARS[q][0]}
-        print("%-26s kept=%d/%d  %s  raised=%s" % (name, ref.kept.sum(), ref.n, "  ".join("%s=%.1e/%.1e" % (q, *tab[q]) for q in L.QUANTITIES), raised or "none"))
+        tab = S.error_table(ref)
+        bars = S.case_bars(ref)
+        raised = {q: "%.1e" % bars[q][0] for q in S.QUANTITIES if bars[q][0] != S.BARS[q][0]}
+        print("%-26s kept=%d/%d  %s  raised=%s" % (name, ref.kept.sum(), ref.n, "  ".join("%s=%.1e/%.1e" % (q, *tab[q]) for q in S.QUANTITIES), raised or "none"))
         if case[0] == "stance":
             assert set(raised) <= {"rew"}, (name, raised)
         elif case[3] <= 2:
@@ -176,7 +177,7 @@ def test_switching_the_contact_off_moves_the_joints():
     what test_no_self_collision_flag asks of the kernels"""
     on, off = L.reference("free", "default", N), L.reference("free", "default", N, flags=L.NS)
     d = np.abs(on.out64["qd"] - off.out64["qd"]).max(1)
-    share = (d > 10 * B.BARS["qd"][0]).mean()
+    share = (d > 10 * S.BARS["qd"][0]).mean()
     print("median on/off difference of qd %.2e rad/s, share beyond 10 x the bar %.2f" % (np.median(d), share))
     assert share >= L.NS_SHARE
 
